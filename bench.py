@@ -13,9 +13,12 @@ view has been enqueued so that it overlaps the rendering of the next batch - onl
 exposed, inside the timed region (north_star: gather of rendered views at the end, never per tile or per view).
 Scaling is "weak".
 
-After the timed region (never inside it): fwd+bwd timing (configs[2]), per-stage HIP-event timing of the same
+A plain run does only what the headline needs: set-up, pre-heat and warm-up, the K timed steps, the outputs of the
+last step (--dump-outputs DIR: color.npy and radii.npy, float32), the result line.  With --full, after the timed
+region (never inside it): the clocks under load, fwd+bwd timing (configs[2]), per-stage HIP-event timing of the same
 launch chain for the roofline objects (every kernel of the forward and backward chains, with its HBM traffic from
-rocprofv3 PMC passes), a parity spot check and the CPU baseline (oracle, rank 0, N == 1 only).
+rocprofv3 PMC passes), a parity spot check, the CPU baseline (oracle, rank 0, N == 1 only), the other workloads, and
+for N > 1 the gather check, the config-5 leg and the strong-scaling leg.
 Camera set-up (gsr_setup_views, one ~4 us launch per batch of views) happens once before the loop and is not part of a step.
 """
 from __future__ import annotations
@@ -202,9 +205,15 @@ def main():
     ap.add_argument("--headline-only", action="store_true", help="stop after the timed region (for rocprofv3 runs of the headline loop alone)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--gaussians", type=int, default=N_GAUSS, help=argparse.SUPPRESS)
-    ap.add_argument("--windows", type=int, default=5,
-                    help="R: the timed region is repeated R times (each window = EXACTLY --steps steps between the same barriers, MAX over "
-                         "ranks); ms_per_step / value report the MEDIAN window, every window is listed in config.windows")
+    ap.add_argument("--windows", type=int, default=None,
+                    help="R (default 1): the timed region is repeated R times (each window = EXACTLY --steps steps between the same barriers, "
+                         "MAX over ranks); ms_per_step / value report the MEDIAN window, every window is listed in config.windows.  "
+                         "The fwd+bwd leg of --full uses R windows too (default 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other measurement and check (clocks, rooflines, PMC traffic, fwd+bwd, CPU "
+                         "baseline, parity spot check, other workloads; N > 1: gather check, config-5 and strong-scaling legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) to DIR/color.npy and DIR/radii.npy, float32")
     ap.add_argument("--config5-gaussians", type=int, default=131072, help=argparse.SUPPRESS)  # (tests: the config-5 leg at a small size)
     ap.add_argument("--no-traffic", action="store_true", help="skip the two rocprofv3 PMC passes behind roofline.traffic")
     ap.add_argument("--traffic-child", choices=("fwd", "train", "cfg4_fwd", "cfg4_train", "views8", "views48", "shard131k", "cfg4s_fwd", "cfg4s_train"), default=None,
@@ -405,10 +414,11 @@ def main():
     clocks = None
     preheat_steps = 0
     if args.preheat_ms > 0:
-        if rank == 0:  # the clocks under load, sampled while ~0.1 s of steps sit in the queue (rocm-smi takes about that long)
+        if rank == 0:  # --full: the clocks under load, sampled while ~0.1 s of steps sit in the queue (rocm-smi takes about that long)
             for _ in range(1500):
                 step()
-            clocks = device_clocks()
+            if args.full:
+                clocks = device_clocks()
             preheat_steps += 1500
         torch.cuda.synchronize()
         if dist_on:  # rank 0 has just spent ~0.2 s more than the others: every rank starts its pre-heat together, so that nobody
@@ -427,7 +437,7 @@ def main():
         step()
     # the headline: eager launches.  R windows of exactly K steps each, back to back (a 20-step window is 1.1 ms long and reads 4 %
     # differently from one lease / clock state to the next: profiles/r04_m_clock_probe.txt); the MEDIAN window is reported
-    R = max(1, args.windows)
+    R = max(1, args.windows if args.windows is not None else 1)
     window_dts = []
     for _ in range(R):
         gathered.clear()
@@ -449,10 +459,16 @@ def main():
         ranks_seen = int(round(float(ones.item())))
     status = be.read_status(plan)
     assert not status["overflow"], status
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step (taken now: the --full legs below render into the same plan)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        last_color = views[K - 1:K] if dist_on else plan["color"]
+        np.save(os.path.join(args.dump_outputs, "color.npy"), last_color.float().cpu().numpy())
+        np.save(os.path.join(args.dump_outputs, "radii.npy"), plan["radii"].float().cpu().numpy())
     launch_mode = "eager"
     eager_dt = dt
     gather_check = None
-    if dist_on:
+    if dist_on and args.full:
         # what arrived: rank r's LAST rendered view must sit at [r] of the gathered tensor (every rank renders its own scene, so
         # the checksums differ and a permuted or stale slot shows)
         box = [None] * world
@@ -561,8 +577,8 @@ def main():
                 "grad_bytes_all_reduced": int(sum(t.numel() for t in last) * 4),
                 "grad_checksum_equal_on_all_ranks": bool(abs(float(hi.item()) - float(lo.item())) <= 1e-6 * max(1.0, float(hi.item()))) and float(hi.item()) > 0.0}
 
-    config5 = config5_leg() if (dist_on and not args.config5) else None
-    strong = strong_leg() if (dist_on and not args.config5) else None
+    config5 = config5_leg() if (dist_on and args.full and not args.config5) else None
+    strong = strong_leg() if (dist_on and args.full and not args.config5) else None
 
     result = {
         "metric": "rendered views/sec, 300k Gaussians @ 256x256 (fwd raster); bwd ms and HBM GB/s vs roofline alongside",
@@ -583,7 +599,8 @@ def main():
     if dist_on:
         result["rccl_ranks"] = ranks_seen
         result["dist_backend"] = backend
-        result["gather_check"] = gather_check
+        if gather_check is not None:
+            result["gather_check"] = gather_check
         if config5 is not None:
             result["config5"] = config5
         if strong is not None:
@@ -595,7 +612,7 @@ def main():
     result["eager_ms_per_step"] = 1e3 * eager_dt / K
     if graph_dt is not None:
         result["graph_ms_per_step"] = 1e3 * graph_dt / K
-    if args.headline_only:
+    if args.headline_only or not args.full:
         if rank == 0:
             print(json.dumps(result))
         if dist_on:
@@ -748,14 +765,15 @@ def main():
         for _ in range(5 + (400 if args.preheat_ms > 0 else 0)):  # (untimed: the legs before this one end in blocking reads - clocks, as above)
             fb()
         fb_windows = []
-        for _ in range(R):  # (same protocol as the headline: R windows, the median one reported)
+        R_fb = max(1, args.windows if args.windows is not None else 5)
+        for _ in range(R_fb):  # (R windows as the headline, 5 unless --windows says otherwise; the median one reported)
             device_idle()  # (rank 0 only runs this leg: no collective here)
             t0 = time.perf_counter()
             for _ in range(n_fb):
                 fb()
             device_idle()
             fb_windows.append(1e3 * (time.perf_counter() - t0) / n_fb)
-        fb_ms = sorted(fb_windows)[(R - 1) // 2]
+        fb_ms = sorted(fb_windows)[(R_fb - 1) // 2]
         bacc = {}
         for _ in range(20):
             be.run_forward(plan_b, viewbuf, means, cov6, opac, shs)  # (the rows are good for one backward)

@@ -242,7 +242,7 @@ def test_bench_py_two_ranks_on_one_gpu_real_hip_path():
     env = dict(os.environ, BENCH_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "16", "--warmup", "3",
-           "--preheat-ms", "20", "--gaussians", "60000"]
+           "--preheat-ms", "20", "--gaussians", "60000", "--full"]
     res = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     line = [ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1]
@@ -274,7 +274,7 @@ def test_bench_py_rccl_communicator_world_size_1():
     env.pop("BENCH_DIST_BACKEND", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "16", "--warmup", "3",
-           "--preheat-ms", "20", "--gaussians", "60000", "--headline-only"]
+           "--preheat-ms", "20", "--gaussians", "60000", "--full", "--headline-only"]
     res = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     line = [ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1]
@@ -300,7 +300,7 @@ def test_bench_py_eight_ranks_on_one_gpu_config5_leg():
     env = dict(os.environ, BENCH_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="2")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "8", "--warmup", "2",
-           "--windows", "2", "--preheat-ms", "0", "--gaussians", "20000", "--config5-gaussians", "16384"]
+           "--windows", "2", "--preheat-ms", "0", "--gaussians", "20000", "--config5-gaussians", "16384", "--full"]
     res = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     line = [ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1]

@@ -11,7 +11,7 @@ export TMPDIR=/tmp
 timeout 900 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1
 tail -1 $O/pytest.log
 timeout 300 python bench.py --steps 20 --warmup 5 > $O/bench_driver_flags.json 2> $O/bench_driver_flags.err
-timeout 600 python bench.py > $O/bench.json 2> $O/bench.err
+timeout 600 python bench.py --full > $O/bench.json 2> $O/bench.err
 tail -2 $O/bench.err
 HL="python bench.py --steps 400 --warmup 20 --headline-only"
 (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats -d $R/$O/prof_headline -o t -- python $R/bench.py --steps 400 --warmup 20 --headline-only > $R/$O/prof_headline.json 2> /dev/null)

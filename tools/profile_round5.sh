@@ -14,7 +14,7 @@ timeout 900 python -m pytest tests -m gpu -q > $O/pytest.log 2>&1
 tail -1 $O/pytest.log
 fi
 timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench_driver_flags.json 2> $O/bench_driver_flags.err
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err
 tail -2 $O/bench.err
 prof() {  # prof <name> <title> <bench.py args...>
   local name=$1 title=$2; shift 2

@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
 tail -1 $O/smoke.log
 timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench_driver_flags.json 2> $O/bench_driver_flags.err
-timeout 900 python bench.py > $O/bench_default_flags.json 2> $O/bench.err
+timeout 900 python bench.py --full > $O/bench_default_flags.json 2> $O/bench.err
 prof() {  # prof <name> <title> <bench.py args...>
   local name=$1 title=$2; shift 2
   (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats -d $R/$O/prof_$name -o t -- python $R/bench.py "$@" > $R/$O/prof_$name.json 2> /dev/null)
