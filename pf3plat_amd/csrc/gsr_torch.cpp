@@ -9,7 +9,9 @@
 //   * workspaces are ONE torch.uint8 allocation per call (three 2 MiB-aligned slices), kept in the autograd context for the backward;
 //   * the pair-count policy (blocking status read + one retry | deferred verification at the end of the backward | lazy) is
 //     HipBackend's of pf3plat_amd/rasterizer.py, moved here with its state (capacity hints, pending status copies);
-//   * `RasterizeFn` is a torch::autograd::Function: no Python frame between torch's engine and gsr_backward.
+//   * `RasterizeFn` is a torch::autograd::Function: no Python frame between torch's engine and gsr_backward;
+//   * the plan API of HipBackend takes its workspaces, sizes and status reads from `Backend` too, and the small ops (camera set-up and
+//     its backward, markVisible, covariances from scales / rotations) are here: only the plan API's launch calls use ctypes.
 // The library itself is reached through dlopen + dlsym of the C ABI's entry points (the same file pf3plat_amd/_lib.py loads): nothing
 // of torch crosses that boundary, only raw device pointers and the stream handle.  No CPU path: tensors must be on a ROCm device.
 #include <torch/extension.h>
@@ -20,6 +22,7 @@
 
 #include <dlfcn.h>
 
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <map>
@@ -52,6 +55,8 @@ struct Abi {
   decltype(&gsr_pack_view) pack_view = nullptr;
   decltype(&gsr_setup_views) setup_views = nullptr;
   decltype(&gsr_setup_views_backward) setup_views_backward = nullptr;
+  decltype(&gsr_setup_views_orthographic) setup_views_orthographic = nullptr;
+  decltype(&gsr_mark_visible) mark_visible = nullptr;
   decltype(&gsr_cov_from_scale_rot) cov_from_scale_rot = nullptr;
   decltype(&gsr_cov_from_scale_rot_backward) cov_from_scale_rot_backward = nullptr;
 } g_abi;
@@ -80,6 +85,8 @@ void init(const std::string& path) {
   resolve(g_abi.pack_view, "gsr_pack_view");
   resolve(g_abi.setup_views, "gsr_setup_views");
   resolve(g_abi.setup_views_backward, "gsr_setup_views_backward");
+  resolve(g_abi.setup_views_orthographic, "gsr_setup_views_orthographic");
+  resolve(g_abi.mark_visible, "gsr_mark_visible");
   resolve(g_abi.cov_from_scale_rot, "gsr_cov_from_scale_rot");
   resolve(g_abi.cov_from_scale_rot_backward, "gsr_cov_from_scale_rot_backward");
   TORCH_CHECK(g_abi.abi_version() == GSR_ABI_VERSION, "pf3plat_amd: raster library ABI ", g_abi.abi_version(), " != ", GSR_ABI_VERSION, "; rebuild");
@@ -148,6 +155,15 @@ GsrDims dims_from(const std::vector<int64_t>& v) {
   return d;
 }
 
+// The per-group rotations of the scale / rotation form: (sets, F, 3, 3) fp32 contiguous, or undefined
+Tensor frames_arg(const Cfg& cfg, const Tensor& frames) {
+  if (!frames.defined()) return frames;
+  if (frames.dim() != 4 || frames.size(0) != cfg.num_sets || frames.size(2) != 3 || frames.size(3) != 3 || frames.size(1) == 0 ||
+      cfg.num_gaussians % frames.size(1))
+    throw pybind11::value_error("frames must be (sets, F, 3, 3) with F dividing the number of Gaussians");
+  return frames.detach().to(at::kFloat).contiguous();  // (a QR factor, e.g., arrives column-major)
+}
+
 struct Status {
   int64_t num_pairs = 0;
   int overflow = 0, max_list = 0;
@@ -195,15 +211,18 @@ struct Sizes { size_t geom = 0, bin = 0, img = 0, scratch = 0; };
 
 class Backend : public std::enable_shared_from_this<Backend> {
  public:
-  // policy (see pf3plat_amd/rasterizer.py::HipBackend for the full statement)
-  std::string sync_policy = "sync";  // or "lazy"
-  int defer_after = 4;
-  std::string on_overflow = "raise";  // or "nan": opted into by callers whose loop skips NaN-gradient steps (DecoderSplattingCUDA does)
-  bool defer_status = false;
-  double spin_us = 300.0;
+  // policy (see pf3plat_amd/rasterizer.py::HipBackend for the full statement).  Atomics: Python sets them while a
+  // forward runs without the GIL and a backward runs on one of the autograd engine's threads.
+  enum class SyncPolicy { sync, lazy };
+  enum class OnOverflow { raise, nan };  // nan: opted into by callers whose loop skips NaN-gradient steps (DecoderSplattingCUDA does)
+  std::atomic<SyncPolicy> sync_policy{SyncPolicy::sync};
+  std::atomic<int> defer_after{4};
+  std::atomic<OnOverflow> on_overflow{OnOverflow::raise};
+  std::atomic<bool> defer_status{false};
+  std::atomic<double> spin_us{300.0};
   // head-room of a workspace sized from a shape's history: running maximum x clamp(1 + headroom_sigmas x sigma / mean, headroom_min, headroom_max)
   // of the pair counts seen for the shape (a new scene every step: tools/skip_rate.py -> profiles/r06_skip_rate.md)
-  double headroom_min = 1.25, headroom_max = 3.0, headroom_sigmas = 4.0;
+  std::atomic<double> headroom_min{1.25}, headroom_max{3.0}, headroom_sigmas{4.0};
 
   ~Backend() {
     for (Pinned& p : pool_) (void)hipHostFree((void*)p.q);
@@ -223,7 +242,7 @@ class Backend : public std::enable_shared_from_this<Backend> {
   double headroom_for(const ShapeKey& k) {
     std::lock_guard<std::mutex> g(mu_);
     auto it = stats_.find(k);
-    return it == stats_.end() ? headroom_min : factor_of(it->second);
+    return it == stats_.end() ? headroom_min.load() : factor_of(it->second);
   }
 
   int64_t capacity_for(const Cfg& cfg, const Status& st, double headroom = 1.25) const {
@@ -231,6 +250,18 @@ class Backend : public std::enable_shared_from_this<Backend> {
     const int64_t need = g_abi.capacity_for(&d, (uint64_t)((double)st.num_pairs * headroom) + 4096u, (uint32_t)((double)st.max_list * headroom) + 16u);
     TORCH_CHECK(need >= 0, "gsr_capacity_for failed with code ", need);
     return need;
+  }
+
+  // The plan API's read-back: the status block at the head of `bin`, copied behind the work on the current stream and waited for.  It
+  // feeds none of the policy's state (hints, statistics, `seen`, `last_status`).
+  Status read_status(const Tensor& bin) {
+    check_device({&bin});
+    TORCH_CHECK(bin.nbytes() >= 16, "read_status: the bin workspace holds no status block");
+    const at::Device dev = bin.device();
+    c10::hip::HIPGuard guard(dev.index());
+    const Pinned host = status_copy(bin, stream_of(dev));
+    wait_status(host, dev.index());
+    return take_status(host);
   }
 
   void release_workspaces() {
@@ -266,11 +297,13 @@ class Backend : public std::enable_shared_from_this<Backend> {
       o.saved = Saved{true, plan.dims, plan.geom, plan.bin, plan.img, 0};
       return o;
     }
-    bool lazy = (sync_policy == "lazy" && known) || defer_status;
-    if (!lazy && known && !reuse_workspaces && (cfg.flags & GSR_FLAG_BACKWARD_FOLLOWS) && defer_after > 0) {
+    const bool lazy_policy = sync_policy == SyncPolicy::lazy, defer_all = defer_status;  // (each knob read once per call)
+    const int after = defer_after;
+    bool lazy = (lazy_policy && known) || defer_all;
+    if (!lazy && known && !reuse_workspaces && (cfg.flags & GSR_FLAG_BACKWARD_FOLLOWS) && after > 0) {
       std::lock_guard<std::mutex> g(mu_);
       auto it = seen_.find(key);
-      if (it != seen_.end() && it->second >= defer_after) lazy = true;
+      if (it != seen_.end() && it->second >= after) lazy = true;
     }
     int64_t cap = capacity > 0 ? capacity : default_capacity(cfg);
     for (int attempt = 0; attempt < 3; ++attempt) {
@@ -287,7 +320,7 @@ class Backend : public std::enable_shared_from_this<Backend> {
       if (lazy) {
         // (the 16 bytes are copied behind the forward on its stream; the caching allocator hands freed memory to later work of that
         // stream only, so nothing here needs to keep the workspace alive)
-        PendingItem it{status_copy(plan.bin, stream), key, cfg, token, sync_policy == "lazy" || defer_status || on_overflow == "raise", (int)dev.index()};
+        PendingItem it{status_copy(plan.bin, stream), key, cfg, token, lazy_policy || defer_all || on_overflow == OnOverflow::raise, (int)dev.index()};
         std::lock_guard<std::mutex> g(mu_);
         pending_.push_back(it);
         return out;
@@ -449,22 +482,6 @@ class Backend : public std::enable_shared_from_this<Backend> {
     return sz;
   }
 
- private:
-  static Tensor frames_arg(const Cfg& cfg, const Tensor& frames) {
-    if (!frames.defined()) return frames;
-    if (frames.dim() != 4 || frames.size(0) != cfg.num_sets || frames.size(2) != 3 || frames.size(3) != 3 || cfg.num_gaussians % frames.size(1))
-      throw pybind11::value_error("frames must be (sets, F, 3, 3) with F dividing the number of Gaussians");
-    return frames.detach().to(at::kFloat).contiguous();  // (a QR factor, e.g., arrives column-major)
-  }
-
-  int64_t default_capacity(const Cfg& cfg) {
-    const ShapeKey key{cfg.num_views, cfg.num_gaussians, cfg.height, cfg.width};
-    std::lock_guard<std::mutex> g(mu_);
-    auto it = hint_.find(key);
-    if (it != hint_.end()) return it->second;
-    return (int64_t)cfg.num_views * std::max<int64_t>(8 * (int64_t)cfg.num_gaussians, 1 << 18);
-  }
-
   // outputs + ONE allocation for the three workspaces, sliced on 2 MiB boundaries (as separate large allocations would sit; the
   // library lays geom's own sub-arrays out on such boundaries too).  reuse: the workspaces come from a per-(shape, stream) cache.
   // one_view (V = 1): the image as (3, H, W) and the radii as (N) - what the per-view operator returns - instead of views of them
@@ -505,6 +522,15 @@ class Backend : public std::enable_shared_from_this<Backend> {
     return p;
   }
 
+ private:
+  int64_t default_capacity(const Cfg& cfg) {
+    const ShapeKey key{cfg.num_views, cfg.num_gaussians, cfg.height, cfg.width};
+    std::lock_guard<std::mutex> g(mu_);
+    auto it = hint_.find(key);
+    if (it != hint_.end()) return it->second;
+    return (int64_t)cfg.num_views * std::max<int64_t>(8 * (int64_t)cfg.num_gaussians, 1 << 18);
+  }
+
   void run_forward(Plan& p, const Cfg& cfg, const Tensor& viewbuf, const Tensor& means, const Tensor& cov, const Tensor& opac, const Tensor& colors,
                    const Tensor& extra, const Tensor& frames, hipStream_t stream) {
     const GsrView* vb = reinterpret_cast<const GsrView*>(viewbuf.data_ptr<float>());
@@ -541,7 +567,7 @@ class Backend : public std::enable_shared_from_this<Backend> {
   // which sleeps instead of spinning and REPORTS a device fault or a stream error.
   void wait_status(const Pinned& host, int device) {
     if (host.arrived()) return;
-    const auto deadline = std::chrono::steady_clock::now() + std::chrono::nanoseconds((int64_t)(spin_us * 1e3));
+    const auto deadline = std::chrono::steady_clock::now() + std::chrono::nanoseconds((int64_t)(spin_us.load() * 1e3));
     while (!host.arrived()) {
       if (std::chrono::steady_clock::now() > deadline) {
         c10::hip::HIPGuard guard(device);
@@ -576,9 +602,10 @@ class Backend : public std::enable_shared_from_this<Backend> {
     double mean = 0.0, m2 = 0.0;
   };
   double factor_of(const ShapeStats& s) const {
-    double f = headroom_min;
+    const double lo = headroom_min, hi = headroom_max;
+    double f = lo;
     if (s.n >= 2 && s.mean > 0.0) f = std::max(f, 1.0 + headroom_sigmas * std::sqrt(s.m2 / (double)(s.n - 1)) / s.mean);
-    return std::min(f, std::max(headroom_max, headroom_min));
+    return std::min(f, std::max(hi, lo));
   }
 
   // The capacity hint of a shape = what its largest pair count (and longest list) seen so far needs, times the head-room factor.  A
@@ -700,6 +727,17 @@ Tensor setup_views_raw(const Tensor& extrinsics, const Tensor& intrinsics, const
   return out;
 }
 
+// (V, 48) camera records + their gradient -> dL/d extrinsics (V, 4, 4), fp32 (gsr_setup_views_backward: fp64 inside)
+Tensor setup_views_backward(const Tensor& viewbuf, const Tensor& d_views) {
+  check_device({&viewbuf, &d_views});
+  const Tensor vb = f32c(viewbuf), dv = f32c(d_views);
+  Tensor out = at::empty({vb.size(0), 4, 4}, vb.options());
+  c10::hip::HIPGuard guard(vb.device().index());
+  const int rc = g_abi.setup_views_backward((int)vb.size(0), reinterpret_cast<const GsrView*>(vb.data_ptr<float>()), fptr(dv), out.data_ptr<float>(), stream_of(vb.device()));
+  if (rc != 0) throw std::runtime_error("gsr_setup_views_backward failed with code " + std::to_string(rc));
+  return out;
+}
+
 struct SetupViewsFn : public torch::autograd::Function<SetupViewsFn> {
   static Tensor forward(torch::autograd::AutogradContext* ctx, Tensor extrinsics, Tensor intrinsics, Tensor near, Tensor far, Tensor background, bool scale_invariant) {
     Tensor vb = setup_views_raw(extrinsics, intrinsics, near, far, background, scale_invariant);
@@ -708,12 +746,7 @@ struct SetupViewsFn : public torch::autograd::Function<SetupViewsFn> {
     return vb;
   }
   static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx, torch::autograd::variable_list grads) {
-    const Tensor vb = ctx->get_saved_variables()[0];
-    const Tensor dv = f32c(grads[0]);
-    Tensor out = at::empty({vb.size(0), 4, 4}, vb.options());
-    c10::hip::HIPGuard guard(vb.device().index());
-    const int rc = g_abi.setup_views_backward((int)vb.size(0), reinterpret_cast<const GsrView*>(vb.data_ptr<float>()), fptr(dv), out.data_ptr<float>(), stream_of(vb.device()));
-    if (rc != 0) throw std::runtime_error("gsr_setup_views_backward failed with code " + std::to_string(rc));
+    const Tensor out = setup_views_backward(ctx->get_saved_variables()[0], grads[0]);
     return {out.to((at::ScalarType)ctx->saved_data["dtype"].toInt()), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
   }
 };
@@ -724,6 +757,60 @@ Tensor views_from_cameras(const Tensor& extrinsics, const Tensor& intrinsics, co
     return SetupViewsFn::apply(extrinsics, intrinsics, near, far, background, scale_invariant);
   at::NoGradGuard ng;
   return setup_views_raw(extrinsics, intrinsics, near, far, background, scale_invariant);
+}
+
+// Cameras of the reference's fake orthographic render (cuda_splatting.py:153-181) in one launch: -> (V, 48) records and the (V, 20)
+// values after the move (extrinsics 16, fov_x, fov_y, near, far)
+std::tuple<Tensor, Tensor> setup_views_orthographic(const Tensor& extrinsics, const Tensor& width, const Tensor& height, const Tensor& near, const Tensor& far,
+                                                    const Tensor& background, double fov_degrees) {
+  check_device({&extrinsics, &width, &height, &near, &far, &background});
+  const int64_t v = extrinsics.size(0);
+  const Tensor ext = f32c(extrinsics), wd = f32c(width).reshape({v}), ht = f32c(height).reshape({v}), nr = f32c(near).reshape({v}),
+               fr = f32c(far).reshape({v}), bg = f32c(background);
+  Tensor out = at::empty({v, kViewFloats}, ext.options()), dump = at::empty({v, 20}, ext.options());
+  c10::hip::HIPGuard guard(ext.device().index());
+  const int rc = g_abi.setup_views_orthographic((int)v, fptr(ext), fptr(wd), fptr(ht), fptr(nr), fptr(fr), fptr(bg), bg.dim() == 2 ? 3 : 0, (float)fov_degrees,
+                                                reinterpret_cast<GsrView*>(out.data_ptr<float>()), dump.data_ptr<float>(), stream_of(ext.device()));
+  if (rc != 0) throw std::runtime_error("gsr_setup_views_orthographic failed with code " + std::to_string(rc));
+  return {out, dump};
+}
+
+// upstream's GaussianRasterizer.markVisible: (S, N) uint8, 1 where the Gaussian passes the near-plane test of view 0 of its set
+Tensor mark_visible(const Cfg& cfg, const Tensor& viewbuf, const Tensor& means) {
+  check_device({&viewbuf, &means});
+  const Tensor vb = f32c(viewbuf), m = f32c(means);
+  Tensor present = at::empty({cfg.num_sets, cfg.num_gaussians}, m.options().dtype(at::kByte));
+  const GsrDims d = cfg.dims(0);
+  c10::hip::HIPGuard guard(m.device().index());
+  const int rc = g_abi.mark_visible(&d, reinterpret_cast<const GsrView*>(vb.data_ptr<float>()), m.data_ptr<float>(), present.data_ptr<uint8_t>(), stream_of(m.device()));
+  if (rc != 0) throw std::runtime_error("gsr_mark_visible failed with code " + std::to_string(rc));
+  return present;
+}
+
+// upstream's scales= / rotations= form: covariances (n, 6) from scales (n, 3) and quaternions (n, 4; r, x, y, z), and their backward
+Tensor cov_from_scale_rot(const Tensor& scales_in, const Tensor& rotations_in, double scale_modifier) {
+  check_device({&scales_in, &rotations_in});
+  const Tensor scales = f32c(scales_in), rotations = f32c(rotations_in);
+  const int64_t n = scales.size(0);
+  TORCH_CHECK(scales.numel() == 3 * n && rotations.numel() == 4 * n, "cov_from_scale_rot: scales (n, 3) and rotations (n, 4) expected");
+  Tensor out = at::empty({n, 6}, scales.options());
+  c10::hip::HIPGuard guard(scales.device().index());
+  const int rc = g_abi.cov_from_scale_rot(n, fptr(scales), fptr(rotations), (float)scale_modifier, out.data_ptr<float>(), stream_of(scales.device()));
+  if (rc != 0) throw std::runtime_error("gsr_cov_from_scale_rot failed with code " + std::to_string(rc));
+  return out;
+}
+std::tuple<Tensor, Tensor> cov_from_scale_rot_backward(const Tensor& scales_in, const Tensor& rotations_in, double scale_modifier, const Tensor& d_cov6_in) {
+  check_device({&scales_in, &rotations_in, &d_cov6_in});
+  const Tensor scales = f32c(scales_in), rotations = f32c(rotations_in), d_cov6 = f32c(d_cov6_in);
+  const int64_t n = scales.size(0);
+  TORCH_CHECK(scales.numel() == 3 * n && rotations.numel() == 4 * n && d_cov6.numel() == 6 * n,
+              "cov_from_scale_rot_backward: scales (n, 3), rotations (n, 4) and d_cov6 (n, 6) expected");
+  Tensor d_s = at::empty_like(scales), d_r = at::empty_like(rotations);
+  c10::hip::HIPGuard guard(scales.device().index());
+  const int rc = g_abi.cov_from_scale_rot_backward(n, fptr(scales), fptr(rotations), (float)scale_modifier, fptr(d_cov6), d_s.data_ptr<float>(),
+                                                   d_r.data_ptr<float>(), stream_of(scales.device()));
+  if (rc != 0) throw std::runtime_error("gsr_cov_from_scale_rot_backward failed with code " + std::to_string(rc));
+  return {d_s, d_r};
 }
 
 // The (1, 48) camera record of one upstream settings object in ONE launch (gsr_pack_view): the matrices, the camera centre (read
@@ -911,16 +998,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("init", &init, "dlopen the raster library and resolve the C ABI");
   pybind11::class_<PyBackend>(m, "Backend")
       .def(pybind11::init<>())
-      .def_property("sync_policy", [](PyBackend& b) { return b.be().sync_policy; },
-                    [](PyBackend& b, const std::string& v) { if (v != "sync" && v != "lazy") throw pybind11::value_error("sync_policy must be 'sync' or 'lazy'"); b.be().sync_policy = v; })
-      .def_property("defer_after", [](PyBackend& b) { return b.be().defer_after; }, [](PyBackend& b, int v) { b.be().defer_after = v; })
-      .def_property("on_overflow", [](PyBackend& b) { return b.be().on_overflow; },
-                    [](PyBackend& b, const std::string& v) { if (v != "nan" && v != "raise") throw pybind11::value_error("on_overflow must be 'nan' or 'raise'"); b.be().on_overflow = v; })
-      .def_property("defer_status", [](PyBackend& b) { return b.be().defer_status; }, [](PyBackend& b, bool v) { b.be().defer_status = v; })
-      .def_property("spin_us", [](PyBackend& b) { return b.be().spin_us; }, [](PyBackend& b, double v) { b.be().spin_us = v; })
-      .def_property("headroom_min", [](PyBackend& b) { return b.be().headroom_min; }, [](PyBackend& b, double v) { b.be().headroom_min = std::max(1.0, v); })
-      .def_property("headroom_max", [](PyBackend& b) { return b.be().headroom_max; }, [](PyBackend& b, double v) { b.be().headroom_max = std::max(1.0, v); })
-      .def_property("headroom_sigmas", [](PyBackend& b) { return b.be().headroom_sigmas; }, [](PyBackend& b, double v) { b.be().headroom_sigmas = std::max(0.0, v); })
+      .def_property("sync_policy", [](PyBackend& b) { return b.be().sync_policy == Backend::SyncPolicy::lazy ? "lazy" : "sync"; },
+                    [](PyBackend& b, const std::string& v) {
+                      if (v != "sync" && v != "lazy") throw pybind11::value_error("sync_policy must be 'sync' or 'lazy'");
+                      b.be().sync_policy = v == "lazy" ? Backend::SyncPolicy::lazy : Backend::SyncPolicy::sync;
+                    })
+      .def_property("defer_after", [](PyBackend& b) { return b.be().defer_after.load(); }, [](PyBackend& b, int v) { b.be().defer_after = v; })
+      .def_property("on_overflow", [](PyBackend& b) { return b.be().on_overflow == Backend::OnOverflow::nan ? "nan" : "raise"; },
+                    [](PyBackend& b, const std::string& v) {
+                      if (v != "nan" && v != "raise") throw pybind11::value_error("on_overflow must be 'nan' or 'raise'");
+                      b.be().on_overflow = v == "nan" ? Backend::OnOverflow::nan : Backend::OnOverflow::raise;
+                    })
+      .def_property("defer_status", [](PyBackend& b) { return b.be().defer_status.load(); }, [](PyBackend& b, bool v) { b.be().defer_status = v; })
+      .def_property("spin_us", [](PyBackend& b) { return b.be().spin_us.load(); }, [](PyBackend& b, double v) { b.be().spin_us = v; })
+      .def_property("headroom_min", [](PyBackend& b) { return b.be().headroom_min.load(); }, [](PyBackend& b, double v) { b.be().headroom_min = std::max(1.0, v); })
+      .def_property("headroom_max", [](PyBackend& b) { return b.be().headroom_max.load(); }, [](PyBackend& b, double v) { b.be().headroom_max = std::max(1.0, v); })
+      .def_property("headroom_sigmas", [](PyBackend& b) { return b.be().headroom_sigmas.load(); }, [](PyBackend& b, double v) { b.be().headroom_sigmas = std::max(0.0, v); })
       .def("headroom_for", [](PyBackend& b, const ShapeKey& k) { return b.be().headroom_for(k); })
       .def_property_readonly("capacity_hint", [](PyBackend& b) { return b.be().capacity_hint(); })
       .def_property_readonly("seen", [](PyBackend& b) { return b.be().seen(); })
@@ -933,6 +1026,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              Status st; st.num_pairs = num_pairs; st.max_list = max_list;
              return b.be().capacity_for(cfg_from(cfgv), st, headroom);
            }, pybind11::arg("cfg"), pybind11::arg("num_pairs"), pybind11::arg("max_list"), pybind11::arg("headroom") = 1.25)
+      .def("read_status", [](PyBackend& b, const Tensor& bin) {
+             Status st;
+             {
+               pybind11::gil_scoped_release nogil;
+               st = b.be().read_status(bin);
+             }
+             return status_dict(st);
+           })
+      .def("make_plan", [](PyBackend& b, const std::vector<int64_t>& cfgv, const at::Device& device, int64_t capacity) {
+             // the plan API's outputs and workspaces: (dims (13 ints), color, extra_img | None, radii, geom, bin, img, backward-scratch bytes)
+             const Cfg cfg = cfg_from(cfgv);
+             const Plan p = b.be().make_plan(cfg, device, capacity, false);
+             pybind11::object e = p.extra_img.defined() ? pybind11::cast(p.extra_img) : pybind11::none();
+             return pybind11::make_tuple(dims_vec(p.dims), p.color, e, p.radii, p.geom, p.bin, p.img, b.be().sized(cfg, capacity).scratch);
+           })
       .def("check_pending", [](PyBackend& b, bool wait, int64_t only_token) { pybind11::gil_scoped_release nogil; b.be().check_pending(wait, only_token); },
            pybind11::arg("wait") = false,
            pybind11::arg("only_token") = -1)
@@ -983,6 +1091,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rasterize_one_view", &rasterize_one_view);
   m.def("views_from_cameras", &views_from_cameras);
   m.def("setup_views", &setup_views_raw);
+  m.def("setup_views_backward", &setup_views_backward);
+  m.def("setup_views_orthographic", &setup_views_orthographic);
+  m.def("mark_visible", [](const std::vector<int64_t>& cfgv, const Tensor& viewbuf, const Tensor& means) { return mark_visible(cfg_from(cfgv), viewbuf, means); });
+  m.def("cov_from_scale_rot", &cov_from_scale_rot);
+  m.def("cov_from_scale_rot_backward", &cov_from_scale_rot_backward);
+  m.def("frames_arg", [](const std::vector<int64_t>& cfgv, const c10::optional<Tensor>& frames) {
+    // -> (frames as the launches take them | None, F): the frames check of the ctypes launches of the plan API
+    const Tensor fr = frames_arg(cfg_from(cfgv), frames.has_value() ? *frames : Tensor());
+    return fr.defined() ? pybind11::make_tuple(fr, fr.size(1)) : pybind11::make_tuple(pybind11::none(), 0);
+  });
   m.def("pack_view", [](const Tensor& vm, const Tensor& pm, const Tensor& cp, const Tensor& bg, double tx, double ty, const c10::optional<Tensor>& txt,
                         const c10::optional<Tensor>& tyt, double scale_modifier, const at::Device& device) {
     return pack_view(vm, pm, cp, bg, tx, ty, txt.has_value() ? *txt : Tensor(), tyt.has_value() ? *tyt : Tensor(), scale_modifier, device);

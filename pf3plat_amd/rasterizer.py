@@ -13,10 +13,6 @@ There is no CPU path here: tensors must live on a ROCm device and the HIP librar
 from __future__ import annotations
 
 import ctypes
-import struct
-import threading
-import time
-import warnings
 from dataclasses import dataclass
 from typing import NamedTuple, Optional
 
@@ -95,13 +91,6 @@ def _ptr(t: Optional[Tensor]):
     return None if t is None else t.data_ptr()  # (a plain int: the argtypes are c_void_p, ctypes converts it without an object per argument)
 
 
-def _f32c(t: Optional[Tensor]) -> Optional[Tensor]:
-    """fp32 + contiguous, touching nothing when the tensor already is (the usual case: two no-op dispatches less per argument)."""
-    if t is None or (t.dtype is torch.float32 and t.is_contiguous()):
-        return t
-    return t.to(torch.float32).contiguous()
-
-
 class _on_device:
     """`with torch.cuda.device(dev)` only when `dev` is not already the current device (the context manager costs ~10 us of
     get / set device calls per use; a training step makes half a dozen library calls)."""
@@ -138,15 +127,13 @@ class HipBackend:
     name = "hip"
 
     def __init__(self):
-        self.lib = _lib.load()  # the C ABI through ctypes: the plan API below (bench.py, tools/, the stage-level tests) and the small ops
-        # The torch-facing path - autograd function, workspaces, the pair-count policy and its state - is the compiled binding
-        # (csrc/gsr_torch.cpp, built by __graft_entry__.build()): `forward` / `backward` / `check_pending` below only hand over to it.
+        # The compiled binding (csrc/gsr_torch.cpp, built by __graft_entry__.build()) is the only place that allocates workspaces, sizes
+        # them, reads status blocks back and runs the small ops; it holds the torch-facing path - autograd function, the pair-count policy
+        # and its state - too.  The methods below hand over to it.  Only the launch calls of the plan API (`run_forward`, `bind_forward`,
+        # `run_backward`: bench.py, tools/, the stage-level tests) go through the C ABI by ctypes.
+        self.lib = _lib.load()
         self._ext = _lib.load_torch_ext()
         self._c = self._ext.Backend()
-        self._pinned = []  # 16-byte pinned status buffers of the plan API (read_status) not in use
-        self._sizes = {}  # (cfg, capacity) -> (GsrDims, geom bytes, bin bytes, img bytes, backward scratch bytes): plan API
-        self._lock = threading.Lock()  # pools / caches of the plan API
-        self._plan_ws = {}  # make_plan(reuse_workspaces=True): (cfg, capacity, device, stream) -> (geom, bin, img)
 
     # ---- the pair-count policy and its state live in the compiled backend (one statement of each: csrc/gsr_torch.cpp::Backend)
     # sync_policy: "sync" (default) | "lazy" (opt-in, inference / benchmarks): see forward()
@@ -178,7 +165,7 @@ class HipBackend:
     pending = property(lambda self: self._c.pending)  # tokens of lazy / deferred forwards not yet verified
     poisoned = property(lambda self: self._c.poisoned)  # tokens of deferred forwards found overflowed (kept: every backward over such a forward answers NaN)
     last_status = property(lambda self: self._c.last_status)
-    workspace_cache = property(lambda self: [None] * (self._c.workspace_cache_size + len(self._plan_ws)))  # (how many cached workspace sets are alive)
+    workspace_cache = property(lambda self: [None] * self._c.workspace_cache_size)  # (how many cached workspace sets are alive)
 
     def set_capacity_hint(self, key, capacity: int):
         """Pre-size a shape: key = (views, N, H, W) -> pair_capacity (the lazy / defer_status contract: "the caller knows a safe
@@ -213,26 +200,10 @@ class HipBackend:
         return g.value, b.value, i.value
 
     def cov_from_scale_rot(self, scales: Tensor, rotations: Tensor, scale_modifier: float) -> Tensor:
-        self._check_device(scales, rotations)
-        n = scales.shape[0]
-        out = torch.empty((n, 6), dtype=torch.float32, device=scales.device)
-        stream = _stream_ptr(scales.device)
-        with _on_device(scales.device):
-            rc = self.lib.gsr_cov_from_scale_rot(n, _ptr(scales), _ptr(rotations), float(scale_modifier), _ptr(out), stream)
-        if rc != 0:
-            raise RuntimeError(f"gsr_cov_from_scale_rot failed with code {rc}")
-        return out
+        return self._ext.cov_from_scale_rot(scales, rotations, float(scale_modifier))
 
     def cov_from_scale_rot_backward(self, scales: Tensor, rotations: Tensor, scale_modifier: float, d_cov6: Tensor):
-        n = scales.shape[0]
-        d_s, d_r = torch.empty_like(scales), torch.empty_like(rotations)
-        stream = _stream_ptr(scales.device)
-        with _on_device(scales.device):
-            rc = self.lib.gsr_cov_from_scale_rot_backward(n, _ptr(scales), _ptr(rotations), float(scale_modifier), _ptr(d_cov6),
-                                                          _ptr(d_s), _ptr(d_r), stream)
-        if rc != 0:
-            raise RuntimeError(f"gsr_cov_from_scale_rot_backward failed with code {rc}")
-        return d_s, d_r
+        return self._ext.cov_from_scale_rot_backward(scales, rotations, float(scale_modifier), d_cov6)
 
     def pack_view(self, rs, device) -> Tensor:
         """The (1, 48) camera record of one `GaussianRasterizationSettings` in ONE launch (gsr_pack_view): the matrices, the
@@ -259,75 +230,24 @@ class HipBackend:
             raise RuntimeError(f"gsr_geom_layout failed (code {rc})")
         return dict(zip(("record_bytes", "aux", "rgbc", "rows"), [int(o) for o in offs]))
 
-    def _check_device(self, *tensors):
-        for t in tensors:
-            if t is not None and not t.is_cuda:
-                raise RuntimeError(
-                    "pf3plat_amd rasterizer: tensors must be on a ROCm device (there is no CPU fallback path)")
-
     def capacity_for(self, cfg: RasterConfig, status: dict, headroom: float = 1.25) -> int:
         """pair_capacity that lets a call of this shape succeed, from the status block of an earlier call (gsr_capacity_for:
         every (view, tile) owns capacity / (views x tiles) entries of the index list, so the longest list decides) + headroom."""
-        dims = self._dims(cfg, 0)
-        need = self.lib.gsr_capacity_for(ctypes.byref(dims), int(status["num_pairs"] * headroom) + 4096,
-                                         int(status["max_list"] * headroom) + 16)
-        if need < 0:
-            raise RuntimeError(f"gsr_capacity_for failed with code {need}")
-        return int(need)
-
-    def _sized(self, cfg: RasterConfig, capacity: int):
-        """(GsrDims, geom, bin, img, backward-scratch bytes) of a call shape: host-only library arithmetic, asked once per shape."""
-        key = (cfg, int(capacity))
-        hit = self._sizes.get(key)
-        if hit is None:
-            dims = self._dims(cfg, capacity)
-            hit = (dims, *self.workspace_sizes(dims), int(self.lib.gsr_backward_scratch_bytes(ctypes.byref(dims))))
-            with self._lock:
-                if len(self._sizes) >= 64:
-                    self._sizes.clear()
-                self._sizes[key] = hit
-        return hit
+        return int(self._c.capacity_for(_cfg_vec(cfg), int(status["num_pairs"]), int(status["max_list"]), float(headroom)))
 
     def release_workspaces(self):
         """Drop the cached workspaces of the no-autograd path (up to 8 sets of geom / bin / img stay alive otherwise), the size
-        caches, and - after verifying them - the status copies still pending."""
+        cache, and - after verifying them - the status copies still pending."""
         self._c.release_workspaces()
-        with self._lock:
-            self._plan_ws.clear()
-            self._sizes.clear()
 
     # ---- plans: outputs + workspaces allocated once, launch chains enqueued many times (bench / HIP-graph capture)
-    def make_plan(self, cfg: RasterConfig, device, capacity: int, backward: bool = False, colors_shape=None,
-                  reuse_workspaces: bool = False) -> dict:
-        """reuse_workspaces: the three workspaces (not the outputs) come from a per-(shape, stream) cache - for forwards that no
-        backward can follow and whose status block is read before the next call (the per-view inference loop: three
-        allocations and a workspace-size query per view less)."""
-        v, h, w, n, s = cfg.num_views, cfg.height, cfg.width, cfg.num_gaussians, cfg.num_sets
+    def make_plan(self, cfg: RasterConfig, device, capacity: int, backward: bool = False, colors_shape=None) -> dict:
+        """Outputs and workspaces of one call shape (the compiled backend's allocation: one block, three slices on 2 MiB boundaries);
+        backward=True adds the gradient outputs and the backward's scratch."""
+        v, n, s = cfg.num_views, cfg.num_gaussians, cfg.num_sets
         f32, u8 = torch.float32, torch.uint8
-        dims, gb, bb, ib, scratch_bytes = self._sized(cfg, capacity)
-        ws = None
-        if reuse_workspaces:
-            key = (cfg, int(capacity), str(device), _stream_ptr(device))
-            ws = self._plan_ws.get(key)
-        if ws is None:  # one allocation, three slices on 2 MiB boundaries (as separate large allocations would sit; the library
-            # lays geom's own sub-arrays out on such boundaries too)
-            al = (2 << 20) - 1
-            o_g = (bb + al) & ~al
-            o_i = o_g + ((gb + al) & ~al)
-            whole = torch.empty(o_i + ib, dtype=u8, device=device)
-            ws = (whole[o_g:o_g + gb], whole[:bb], whole[o_i:o_i + ib])
-            if reuse_workspaces:
-                with self._lock:
-                    if len(self._plan_ws) >= 8:
-                        self._plan_ws.clear()
-                    self._plan_ws[key] = ws
-        plan = dict(
-            cfg=cfg, dims=_lib.GsrDims.from_buffer_copy(dims), device=device,  # (a copy: tools flip flag bits in a plan's dims)
-            color=torch.empty((v, 3, h, w), dtype=f32, device=device),
-            extra_img=torch.empty((v, h, w), dtype=f32, device=device) if cfg.has_extra else None,
-            radii=torch.empty((v, n), dtype=torch.int32, device=device),
-            geom=ws[0], bin=ws[1], img=ws[2],
-        )
+        dims, color, extra_img, radii, geom, binb, img, scratch_bytes = self._c.make_plan(_cfg_vec(cfg), torch.device(device), int(capacity))
+        plan = dict(cfg=cfg, dims=_lib.GsrDims(*dims), device=device, color=color, extra_img=extra_img, radii=radii, geom=geom, bin=binb, img=img)
         if backward:
             if colors_shape is None:
                 if cfg.sh_coeffs > 0:
@@ -347,15 +267,6 @@ class HipBackend:
             )
         return plan
 
-    @staticmethod
-    def _frames_args(cfg, frames):
-        if frames is None:
-            return None, 0
-        if frames.dim() != 4 or frames.shape[0] != cfg.num_sets or frames.shape[2:] != (3, 3) or cfg.num_gaussians % frames.shape[1]:
-            raise ValueError("frames must be (sets, F, 3, 3) with F dividing the number of Gaussians")
-        frames = frames.detach().to(torch.float32).contiguous()  # (a QR factor, e.g., arrives column-major)
-        return frames, int(frames.shape[1])
-
     def run_forward(self, plan: dict, viewbuf, means, cov6, opac, colors, extra=None, profile: bool = False, out_color=None,
                     frames=None):
         """Enqueue one forward launch chain on the current stream.  profile=True returns per-stage ms (synchronises).
@@ -370,7 +281,7 @@ class HipBackend:
                 _ptr(plan["img"]), stream)
         with _on_device(plan["device"]):  # kernels launch on the process's current device: make it the tensors' device
             if plan["cfg"].scale_rot:
-                fr, nf = self._frames_args(plan["cfg"], frames)
+                fr, nf = self._ext.frames_arg(_cfg_vec(plan["cfg"]), frames)
                 ms = None
                 rc = self.lib.gsr_forward_scale_rot(*args[:4], _ptr(fr), nf, *args[4:])
             elif profile:
@@ -423,7 +334,7 @@ class HipBackend:
                 _ptr(plan["d_means2d"] if want_means2d else None), stream)
         with _on_device(plan["device"]):
             if d_views is not None:
-                fr, nf = self._frames_args(cfg, frames) if cfg.scale_rot else (None, 0)
+                fr, nf = self._ext.frames_arg(_cfg_vec(cfg), frames) if cfg.scale_rot else (None, 0)
                 partials = plan.get("pose_partials")
                 if partials is None:
                     partials = plan["pose_partials"] = torch.empty(
@@ -432,7 +343,7 @@ class HipBackend:
                 ms = None
                 rc = self.lib.gsr_backward_ex(*args[:-1], ctypes.byref(opt), stream)
             elif cfg.scale_rot:
-                fr, nf = self._frames_args(cfg, frames)
+                fr, nf = self._ext.frames_arg(_cfg_vec(cfg), frames)
                 ms = None
                 rc = self.lib.gsr_backward_scale_rot(*args[:4], _ptr(fr), nf, *args[4:])
             elif profile:
@@ -444,57 +355,10 @@ class HipBackend:
         self._rc(rc, "gsr_backward", _lib.BWD_STAGES)
         return None if ms is None else dict(zip(_lib.BWD_STAGES, [float(x) for x in ms]))
 
-    # The status block travels to the host through a pinned 16-byte buffer that the host fills with a sentinel first: the copy
-    # has landed when the sentinel is gone (num_pairs and max_list are never negative).  No event object, no blocking call - a
-    # blocking copy / synchronize sleeps and wakes up 30-60 us late, an Event costs ~6 us to create and record.
-    _SENTINEL = -1
-
-    def _pinned_status(self):
-        with self._lock:
-            host = self._pinned.pop() if self._pinned else None
-        if host is None:
-            buf = torch.empty(16, dtype=torch.uint8, pin_memory=True)
-            host = (buf, buf.numpy().view("<i8"), buf.numpy().view("<i4"))  # (tensor, num_pairs view, (.., .., overflow, max_list) view)
-        host[1][0] = self._SENTINEL
-        host[2][3] = self._SENTINEL
-        return host
-
-    def _status_copy(self, binb: Tensor):
-        """Enqueue the 16-byte status block's copy into a pinned buffer behind the forward (torch's current stream)."""
-        host = self._pinned_status()
-        host[0].copy_(binb[:16], non_blocking=True)
-        return host
-
-    @staticmethod
-    def _arrived(host) -> bool:
-        return host[1][0] != HipBackend._SENTINEL and host[2][3] != HipBackend._SENTINEL
-
-    def _take_status(self, host) -> dict:
-        st = {"num_pairs": int(host[1][0]), "overflow": int(host[2][2]), "max_list": int(host[2][3])}
-        with self._lock:
-            self._pinned.append(host)
-        return st
-
-    def _wait_status(self, host, dev=None):
-        """Wait for a status copy: a short poll of the pinned buffer (a blocking call sleeps and wakes up 30-60 us late), bounded -
-        after `spin_us` the wait becomes a device synchronize, which sleeps instead of holding the GIL and REPORTS a device fault
-        or a stream error (the poll alone would spin on the sentinel for ever)."""
-        if self._arrived(host):
-            return
-        deadline = time.perf_counter() + self.spin_us * 1e-6
-        while not self._arrived(host):
-            if time.perf_counter() > deadline:
-                torch.cuda.synchronize(dev)  # raises on a device error
-                if not self._arrived(host):
-                    raise RuntimeError("gsr_forward: the status block's copy did not execute (was the forward issued under "
-                                       "stream capture? pass a `capacity` and do not read the status there)")
-                return
-
     def read_status(self, plan: dict) -> dict:
-        """The status block of the plan's last forward, waited for (bounded poll): the one host sync of the default policy."""
-        host = self._status_copy(plan["bin"])
-        self._wait_status(host, plan["bin"].device)
-        return self._take_status(host)
+        """The status block of the plan's last forward, waited for (bounded poll, then a device synchronize): the one host sync of the
+        default policy.  It changes none of the policy's state (`seen`, `capacity_hint`, `last_status`)."""
+        return self._c.read_status(plan["bin"])
 
     # ---- autograd-facing calls: fresh outputs per call; fresh workspaces too (kept alive for the backward) unless the caller says
     # that nothing will be differentiated.  Implemented by the compiled backend; these are its Python entry points (the tests and the
@@ -556,32 +420,13 @@ class HipBackend:
 
     def setup_views_backward(self, viewbuf: Tensor, d_views: Tensor) -> Tensor:
         """(V, 48) camera records + their gradient -> dL/d extrinsics (V, 4, 4), one launch (gsr_setup_views_backward)."""
-        self._check_device(viewbuf, d_views)
-        v = viewbuf.shape[0]
-        vb, dv = _f32c(viewbuf), _f32c(d_views)
-        out = torch.empty((v, 4, 4), dtype=torch.float32, device=vb.device)
-        with _on_device(vb.device):
-            rc = self.lib.gsr_setup_views_backward(v, _ptr(vb), _ptr(dv), _ptr(out), _stream_ptr(vb.device))
-        if rc != 0:
-            raise RuntimeError(f"gsr_setup_views_backward failed with code {rc}")
-        return out
+        return self._ext.setup_views_backward(viewbuf, d_views)
 
     def setup_views_orthographic(self, extrinsics, width, height, near, far, background, fov_degrees: float):
         """Cameras of the reference's fake orthographic render (cuda_splatting.py:153-181) in one launch
         (gsr_setup_views_orthographic) -> ((V,48) records, dict(extrinsics, fov_x, fov_y, near, far) after the move)."""
-        self._check_device(extrinsics, width, height, near, far, background)
-        v = extrinsics.shape[0]
-        f32 = torch.float32
-        c = lambda t: t.to(f32).contiguous()
-        ext, wd, ht, nr, fr, bg = c(extrinsics), c(width).reshape(v), c(height).reshape(v), c(near).reshape(v), c(far).reshape(v), c(background)
-        out = torch.empty((v, VIEW_FLOATS), dtype=f32, device=ext.device)
-        dump = torch.empty((v, 20), dtype=f32, device=ext.device)
-        stream = _stream_ptr(ext.device)
-        with _on_device(ext.device):
-            rc = self.lib.gsr_setup_views_orthographic(v, _ptr(ext), _ptr(wd), _ptr(ht), _ptr(nr), _ptr(fr), _ptr(bg),
-                                                       3 if bg.dim() == 2 else 0, float(fov_degrees), _ptr(out), _ptr(dump), stream)
-        if rc != 0:
-            raise RuntimeError(f"gsr_setup_views_orthographic failed with code {rc}")
+        out, dump = self._ext.setup_views_orthographic(extrinsics, width, height, near, far, background, float(fov_degrees))
+        v = out.shape[0]
         moved = {"extrinsics": dump[:, :16].reshape(v, 4, 4), "fov_x": dump[0, 16], "fov_y": dump[:, 17], "near": dump[:, 18],
                  "far": dump[:, 19]}
         return out, moved
@@ -591,15 +436,7 @@ class HipBackend:
         return torch.device("cuda", torch.cuda.current_device())
 
     def mark_visible(self, cfg: RasterConfig, viewbuf, means):
-        self._check_device(viewbuf, means)
-        present = torch.empty((cfg.num_sets, cfg.num_gaussians), dtype=torch.uint8, device=means.device)
-        dims = self._dims(cfg, 0)
-        stream = _stream_ptr(means.device)
-        with _on_device(means.device):
-            rc = self.lib.gsr_mark_visible(ctypes.byref(dims), _ptr(viewbuf), _ptr(means), _ptr(present), stream)
-        if rc != 0:
-            raise RuntimeError(f"gsr_mark_visible failed with code {rc}")
-        return present.bool()
+        return self._ext.mark_visible(_cfg_vec(cfg), viewbuf, means).bool()
 
 
 def _cfg_vec(cfg: RasterConfig):

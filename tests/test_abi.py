@@ -233,6 +233,7 @@ def test_compiled_torch_binding_loads_and_carries_the_policy_defaults():
         assert hasattr(ext, name), name
     be = rasterizer.HipBackend()
     assert (be.sync_policy, be.defer_after, be.on_overflow, be.defer_status) == ("sync", 4, "raise", False)
+    assert (be.spin_us, be.headroom_min, be.headroom_max, be.headroom_sigmas) == (300.0, 1.25, 3.0, 4.0)
     assert be.pending == [] and be.seen == {} and be.capacity_hint == {} and be.last_status is None and not be.poisoned
     be.sync_policy, be.defer_after, be.on_overflow = "lazy", 0, "nan"
     assert (be._c.sync_policy, be._c.defer_after, be._c.on_overflow) == ("lazy", 0, "nan")
@@ -240,11 +241,26 @@ def test_compiled_torch_binding_loads_and_carries_the_policy_defaults():
         be.sync_policy = "sometimes"
     with pytest.raises(ValueError):
         be.on_overflow = "ignore"
-    # the capacity arithmetic of the two sides of the binding agrees (C++ policy code vs the ctypes plan API)
+    assert (be.sync_policy, be.on_overflow) == ("lazy", "nan")  # (a rejected value leaves the knob as it was)
+    # the capacity of a status block with the default 1.25 x head-room is the C ABI's arithmetic on the scaled counts
     cfg = rasterizer.RasterConfig(3, 1, 3, 131072, 256, 256, 4, 25, 4, True, 1 << 4)
     st = {"num_pairs": 1645303, "overflow": 0, "max_list": 766}
-    assert be._c.capacity_for(rasterizer._cfg_vec(cfg), st["num_pairs"], st["max_list"], 1.25) == be.capacity_for(cfg, st)
+    lib = _lib.load()
+    dims = be._dims(cfg, 0)
+    assert be.capacity_for(cfg, st) == lib.gsr_capacity_for(ctypes.byref(dims), int(st["num_pairs"] * 1.25) + 4096, int(st["max_list"] * 1.25) + 16)
     # CPU tensors are refused by the compiled path itself
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         be.forward(cfg, torch.zeros(3, 48), torch.zeros(1, 131072, 3), torch.zeros(1, 131072, 6), torch.zeros(1, 131072),
                    torch.zeros(1, 131072, 25, 3), None)
+    for small_op in (lambda: be.mark_visible(cfg, torch.zeros(3, 48), torch.zeros(1, 131072, 3)),
+                     lambda: be.cov_from_scale_rot(torch.ones(4, 3), torch.ones(4, 4), 1.0),
+                     lambda: be.setup_views_backward(torch.zeros(3, 48), torch.zeros(3, 48)),
+                     lambda: be.read_status({"bin": torch.zeros(16, dtype=torch.uint8)})):
+        with pytest.raises(RuntimeError, match="no CPU fallback"):
+            small_op()
+    # the frames of the scale / rotation form are checked before any launch (F = 0 included)
+    for frames in (torch.zeros(1, 3, 3, 3), torch.zeros(1, 0, 3, 3), torch.zeros(2, 1, 3, 3)):
+        with pytest.raises(ValueError, match="frames must be"):
+            ext.frames_arg(rasterizer._cfg_vec(cfg), frames)
+    fr, nf = ext.frames_arg(rasterizer._cfg_vec(cfg), torch.eye(3).expand(1, 2, 3, 3))
+    assert nf == 2 and fr.is_contiguous() and ext.frames_arg(rasterizer._cfg_vec(cfg), None) == (None, 0)

@@ -850,7 +850,9 @@ def test_compiled_backend_status_wait_falls_back_to_a_synchronize_and_forward_un
     for _ in range(3):
         plan["color"].zero_()
         step()
+    seen, last, hint = be.seen, be.last_status, be.capacity_hint
     assert torch.equal(plan["color"], c0) and not be.read_status(plan)["overflow"]
+    assert be.seen == seen and be.last_status == last and be.capacity_hint == hint  # a plan-API read feeds none of the policy's state
 
 
 # ------------------------------------------------------------------ launch-path coverage: every binning variant the host code can pick
