@@ -47,6 +47,22 @@ extern "C" {
 #define GSR_FLAG_SH_PLANAR 0x4  /* colors are (num_sets, N, 3, M) "harmonics" instead of (num_sets, N, M, 3); grads likewise */
 #define GSR_FLAG_COV_3X3 0x8    /* cov6 points at (num_sets, N, 3, 3) symmetric matrices; dL_dcov6 is (num_sets, N, 3, 3) with
                                    the gradient on the upper triangle only (as the reference's triu gather yields) */
+/* Harmonics in their group's frame (the encoder's adapter hands them over unrotated: gaussian_adapter.py:90-92 rotates them by
+ * the source view's camera-to-world rotation F in torch).  GSR_FLAG_SH_IN_FRAME: the harmonics of Gaussian i of set s are in
+ * the coordinates of frames[s, i / (N / F)] (the `frames` of gsr_forward_scale_rot), and the kernels evaluate them at the view
+ * direction d carried into that frame instead of rotating the coefficients.  With B the basis the kernels evaluate and
+ * rotate_sh the rotation of pf3plat_amd/sh_rotation.py, for every rotation F and unit direction d:
+ *   basis "rasterizer" (no second bit):     B(d) . rotate_sh(c, F) = B(F^T d) . c
+ *   basis "e3nn" (GSR_FLAG_SH_FRAME_E3NN):   B(d) . rotate_sh(c, F) = B(G^T d) . c,  G = M F M^T,  M = Z P,
+ *     P: (x, y, z) -> (z, x, y) (e3nn's polar axis is y), Z = diag(-1, -1, 1) (the (-1)^m phase: a half-turn about z).
+ * The image and every gradient are those of the rotated coefficients; dL_dcolors comes back in the frame's coordinates, the
+ * direction's gradient (dL_dmeans, and the camera centre of gsr_backward_ex) in world coordinates.  Frames get no gradient.
+ * Valid only through gsr_forward_scale_rot, gsr_backward_scale_rot and gsr_backward_ex with opt->scale_rot != 0, with
+ * non-NULL frames and sh_coeffs > 0 (GSR_FLAG_SH_FRAME_E3NN only together with GSR_FLAG_SH_IN_FRAME); anything else, and
+ * gsr_workspace_sizes and the other helpers, return GSR_ERR_INVALID_ARGUMENT.  The bits do not change any workspace size:
+ * size with the same dims without them.  At an evaluated degree of 0 they change nothing. */
+#define GSR_FLAG_SH_IN_FRAME 0x40000
+#define GSR_FLAG_SH_FRAME_E3NN 0x80000
 /* GsrDims.flags bits 4-6: built-in extra channel.  0 = blend the caller's `extra` array; otherwise `extra` may be NULL and
  * the kernels blend f(z) of the camera-space depth in un-normalised units, i.e. the image the reference's
  * render_depth_cuda produces in each DepthRenderingMode (cuda_splatting.py:238-251) - in the same pass as the colour.
@@ -84,7 +100,8 @@ extern "C" {
 #define GSR_FLAG_FULL_LISTS 0x20000
 /* Every other bit is rejected (GSR_ERR_INVALID_ARGUMENT). */
 #define GSR_FLAG_VALID_MASK (GSR_FLAG_PREFILTERED | GSR_FLAG_DEBUG | GSR_FLAG_SH_PLANAR | GSR_FLAG_COV_3X3 | 0x70 | \
-                             GSR_FLAG_DETERMINISTIC | GSR_FLAG_WINDOWED_BINNING | GSR_FLAG_BACKWARD_FOLLOWS | GSR_FLAG_FULL_LISTS)
+                             GSR_FLAG_DETERMINISTIC | GSR_FLAG_WINDOWED_BINNING | GSR_FLAG_BACKWARD_FOLLOWS | GSR_FLAG_FULL_LISTS | \
+                             GSR_FLAG_SH_IN_FRAME | GSR_FLAG_SH_FRAME_E3NN)
 #ifdef GSR_ABLATE
 /* Measurement-only build (tools/ablate.py compiles its own copy of the library with -DGSR_ABLATE; the product library does
  * not contain these branches and rejects the bits): switches that make results WRONG on purpose to time a kernel without

@@ -26,6 +26,8 @@ FLAG_COV_3X3 = 0x8
 FLAG_DETERMINISTIC = 0x80  # backward accumulates in 64-bit fixed point: bit-identical from run to run
 FLAG_BACKWARD_FOLLOWS = 0x10000  # forward zero-fills the backward's accumulator rows (inside geom); backward scratch may be None
 FLAG_FULL_LISTS = 0x20000  # test aid: every per-tile list depth-ordered to its end (default: the nearest ~512 entries + what the blend walks)
+FLAG_SH_IN_FRAME = 0x40000  # harmonics in the coordinates of their group's frame (scale / rotation form with frames only)
+FLAG_SH_FRAME_E3NN = 0x80000  # ... in the reference's e3nn convention (only together with FLAG_SH_IN_FRAME)
 FLAG_WINDOWED_BINNING = 0x4000  # test aid: the windowed binning path on an image small enough for the fused one
 
 # (-falign-functions=4096: every kernel starts on a page of its own.  Without it the layout of one kernel's hot loop in the instruction

@@ -10,7 +10,10 @@ kernels.  `AdaptedGaussians.covariances` still yields the matrices (as different
 
 The harmonics are rotated into world space by `pf3plat_amd.sh_rotation.rotate_sh` (the reference uses its e3nn-based
 src/misc/sh_rotation.py at gaussian_adapter.py:90); another callable of that signature, or None for no rotation, can be
-passed to the constructor.
+passed to the constructor.  With `fuse_sh_rotation=True` they are not rotated at all: they stay in the source camera's frame
+(`AdaptedGaussians.sh_frame` names the convention, `sh_basis`) and the raster kernels evaluate them at the view direction
+carried into that frame (GSR_FLAG_SH_IN_FRAME) - the same image and gradients without the rotated copy and the per-Gaussian band
+matrices torch's broadcasting builds.  `AdaptedGaussians.world_harmonics` still yields the rotated coefficients.
 """
 from __future__ import annotations
 
@@ -45,6 +48,18 @@ class AdaptedGaussians:
     harmonics: Tensor  # (b, v, *rest, 3, d_sh)
     opacities: Tensor  # (b, v, *rest)
     frames: Tensor  # (b, v, 3, 3) camera-to-world rotation of every source view (no gradient)
+    # None: `harmonics` are in world space; "e3nn" | "rasterizer": in the source camera's frame, to be rotated by `frames` in that
+    # convention (GaussianAdapter(fuse_sh_rotation=True) - the raster kernels do it on the fly)
+    sh_frame: Optional[str] = None
+
+    @property
+    def world_harmonics(self) -> Tensor:
+        """(b, v, *rest, 3, d_sh) harmonics in world space, rotated with torch ops when they are in their frames (sh_frame): what the
+        default adapter returns as `harmonics`, for callers that read the coefficients themselves (a .ply export, indexing)."""
+        if self.sh_frame is None:
+            return self.harmonics
+        rest = self.opacities.dim() - 2
+        return _rotate_sh(self.harmonics, self.frames[(slice(None), slice(None)) + (None,) * (rest + 1)], basis=self.sh_frame)
 
     @property
     def covariances(self) -> Tensor:
@@ -67,14 +82,23 @@ class AdaptedGaussians:
         flat = lambda t, k: pick(t).reshape(b, -1, *t.shape[t.dim() - k:])
         return Gaussians(means=flat(self.means, 1), covariances=None, harmonics=flat(self.harmonics, 2),
                          opacities=flat(self.opacities, 0), scales=flat(self.scales, 1), rotations=flat(self.rotations, 1),
-                         frames=pick(self.frames))
+                         frames=pick(self.frames), sh_frame=self.sh_frame)
 
 
 class GaussianAdapter(nn.Module):
-    def __init__(self, cfg: GaussianAdapterCfg, rotate_sh: Optional[Callable[[Tensor, Tensor], Tensor]] = _rotate_sh):
+    """fuse_sh_rotation: leave the harmonics in the source camera's frame and let the raster kernels rotate the view direction
+    instead (module docstring); `sh_basis` is then the convention ("e3nn", the reference's, or "rasterizer") and `rotate_sh` is
+    not used."""
+
+    def __init__(self, cfg: GaussianAdapterCfg, rotate_sh: Optional[Callable[[Tensor, Tensor], Tensor]] = _rotate_sh,
+                 fuse_sh_rotation: bool = False, sh_basis: str = "e3nn"):
         super().__init__()
+        if sh_basis not in ("e3nn", "rasterizer"):
+            raise ValueError(f"sh_basis must be 'e3nn' or 'rasterizer', got {sh_basis!r}")
         self.cfg = cfg
         self.rotate_sh = rotate_sh
+        self.fuse_sh_rotation = fuse_sh_rotation
+        self.sh_basis = sh_basis
         # band l of the harmonics starts small (0.1 x 0.25^l): the DC term dominates at initialisation
         band = torch.arange(self.d_sh, dtype=torch.float32).sqrt().floor()
         self.register_buffer("sh_mask", torch.where(band == 0, torch.ones(()), 0.1 * 0.25 ** band), persistent=False)
@@ -119,8 +143,14 @@ class GaussianAdapter(nn.Module):
         ray = F.normalize(ray, dim=-1)
         direction = (extrinsics[..., :3, :3] @ ray.unsqueeze(-1)).squeeze(-1)
         means = extrinsics[..., :3, 3] + direction * depths[..., None]
-        if self.rotate_sh is not None:
+        sh_frame = None
+        if self.fuse_sh_rotation:
+            # rotate_sh's rule (reference sh_rotation.py:20-21): no rotation at all unless every frame is proper - then the
+            # harmonics are left as they are and count as world space (sh_frame None), exactly what the torch rotation returns
+            if torch.allclose(torch.det(c2w), c2w.new_tensor(1)):
+                sh_frame = self.sh_basis
+        elif self.rotate_sh is not None:
             harmonics = self.rotate_sh(harmonics, c2w[..., None, :, :])
         return AdaptedGaussians(means=means.broadcast_to((*full, 3)), scales=scales.broadcast_to((*full, 3)),
                                 rotations=rotations.broadcast_to((*full, 4)), harmonics=harmonics, opacities=opacities,
-                                frames=c2w.reshape(*full[:2], 3, 3))
+                                frames=c2w.reshape(*full[:2], 3, 3), sh_frame=sh_frame)

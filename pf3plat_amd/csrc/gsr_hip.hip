@@ -27,6 +27,7 @@
 #include <stdint.h>
 #include <algorithm>
 #include <atomic>
+#include <type_traits>
 
 #include "../../include/gsr.h"
 
@@ -477,6 +478,44 @@ __device__ __forceinline__ void load_covariance(const Params& p, int set, int i,
   } else {
     load_cov6(p.cov6, gi, (p.d.flags & GSR_FLAG_COV_3X3) != 0, o);
   }
+}
+
+// GSR_FLAG_SH_IN_FRAME: the harmonics of Gaussian i of `set` are in the coordinates of G = F = frames[set, i / (N / F)], or, with
+// GSR_FLAG_SH_FRAME_E3NN, of G = M F M^T (M = Z P, P: (x, y, z) -> (z, x, y), Z = diag(-1, -1, 1)).  Evaluating them at the
+// view direction d' = G^T d is the same as evaluating rotate_sh(harmonics, F, basis) at d.  T receives G^T row by row (T[3k + j]
+// = G[j][k]); the direction gradient goes back to world coordinates as dd = T^T dd'.  M is a signed permutation, so the e3nn
+// form is a re-indexing with signs: G[j][k] = s_j s_k F[pi_j][pi_k], pi = (2, 0, 1), s = (-1, -1, 1).  The lanes of a unit read
+// the same 36 bytes unless a group boundary falls inside the unit (one cache line per load instruction either way).
+__device__ __forceinline__ void load_dir_frame(const Params& p, int set, int i, float (&T)[9]) {
+  const int N = p.d.num_gaussians;
+  const int f = min(i, N - 1) / (N / p.num_frames);
+  const float* F = p.frames + ((size_t)set * p.num_frames + f) * 9;
+  float R[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) R[k] = F[k];
+  if (p.d.flags & GSR_FLAG_SH_FRAME_E3NN) {
+    const int pi[3] = {2, 0, 1};
+    const float s[3] = {-1.f, -1.f, 1.f};
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) T[3 * k + j] = s[j] * s[k] * R[3 * pi[j] + pi[k]];
+  } else {
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) T[3 * k + j] = R[3 * j + k];
+  }
+}
+// d' = T d (the direction in the harmonics' frame); in place
+__device__ __forceinline__ void dir_to_frame(const float (&T)[9], float& x, float& y, float& z) {
+  const float a = T[0] * x + T[1] * y + T[2] * z, b = T[3] * x + T[4] * y + T[5] * z, c = T[6] * x + T[7] * y + T[8] * z;
+  x = a; y = b; z = c;
+}
+// dd = T^T dd' (a gradient w.r.t. the frame's direction back to world coordinates); in place
+__device__ __forceinline__ void grad_to_world(const float (&T)[9], float& x, float& y, float& z) {
+  const float a = T[0] * x + T[3] * y + T[6] * z, b = T[1] * x + T[4] * y + T[7] * z, c = T[2] * x + T[5] * y + T[8] * z;
+  x = a; y = b; z = c;
 }
 
 // Built-in extra channel (GsrDims.flags bits 4-6, GSR_EXTRA_*): the scalar the reference's depth render blends
@@ -953,11 +992,16 @@ constexpr int kColorLdsFloats = 64 * 75;  // a full unit at M = 25 (row stride 7
 // them ahead of the arithmetic instead of three at a time between branches) - same expression tree, same bits.
 // The camera of a view is wave-uniform: its scale and centre are fetched with scalar loads (readfirstlane on the view index), not
 // with a per-lane global load that every unit's evaluation then waits a full memory round trip for, under the colour stream.
-template <bool kJ, bool kFull>
+// kShFrame (GSR_FLAG_SH_IN_FRAME): the harmonics are in the Gaussian's frame - evaluated at the direction carried into it
+// (load_dir_frame); the saved Jacobian (kJ) is carried back to world coordinates here, so the backward's direction chain reads it
+// as it reads the plain one.  The flag-off instances are the code as it was.
+template <bool kJ, bool kFull, bool kShFrame>
 __device__ __forceinline__ void color_eval_lane(const Params& p, int set, int i, const float* sh, int vbegin, int vstep, int vend,
                                                 float rmx, float rmy, float rmz, const CamLite& cam0) {
   const int N = p.d.num_gaussians, Vs = p.d.views_per_set, M = kFull ? 25 : p.d.sh_coeffs;
   const int deg = kFull ? 4 : min(p.d.sh_degree, p.d.max_sh_eval);
+  float T[9];
+  if (kShFrame) load_dir_frame(p, set, i, T);
   // coefficient k of channel c sits at k * ks + c * cs: (3, 1) for (N, M, 3), (1, M) for the planar (N, 3, M) layout.  The
   // common layouts get compile-time strides (one base register + immediate offsets); computed per coefficient at run time
   // the 75 LDS addresses occupied 75 registers.
@@ -971,6 +1015,7 @@ __device__ __forceinline__ void color_eval_lane(const Params& p, int set, int i,
       float dx = mx - cam.cx, dy = my - cam.cy, dz = mz - cam.cz;
       const float len = sqrtf(dx * dx + dy * dy + dz * dz);
       dx = dx / len; dy = dy / len; dz = dz / len;
+      if (kShFrame) dir_to_frame(T, dx, dy, dz);
       float cr = 0, cg = 0, cb = 0;
       float jx[3] = {0, 0, 0}, jy[3] = {0, 0, 0}, jz[3] = {0, 0, 0};
       if (kJ) {  // a backward follows: d rgb / d direction as well, from the coefficients that are in LDS right now
@@ -996,6 +1041,9 @@ __device__ __forceinline__ void color_eval_lane(const Params& p, int set, int i,
       cr += 0.5f; cg += 0.5f; cb += 0.5f;
       const uint32_t clampbits = (cr < 0.f ? 1u : 0u) | (cg < 0.f ? 2u : 0u) | (cb < 0.f ? 4u : 0u);
       if (kJ) {  // rows x, y, z of the Jacobian; the clamp mask rides in the spare slot (the backward then needs nothing else from here)
+        if (kShFrame)
+#pragma unroll
+          for (int c = 0; c < 3; ++c) grad_to_world(T, jx[c], jy[c], jz[c]);
         float4* o = p.shj + ((size_t)v * N + i) * 3;
         o[0] = make_float4(jx[0], jx[1], jx[2], __uint_as_float(clampbits));
         o[1] = make_float4(jy[0], jy[1], jy[2], 0.f); o[2] = make_float4(jz[0], jz[1], jz[2], 0.f);
@@ -1010,17 +1058,18 @@ __device__ __forceinline__ void color_eval_lane(const Params& p, int set, int i,
 }
 // wave-uniform choice of the instance.  kAllowFull: only the colour waves of the binning launch in inference take the compile-time
 // instance - with its loads hoisted it needs ~40 registers more, which the Jacobian variant (twelve accumulators) and the
-// stand-alone k_color (eight workgroups per CU) do not have.
-template <bool kJ, bool kAllowFull>
+// stand-alone k_color (eight workgroups per CU) do not have; nor does the frame's direction transform (kShFrame: 28 bytes of
+// scratch per lane with it).
+template <bool kJ, bool kAllowFull, bool kShFrame>
 __device__ __forceinline__ void color_eval(const Params& p, int set, int i, const float* sh, int vbegin, int vstep, int vend,
                                            float rmx, float rmy, float rmz, const CamLite& cam0) {
-  if (kAllowFull && p.d.sh_coeffs == 25 && min(p.d.sh_degree, p.d.max_sh_eval) == 4) color_eval_lane<kJ, true>(p, set, i, sh, vbegin, vstep, vend, rmx, rmy, rmz, cam0);
-  else color_eval_lane<kJ, false>(p, set, i, sh, vbegin, vstep, vend, rmx, rmy, rmz, cam0);
+  if (kAllowFull && !kShFrame && p.d.sh_coeffs == 25 && min(p.d.sh_degree, p.d.max_sh_eval) == 4) color_eval_lane<kJ, true, kShFrame>(p, set, i, sh, vbegin, vstep, vend, rmx, rmy, rmz, cam0);
+  else color_eval_lane<kJ, false, kShFrame>(p, set, i, sh, vbegin, vstep, vend, rmx, rmy, rmz, cam0);
 }
 
 // `tid` = thread within the group (0 .. kColorThreads - 1), `lds` = the group's 19 200 B; the one barrier inside is the
 // workgroup's, so every group of a workgroup must come here together - a group without a unit passes valid = false.
-template <bool kJ>
+template <bool kJ, bool kShFrame>
 __device__ __forceinline__ void color_unit(const Params& p, uint32_t cu, bool valid, float* lds, int tid) {
   const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
   const int lane = tid & 63, wave = tid >> 6;
@@ -1073,7 +1122,7 @@ __device__ __forceinline__ void color_unit(const Params& p, uint32_t cu, bool va
   const bool dbg = GSR_ABL(p.d.flags, GSR_FLAG_DEBUG_TIMING) && set == 0 && tid == 0;
   if (dbg) dbg_stamps(p, 16384 + unit)[0] = t_start;
   // (the stand-alone colour launch lives on bandwidth at eight workgroups per CU: the compile-time instance buys it nothing)
-  color_eval<kJ, false>(p, set, i, lds + lane * ldstride, wave, kColorThreads / 64, Vs, rmx, rmy, rmz,
+  color_eval<kJ, false, kShFrame>(p, set, i, lds + lane * ldstride, wave, kColorThreads / 64, Vs, rmx, rmy, rmz,
                         cam_lite(p.views, __builtin_amdgcn_readfirstlane(set * Vs + min(wave, Vs - 1))));
   if (dbg) dbg_stamps(p, 16384 + unit)[1] = __builtin_amdgcn_s_memrealtime();
 }
@@ -1081,7 +1130,7 @@ __device__ __forceinline__ void color_unit(const Params& p, uint32_t cu, bool va
 // The same unit of work by ONE wavefront (the colour waves of k_preprocess_bin): the unit's rows come in by LDS-DMA (1 KB per
 // instruction, lane l's 16 bytes land at base + 16 l; nothing passes through registers), the wave waits for them and evaluates
 // every view of the set, lane = Gaussian.  `lds`: this wave's own kColorLdsFloats floats - no barrier, no other wave involved.
-template <bool kJ>
+template <bool kJ, bool kShFrame>
 __device__ __forceinline__ void color_unit_wave(const Params& p, int set, int unit, float* lds, int lane, int vbegin, int vend) {
   const int N = p.d.num_gaussians, Vs = p.d.views_per_set, M = p.d.sh_coeffs;
   const int g0 = unit * 64, i = g0 + lane;
@@ -1125,16 +1174,17 @@ __device__ __forceinline__ void color_unit_wave(const Params& p, int set, int un
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   if (dbg) stamp[2] = __builtin_amdgcn_s_memrealtime();
   __builtin_amdgcn_s_setprio(2);
-  if (in_range) color_eval<kJ, true>(p, set, i, lds + lane * ldstride, vbegin, 1, vend, rmx, rmy, rmz, cam0);
+  if (in_range) color_eval<kJ, true, kShFrame>(p, set, i, lds + lane * ldstride, vbegin, 1, vend, rmx, rmy, rmz, cam0);
   __builtin_amdgcn_s_setprio(0);
   if (dbg) stamp[3] = __builtin_amdgcn_s_memrealtime();
 }
 
 // The colour pass as a launch of its own (independent of the binning; images too large for k_preprocess_bin<true, .>).
-template <bool kJ>  // kJ: a backward was announced and the colours are harmonics - also save d rgb / d direction (Params::shj)
+// kShFrame: GSR_FLAG_SH_IN_FRAME (see color_eval_lane).
+template <bool kJ, bool kShFrame>  // kJ: a backward was announced and the colours are harmonics - also save d rgb / d direction (Params::shj)
 __global__ __launch_bounds__(kColorThreads) void k_color(const Params p) {
   __shared__ __attribute__((aligned(16))) float lds[kColorLdsFloats];
-  color_unit<kJ>(p, blockIdx.x, true, lds, (int)threadIdx.x);
+  color_unit<kJ, kShFrame>(p, blockIdx.x, true, lds, (int)threadIdx.x);
 }
 
 // K1 (images of up to kTileWindow tiles): preprocess AND the whole binning of this workgroup's `chunk` Gaussians.
@@ -1198,7 +1248,8 @@ static bool color_in_bin_by_dims(const GsrDims& d, const Grid& g) {
   return fused_bin && !GSR_ABL(d.flags, GSR_FLAG_ABLATE_NO_SH) && d.views_per_set <= GSR_CIB_MAX_VPS &&
          g.T <= kColorBinMaxTiles && bin_lds_bytes(g.T, true) + 10400u <= 160u * 1024u;  // (+ 10.1 KB static)
 }
-template <bool kColor, bool kJ, int kMaxT = kFusedMaxTiles>
+// kShFrame: the colour waves evaluate harmonics given in their group's frame (GSR_FLAG_SH_IN_FRAME; only with kColor)
+template <bool kColor, bool kJ, int kMaxT = kFusedMaxTiles, bool kShFrame = false>
 __global__ __launch_bounds__(kBinThreads, (!kColor && kMaxT == kBinTwoMaxT) ? 8 : 4) void k_preprocess_bin(const Params p) {
   extern __shared__ float4 dyn_stage[];  // kBinThreads / 64 waves x 4 KB: record transpose, then pair staging; then T counters;
                                          // then (kColor) one 19 200-byte unit buffer per colour wave
@@ -1252,7 +1303,7 @@ __global__ __launch_bounds__(kBinThreads, (!kColor && kMaxT == kBinTwoMaxT) ? 8 
       const int t = vv + Vs * (int)__builtin_amdgcn_readfirstlane((int)k);
       if (t >= ntasks) break;
       const int u = u0 + t / groups, g0v = (t - (t / groups) * groups) * kColorViewGroup;
-      color_unit_wave<kJ>(p, set, u, buf, lane, g0v, min(Vs, g0v + kColorViewGroup));
+      color_unit_wave<kJ, kShFrame>(p, set, u, buf, lane, g0v, min(Vs, g0v + kColorViewGroup));
     }
   };  // (s_setprio 3 for these waves, or for the binning waves: no gain once the binning waves no longer wait for them)
   if (kColor && w >= kWavesA) colour_role(w - kWavesA);
@@ -3353,8 +3404,11 @@ constexpr int kPoseFloats = 35;  // dL/d viewmatrix (16), projmatrix (16), campo
 // kPose: 0 no camera gradient; 1 all of it (35 floats per view); 2 only what the built-in depth channel contributes - the four
 // entries 2, 6, 10, 14 of the view matrix that form z: the ONE camera gradient the reference's own graph carries (its depth render
 // reads extrinsics.inverse() in torch, cuda_splatting.py:239-242; nothing reaches a camera through the rasterizer)
+// kShFrame: GSR_FLAG_SH_IN_FRAME - dL/dsh is evaluated at the direction carried into the Gaussian's frame, and the direction
+// gradient of the recomputing form goes back to world coordinates before the chain into dL/dmeans and dL/dcampos (the saved
+// Jacobian of the kJ form is in world coordinates already: color_eval_lane).  The flag-off instances are the code as it was.
 constexpr int kPoseZFloats = 4;
-template <int kPose, bool kJ>
+template <int kPose, bool kJ, bool kShFrame = false>
 __global__ __launch_bounds__(64) void k_preprocess_bwd(const Params p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int lane = threadIdx.x, set = blockIdx.y;
@@ -3397,6 +3451,7 @@ __global__ __launch_bounds__(64) void k_preprocess_bwd(const Params p) {
     load_covariance(p, set, i, gi, rcov);
     load_row(0, sg_first);
   }
+  float T[9];  // kShFrame: the direction transform of this lane's group, loaded where it is used (L1-resident: the lanes share it)
   if (M > 0 && !kJ) {
     const float* sh_src = p.colors + ((size_t)set * N + g0) * rowf;
     const int sh_total = cnt * rowf, sh_n4 = sh_total >> 2;
@@ -3559,7 +3614,8 @@ __global__ __launch_bounds__(64) void k_preprocess_bwd(const Params p) {
     if (M > 0) {
       const float ox = mx - cam.campos[0], oy = my - cam.campos[1], oz = mz - cam.campos[2];
       const float len = sqrtf(ox * ox + oy * oy + oz * oz);
-      const float x = ox / len, y = oy / len, z = oz / len;
+      float x = ox / len, y = oy / len, z = oz / len;
+      if (kShFrame) { load_dir_frame(p, set, i, T); dir_to_frame(T, x, y, z); }
       const uint32_t cl = bits >> 28;
       const float d0 = (cl & 1u) ? 0.f : sg[6], d1 = (cl & 2u) ? 0.f : sg[7], d2 = (cl & 4u) ? 0.f : sg[8];
       const float* sh = sh_in + lane * ldstride;
@@ -3591,6 +3647,7 @@ __global__ __launch_bounds__(64) void k_preprocess_bwd(const Params p) {
       if (!(p.d.flags & GSR_FLAG_SH_PLANAR)) sh_block([] { return 3; }, [] { return 1; });
       else if (M == 25) sh_block([] { return 1; }, [] { return 25; });
       else sh_block([] { return 1; }, [&] { return M; });
+      if (kShFrame && !kJ) grad_to_world(T, ddx, ddy, ddz);
       const float sum2 = ox * ox + oy * oy + oz * oz;
       const float invsum32 = 1.0f / sqrtf(sum2 * sum2 * sum2);
       const float gdir0 = ((sum2 - ox * ox) * ddx - oy * ox * ddy - oz * ox * ddz) * invsum32;
@@ -3667,6 +3724,7 @@ __global__ __launch_bounds__(64) void k_preprocess_bwd(const Params p) {
     float* dsh = sh_in + lane * ldstride;  // this lane's row: the coefficients are no longer needed
     for (int k = 0; k < rowf; ++k) dsh[k] = 0.f;
     const int deg = min(p.d.sh_degree, p.d.max_sh_eval);
+    if (kShFrame) load_dir_frame(p, set, i, T);
     auto second_walk = [&](auto ks_c, auto cs_c) {
     const int ks = ks_c(), cs = cs_c();
     for (int vv = 0; vv < Vs && in_range; ++vv) {
@@ -3686,7 +3744,9 @@ __global__ __launch_bounds__(64) void k_preprocess_bwd(const Params p) {
       const float d0 = (cl & 1u) ? 0.f : c0, d1 = (cl & 2u) ? 0.f : c1, d2 = (cl & 4u) ? 0.f : c2;
       const float ox = rmx * cam.scale - cam.campos[0], oy = rmy * cam.scale - cam.campos[1], oz = rmz * cam.scale - cam.campos[2];
       const float len = sqrtf(ox * ox + oy * oy + oz * oz);
-      sh_visit(deg, ox / len, oy / len, oz / len, [&](int k, float bk, float, float, float) {
+      float x = ox / len, y = oy / len, z = oz / len;
+      if (kShFrame) dir_to_frame(T, x, y, z);
+      sh_visit(deg, x, y, z, [&](int k, float bk, float, float, float) {
         if (k < M) { dsh[k * ks + 0 * cs] += bk * d0; dsh[k * ks + 1 * cs] += bk * d1; dsh[k * ks + 2 * cs] += bk * d2; }
       });
     }
@@ -3982,8 +4042,10 @@ __global__ __launch_bounds__(256) void k_mark_visible(const Params p, uint8_t* p
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-static bool dims_ok(const GsrDims* d) {
+// sh_frame_ok: the GSR_FLAG_SH_IN_FRAME bits may be set (only the launches of the scale / rotation form take them: sh_frame_args_ok)
+static bool dims_ok(const GsrDims* d, bool sh_frame_ok = false) {
   if (!d || d->abi_version != GSR_ABI_VERSION) return false;
+  if (!sh_frame_ok && (d->flags & (GSR_FLAG_SH_IN_FRAME | GSR_FLAG_SH_FRAME_E3NN))) return false;
   if (d->num_views < 0 || d->num_sets < 0 || d->views_per_set < 0 || d->num_gaussians < 0) return false;
   if ((int64_t)d->num_sets * d->views_per_set != d->num_views) return false;
   if (d->height <= 0 || d->width <= 0 || d->height > 32768 || d->width > 32768) return false;
@@ -4147,7 +4209,11 @@ static int ensure_bin_attributes(int* dev_out) {
   GSR_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_preprocess_bin<false, false, kBinTwoMaxT>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)bin_lds_bytes(kBinTwoMaxT, false)));
   const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(k_preprocess_bin<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, with_color) == hipSuccess &&
-                  hipFuncSetAttribute(reinterpret_cast<const void*>(k_preprocess_bin<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, with_color) == hipSuccess;
+                  hipFuncSetAttribute(reinterpret_cast<const void*>(k_preprocess_bin<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, with_color) == hipSuccess &&
+                  hipFuncSetAttribute(reinterpret_cast<const void*>(k_preprocess_bin<true, false, kFusedMaxTiles, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      with_color) == hipSuccess &&
+                  hipFuncSetAttribute(reinterpret_cast<const void*>(k_preprocess_bin<true, true, kFusedMaxTiles, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      with_color) == hipSuccess;
   if (ok) g_color_bin_ok.fetch_or(bit, std::memory_order_relaxed);
   else (void)hipGetLastError();
   g_lds_set.fetch_or(bit, std::memory_order_release);
@@ -4164,10 +4230,13 @@ int gsr_colour_in_binning(const GsrDims* dims) {
   return color_in_bin_for(*dims, make_grid(dims->width, dims->height), dev) ? 1 : 0;
 }
 
+static size_t scratch_bytes_of(const GsrDims& d) {
+  const size_t rows = (size_t)d.num_views * (size_t)d.num_gaussians;
+  return rows * GSR_SCREEN_GRAD_FLOATS * ((d.flags & GSR_FLAG_DETERMINISTIC) ? sizeof(long long) : sizeof(float));
+}
 size_t gsr_backward_scratch_bytes(const GsrDims* dims) {
   if (!dims_ok(dims)) return 0;
-  const size_t rows = (size_t)dims->num_views * (size_t)dims->num_gaussians;
-  return rows * GSR_SCREEN_GRAD_FLOATS * ((dims->flags & GSR_FLAG_DETERMINISTIC) ? sizeof(long long) : sizeof(float));
+  return scratch_bytes_of(*dims);
 }
 
 int gsr_workspace_sizes(const GsrDims* dims, size_t* geom_bytes, size_t* bin_bytes, size_t* img_bytes) {
@@ -4222,12 +4291,20 @@ static bool sr_ok(const GsrDims* d, const SrArgs* sr) {
   if (!sr->frames) return sr->num_frames == 0;
   return sr->num_frames > 0 && d->num_gaussians % sr->num_frames == 0;
 }
+// the call shape of the launches: GSR_FLAG_SH_IN_FRAME needs the scale / rotation form with frames and harmonics; the e3nn bit
+// goes with it
+static bool call_dims_ok(const GsrDims* d, const SrArgs* sr) {
+  if (!d) return false;
+  const int fl = d->flags & (GSR_FLAG_SH_IN_FRAME | GSR_FLAG_SH_FRAME_E3NN);
+  if (fl && (!(fl & GSR_FLAG_SH_IN_FRAME) || !sr || !sr->frames || d->sh_coeffs <= 0)) return false;
+  return dims_ok(d, true) && sr_ok(d, sr);
+}
 
 static int forward_impl(const GsrDims* dims, const GsrView* views, const float* means, const float* cov6,
                         const float* opacities, const float* colors, const float* extra, float* out_color,
                         float* out_extra, int32_t* radii, void* geom, void* bin, void* img, hipStream_t st,
                         hipEvent_t* ev, const SrArgs* sr = nullptr) {
-  if (!dims_ok(dims) || !sr_ok(dims, sr)) return GSR_ERR_INVALID_ARGUMENT;
+  if (!call_dims_ok(dims, sr)) return GSR_ERR_INVALID_ARGUMENT;
   const GsrDims& d = *dims;
   const size_t V = d.num_views, N = d.num_gaussians, HW = (size_t)d.height * d.width;
   if (V == 0) return GSR_OK;
@@ -4276,10 +4353,14 @@ static int forward_impl(const GsrDims* dims, const GsrView* views, const float* 
     if (rc != GSR_OK) return rc;
   }
   const bool color_in_bin = color_blocks && color_in_bin_for(d, p.g, dev);
+  // harmonics in their group's frame (GSR_FLAG_SH_IN_FRAME): the colour passes' own instances
+  const bool sh_frame = (d.flags & GSR_FLAG_SH_IN_FRAME) && d.sh_coeffs > 0;
   GSR_MARK();
   if (color_blocks && !color_in_bin) {
-    if (p.shj) hipLaunchKernelGGL(k_color<true>, dim3(color_blocks), dim3(kColorThreads), 0, st, p);
-    else hipLaunchKernelGGL(k_color<false>, dim3(color_blocks), dim3(kColorThreads), 0, st, p);
+    if (sh_frame && p.shj) hipLaunchKernelGGL((k_color<true, true>), dim3(color_blocks), dim3(kColorThreads), 0, st, p);
+    else if (sh_frame) hipLaunchKernelGGL((k_color<false, true>), dim3(color_blocks), dim3(kColorThreads), 0, st, p);
+    else if (p.shj) hipLaunchKernelGGL((k_color<true, false>), dim3(color_blocks), dim3(kColorThreads), 0, st, p);
+    else hipLaunchKernelGGL((k_color<false, false>), dim3(color_blocks), dim3(kColorThreads), 0, st, p);
   }
   GSR_STAGE_DONE(0);
   GSR_MARK();
@@ -4290,6 +4371,8 @@ static int forward_impl(const GsrDims* dims, const GsrView* views, const float* 
     const bool two_per_cu = bin_two_per_cu(p.g, color_in_bin);
     if (two_per_cu) hipLaunchKernelGGL((k_preprocess_bin<false, false, kBinTwoMaxT>), bgrid, dim3(kBinThreads), shmem, st, p);
     else if (!color_in_bin) hipLaunchKernelGGL((k_preprocess_bin<false, false>), bgrid, dim3(kBinThreads), shmem, st, p);
+    else if (sh_frame && p.shj) hipLaunchKernelGGL((k_preprocess_bin<true, true, kFusedMaxTiles, true>), bgrid, dim3(kBinThreads), shmem, st, p);
+    else if (sh_frame) hipLaunchKernelGGL((k_preprocess_bin<true, false, kFusedMaxTiles, true>), bgrid, dim3(kBinThreads), shmem, st, p);
     else if (p.shj) hipLaunchKernelGGL((k_preprocess_bin<true, true>), bgrid, dim3(kBinThreads), shmem, st, p);
     else hipLaunchKernelGGL((k_preprocess_bin<true, false>), bgrid, dim3(kBinThreads), shmem, st, p);
   } else {
@@ -4389,7 +4472,7 @@ static int backward_impl(const GsrDims* dims, const GsrView* views, const float*
                          void* scratch, float* dL_dmeans, float* dL_dcov6, float* dL_dopacities,
                          float* dL_dcolors, float* dL_dextra, float* dL_dmeans2D, void* stream_, const SrArgs* sr,
                          float* dL_dviews = nullptr, float* pose_partials = nullptr, int depth_term_only = 0) {
-  if (!dims_ok(dims) || !sr_ok(dims, sr)) return GSR_ERR_INVALID_ARGUMENT;
+  if (!call_dims_ok(dims, sr)) return GSR_ERR_INVALID_ARGUMENT;
   hipStream_t st = static_cast<hipStream_t>(stream_);
   const GsrDims& d = *dims;
   const size_t V = d.num_views, N = d.num_gaussians;
@@ -4418,7 +4501,7 @@ static int backward_impl(const GsrDims* dims, const GsrView* views, const float*
   } while (0)
   if (ev) GSR_CHECK(hipEventRecord(ev[e++], st));
   const bool det = (d.flags & GSR_FLAG_DETERMINISTIC) != 0;
-  if (!own_rows) GSR_CHECK(hipMemsetAsync(scratch, 0, gsr_backward_scratch_bytes(dims), st));
+  if (!own_rows) GSR_CHECK(hipMemsetAsync(scratch, 0, scratch_bytes_of(d), st));
   const dim3 bgrid((unsigned)p.g.T, (unsigned)V);
   if (p.dL_dextra_img) {
     if (det) hipLaunchKernelGGL((k_blend_bwd<true, true>), bgrid, dim3(kBwdThreads), 0, st, p);
@@ -4432,17 +4515,23 @@ static int backward_impl(const GsrDims* dims, const GsrView* views, const float*
   const int rowf = 3 * d.sh_coeffs, ldstride = rowf | 1;
   const size_t shmem = d.sh_coeffs > 0 ? (size_t)64 * ldstride * sizeof(float) : 0;
   const dim3 pgrid((unsigned)((N + 63) / 64), (unsigned)d.num_sets);
+  const bool sh_frame = (d.flags & GSR_FLAG_SH_IN_FRAME) && d.sh_coeffs > 0;
+  auto launch_pbwd = [&](auto pose_c) {  // the instance of the call: camera gradient, saved Jacobian, harmonics in their frame
+    constexpr int kP = decltype(pose_c)::value;
+    if (sh_frame && p.shj) hipLaunchKernelGGL((k_preprocess_bwd<kP, true, true>), pgrid, dim3(64), shmem, st, p);
+    else if (sh_frame) hipLaunchKernelGGL((k_preprocess_bwd<kP, false, true>), pgrid, dim3(64), shmem, st, p);
+    else if (p.shj) hipLaunchKernelGGL((k_preprocess_bwd<kP, true>), pgrid, dim3(64), shmem, st, p);
+    else hipLaunchKernelGGL((k_preprocess_bwd<kP, false>), pgrid, dim3(64), shmem, st, p);
+  };
   if (dL_dviews && depth_term_only) {
     if (!pose_partials) return GSR_ERR_INVALID_ARGUMENT;
     p.pose_partials = pose_partials;
     const int emode = (d.flags >> 4) & 7;
     if (!d.has_extra || emode == 0) {  // no built-in depth channel: nothing of this call reads the camera's z row
       GSR_CHECK(hipMemsetAsync(dL_dviews, 0, V * sizeof(GsrView), st));
-      if (p.shj) hipLaunchKernelGGL((k_preprocess_bwd<0, true>), pgrid, dim3(64), shmem, st, p);
-      else hipLaunchKernelGGL((k_preprocess_bwd<0, false>), pgrid, dim3(64), shmem, st, p);
+      launch_pbwd(std::integral_constant<int, 0>{});
     } else {
-      if (p.shj) hipLaunchKernelGGL((k_preprocess_bwd<2, true>), pgrid, dim3(64), shmem, st, p);
-      else hipLaunchKernelGGL((k_preprocess_bwd<2, false>), pgrid, dim3(64), shmem, st, p);
+      launch_pbwd(std::integral_constant<int, 2>{});
       // one 16-byte row per (view, 64-Gaussian unit): up to 16 384 rows per view are summed by one block per view in one launch
       const int rows1 = (int)pgrid.x, blocks1 = rows1 <= 16384 ? 1 : 64;
       float* level1 = pose_partials + (size_t)V * rows1 * kPoseZFloats;  // behind the rows of the first level
@@ -4456,15 +4545,13 @@ static int backward_impl(const GsrDims* dims, const GsrView* views, const float*
   } else if (dL_dviews) {
     if (!pose_partials) return GSR_ERR_INVALID_ARGUMENT;
     p.pose_partials = pose_partials;
-    if (p.shj) hipLaunchKernelGGL((k_preprocess_bwd<1, true>), pgrid, dim3(64), shmem, st, p);
-    else hipLaunchKernelGGL((k_preprocess_bwd<1, false>), pgrid, dim3(64), shmem, st, p);
+    launch_pbwd(std::integral_constant<int, 1>{});
     const int rows1 = (int)pgrid.x * 4;
     float* level1 = pose_partials + (size_t)V * rows1 * kPoseFloats;  // behind the rows of the first level
     hipLaunchKernelGGL(k_pose_reduce, dim3((unsigned)V, kPoseBlocks), dim3(256), 0, st, pose_partials, rows1, level1, kPoseFloats, kPoseBlocks);
     hipLaunchKernelGGL(k_pose_reduce, dim3((unsigned)V, 1), dim3(256), 0, st, level1, kPoseBlocks, dL_dviews, 48, 1);
   } else {
-    if (p.shj) hipLaunchKernelGGL((k_preprocess_bwd<0, true>), pgrid, dim3(64), shmem, st, p);
-    else hipLaunchKernelGGL((k_preprocess_bwd<0, false>), pgrid, dim3(64), shmem, st, p);
+    launch_pbwd(std::integral_constant<int, 0>{});
   }
   GSR_STAGE_DONE(1);
 #undef GSR_STAGE_DONE

@@ -125,13 +125,20 @@ struct Cfg {
   int has_extra = 0, flags = 0, scale_rot = 0;
   auto tie() const { return std::tie(num_views, num_sets, views_per_set, num_gaussians, height, width, sh_degree, sh_coeffs, max_sh_eval, has_extra, flags, scale_rot); }
   bool operator<(const Cfg& o) const { return tie() < o.tie(); }
+  // the dims of the sizing helpers: without the GSR_FLAG_SH_IN_FRAME bits, which only the launches take (they size nothing)
   GsrDims dims(int64_t capacity) const {
+    GsrDims d = launch_dims(capacity);
+    d.flags &= ~kShFrameBits;
+    return d;
+  }
+  GsrDims launch_dims(int64_t capacity) const {
     GsrDims d;
     d.abi_version = GSR_ABI_VERSION; d.num_views = num_views; d.num_sets = num_sets; d.views_per_set = views_per_set;
     d.num_gaussians = num_gaussians; d.height = height; d.width = width; d.sh_degree = sh_degree; d.sh_coeffs = sh_coeffs;
     d.max_sh_eval = max_sh_eval; d.has_extra = has_extra; d.flags = flags; d.pair_capacity = capacity;
     return d;
   }
+  static constexpr int kShFrameBits = GSR_FLAG_SH_IN_FRAME | GSR_FLAG_SH_FRAME_E3NN;
   int extra_mode() const { return (flags >> 4) & 7; }
 };
 Cfg cfg_from(const std::vector<int64_t>& v) {
@@ -431,7 +438,9 @@ class Backend : public std::enable_shared_from_this<Backend> {
       const GsrView* vb = reinterpret_cast<const GsrView*>(viewbuf.data_ptr<float>());
       if (want_views) {
         Tensor fr = cfg.scale_rot ? frames_arg(cfg, frames) : Tensor();
-        Tensor partials = at::empty({(int64_t)std::max<size_t>(16, g_abi.pose_partials_bytes(&saved.dims))}, f32.dtype(at::kByte));
+        GsrDims sizing_dims = saved.dims;  // (the helpers take no GSR_FLAG_SH_IN_FRAME bits; they change no size)
+        sizing_dims.flags &= ~Cfg::kShFrameBits;
+        Tensor partials = at::empty({(int64_t)std::max<size_t>(16, g_abi.pose_partials_bytes(&sizing_dims))}, f32.dtype(at::kByte));
         GsrBackwardOptions opt;
         opt.frames = fptr(fr); opt.num_frames = fr.defined() ? (int)fr.size(1) : 0; opt.scale_rot = cfg.scale_rot;
         opt.dL_dviews = d_views.data_ptr<float>(); opt.pose_partials = reinterpret_cast<float*>(partials.data_ptr()); opt.depth_term_only = want_views == 2;
@@ -488,7 +497,7 @@ class Backend : public std::enable_shared_from_this<Backend> {
   Plan make_plan(const Cfg& cfg, const at::Device& dev, int64_t capacity, bool reuse, bool one_view = false) {
     const Sizes sz = sized(cfg, capacity);
     Plan p;
-    p.dims = cfg.dims(capacity);
+    p.dims = cfg.launch_dims(capacity);
     const auto u8 = at::TensorOptions().dtype(at::kByte).device(dev);
     const auto f32 = u8.dtype(at::kFloat);
     Tensor whole;
@@ -898,7 +907,7 @@ struct Prepared {
 Prepared prepare_call(const Tensor& means_in, const Tensor& cov_in, const Tensor& opac_in, const Tensor& colors_in, const Tensor& viewbuf_in, int64_t h, int64_t w,
                       int64_t sh_degree, bool use_sh, int64_t views_per_set, const c10::optional<Tensor>& extra_in, const c10::optional<Tensor>& means2d,
                       int64_t max_sh_eval, bool sh_planar, bool cov_3x3, int64_t extra_mode, bool debug, bool prefiltered, int64_t deterministic, bool scale_rot,
-                      const c10::optional<Tensor>& frames_in, int64_t camera_gradient) {
+                      const c10::optional<Tensor>& frames_in, int64_t camera_gradient, int64_t sh_frame /* 0 none, 1 "rasterizer", 2 "e3nn" */) {
   Prepared p;
   const int64_t s = means_in.size(0), n = means_in.size(1), v = viewbuf_in.size(0);
   if (v != s * views_per_set) throw pybind11::value_error(std::to_string(v) + " views != " + std::to_string(s) + " sets x " + std::to_string(views_per_set) + " views per set");
@@ -930,6 +939,12 @@ Prepared prepare_call(const Tensor& means_in, const Tensor& cov_in, const Tensor
   }
   const bool has_extra = p.extra.has_value() || extra_mode != 0;
   if (camera_gradient != 1 && camera_gradient != 2) throw pybind11::value_error("camera_gradient must be 'full' or 'depth'");
+  if (sh_frame < 0 || sh_frame > 2) throw pybind11::value_error("sh_frame must be None, 'rasterizer' or 'e3nn'");
+  if (sh_frame) {  // harmonics in the frames' coordinates (GSR_FLAG_SH_IN_FRAME): the frames of the scale / rotation form
+    if (!scale_rot || !p.frames.has_value()) throw pybind11::value_error("sh_frame needs scale_rot=True and `frames`");
+    if (!use_sh) throw pybind11::value_error("sh_frame needs use_sh=True (harmonics)");
+    flags |= GSR_FLAG_SH_IN_FRAME | (sh_frame == 2 ? GSR_FLAG_SH_FRAME_E3NN : 0);
+  }
   p.cfgv = {v, s, views_per_set, n, h, w, sh_degree, m, max_sh_eval, has_extra ? 1 : 0, flags, scale_rot ? 1 : 0};
   p.viewbuf = f32c(viewbuf_in);
   return p;
@@ -939,12 +954,13 @@ Prepared prepare_call(const Tensor& means_in, const Tensor& cov_in, const Tensor
 pybind11::tuple rasterize_views(PyBackend& pb, const Tensor& means_in, const Tensor& cov_in, const Tensor& opac_in, const Tensor& colors_in, const Tensor& viewbuf_in,
                                 int64_t h, int64_t w, int64_t sh_degree, bool use_sh, int64_t views_per_set, const c10::optional<Tensor>& extra_in,
                                 const c10::optional<Tensor>& means2d, int64_t max_sh_eval, bool sh_planar, bool cov_3x3, int64_t extra_mode, bool debug,
-                                bool prefiltered, int64_t deterministic, bool scale_rot, const c10::optional<Tensor>& frames_in, int64_t camera_gradient) {
+                                bool prefiltered, int64_t deterministic, bool scale_rot, const c10::optional<Tensor>& frames_in, int64_t camera_gradient,
+                                int64_t sh_frame) {
   RasterOut result;
   {
   pybind11::gil_scoped_release nogil;
   const Prepared p = prepare_call(means_in, cov_in, opac_in, colors_in, viewbuf_in, h, w, sh_degree, use_sh, views_per_set, extra_in, means2d, max_sh_eval, sh_planar,
-                                  cov_3x3, extra_mode, debug, prefiltered, deterministic, scale_rot, frames_in, camera_gradient);
+                                  cov_3x3, extra_mode, debug, prefiltered, deterministic, scale_rot, frames_in, camera_gradient, sh_frame);
   result = rasterize_impl(pb, p.means, p.cov, p.opac, p.colors, p.extra, means2d, p.viewbuf, p.cfgv, p.frames, camera_gradient);
   }
   return raster_tuple(result);
@@ -1081,9 +1097,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("prepare_call", [](const Tensor& means, const Tensor& cov, const Tensor& opac, const Tensor& colors, const Tensor& viewbuf, int64_t h, int64_t w, int64_t sh_degree,
                            bool use_sh, int64_t views_per_set, const c10::optional<Tensor>& extra, const c10::optional<Tensor>& means2d, int64_t max_sh_eval,
                            bool sh_planar, bool cov_3x3, int64_t extra_mode, bool debug, bool prefiltered, int64_t deterministic, bool scale_rot,
-                           const c10::optional<Tensor>& frames, int64_t camera_gradient) {
+                           const c10::optional<Tensor>& frames, int64_t camera_gradient, int64_t sh_frame) {
     const Prepared p = prepare_call(means, cov, opac, colors, viewbuf, h, w, sh_degree, use_sh, views_per_set, extra, means2d, max_sh_eval, sh_planar, cov_3x3,
-                                    extra_mode, debug, prefiltered, deterministic, scale_rot, frames, camera_gradient);
+                                    extra_mode, debug, prefiltered, deterministic, scale_rot, frames, camera_gradient, sh_frame);
     pybind11::object e = p.extra.has_value() ? pybind11::cast(*p.extra) : pybind11::none();
     pybind11::object f = p.frames.has_value() ? pybind11::cast(*p.frames) : pybind11::none();
     return pybind11::make_tuple(p.cfgv, p.means, p.cov, p.opac, p.colors, e, f, p.viewbuf);

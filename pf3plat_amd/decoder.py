@@ -78,7 +78,7 @@ class DecoderSplattingCUDA(Decoder):
             self.background_color.to(extrinsics.device),
             gaussians.means, gaussians.covariances, gaussians.harmonics, gaussians.opacities,
             depth_mode=depth_mode, gaussian_scales=gaussians.scales, gaussian_rotations=gaussians.rotations, frames=gaussians.frames,
-            pose_gradients=pose_gradients,
+            pose_gradients=pose_gradients, sh_frame=gaussians.sh_frame,
         )
         return DecoderOutput(color, depth)
 

@@ -23,6 +23,7 @@ from . import _lib
 
 VIEW_FLOATS = 48  # sizeof(GsrView) / 4
 EXTRA_MODES = {"depth": 1, "disparity": 2, "relative_disparity": 3, "log": 4}  # GSR_EXTRA_* (include/gsr.h)
+SH_FRAMES = {None: 0, "rasterizer": 1, "e3nn": 2}  # rasterize_views(sh_frame=...): GSR_FLAG_SH_IN_FRAME (| GSR_FLAG_SH_FRAME_E3NN)
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -125,6 +126,7 @@ class HipBackend:
     """Calls libgsr_hip.so with raw device pointers on torch's current HIP stream."""
 
     name = "hip"
+    sh_frame = True  # the kernels evaluate harmonics given in their group's frame (rasterize_views(sh_frame=...))
 
     def __init__(self):
         # The compiled binding (csrc/gsr_torch.cpp, built by __graft_entry__.build()) is the only place that allocates workspaces, sizes
@@ -510,12 +512,24 @@ class _RasterizeViews(torch.autograd.Function):
         return d_means, d_cov6, d_opac, d_colors, d_extra, d_means2d, d_views, None, None, None
 
 
+def _rotate_in_frames(colors: Tensor, frames: Tensor, planar: bool, basis: str) -> Tensor:
+    """Harmonics (S, N, 3, M) (planar) or (S, N, M, 3) in the coordinates of frames (S, F, 3, 3) -> world space, with torch ops
+    (`sh_rotation.rotate_sh`; the frames broadcast over their N / F Gaussians, nothing is expanded to one matrix per Gaussian)."""
+    from .sh_rotation import rotate_sh
+
+    s, n = colors.shape[:2]
+    f = frames.shape[1]
+    sh = colors if planar else colors.transpose(-1, -2)
+    out = rotate_sh(sh.reshape(s, f, n // f, *sh.shape[2:]), frames[:, :, None, None], basis=basis).reshape(sh.shape)
+    return out if planar else out.transpose(-1, -2).contiguous()
+
+
 def rasterize_views(means: Tensor, cov6: Tensor, opacities: Tensor, colors: Tensor, viewbuf: Tensor, *,
                     image_shape, sh_degree: int, use_sh: bool, views_per_set: int, extra: Optional[Tensor] = None,
                     means2d: Optional[Tensor] = None, max_sh_eval: int = 4, sh_planar: bool = False, cov_3x3: bool = False,
                     extra_mode: Optional[str] = None, debug: bool = False, prefiltered: bool = False,
                     deterministic: Optional[bool] = None, scale_rot: bool = False, frames: Optional[Tensor] = None,
-                    camera_gradient: str = "full"):
+                    camera_gradient: str = "full", sh_frame: Optional[str] = None):
     """Render V = num_sets * views_per_set views in one launch chain.
 
     means (S,N,3); cov6 (S,N,6) or, with cov_3x3, the full symmetric (S,N,3,3); opacities (S,N); colors (S,N,M,3) or, with
@@ -531,12 +545,20 @@ def rasterize_views(means: Tensor, cov6: Tensor, opacities: Tensor, colors: Tens
     camera_gradient (only matters when `viewbuf` requires grad, i.e. comes from `views_from_cameras(pose_gradients=True)`): "full" -
     every place the forward reads a camera (an extension); "depth" - only the built-in depth channel's term, which
     is what the reference's own graph sends to `extrinsics` (cuda_splatting.py:239-242).
+    sh_frame: "rasterizer" or "e3nn" - the harmonics of each group are in the coordinates of its frame (what the encoder's adapter
+    produces before its SH rotation, reference gaussian_adapter.py:90-92); the image and every gradient are those of
+    `sh_rotation.rotate_sh(harmonics, frame, basis=sh_frame)` rendered as usual, but the kernels evaluate the unrotated coefficients
+    at the view direction carried into the frame (GSR_FLAG_SH_IN_FRAME) - no rotated copy exists.  Needs scale_rot, `frames` (proper
+    rotations) and use_sh.  A backend without the capability gets the coefficients rotated in torch.
     debug: upstream's `settings.debug` - the library synchronises and checks for errors after every stage and names the
     stage that failed.  deterministic: the backward accumulates per-Gaussian gradients in 64-bit fixed point (bit-identical
     from run to run); None = follow `torch.are_deterministic_algorithms_enabled()`.
     """
     backend = get_backend()
-    if isinstance(backend, HipBackend):
+    if sh_frame not in SH_FRAMES:
+        raise ValueError(f"sh_frame must be None, 'rasterizer' or 'e3nn', got {sh_frame!r}")
+    sh_code = SH_FRAMES[sh_frame]
+    if isinstance(backend, HipBackend) and (not sh_code or getattr(backend, "sh_frame", False)):
         # the product path, one crossing: checks, normalisation, call shape, flags and the compiled autograd function
         # (csrc/gsr_torch.cpp::rasterize_views / RasterizeFn; a plain call when nothing can be differentiated)
         if camera_gradient not in ("full", "depth"):
@@ -545,7 +567,7 @@ def rasterize_views(means: Tensor, cov6: Tensor, opacities: Tensor, colors: Tens
             backend._c, means, cov6, opacities, colors, viewbuf, int(image_shape[0]), int(image_shape[1]), int(sh_degree), bool(use_sh),
             int(views_per_set), extra, means2d, int(max_sh_eval), bool(sh_planar), bool(cov_3x3), EXTRA_MODES[extra_mode] if extra_mode is not None else 0,
             bool(debug), bool(prefiltered), -1 if deterministic is None else int(bool(deterministic)), bool(scale_rot), frames,
-            2 if camera_gradient == "depth" else 1)
+            2 if camera_gradient == "depth" else 1, sh_code)
     # any other backend object (tests slide the CPU oracle under the host wrappers): the SAME statement of the call shape - the
     # compiled `prepare_call` (csrc/gsr_torch.cpp: checks, normalisation, flags; it touches no device) - then that backend's forward
     if camera_gradient not in ("full", "depth"):
@@ -554,7 +576,10 @@ def rasterize_views(means: Tensor, cov6: Tensor, opacities: Tensor, colors: Tens
         means, cov6, opacities, colors, viewbuf, int(image_shape[0]), int(image_shape[1]), int(sh_degree), bool(use_sh), int(views_per_set),
         extra, means2d, int(max_sh_eval), bool(sh_planar), bool(cov_3x3), EXTRA_MODES[extra_mode] if extra_mode is not None else 0,
         bool(debug), bool(prefiltered), -1 if deterministic is None else int(bool(deterministic)), bool(scale_rot), frames,
-        2 if camera_gradient == "depth" else 1)
+        2 if camera_gradient == "depth" else 1, sh_code)
+    if sh_code and not getattr(backend, "sh_frame", False):  # (checked above) the coefficients rotated in torch, rendered as usual
+        cfgv[10] &= ~(_lib.FLAG_SH_IN_FRAME | _lib.FLAG_SH_FRAME_E3NN)
+        colors = _rotate_in_frames(colors, frames, bool(sh_planar), sh_frame)
     cfg = RasterConfig(*cfgv[:9], bool(cfgv[9]), int(cfgv[10]), bool(cfgv[11]))
     flags, has_extra = cfg.flags, cfg.has_extra
     if not (flags & _lib.FLAG_BACKWARD_FOLLOWS):  # nothing here can be differentiated: no autograd node, no saved workspaces

@@ -159,5 +159,19 @@ def rotate_sh(sh_coefficients: Tensor, rotations: Tensor, basis: str | None = No
     return torch.cat(out, dim=-1)
 
 
+def direction_frame(rotations: Tensor, basis: str = "e3nn") -> Tensor:
+    """(..., 3, 3) -> (..., 3, 3) G such that evaluating coefficients c at the direction G^T d equals evaluating
+    rotate_sh(c, R, basis) at d, for every unit direction d:  B(d) . rotate_sh(c, R, basis) = B(G^T d) . c.  "rasterizer": G = R;
+    "e3nn": G = M R M^T with M = Z P (P as in e3nn_band_rotations, Z = diag(-1, -1, 1): the (-1)^m phase is the representation of
+    a half-turn about z).  This is the transform the raster kernels apply to the view direction of harmonics given in their
+    frame (GSR_FLAG_SH_IN_FRAME, rasterize_views(sh_frame=...))."""
+    if basis == "rasterizer":
+        return rotations
+    if basis != "e3nn":
+        raise ValueError(f"basis must be 'e3nn' or 'rasterizer', got {basis!r}")
+    m = torch.tensor(((0.0, 0.0, -1.0), (-1.0, 0.0, 0.0), (0.0, 1.0, 0.0)), dtype=rotations.dtype, device=rotations.device)
+    return m @ rotations @ m.T
+
+
 def rotate_sh_rasterizer_basis(sh_coefficients: Tensor, rotations: Tensor) -> Tensor:
     return rotate_sh(sh_coefficients, rotations, basis="rasterizer")

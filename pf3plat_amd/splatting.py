@@ -185,6 +185,7 @@ def render_views(
     gaussian_rotations: Optional[Tensor] = None,  # (scene, gaussian, 4) } the covariance is built inside the kernels
     frames: Optional[Tensor] = None,  # (scene, F, 3, 3) world rotation per group of gaussian / F consecutive Gaussians
     pose_gradients: bool = False,  # opt-in: the render's gradient reaches `extrinsics` (the reference's does not)
+    sh_frame: Optional[str] = None,  # "e3nn" | "rasterizer": the harmonics are in the coordinates of `frames` (rasterize_views)
 ):
     """Fused decoder path: all views of all scenes in one launch chain, Gaussians read once per scene
     (no V-fold `repeat`, reference decoder_splatting_cuda.py:52-56), depth as a 4th blended channel.
@@ -206,11 +207,12 @@ def render_views(
         records = torch.cat((gaussian_scales, gaussian_rotations), dim=-1)
         color, depth, _ = rasterize_views(
             gaussian_means, records, gaussian_opacities, gaussian_sh_coefficients, viewbuf, image_shape=image_shape,
-            sh_degree=degree, use_sh=True, views_per_set=v, sh_planar=True, scale_rot=True, frames=frames, **channel)
+            sh_degree=degree, use_sh=True, views_per_set=v, sh_planar=True, scale_rot=True, frames=frames, sh_frame=sh_frame, **channel)
     else:
         color, depth, _ = rasterize_views(
             gaussian_means, gaussian_covariances, gaussian_opacities, gaussian_sh_coefficients, viewbuf,
-            image_shape=image_shape, sh_degree=degree, use_sh=True, views_per_set=v, sh_planar=True, cov_3x3=True, **channel)
+            image_shape=image_shape, sh_degree=degree, use_sh=True, views_per_set=v, sh_planar=True, cov_3x3=True, sh_frame=sh_frame,
+            **channel)
     h, w = image_shape
     color = color.reshape(s, v, 3, h, w)
     if depth is not None:

@@ -22,12 +22,16 @@ class Gaussians:
     scales: Optional[Tensor] = None  # (scene, gaussian, 3)
     rotations: Optional[Tensor] = None  # (scene, gaussian, 4) quaternions x, y, z, w
     frames: Optional[Tensor] = None  # (scene, F, 3, 3) world rotation of each of the F equal consecutive groups of Gaussians
+    # "e3nn" | "rasterizer": `harmonics` are in the coordinates of `frames`, to be rotated by them in this convention
+    # (sh_rotation.rotate_sh) - the kernels evaluate them at the view direction carried into the frame; None: world space
+    sh_frame: Optional[str] = None
 
     def clone(self) -> "Gaussians":
         """A deep copy (reference src/model/types.py:12-18), the optional fields included when present."""
         c = lambda t: None if t is None else t.clone()
         return Gaussians(means=self.means.clone(), covariances=c(self.covariances), harmonics=self.harmonics.clone(),
-                         opacities=self.opacities.clone(), scales=c(self.scales), rotations=c(self.rotations), frames=c(self.frames))
+                         opacities=self.opacities.clone(), scales=c(self.scales), rotations=c(self.rotations), frames=c(self.frames),
+                         sh_frame=self.sh_frame)
 
 
 @dataclass
