@@ -217,9 +217,17 @@ class HipBackend:
         return self._ext.pack_view(rs.viewmatrix, rs.projmatrix, rs.campos, rs.bg, 0.0 if tx_t else float(tx), 0.0 if ty_t else float(ty),
                                    tx if tx_t else None, ty if ty_t else None, float(rs.scale_modifier), torch.device(device))
 
+    @staticmethod
+    def _sizing_dims(dims: _lib.GsrDims) -> _lib.GsrDims:
+        """A copy of launch dims without the GSR_FLAG_SH_IN_FRAME bits: what the sizing and layout helpers take (the bits size
+        nothing, and the helpers refuse them; a plan's dims and a forward's saved dims carry them)."""
+        d = _lib.GsrDims.from_buffer_copy(dims)
+        d.flags &= ~(_lib.FLAG_SH_IN_FRAME | _lib.FLAG_SH_FRAME_E3NN)
+        return d
+
     def workspace_layout(self, dims: _lib.GsrDims):
         offs = (ctypes.c_int64 * 8)()
-        rc = self.lib.gsr_workspace_layout(ctypes.byref(dims), offs)
+        rc = self.lib.gsr_workspace_layout(ctypes.byref(self._sizing_dims(dims)), offs)
         if rc != 0:
             raise RuntimeError(f"gsr_workspace_layout failed (code {rc})")
         return dict(zip(("status", "counts", "tile_total", "ranges", "keys", "point_list", "final_T", "n_contrib"),
@@ -227,7 +235,7 @@ class HipBackend:
 
     def geom_layout(self, dims: _lib.GsrDims):
         offs = (ctypes.c_int64 * 4)()
-        rc = self.lib.gsr_geom_layout(ctypes.byref(dims), offs)
+        rc = self.lib.gsr_geom_layout(ctypes.byref(self._sizing_dims(dims)), offs)
         if rc != 0:
             raise RuntimeError(f"gsr_geom_layout failed (code {rc})")
         return dict(zip(("record_bytes", "aux", "rgbc", "rows"), [int(o) for o in offs]))
@@ -340,7 +348,8 @@ class HipBackend:
                 partials = plan.get("pose_partials")
                 if partials is None:
                     partials = plan["pose_partials"] = torch.empty(
-                        max(16, int(self.lib.gsr_pose_partials_bytes(args[0]))), dtype=torch.uint8, device=plan["device"])
+                        max(16, int(self.lib.gsr_pose_partials_bytes(ctypes.byref(self._sizing_dims(plan["dims"]))))), dtype=torch.uint8,
+                        device=plan["device"])
                 opt = _lib.GsrBackwardOptions(_ptr(fr), nf, int(cfg.scale_rot), _ptr(d_views), _ptr(partials), int(bool(depth_term_only)), 0)
                 ms = None
                 rc = self.lib.gsr_backward_ex(*args[:-1], ctypes.byref(opt), stream)

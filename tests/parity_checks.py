@@ -191,6 +191,26 @@ def check_image_state(res, cfg, v=0):
     return m
 
 
+def check_camera_grads(res, tol=TOL):
+    """Camera gradients (gsr_backward_ex dL_dviews) per view and block (view matrix, projection matrix, camera centre): rel-L2 < tol,
+    no row set aside; a block the oracle leaves at zero must be zero, and so must every record entry the forward never reads."""
+    h, o = res["hip"]["grads"]["views"], res["oracle"]["grads"]["views"]
+    assert h.shape == o.shape and h.shape[1] == 48 and np.isfinite(h).all()
+    worst = 0.0
+    for v in range(h.shape[0]):
+        for name, lo, hi in (("viewmatrix", 0, 16), ("projmatrix", 16, 32), ("campos", 32, 35)):
+            scale = float(np.linalg.norm(o[v, lo:hi]))
+            if scale == 0.0:
+                assert not h[v, lo:hi].any(), (v, name)
+                continue
+            err = float(np.linalg.norm(h[v, lo:hi].astype(np.float64) - o[v, lo:hi])) / scale
+            worst = max(worst, err)
+            assert err < tol, (v, name, err, h[v, lo:hi], o[v, lo:hi])
+        assert not h[v, 35:].any()  # tan-fov, background, scale, near / far: no gradient
+        assert not h[v, [3, 7, 11, 15]].any() and not h[v, [18, 22, 26, 30]].any()  # entries the forward never reads
+    return worst
+
+
 def check_grads(res, cfg, tol=TOL):
     """rel-L2 per gradient tensor < tol.  A pixel whose threshold decision (alpha < 1/255, T < 1e-4) falls the other way
     within fp32 rounding (counted by check_image: `outlier_pixels`) changes the gradient of the splats blended at that one

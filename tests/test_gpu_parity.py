@@ -631,24 +631,6 @@ def test_deterministic_backward_is_bit_identical_and_within_tolerance():
     parity_checks.check_grads(a, cfg)
 
 
-def _check_camera_grads(res, tol=parity_checks.TOL):
-    h, o = res["hip"]["grads"]["views"], res["oracle"]["grads"]["views"]
-    assert h.shape == o.shape and h.shape[1] == 48 and np.isfinite(h).all()
-    worst = 0.0
-    for v in range(h.shape[0]):
-        for name, lo, hi in (("viewmatrix", 0, 16), ("projmatrix", 16, 32), ("campos", 32, 35)):
-            scale = float(np.linalg.norm(o[v, lo:hi]))
-            if scale == 0.0:
-                assert not h[v, lo:hi].any(), (v, name)
-                continue
-            err = float(np.linalg.norm(h[v, lo:hi].astype(np.float64) - o[v, lo:hi])) / scale
-            worst = max(worst, err)
-            assert err < tol, (v, name, err, h[v, lo:hi], o[v, lo:hi])
-        assert not h[v, 35:].any()  # tan-fov, background, scale, near / far: no gradient
-        assert not h[v, [3, 7, 11, 15]].any() and not h[v, [18, 22, 26, 30]].any()  # entries the forward never reads
-    return worst
-
-
 @pytest.mark.parametrize("case", ["sh_depth_3views", "rgb_2sets", "disparity", "scale_rot"])
 def test_camera_gradients_match_the_oracle(case):
     """SURVEY 8f-3 (gsr_backward_ex with dL_dviews): gradient of viewmatrix / projmatrix / campos of every view against the
@@ -682,7 +664,7 @@ def test_camera_gradients_match_the_oracle(case):
     gc = torch.tensor(rng.uniform(0, 1, (v, 3, h, w)).astype(np.float32))
     ge = torch.tensor(rng.uniform(0, 1, (v, h, w)).astype(np.float32)) if cfg.has_extra else None
     res = gpu_util.run_both(cfg, vb, *args, None, gc, ge, want_views=True)
-    worst = _check_camera_grads(res)
+    worst = parity_checks.check_camera_grads(res)
     parity_checks.check_grads(res, cfg)
     assert worst < parity_checks.TOL
 
@@ -702,7 +684,7 @@ def test_camera_gradients_do_not_disturb_the_other_gradients_and_are_determinist
     np.testing.assert_array_equal(a["hip"]["grads"]["views"], b["hip"]["grads"]["views"])
     for k in ("means", "cov6", "opac", "colors", "means2d"):
         np.testing.assert_array_equal(a["hip"]["grads"][k], c["grads"][k], err_msg=k)
-    _check_camera_grads(a)
+    parity_checks.check_camera_grads(a)
 
 
 def test_pose_gradients_through_the_decoder_on_the_device():

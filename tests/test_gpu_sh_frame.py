@@ -132,21 +132,24 @@ def test_fused_backward_is_deterministic_and_carries_camera_gradients():
             assert rel_l2(gf[0].cpu().numpy(), gr[0].cpu().numpy()) <= 1e-4, want_views
 
 
-def _adapter_inputs(seed=11, hs=256, ws=256):
-    """Two source cameras (x = -0.5 / +0.5, turned by a few degrees - proper, non-trivial frames), one Gaussian per pixel of each."""
+def _adapter_inputs(seed=11, hs=256, ws=256, b=1):
+    """Two source cameras per scene (x = -0.5 / +0.5, turned by a few degrees - proper, non-trivial frames; scene k > 0 turned a little
+    further, so that every scene has frames of its own), one Gaussian per pixel of each.  b scenes."""
     g = torch.Generator().manual_seed(seed)
-    ext = torch.eye(4).repeat(1, 2, 1, 1)
-    for v, (x, ang) in enumerate(((-0.5, 0.12), (0.5, -0.09))):
-        c, s = np.cos(ang), np.sin(ang)
-        ext[0, v, :3, :3] = torch.tensor([[c, 0, s], [0, 1, 0], [-s, 0, c]], dtype=torch.float32) @ \
-            torch.tensor([[1, 0, 0], [0, np.cos(0.05), -np.sin(0.05)], [0, np.sin(0.05), np.cos(0.05)]], dtype=torch.float32)
-        ext[0, v, 0, 3] = x
-    intr = torch.tensor([[0.86, 0, 0.5], [0, 0.86, 0.5], [0, 0, 1]]).repeat(1, 2, 1, 1)
+    ext = torch.eye(4).repeat(b, 2, 1, 1)
+    for k in range(b):
+        for v, (x, ang) in enumerate(((-0.5, 0.12), (0.5, -0.09))):
+            ang += 0.07 * k
+            c, s = np.cos(ang), np.sin(ang)
+            ext[k, v, :3, :3] = torch.tensor([[c, 0, s], [0, 1, 0], [-s, 0, c]], dtype=torch.float32) @ \
+                torch.tensor([[1, 0, 0], [0, np.cos(0.05), -np.sin(0.05)], [0, np.sin(0.05), np.cos(0.05)]], dtype=torch.float32)
+            ext[k, v, 0, 3] = x
+    intr = torch.tensor([[0.86, 0, 0.5], [0, 0.86, 0.5], [0, 0, 1]]).repeat(b, 2, 1, 1)
     yy, xx = torch.meshgrid((torch.arange(hs) + 0.5) / hs, (torch.arange(ws) + 0.5) / ws, indexing="ij")
-    coords = torch.stack((xx, yy), -1).reshape(1, 1, hs * ws, 2).expand(1, 2, hs * ws, 2)
-    depths = 3.0 + torch.sin(6 * xx + 2 * yy).reshape(1, 1, hs * ws) + 0.02 * torch.rand((1, 2, hs * ws), generator=g)
-    opac = 0.1 + 0.85 * torch.rand((1, 2, hs * ws), generator=g)
-    raw = torch.randn((1, 2, hs * ws, 82), generator=g)
+    coords = torch.stack((xx, yy), -1).reshape(1, 1, hs * ws, 2).expand(b, 2, hs * ws, 2)
+    depths = 3.0 + torch.sin(6 * xx + 2 * yy).reshape(1, 1, hs * ws) + 0.02 * torch.rand((b, 2, hs * ws), generator=g)
+    opac = 0.1 + 0.85 * torch.rand((b, 2, hs * ws), generator=g)
+    raw = torch.randn((b, 2, hs * ws, 82), generator=g)
     return ext, intr, coords, depths, opac, raw
 
 
