@@ -312,6 +312,37 @@ int gsr_image_loss(int num_images, int height, int width, const float* predictio
 int gsr_image_loss_finish(int num_images, int height, int width, const float* partials, float mse_weight, float ssim_weight,
                           float* sums, float* totals, void* stream);
 
+/* The encoder-side Gaussian adapter, the step right in front of the raster path (reference
+ * src/model/encoder/common/gaussian_adapter.py:60-87 with get_world_rays), one launch: G groups (scene x source view) of P
+ * pixel-aligned Gaussians each, M = (sh_degree + 1)^2 for sh_degree 0..4.
+ *   extrinsics (G, 4, 4) camera-to-world, intrinsics (G, 3, 3) normalised, coordinates (G, P, 2), depths (G, P);
+ *   raw: G x P rows of 7 + 3 M floats = scale features (3) | quaternion x, y, z, w (4) | harmonics (3, M), consecutive rows
+ *        `raw_row_stride` floats apart (>= 7 + 3 M) - the encoder hands over the slice `gaussians[..., 2:]` of an 84-wide tensor
+ *        (encoder_costvolume.py:535-538), which is read where it is (stride 84);
+ *   means (G, P, 3) = t + depth R normalise(K^-1 (u, v, 1));
+ *   scale_rot (G, P, 7), the record form gsr_forward_scale_rot takes: (scale_min + (scale_max - scale_min) sigmoid(r)) x depth x
+ *        0.1 sum(K[:2, :2]^-1 (1 / width, 1 / height)), and q / (|q| + eps);
+ *   harmonics (G, P, 3, M) (GSR_FLAG_SH_PLANAR layout): the raw coefficients times 1 (DC) or 0.1 x 0.25^l (band l).
+ * K^-1 and the multiplier are formed once per group.  Opacities do not pass through here.
+ * gsr_adapt_backward takes the forward's inputs again (everything is recomputed: nothing is saved) and the cotangents dL_dmeans
+ * (G, P, 3), dL_dscale_rot (G, P, 7) - the array gsr_backward_scale_rot writes - and dL_dharmonics (G, P, 3, M), each of which
+ * may be NULL (zeros).  Outputs, all fully written: dL_draw (G, P, 7 + 3 M) contiguous, dL_ddepths (G, P), dL_dcoordinates (G, P, 2)
+ * and dL_dextrinsics (G, 4, 4): rows 0-2 x columns 0-2 the sum over the group of dmean (x) (depth ray), column 3 the sum of
+ * dmean, bottom row zero (PF3plat's extrinsics are learned poses: this is how the render loss reaches them through the means).
+ * That sum is formed in a fixed order - one row per workgroup in `partials` (gsr_adapt_partials_bytes(G, P) bytes of scratch:
+ * host arithmetic), then one reduce launch - so the same bits come out on every run.  Intrinsics get no gradient; a zero
+ * quaternion takes the norm's gradient as 0, as torch does.  Both calls: GSR_ERR_INVALID_ARGUMENT on negative sizes, a degree
+ * outside 0..4, a stride below 7 + 3 M or a NULL required pointer; nothing is launched when G or P is 0. */
+size_t gsr_adapt_partials_bytes(int num_groups, int gaussians_per_group);
+int gsr_adapt(int num_groups, int gaussians_per_group, int sh_degree, const float* extrinsics, const float* intrinsics,
+              const float* coordinates, const float* depths, const float* raw, int64_t raw_row_stride, float scale_min,
+              float scale_max, int height, int width, float eps, float* means, float* scale_rot, float* harmonics, void* stream);
+int gsr_adapt_backward(int num_groups, int gaussians_per_group, int sh_degree, const float* extrinsics, const float* intrinsics,
+                       const float* coordinates, const float* depths, const float* raw, int64_t raw_row_stride, float scale_min,
+                       float scale_max, int height, int width, float eps, const float* dL_dmeans, const float* dL_dscale_rot,
+                       const float* dL_dharmonics, float* dL_draw, float* dL_ddepths, float* dL_dcoordinates, float* dL_dextrinsics,
+                       float* partials, void* stream);
+
 /* Measurement aids for bench.py (never on the product path): the same launch chains with a HIP event recorded on
  * `stream` between stages; they synchronise the stream and return per-stage milliseconds.
  * Forward stages, in launch order: 0 the colour pass when it is a launch of its own (gsr_colour_in_binning == 0; otherwise

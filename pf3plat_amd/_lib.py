@@ -264,6 +264,13 @@ def load():
     lib.gsr_setup_views_backward.argtypes = [ctypes.c_int, vp, vp, vp, vp]
     lib.gsr_setup_views_orthographic.restype = ctypes.c_int
     lib.gsr_setup_views_orthographic.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_float, vp, vp, vp]
+    adapt_head = [ctypes.c_int] * 3 + [vp] * 5 + [ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_float]
+    lib.gsr_adapt_partials_bytes.restype = ctypes.c_size_t
+    lib.gsr_adapt_partials_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
+    lib.gsr_adapt.restype = ctypes.c_int
+    lib.gsr_adapt.argtypes = adapt_head + [vp] * 4
+    lib.gsr_adapt_backward.restype = ctypes.c_int
+    lib.gsr_adapt_backward.argtypes = adapt_head + [vp] * 9
     fp = ctypes.POINTER(ctypes.c_float)
     lib.gsr_forward_profile.restype = ctypes.c_int
     lib.gsr_forward_profile.argtypes = [dp] + [vp] * 13 + [fp]
@@ -281,6 +288,7 @@ EXPORTED_SYMBOLS = (
     "gsr_capacity_for", "gsr_cov_from_scale_rot", "gsr_cov_from_scale_rot_backward", "gsr_last_failed_stage",
     "gsr_colour_in_binning", "gsr_geom_layout", "gsr_backward_ex", "gsr_pose_partials_bytes", "gsr_backward_scratch_bytes", "gsr_setup_views_orthographic", "gsr_forward_scale_rot", "gsr_backward_scale_rot",
     "gsr_image_loss", "gsr_image_loss_partials", "gsr_image_loss_finish", "gsr_pack_view", "gsr_setup_views_backward",
+    "gsr_adapt", "gsr_adapt_backward", "gsr_adapt_partials_bytes",
 )
 # gsr_forward_profile's stages.  On images of up to 20 480 tiles (the fused binning path) "preprocess" is the whole binning
 # kernel and "count_scan" / "emit" have no launch (their entries are one empty event gap each).

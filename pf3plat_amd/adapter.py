@@ -14,6 +14,15 @@ passed to the constructor.  With `fuse_sh_rotation=True` they are not rotated at
 (`AdaptedGaussians.sh_frame` names the convention, `sh_basis`) and the raster kernels evaluate them at the view direction
 carried into that frame (GSR_FLAG_SH_IN_FRAME) - the same image and gradients without the rotated copy and the per-Gaussian band
 matrices torch's broadcasting builds.  `AdaptedGaussians.world_harmonics` still yields the rotated coefficients.
+
+With `fused=True` the adapter's own arithmetic - K^-1, the ray, the mean, sigmoid and footprint of the scales, the quaternion
+normalisation, the masked copy of the harmonics - is ONE HIP launch in each direction (`gsr_adapt` / `gsr_adapt_backward`, an
+autograd node of the compiled binding) instead of torch ops: `raw_gaussians` is read where it lies (the encoder's
+`gaussians[..., 2:]` slice included), scales and rotations come back as the two slices of one (..., 7) record tensor - the form
+the raster kernels take, which the decoder then passes on without a `cat` - and gradients reach raw_gaussians, depths,
+coordinates and extrinsics.  It applies to calls whose per-Gaussian arguments all cover the full (b, v, *rest) shape, in float32,
+with intrinsics that do not require grad; any other call runs the torch ops below unchanged (`last_path` says which ran).  It is
+independent of `fuse_sh_rotation`; PF3plat's training configuration is both.
 """
 from __future__ import annotations
 
@@ -88,10 +97,10 @@ class AdaptedGaussians:
 class GaussianAdapter(nn.Module):
     """fuse_sh_rotation: leave the harmonics in the source camera's frame and let the raster kernels rotate the view direction
     instead (module docstring); `sh_basis` is then the convention ("e3nn", the reference's, or "rasterizer") and `rotate_sh` is
-    not used."""
+    not used.  fused: run the adapter's arithmetic as one HIP launch each way where the call's shapes allow it (module docstring)."""
 
     def __init__(self, cfg: GaussianAdapterCfg, rotate_sh: Optional[Callable[[Tensor, Tensor], Tensor]] = _rotate_sh,
-                 fuse_sh_rotation: bool = False, sh_basis: str = "e3nn"):
+                 fuse_sh_rotation: bool = False, sh_basis: str = "e3nn", fused: bool = False):
         super().__init__()
         if sh_basis not in ("e3nn", "rasterizer"):
             raise ValueError(f"sh_basis must be 'e3nn' or 'rasterizer', got {sh_basis!r}")
@@ -99,6 +108,8 @@ class GaussianAdapter(nn.Module):
         self.rotate_sh = rotate_sh
         self.fuse_sh_rotation = fuse_sh_rotation
         self.sh_basis = sh_basis
+        self.fused = fused
+        self._last_path: Optional[str] = None
         # band l of the harmonics starts small (0.1 x 0.25^l): the DC term dominates at initialisation
         band = torch.arange(self.d_sh, dtype=torch.float32).sqrt().floor()
         self.register_buffer("sh_mask", torch.where(band == 0, torch.ones(()), 0.1 * 0.25 ** band), persistent=False)
@@ -110,6 +121,24 @@ class GaussianAdapter(nn.Module):
     @property
     def d_in(self) -> int:
         return 7 + 3 * self.d_sh
+
+    @property
+    def last_path(self) -> Optional[str]:
+        """Which path the last `forward` took: "hip" (the compiled launch) or "torch" (the torch ops); None before the first call."""
+        return self._last_path
+
+    def _hip_applies(self, extrinsics: Tensor, intrinsics: Tensor, coordinates: Tensor, depths: Tensor, raw_gaussians: Tensor, full: tuple) -> bool:
+        """The compiled path covers calls whose per-Gaussian arguments all have the full (b, v, *rest) shape (every shipped config:
+        one surface, one Gaussian per pixel) and one camera per view, in float32, with no gradient wanted for the intrinsics."""
+        if not self.fused or self.cfg.sh_degree > 4:
+            return False
+        if tuple(depths.shape) != full or tuple(coordinates.shape) != (*full, 2) or tuple(raw_gaussians.shape) != (*full, self.d_in):
+            return False
+        if tuple(intrinsics.shape[:2]) != full[:2] or any(d != 1 for d in intrinsics.shape[2:-2]) or tuple(intrinsics.shape[-2:]) != (3, 3):
+            return False
+        if any(t.dtype != torch.float32 for t in (extrinsics, intrinsics, coordinates, depths, raw_gaussians)):
+            return False
+        return not (torch.is_grad_enabled() and intrinsics.requires_grad)
 
     def get_scale_multiplier(self, intrinsics: Tensor, pixel_size: Tensor, multiplier: float = 0.1) -> Tensor:
         """How large one pixel is at unit depth, summed over x and y: (K[:2, :2]^-1 pixel_size) . (1, 1), times `multiplier`."""
@@ -130,19 +159,21 @@ class GaussianAdapter(nn.Module):
         if any(d != 1 for d in extrinsics.shape[2:-2]) or tuple(extrinsics.shape[:2]) != full[:2]:
             raise ValueError("one camera per (scene, view): extrinsics must be (b, v, 1.., 4, 4); a rotation per Gaussian cannot be "
                              "expressed as the per-view frames the raster kernels take")
-        raw_scale, raw_quat, raw_sh = raw_gaussians.split((3, 4, 3 * self.d_sh), dim=-1)
         lo, hi = self.cfg.gaussian_scale_min, self.cfg.gaussian_scale_max
-        pixel = torch.tensor((1.0 / w, 1.0 / h), dtype=torch.float32, device=extrinsics.device)
-        footprint = depths * self.get_scale_multiplier(intrinsics, pixel)  # world size of 0.1 pixel at the Gaussian's depth
-        scales = (lo + (hi - lo) * raw_scale.sigmoid()) * footprint[..., None]
-        rotations = raw_quat / (raw_quat.norm(dim=-1, keepdim=True) + eps)
-        harmonics = raw_sh.unflatten(-1, (3, self.d_sh)).broadcast_to((*full, 3, self.d_sh)) * self.sh_mask
         c2w = extrinsics[..., :3, :3].detach()
-        # mean = camera centre + depth x (unit ray through the pixel, rotated into world space)
-        ray = torch.linalg.solve(intrinsics, F.pad(coordinates, (0, 1), value=1.0).unsqueeze(-1)).squeeze(-1)
-        ray = F.normalize(ray, dim=-1)
-        direction = (extrinsics[..., :3, :3] @ ray.unsqueeze(-1)).squeeze(-1)
-        means = extrinsics[..., :3, 3] + direction * depths[..., None]
+        if self._hip_applies(extrinsics, intrinsics, coordinates, depths, raw_gaussians, full):
+            from . import _lib
+
+            groups = full[0] * full[1]
+            means, records, harmonics = _lib.load_torch_ext().adapt(
+                extrinsics.reshape(groups, 4, 4), intrinsics.reshape(groups, 3, 3), coordinates.reshape(groups, -1, 2), depths.reshape(groups, -1),
+                raw_gaussians, float(lo), float(hi), int(h), int(w), float(eps), int(self.cfg.sh_degree))
+            self._last_path = "hip"
+            means, records, harmonics = means.view(*full, 3), records.view(*full, 7), harmonics.view(*full, 3, self.d_sh)
+            scales, rotations = records[..., :3], records[..., 3:]  # two slices of ONE record tensor: the decoder passes it on as it is
+        else:
+            self._last_path = "torch"
+            means, scales, rotations, harmonics = self._torch_forward(extrinsics, intrinsics, coordinates, depths, raw_gaussians, full, h, w, eps)
         sh_frame = None
         if self.fuse_sh_rotation:
             # rotate_sh's rule (reference sh_rotation.py:20-21): no rotation at all unless every frame is proper - then the
@@ -151,6 +182,22 @@ class GaussianAdapter(nn.Module):
                 sh_frame = self.sh_basis
         elif self.rotate_sh is not None:
             harmonics = self.rotate_sh(harmonics, c2w[..., None, :, :])
-        return AdaptedGaussians(means=means.broadcast_to((*full, 3)), scales=scales.broadcast_to((*full, 3)),
-                                rotations=rotations.broadcast_to((*full, 4)), harmonics=harmonics, opacities=opacities,
+        return AdaptedGaussians(means=means, scales=scales, rotations=rotations, harmonics=harmonics, opacities=opacities,
                                 frames=c2w.reshape(*full[:2], 3, 3), sh_frame=sh_frame)
+
+    def _torch_forward(self, extrinsics: Tensor, intrinsics: Tensor, coordinates: Tensor, depths: Tensor, raw_gaussians: Tensor, full: tuple,
+                       h: int, w: int, eps: float):
+        """The adapter's arithmetic as torch ops -> means, scales, rotations (each broadcast to `full`) and masked, un-rotated harmonics."""
+        lo, hi = self.cfg.gaussian_scale_min, self.cfg.gaussian_scale_max
+        raw_scale, raw_quat, raw_sh = raw_gaussians.split((3, 4, 3 * self.d_sh), dim=-1)
+        pixel = torch.tensor((1.0 / w, 1.0 / h), dtype=intrinsics.dtype, device=extrinsics.device)
+        footprint = depths * self.get_scale_multiplier(intrinsics, pixel)  # world size of 0.1 pixel at the Gaussian's depth
+        scales = (lo + (hi - lo) * raw_scale.sigmoid()) * footprint[..., None]
+        rotations = raw_quat / (raw_quat.norm(dim=-1, keepdim=True) + eps)
+        harmonics = raw_sh.unflatten(-1, (3, self.d_sh)).broadcast_to((*full, 3, self.d_sh)) * self.sh_mask
+        # mean = camera centre + depth x (unit ray through the pixel, rotated into world space)
+        ray = torch.linalg.solve(intrinsics, F.pad(coordinates, (0, 1), value=1.0).unsqueeze(-1)).squeeze(-1)
+        ray = F.normalize(ray, dim=-1)
+        direction = (extrinsics[..., :3, :3] @ ray.unsqueeze(-1)).squeeze(-1)
+        means = extrinsics[..., :3, 3] + direction * depths[..., None]
+        return means.broadcast_to((*full, 3)), scales.broadcast_to((*full, 3)), rotations.broadcast_to((*full, 4)), harmonics

@@ -59,6 +59,9 @@ struct Abi {
   decltype(&gsr_mark_visible) mark_visible = nullptr;
   decltype(&gsr_cov_from_scale_rot) cov_from_scale_rot = nullptr;
   decltype(&gsr_cov_from_scale_rot_backward) cov_from_scale_rot_backward = nullptr;
+  decltype(&gsr_adapt) adapt = nullptr;
+  decltype(&gsr_adapt_backward) adapt_backward = nullptr;
+  decltype(&gsr_adapt_partials_bytes) adapt_partials_bytes = nullptr;
 } g_abi;
 
 template <class F>
@@ -89,6 +92,9 @@ void init(const std::string& path) {
   resolve(g_abi.mark_visible, "gsr_mark_visible");
   resolve(g_abi.cov_from_scale_rot, "gsr_cov_from_scale_rot");
   resolve(g_abi.cov_from_scale_rot_backward, "gsr_cov_from_scale_rot_backward");
+  resolve(g_abi.adapt, "gsr_adapt");
+  resolve(g_abi.adapt_backward, "gsr_adapt_backward");
+  resolve(g_abi.adapt_partials_bytes, "gsr_adapt_partials_bytes");
   TORCH_CHECK(g_abi.abi_version() == GSR_ABI_VERSION, "pf3plat_amd: raster library ABI ", g_abi.abi_version(), " != ", GSR_ABI_VERSION, "; rebuild");
 }
 
@@ -843,6 +849,85 @@ Tensor pack_view(const Tensor& viewmatrix, const Tensor& projmatrix, const Tenso
   return out;
 }
 
+// ---- the Gaussian adapter (gsr_adapt / gsr_adapt_backward): one autograd node around the two calls ---------------------------------
+// raw (..., 7 + 3 M) is read where it is: its rows must lie a constant number of floats apart (the encoder's `gaussians[..., 2:]`
+// slice of an 84-wide tensor does: stride 84); only a tensor whose leading dims do not collapse to one row stride is copied.
+bool rows_evenly_spaced(const Tensor& t, int64_t* row_stride) {
+  *row_stride = t.size(-1);
+  if (t.dim() < 2 || (t.size(-1) > 1 && t.stride(-1) != 1)) return false;
+  int64_t expect = -1;
+  for (int64_t d = t.dim() - 2; d >= 0; --d) {
+    if (t.size(d) == 1) continue;  // (the stride of a dim of one entry says nothing)
+    if (expect < 0) {
+      expect = *row_stride = t.stride(d);
+      if (expect < t.size(-1)) return false;
+    } else if (t.stride(d) != expect) {
+      return false;
+    }
+    expect *= t.size(d);
+  }
+  return true;
+}
+struct AdaptFn : public torch::autograd::Function<AdaptFn> {
+  static torch::autograd::variable_list forward(torch::autograd::AutogradContext* ctx, Tensor extrinsics, Tensor intrinsics, Tensor coordinates, Tensor depths,
+                                                Tensor raw_in, double lo, double hi, int64_t height, int64_t width, double eps, int64_t degree) {
+    check_device({&extrinsics, &intrinsics, &coordinates, &depths, &raw_in});
+    TORCH_CHECK(degree >= 0 && degree <= 4, "adapt: sh_degree must be 0..4, got ", degree);
+    const int64_t m = (degree + 1) * (degree + 1), rowf = 7 + 3 * m;
+    for (const Tensor* t : {&extrinsics, &intrinsics, &coordinates, &depths, &raw_in})
+      TORCH_CHECK(t->scalar_type() == at::kFloat, "adapt: float32 tensors expected");
+    TORCH_CHECK(extrinsics.dim() == 3 && extrinsics.size(1) == 4 && extrinsics.size(2) == 4, "adapt: extrinsics (G, 4, 4) expected");
+    const int64_t g = extrinsics.size(0);
+    TORCH_CHECK(intrinsics.dim() == 3 && intrinsics.size(0) == g && intrinsics.size(1) == 3 && intrinsics.size(2) == 3, "adapt: intrinsics (G, 3, 3) expected");
+    TORCH_CHECK(depths.dim() == 2 && depths.size(0) == g, "adapt: depths (G, P) expected");
+    const int64_t p = depths.size(1);
+    TORCH_CHECK(g < (1 << 30) && p < (1 << 30), "adapt: too many Gaussians for one call");
+    TORCH_CHECK(coordinates.numel() == g * p * 2 && coordinates.size(-1) == 2, "adapt: coordinates (G, P, 2) expected");
+    TORCH_CHECK(raw_in.dim() >= 2 && raw_in.size(-1) == rowf && raw_in.numel() == g * p * rowf, "adapt: raw (G, P, ", rowf, ") expected");
+    const Tensor ext = extrinsics.contiguous(), intr = intrinsics.contiguous(), coords = coordinates.contiguous(), dep = depths.contiguous();
+    int64_t row_stride = rowf;
+    const bool in_place = rows_evenly_spaced(raw_in, &row_stride);
+    const Tensor raw = in_place ? raw_in : raw_in.contiguous();
+    if (!in_place) row_stride = rowf;
+    Tensor means = at::empty({g, p, 3}, ext.options()), records = at::empty({g, p, 7}, ext.options()), harmonics = at::empty({g, p, 3, m}, ext.options());
+    c10::hip::HIPGuard guard(ext.device().index());
+    const int rc = g_abi.adapt((int)g, (int)p, (int)degree, fptr(ext), fptr(intr), fptr(coords), fptr(dep), fptr(raw), row_stride, (float)lo, (float)hi,
+                               (int)height, (int)width, (float)eps, means.data_ptr<float>(), records.data_ptr<float>(), harmonics.data_ptr<float>(), stream_of(ext.device()));
+    if (rc != 0) throw std::runtime_error("gsr_adapt failed with code " + std::to_string(rc));
+    ctx->save_for_backward({ext, intr, coords, dep, raw});
+    ctx->saved_data["shape"] = std::vector<int64_t>{g, p, row_stride, degree, height, width};
+    ctx->saved_data["scalars"] = std::vector<double>{lo, hi, eps};
+    ctx->saved_data["raw_sizes"] = raw_in.sizes().vec();
+    ctx->saved_data["coord_sizes"] = coordinates.sizes().vec();
+    return {means, records, harmonics};
+  }
+  static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx, torch::autograd::variable_list grads) {
+    const auto saved = ctx->get_saved_variables();
+    const Tensor &ext = saved[0], &intr = saved[1], &coords = saved[2], &dep = saved[3], &raw = saved[4];
+    const auto shape = ctx->saved_data["shape"].toIntVector();
+    const auto scal = ctx->saved_data["scalars"].toDoubleVector();
+    const int64_t g = shape[0], p = shape[1], stride = shape[2], degree = shape[3], m = (degree + 1) * (degree + 1);
+    check_device({&grads[0], &grads[1], &grads[2]});
+    const Tensor d_means = f32c(grads[0]), d_rec = f32c(grads[1]), d_harm = f32c(grads[2]);
+    Tensor d_raw = at::empty({g, p, 7 + 3 * m}, ext.options()), d_dep = at::empty({g, p}, ext.options()), d_coords = at::empty({g, p, 2}, ext.options());
+    Tensor d_ext = g * p > 0 ? at::empty({g, 4, 4}, ext.options()) : at::zeros({g, 4, 4}, ext.options());
+    c10::hip::HIPGuard guard(ext.device().index());
+    Tensor partials = at::empty({(int64_t)g_abi.adapt_partials_bytes((int)g, (int)p)}, ext.options().dtype(at::kByte));
+    const int rc = g_abi.adapt_backward((int)g, (int)p, (int)degree, fptr(ext), fptr(intr), fptr(coords), fptr(dep), fptr(raw), stride, (float)scal[0], (float)scal[1],
+                                        (int)shape[4], (int)shape[5], (float)scal[2], fptr(d_means), fptr(d_rec), fptr(d_harm), d_raw.data_ptr<float>(),
+                                        d_dep.data_ptr<float>(), d_coords.data_ptr<float>(), d_ext.data_ptr<float>(),
+                                        reinterpret_cast<float*>(partials.data_ptr<uint8_t>()), stream_of(ext.device()));
+    if (rc != 0) throw std::runtime_error("gsr_adapt_backward failed with code " + std::to_string(rc));
+    return {d_ext, Tensor(), d_coords.reshape(ctx->saved_data["coord_sizes"].toIntVector()), d_dep, d_raw.reshape(ctx->saved_data["raw_sizes"].toIntVector()),
+            Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+  }
+};
+std::tuple<Tensor, Tensor, Tensor> adapt(const Tensor& extrinsics, const Tensor& intrinsics, const Tensor& coordinates, const Tensor& depths, const Tensor& raw, double lo,
+                                         double hi, int64_t height, int64_t width, double eps, int64_t degree) {
+  auto out = AdaptFn::apply(extrinsics, intrinsics, coordinates, depths, raw, lo, hi, height, width, eps, degree);
+  return {out[0], out[1], out[2]};
+}
+
 // ---- what Python calls ------------------------------------------------------------------------------------------------------
 struct PyBackend {
   c10::intrusive_ptr<BackendHolder> holder;
@@ -1110,6 +1195,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("setup_views_backward", &setup_views_backward);
   m.def("setup_views_orthographic", &setup_views_orthographic);
   m.def("mark_visible", [](const std::vector<int64_t>& cfgv, const Tensor& viewbuf, const Tensor& means) { return mark_visible(cfg_from(cfgv), viewbuf, means); });
+  m.def("adapt", &adapt, "Gaussian adapter, one launch each way: (means (G, P, 3), scale + quaternion records (G, P, 7), masked harmonics (G, P, 3, M))");
   m.def("cov_from_scale_rot", &cov_from_scale_rot);
   m.def("cov_from_scale_rot_backward", &cov_from_scale_rot_backward);
   m.def("frames_arg", [](const std::vector<int64_t>& cfgv, const c10::optional<Tensor>& frames) {

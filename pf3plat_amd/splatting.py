@@ -55,6 +55,27 @@ def depth_fake_color(extrinsics: Tensor, near: Tensor, far: Tensor, gaussian_mea
     return z
 
 
+def _scale_rot_records(scales: Tensor, rotations: Tensor) -> Tensor:
+    """(..., 7) scale + quaternion records for the raster kernels.  When `scales` and `rotations` are the two slices [..., :3] and
+    [..., 3:] of one contiguous (..., 7) tensor - what GaussianAdapter(fused=True) returns, also after `for_decoder`'s reshapes - that
+    tensor is passed on as it is (same values, one copy fewer in each direction); anything else is concatenated."""
+    base = scales._base
+    lead = tuple(scales.shape[:-1])
+    if (base is not None and rotations._base is base and base.dim() >= 1 and base.shape[-1] == 7 and base.is_contiguous()
+            and scales.shape[-1] == 3 and rotations.shape[-1] == 4 and tuple(rotations.shape[:-1]) == lead
+            and base.numel() == 7 * scales.numel() // 3 and scales.dtype == base.dtype
+            and scales.storage_offset() == base.storage_offset() and rotations.storage_offset() == base.storage_offset() + 3):
+        want, step = [], 7  # the strides a (*lead, 7) view of the whole of `base` gives both slices
+        for size in reversed(lead):
+            want.append(step)
+            step *= size
+        want = tuple(reversed(want)) + (1,)
+        same = lambda t: all(sz == 1 or st == w for sz, st, w in zip(t.shape, t.stride(), want))
+        if same(scales) and same(rotations):
+            return base.view(*lead, 7)
+    return torch.cat((scales, rotations), dim=-1)
+
+
 def _camera_wants_depth_gradient(extrinsics: Tensor) -> bool:
     return torch.is_grad_enabled() and extrinsics.requires_grad
 
@@ -159,7 +180,7 @@ def render_depth_cuda(
     channel = dict(extra_mode=mode, camera_gradient="depth")
     if gaussian_covariances is None:
         cov = dict(scale_rot=True, frames=frames)
-        gaussian_covariances = torch.cat((gaussian_scales, gaussian_rotations), dim=-1)
+        gaussian_covariances = _scale_rot_records(gaussian_scales, gaussian_rotations)
     else:
         cov = dict(cov_3x3=True)
     _, depth, _ = rasterize_views(
@@ -204,7 +225,7 @@ def render_views(
     viewbuf = _viewbuf(ext, intr, nr, fr, background_color.reshape(3), scale_invariant, pose_gradients or depth_cam)
     channel = dict(extra_mode=depth_mode, camera_gradient="depth" if depth_cam else "full")
     if gaussian_covariances is None:  # scale + quaternion records, as the encoder's adapter emits them
-        records = torch.cat((gaussian_scales, gaussian_rotations), dim=-1)
+        records = _scale_rot_records(gaussian_scales, gaussian_rotations)
         color, depth, _ = rasterize_views(
             gaussian_means, records, gaussian_opacities, gaussian_sh_coefficients, viewbuf, image_shape=image_shape,
             sh_degree=degree, use_sh=True, views_per_set=v, sh_planar=True, scale_rot=True, frames=frames, sh_frame=sh_frame, **channel)

@@ -1,7 +1,8 @@
 """Adapter -> decoder training step at PF3plat's training batch, harmonics rotated by torch (`rotate_sh`, the default adapter)
 against harmonics left in their source camera's frame and rotated in the raster kernels (GaussianAdapter(fuse_sh_rotation=True),
-GSR_FLAG_SH_IN_FRAME).  Shape: 4 scenes x 2 source views x 256^2 pixel-aligned Gaussians (131 072 per scene, degree 4), 3 target
-views of 256^2 per scene, colour + depth loss, forward + backward.  HIP events around each step, warm-up first, the two forms
+GSR_FLAG_SH_IN_FRAME), and against that with the adapter itself compiled as well (GaussianAdapter(fuse_sh_rotation=True,
+fused=True): gsr_adapt / gsr_adapt_backward, one launch each way, the same inputs).  Shape: 4 scenes x 2 source views x 256^2 pixel-aligned Gaussians (131 072 per scene, degree 4), 3 target
+views of 256^2 per scene, colour + depth loss, forward + backward.  HIP events around each step, warm-up first, the three forms
 alternated call by call; reports median and spread of the repeats and torch.cuda.max_memory_allocated of one step of each.
 usage (GPU box): python tools/adapter_step.py [steps per repeat] [repeats] [out.json]"""
 import json
@@ -51,7 +52,8 @@ def main():
     dev = torch.device("cuda:0")
     (ext, intr, coords, depths, opac, raw0, w, wd), cams = inputs(dev)
     cfg = GaussianAdapterCfg(0.5, 15.0, 4)
-    adapters = {"torch_rotation": GaussianAdapter(cfg).to(dev), "fused": GaussianAdapter(cfg, fuse_sh_rotation=True).to(dev)}
+    adapters = {"torch_rotation": GaussianAdapter(cfg).to(dev), "fused": GaussianAdapter(cfg, fuse_sh_rotation=True).to(dev),
+                "hip_adapter": GaussianAdapter(cfg, fuse_sh_rotation=True, fused=True).to(dev)}
     dec = pf3plat_amd.DecoderSplattingCUDA().to(dev)
     raw = raw0.clone().requires_grad_(True)
 
@@ -67,8 +69,10 @@ def main():
     for name in adapters:
         o = step(name)
         res[name] = (o.color.detach().clone(), o.depth.detach().clone(), raw.grad.detach().clone())
+    assert adapters["hip_adapter"].last_path == "hip" and adapters["fused"].last_path == "torch"
     rel = lambda a, b: float((a - b).double().norm() / b.double().norm())
     agree = {k: rel(res["fused"][i], res["torch_rotation"][i]) for i, k in enumerate(("color", "depth", "d_raw"))}
+    agree_hip = {k: rel(res["hip_adapter"][i], res["fused"][i]) for i, k in enumerate(("color", "depth", "d_raw"))}
     mem = {}
     for name in adapters:
         for _ in range(3):
@@ -93,7 +97,8 @@ def main():
                for k, v in times.items()}
     out = {"shape": f"{B} scenes x 2 x {HS}x{WS} Gaussians (131072 per scene, degree 4), 3 target views {HW}, colour + depth, fwd + bwd",
            "steps_per_repeat": steps, "repeats": repeats, "time": summary, "memory": mem, "fused_vs_torch_rel_l2": agree,
-           "saving_ms": summary["torch_rotation"]["median_ms"] - summary["fused"]["median_ms"]}
+           "hip_adapter_vs_fused_rel_l2": agree_hip, "saving_ms": summary["torch_rotation"]["median_ms"] - summary["fused"]["median_ms"],
+           "hip_adapter_saving_ms": summary["fused"]["median_ms"] - summary["hip_adapter"]["median_ms"]}
     print(json.dumps(out))
     if out_path:
         with open(out_path, "w") as f:
