@@ -58,12 +58,20 @@ def find_hipcc() -> str:
     raise RuntimeError("hipcc not found (looked at $HIPCC, /opt/rocm/bin/hipcc, PATH)")
 
 
-def _source_stamp(extra_flags=()) -> str:
-    """What a built library was made from: a hash of the kernel source, the header and the compiler flags."""
+def hip_sources(csrc: str = None, header: str = None) -> list:
+    """Every file libgsr_hip.so is built from: csrc/gsr_hip.hip, any header next to it that it includes (all of csrc/ but the
+    torch binding, which is a library of its own) and include/gsr.h."""
+    csrc = csrc or os.path.dirname(SRC)
+    return [os.path.join(csrc, n) for n in sorted(os.listdir(csrc)) if n != "gsr_torch.cpp" and os.path.isfile(os.path.join(csrc, n))] + [header or HEADER]
+
+
+def _source_stamp(extra_flags=(), csrc: str = None, header: str = None) -> str:
+    """What a built library was made from: a hash of its sources (hip_sources: names and contents) and the compiler flags."""
     import hashlib
 
     h = hashlib.sha256()
-    for path in (SRC, HEADER):
+    for path in hip_sources(csrc, header):
+        h.update(os.path.basename(path).encode() + b"\0")
         with open(path, "rb") as f:
             h.update(f.read())
     h.update(" ".join([*HIPCC_FLAGS, *extra_flags]).encode())
@@ -81,7 +89,7 @@ def is_stale() -> bool:
             return f.read().strip() != _source_stamp()
     except OSError:
         t = os.path.getmtime(LIB_PATH)  # (a library from before the stamp file existed)
-        return any(os.path.getmtime(s) > t for s in (SRC, HEADER))
+        return any(os.path.getmtime(s) > t for s in hip_sources())
 
 
 class RasterOverflowWarning(RuntimeWarning):
@@ -96,7 +104,7 @@ def build(force: bool = False, verbose: bool = False, extra_flags=(), out: str =
     """Compile csrc/gsr_hip.hip -> libgsr_hip.so for gfx950 (seconds; no GPU needed).  `extra_flags` / `out`: measurement
     builds (tools/ablate.py: -DGSR_ABLATE into its own file)."""
     out = out or LIB_PATH
-    stale = is_stale() if out == LIB_PATH else (not os.path.exists(out) or any(os.path.getmtime(s) > os.path.getmtime(out) for s in (SRC, HEADER)))
+    stale = is_stale() if out == LIB_PATH else (not os.path.exists(out) or any(os.path.getmtime(s) > os.path.getmtime(out) for s in hip_sources()))
     if force or stale:
         cmd = [find_hipcc(), *HIPCC_FLAGS, *extra_flags, "-o", out + ".tmp", SRC]
         res = subprocess.run(cmd, capture_output=True, text=True)

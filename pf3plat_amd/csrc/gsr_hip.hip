@@ -960,6 +960,9 @@ __device__ __forceinline__ uint32_t take_pages(unsigned long long* counter, uint
 __device__ __forceinline__ unsigned long long* dbg_stamps(const Params& p, size_t slot) {
   return p.keys + (size_t)p.pool_off + (size_t)p.key_pages * kPage - (slot + 1) * 8;  // (the padding lies behind)
 }
+// (in a kernel that has `dbg`, `tid` and its slot `stamp` / a second slot `stamp2`)
+#define GSR_STAMP(k) do { if (dbg && tid == 0) stamp[k] = __builtin_amdgcn_s_memrealtime(); } while (0)
+#define GSR_STAMP2(k) do { if (dbg && tid == 0) stamp2[k] = __builtin_amdgcn_s_memrealtime(); } while (0)
 
 __device__ __forceinline__ Foot foot_from_lds(const float* b, const Grid& g) {
   Foot f;
@@ -1261,7 +1264,6 @@ __global__ __launch_bounds__(kBinThreads, (!kColor && kMaxT == kBinTwoMaxT) ? 8 
   const int T = p.g.T, N = p.d.num_gaussians;
   const bool dbg = GSR_ABL(p.d.flags, GSR_FLAG_DEBUG_TIMING);
   unsigned long long* stamp = dbg_stamps(p, (size_t)(blockIdx.y * gridDim.x + blockIdx.x));
-#define GSR_STAMP(k) do { if (dbg && tid == 0) stamp[k] = __builtin_amdgcn_s_memrealtime(); } while (0)
   GSR_STAMP(0);
   for (int k = tid; k < T; k += kBinThreads) hist[k] = 0;
   if (tid == 0) {
@@ -1540,7 +1542,6 @@ __global__ __launch_bounds__(kBinThreads, (!kColor && kMaxT == kBinTwoMaxT) ? 8 
     for (uint32_t k = tid; k < total; k += kBinThreads) region[k] = lds_keys[k];
   }
   GSR_STAMP(4);
-#undef GSR_STAMP
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1718,7 +1719,6 @@ __global__ __launch_bounds__(kBinThreads) void k_emit(const Params p) {
   const uint32_t cap = (uint32_t)p.d.pair_capacity;
   const bool dbg = GSR_ABL(p.d.flags, GSR_FLAG_DEBUG_TIMING);
   unsigned long long* stamp = p.keys + (size_t)cap - (size_t)(blockIdx.x + 1) * 8;
-#define GSR_STAMP(k) do { if (dbg && tid == 0) stamp[k] = __builtin_amdgcn_s_memrealtime(); } while (0)
   GSR_STAMP(0);
   if (kScan) {
     const int VT = p.d.num_views * T;
@@ -1838,7 +1838,6 @@ __global__ __launch_bounds__(kBinThreads) void k_emit(const Params p) {
     });
     __syncthreads();
   }
-#undef GSR_STAMP
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1954,8 +1953,6 @@ __device__ __forceinline__ uint2 sort_tile(const Params& p, const uint32_t bid, 
   const bool dbg = GSR_ABL(p.d.flags, GSR_FLAG_DEBUG_TIMING);
   unsigned long long* stamp = dbg_stamps(p, 8192 + bid);
   unsigned long long* stamp2 = dbg_stamps(p, 8192 + p.sort_blocks + bid);
-#define GSR_STAMP(k) do { if (dbg && tid == 0) stamp[k] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#define GSR_STAMP2(k) do { if (dbg && tid == 0) stamp2[k] = __builtin_amdgcn_s_memrealtime(); } while (0)
   GSR_STAMP(0);
   int n;
   uint32_t obase = 0;  // where the tile's list starts in the index list
@@ -2187,8 +2184,6 @@ __device__ __forceinline__ uint2 sort_tile(const Params& p, const uint32_t bid, 
   for (int k = tid; k < n; k += kSortThreads) out[k] = (uint32_t)sk[k];
   GSR_STAMP(6);
   return make_uint2(obase, obase + (uint32_t)n);
-#undef GSR_STAMP
-#undef GSR_STAMP2
 }
 
 
@@ -2661,8 +2656,6 @@ __global__ __launch_bounds__(kFwdThreads, kCompact ? 6 : 4) void k_tile_fwd_pref
   const bool dbg = GSR_ABL(p.d.flags, GSR_FLAG_DEBUG_TIMING);
   unsigned long long* stamp = dbg_stamps(p, 8192 + bid);
   unsigned long long* stamp2 = dbg_stamps(p, 8192 + p.sort_blocks + bid);
-#define GSR_STAMP(k) do { if (dbg && tid == 0) stamp[k] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#define GSR_STAMP2(k) do { if (dbg && tid == 0) stamp2[k] = __builtin_amdgcn_s_memrealtime(); } while (0)
   __builtin_amdgcn_s_setprio(2);
   GSR_STAMP(0);
   const int T = p.g.T, R = p.rows;
@@ -2959,8 +2952,6 @@ __global__ __launch_bounds__(kFwdThreads, kCompact ? 6 : 4) void k_tile_fwd_pref
     blend_finish<kExtra>(p, v, t, n, *reinterpret_cast<BlendFin*>(smem), acc, pxi, pyi, inside, bg0, bg1, bg2);
   }
   report_length();
-#undef GSR_STAMP
-#undef GSR_STAMP2
   (void)sInfo;
 }
 
@@ -4112,11 +4103,20 @@ static Params base_params(const GsrDims* d, const GsrView* views, const float* m
     if ((expr) != hipSuccess) return GSR_ERR_LAUNCH; \
   } while (0)
 
+// Run-time bools as compile-time constants: dispatch_bools(f, a, b) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}).  A generic
+// lambda f names a kernel's template arguments once, where it is launched; every combination of its bools is instantiated.
+template <class F>
+static inline void dispatch_bools(F&& f) { f(); }
+template <class F, class... Bools>
+static inline void dispatch_bools(F&& f, bool b, Bools... rest) {
+  if (b) dispatch_bools([&](auto... cs) { f(std::true_type{}, cs...); }, rest...);
+  else dispatch_bools([&](auto... cs) { f(std::false_type{}, cs...); }, rest...);
+}
+
 }  // namespace gsr
 
 using namespace gsr;
 
-static hipEvent_t* g_bwd_events = nullptr;
 static thread_local int g_failed_stage = -1;  // debug mode: stage whose check failed (gsr_last_failed_stage)
 
 // ------------------------------------------------------------------------------------------------
@@ -4198,22 +4198,34 @@ int gsr_last_failed_stage(void) { return g_failed_stage; }
 // the variants with the colour pass inside want all of a CU's 160 KB - a device (or runtime) that does not grant that runs the
 // colour pass as a launch of its own instead (bit in g_color_bin_ok).
 static std::atomic<unsigned long long> g_lds_set{0ull}, g_color_bin_ok{0ull};
+// The instances of k_preprocess_bin, named here and nowhere else, each with the most dynamic LDS it is launched with: ensure_bin_attributes
+// walks them all, forward_impl picks one.  0: plain; 1: plain, two workgroups per CU; 2 + kJ + 2 * kShFrame: the colour pass inside.
+struct BinInstance {
+  void (*kernel)(const Params);
+  int max_lds;
+};
+constexpr int kBinInstances = 6;
+static BinInstance bin_instance(int i) {
+  if (i == 0) return {k_preprocess_bin<false, false>, (int)bin_lds_bytes(kFusedMaxTiles, false)};
+  if (i == 1) return {k_preprocess_bin<false, false, kBinTwoMaxT>, (int)bin_lds_bytes(kBinTwoMaxT, false)};
+  BinInstance b{nullptr, 160 * 1024 - 10400};
+  // (the bools negated: the four are then emitted in the order of their indices, where the code object has always had them)
+  dispatch_bools([&](auto no_frame, auto no_j) { b.kernel = k_preprocess_bin<true, !no_j.value, kFusedMaxTiles, !no_frame.value>; }, i < 4, (i & 1) == 0);
+  return b;
+}
 static int ensure_bin_attributes(int* dev_out) {
   int dev = 0;
   GSR_CHECK(hipGetDevice(&dev));
   if (dev_out) *dev_out = dev;
   const unsigned long long bit = 1ull << (dev & 63);
   if (g_lds_set.load(std::memory_order_acquire) & bit) return GSR_OK;
-  const int plain = (int)bin_lds_bytes(kFusedMaxTiles, false), with_color = 160 * 1024 - 10400;
-  GSR_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_preprocess_bin<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, plain));
-  GSR_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_preprocess_bin<false, false, kBinTwoMaxT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)bin_lds_bytes(kBinTwoMaxT, false)));
-  const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(k_preprocess_bin<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, with_color) == hipSuccess &&
-                  hipFuncSetAttribute(reinterpret_cast<const void*>(k_preprocess_bin<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, with_color) == hipSuccess &&
-                  hipFuncSetAttribute(reinterpret_cast<const void*>(k_preprocess_bin<true, false, kFusedMaxTiles, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      with_color) == hipSuccess &&
-                  hipFuncSetAttribute(reinterpret_cast<const void*>(k_preprocess_bin<true, true, kFusedMaxTiles, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      with_color) == hipSuccess;
+  bool ok = true;
+  for (int i = 0; i < kBinInstances; ++i) {
+    const BinInstance b = bin_instance(i);
+    const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(b.kernel), hipFuncAttributeMaxDynamicSharedMemorySize, b.max_lds);
+    if (i < 2) GSR_CHECK(err);
+    else ok = ok && err == hipSuccess;
+  }
   if (ok) g_color_bin_ok.fetch_or(bit, std::memory_order_relaxed);
   else (void)hipGetLastError();
   g_lds_set.fetch_or(bit, std::memory_order_release);
@@ -4300,6 +4312,19 @@ static bool call_dims_ok(const GsrDims* d, const SrArgs* sr) {
   return dims_ok(d, true) && sr_ok(d, sr);
 }
 
+// debug (flags bit 1, upstream's `debug`): synchronise and check after every stage, report the stage that failed
+#define GSR_STAGE_DONE(idx)                                                            \
+  do {                                                                                  \
+    if (d.flags & GSR_FLAG_DEBUG) {                                                     \
+      if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) {  \
+        g_failed_stage = (idx);                                                         \
+        return GSR_ERR_LAUNCH;                                                          \
+      }                                                                                 \
+    }                                                                                   \
+  } while (0)
+// the profile entry points' events: one between every two stages (ev: null on the product path)
+#define GSR_MARK() do { if (ev) GSR_CHECK(hipEventRecord(ev[e++], st)); } while (0)
+
 static int forward_impl(const GsrDims* dims, const GsrView* views, const float* means, const float* cov6,
                         const float* opacities, const float* colors, const float* extra, float* out_color,
                         float* out_extra, int32_t* radii, void* geom, void* bin, void* img, hipStream_t st,
@@ -4327,17 +4352,6 @@ static int forward_impl(const GsrDims* dims, const GsrView* views, const float* 
   if (!means || !cov6 || !opacities || !colors || !radii || !geom) return GSR_ERR_INVALID_ARGUMENT;
   const size_t VT = V * (size_t)p.g.T;
   int e = 0;
-  // debug (flags bit 1, upstream's `debug`): synchronise and check after every stage, report the stage that failed
-#define GSR_STAGE_DONE(idx)                                                            \
-  do {                                                                                  \
-    if (d.flags & GSR_FLAG_DEBUG) {                                                     \
-      if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) {  \
-        g_failed_stage = (idx);                                                         \
-        return GSR_ERR_LAUNCH;                                                          \
-      }                                                                                 \
-    }                                                                                   \
-  } while (0)
-#define GSR_MARK() do { if (ev) GSR_CHECK(hipEventRecord(ev[e++], st)); } while (0)
   const bool do_color = !GSR_ABL(d.flags, GSR_FLAG_ABLATE_NO_SH);
   p.color_units = (uint32_t)((N + 63) / 64);
   const unsigned color_blocks = do_color ? p.color_units * (unsigned)d.num_sets : 0u;
@@ -4356,12 +4370,9 @@ static int forward_impl(const GsrDims* dims, const GsrView* views, const float* 
   // harmonics in their group's frame (GSR_FLAG_SH_IN_FRAME): the colour passes' own instances
   const bool sh_frame = (d.flags & GSR_FLAG_SH_IN_FRAME) && d.sh_coeffs > 0;
   GSR_MARK();
-  if (color_blocks && !color_in_bin) {
-    if (sh_frame && p.shj) hipLaunchKernelGGL((k_color<true, true>), dim3(color_blocks), dim3(kColorThreads), 0, st, p);
-    else if (sh_frame) hipLaunchKernelGGL((k_color<false, true>), dim3(color_blocks), dim3(kColorThreads), 0, st, p);
-    else if (p.shj) hipLaunchKernelGGL((k_color<true, false>), dim3(color_blocks), dim3(kColorThreads), 0, st, p);
-    else hipLaunchKernelGGL((k_color<false, false>), dim3(color_blocks), dim3(kColorThreads), 0, st, p);
-  }
+  if (color_blocks && !color_in_bin)
+    dispatch_bools([&](auto frame, auto j) { hipLaunchKernelGGL((k_color<j.value, frame.value>), dim3(color_blocks), dim3(kColorThreads), 0, st, p); },
+                   sh_frame, p.shj != nullptr);
   GSR_STAGE_DONE(0);
   GSR_MARK();
   if (fused_bin) {
@@ -4369,12 +4380,8 @@ static int forward_impl(const GsrDims* dims, const GsrView* views, const float* 
     const size_t shmem = bin_lds_bytes(p.g.T, color_in_bin);
     // (two plain workgroups per CU where the image's tile counters leave the LDS for it: LDS comes in 1280-byte steps)
     const bool two_per_cu = bin_two_per_cu(p.g, color_in_bin);
-    if (two_per_cu) hipLaunchKernelGGL((k_preprocess_bin<false, false, kBinTwoMaxT>), bgrid, dim3(kBinThreads), shmem, st, p);
-    else if (!color_in_bin) hipLaunchKernelGGL((k_preprocess_bin<false, false>), bgrid, dim3(kBinThreads), shmem, st, p);
-    else if (sh_frame && p.shj) hipLaunchKernelGGL((k_preprocess_bin<true, true, kFusedMaxTiles, true>), bgrid, dim3(kBinThreads), shmem, st, p);
-    else if (sh_frame) hipLaunchKernelGGL((k_preprocess_bin<true, false, kFusedMaxTiles, true>), bgrid, dim3(kBinThreads), shmem, st, p);
-    else if (p.shj) hipLaunchKernelGGL((k_preprocess_bin<true, true>), bgrid, dim3(kBinThreads), shmem, st, p);
-    else hipLaunchKernelGGL((k_preprocess_bin<true, false>), bgrid, dim3(kBinThreads), shmem, st, p);
+    const BinInstance b = bin_instance(two_per_cu ? 1 : !color_in_bin ? 0 : 2 + (p.shj != nullptr) + 2 * sh_frame);
+    hipLaunchKernelGGL(b.kernel, bgrid, dim3(kBinThreads), shmem, st, p);
   } else {
     hipLaunchKernelGGL(k_preprocess, dim3((unsigned)((N + kPreThreads - 1) / kPreThreads), (unsigned)V), dim3(kPreThreads), 0, st, p);
   }
@@ -4397,40 +4404,29 @@ static int forward_impl(const GsrDims* dims, const GsrView* views, const float* 
   p.sort_blocks = (uint32_t)VT;
   {
     const dim3 tgrid((unsigned)VT);
-#define GSR_TILES(G, L)                                                                                  \
-  do {                                                                                                   \
-    if (d.has_extra) hipLaunchKernelGGL((k_tile_fwd<G, L, true>), tgrid, dim3(kFwdThreads), 0, st, p);   \
-    else hipLaunchKernelGGL((k_tile_fwd<G, L, false>), tgrid, dim3(kFwdThreads), 0, st, p);              \
-  } while (0)
+    const bool extra = d.has_extra != 0;
     // every list that sits in its slot is at most `stride` long: a small slot means short lists, and the 2048-key variant
     // (windowed chain: lists are contiguous ranges of any length; short ones on average - a large image - sort in the 2048-key
     // variant, whose smaller LDS footprint lets six workgroups share a CU; a list longer than the LDS array sorts in memory either way)
-    if (!fused_bin) {
-      if (VT > 0 && (size_t)d.pair_capacity / VT <= (size_t)GSR_WINDOWED_SHORT) GSR_TILES(false, 2048);
-      else GSR_TILES(false, 4096);
-    }
+    auto tiles = [&](auto gather, bool short_lists) {
+      dispatch_bools([&](auto sh, auto x) { hipLaunchKernelGGL((k_tile_fwd<decltype(gather)::value, sh.value ? 2048 : 4096, x.value>), tgrid, dim3(kFwdThreads), 0, st, p); },
+                     short_lists, extra);
+    };
+    // (more tiles than five workgroups per CU hold at once: the compact instance, six per CU.  Round 5: with the extra channel too - until
+    // stage A formed its weights after the death decision (blend_range) that instance spilled the record in flight at 80 registers)
+    const bool compact = VT > (size_t)GSR_PF_COMPACT_MIN_TILES;
+    if (!fused_bin) tiles(std::false_type{}, VT > 0 && (size_t)d.pair_capacity / VT <= (size_t)GSR_WINDOWED_SHORT);
     // the usual case (cursor gather + prefix rank): long lists.  A slot of at most kPrefix (+ 25 %) entries means lists that are
     // ranked whole anyway - many small tiles, e.g. one 1024 x 1024 view of the 300 k scene: 78 entries per tile.  With the 32 KB
     // instance those were better off with k_tile_fwd's smaller LDS footprint (192 vs 217 us for that view, round 4); the COMPACT
     // instance (25.8 KB, 80 registers: six workgroups per CU, like k_tile_fwd's) keeps its cheaper gather - no scan over the rows,
     // four barriers fewer - and takes them when the call has more tiles than the chip holds at once: that view 174.3 -> 167.3 us.
-    else if (p.stride <= 2048u && (p.stride > (uint32_t)(kPrefix + kPrefix / 4) || VT > (size_t)GSR_PF_COMPACT_MIN_TILES) &&
-             p.rows <= kSortThreads) {
-      // (more tiles than five workgroups per CU hold at once: the compact instance, six per CU.  Round 5: with the extra channel too - until
-      // stage A formed its weights after the death decision (blend_range) that instance spilled the record in flight at 80 registers)
-      const bool compact = VT > (size_t)GSR_PF_COMPACT_MIN_TILES;
-      if (d.has_extra && compact) hipLaunchKernelGGL((k_tile_fwd_prefix<true, true>), tgrid, dim3(kFwdThreads), 0, st, p);
-      else if (d.has_extra) hipLaunchKernelGGL((k_tile_fwd_prefix<true, false>), tgrid, dim3(kFwdThreads), 0, st, p);
-      else if (compact) hipLaunchKernelGGL((k_tile_fwd_prefix<false, true>), tgrid, dim3(kFwdThreads), 0, st, p);
-      else hipLaunchKernelGGL((k_tile_fwd_prefix<false, false>), tgrid, dim3(kFwdThreads), 0, st, p);
-    } else if (p.stride <= 2048u) GSR_TILES(true, 2048);
-    else GSR_TILES(true, 4096);
-#undef GSR_TILES
+    else if (p.stride <= 2048u && (p.stride > (uint32_t)(kPrefix + kPrefix / 4) || compact) && p.rows <= kSortThreads)
+      dispatch_bools([&](auto x, auto c) { hipLaunchKernelGGL((k_tile_fwd_prefix<x.value, c.value>), tgrid, dim3(kFwdThreads), 0, st, p); }, extra, compact);
+    else tiles(std::true_type{}, p.stride <= 2048u);
   }
   GSR_STAGE_DONE(4);
   GSR_MARK();
-#undef GSR_STAGE_DONE
-#undef GSR_MARK
   GSR_CHECK(hipGetLastError());
   return GSR_OK;
 }
@@ -4470,8 +4466,8 @@ static int backward_impl(const GsrDims* dims, const GsrView* views, const float*
                          const float* opacities, const float* colors, const float* extra, const void* geom,
                          const void* bin, const void* img, const float* dL_dcolor, const float* dL_dextra_img,
                          void* scratch, float* dL_dmeans, float* dL_dcov6, float* dL_dopacities,
-                         float* dL_dcolors, float* dL_dextra, float* dL_dmeans2D, void* stream_, const SrArgs* sr,
-                         float* dL_dviews = nullptr, float* pose_partials = nullptr, int depth_term_only = 0) {
+                         float* dL_dcolors, float* dL_dextra, float* dL_dmeans2D, void* stream_, hipEvent_t* ev,
+                         const SrArgs* sr, float* dL_dviews = nullptr, float* pose_partials = nullptr, int depth_term_only = 0) {
   if (!call_dims_ok(dims, sr)) return GSR_ERR_INVALID_ARGUMENT;
   hipStream_t st = static_cast<hipStream_t>(stream_);
   const GsrDims& d = *dims;
@@ -4488,40 +4484,22 @@ static int backward_impl(const GsrDims* dims, const GsrView* views, const float*
   p.scratch = own_rows ? reinterpret_cast<float*>(p.grad_rows) : static_cast<float*>(scratch);
   p.dL_dmeans = dL_dmeans; p.dL_dcov6 = dL_dcov6; p.dL_dopac = dL_dopacities; p.dL_dcolors = dL_dcolors;
   p.dL_dextra = d.has_extra ? dL_dextra : nullptr; p.dL_dmeans2D = dL_dmeans2D;
-  hipEvent_t* ev = g_bwd_events;
   int e = 0;
-#define GSR_STAGE_DONE(idx)                                                            \
-  do {                                                                                  \
-    if (d.flags & GSR_FLAG_DEBUG) {                                                     \
-      if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) {  \
-        g_failed_stage = (idx);                                                         \
-        return GSR_ERR_LAUNCH;                                                          \
-      }                                                                                 \
-    }                                                                                   \
-  } while (0)
-  if (ev) GSR_CHECK(hipEventRecord(ev[e++], st));
+  GSR_MARK();
   const bool det = (d.flags & GSR_FLAG_DETERMINISTIC) != 0;
   if (!own_rows) GSR_CHECK(hipMemsetAsync(scratch, 0, scratch_bytes_of(d), st));
   const dim3 bgrid((unsigned)p.g.T, (unsigned)V);
-  if (p.dL_dextra_img) {
-    if (det) hipLaunchKernelGGL((k_blend_bwd<true, true>), bgrid, dim3(kBwdThreads), 0, st, p);
-    else hipLaunchKernelGGL((k_blend_bwd<true, false>), bgrid, dim3(kBwdThreads), 0, st, p);
-  } else {
-    if (det) hipLaunchKernelGGL((k_blend_bwd<false, true>), bgrid, dim3(kBwdThreads), 0, st, p);
-    else hipLaunchKernelGGL((k_blend_bwd<false, false>), bgrid, dim3(kBwdThreads), 0, st, p);
-  }
+  dispatch_bools([&](auto x, auto dt) { hipLaunchKernelGGL((k_blend_bwd<x.value, dt.value>), bgrid, dim3(kBwdThreads), 0, st, p); },
+                 p.dL_dextra_img != nullptr, det);
   GSR_STAGE_DONE(0);
-  if (ev) GSR_CHECK(hipEventRecord(ev[e++], st));
+  GSR_MARK();
   const int rowf = 3 * d.sh_coeffs, ldstride = rowf | 1;
   const size_t shmem = d.sh_coeffs > 0 ? (size_t)64 * ldstride * sizeof(float) : 0;
   const dim3 pgrid((unsigned)((N + 63) / 64), (unsigned)d.num_sets);
   const bool sh_frame = (d.flags & GSR_FLAG_SH_IN_FRAME) && d.sh_coeffs > 0;
-  auto launch_pbwd = [&](auto pose_c) {  // the instance of the call: camera gradient, saved Jacobian, harmonics in their frame
-    constexpr int kP = decltype(pose_c)::value;
-    if (sh_frame && p.shj) hipLaunchKernelGGL((k_preprocess_bwd<kP, true, true>), pgrid, dim3(64), shmem, st, p);
-    else if (sh_frame) hipLaunchKernelGGL((k_preprocess_bwd<kP, false, true>), pgrid, dim3(64), shmem, st, p);
-    else if (p.shj) hipLaunchKernelGGL((k_preprocess_bwd<kP, true>), pgrid, dim3(64), shmem, st, p);
-    else hipLaunchKernelGGL((k_preprocess_bwd<kP, false>), pgrid, dim3(64), shmem, st, p);
+  auto launch_pbwd = [&](auto pose) {  // the instance of the call: camera gradient, saved Jacobian, harmonics in their frame
+    dispatch_bools([&](auto frame, auto j) { hipLaunchKernelGGL((k_preprocess_bwd<decltype(pose)::value, j.value, frame.value>), pgrid, dim3(64), shmem, st, p); },
+                   sh_frame, p.shj != nullptr);
   };
   if (dL_dviews && depth_term_only) {
     if (!pose_partials) return GSR_ERR_INVALID_ARGUMENT;
@@ -4554,8 +4532,7 @@ static int backward_impl(const GsrDims* dims, const GsrView* views, const float*
     launch_pbwd(std::integral_constant<int, 0>{});
   }
   GSR_STAGE_DONE(1);
-#undef GSR_STAGE_DONE
-  if (ev) GSR_CHECK(hipEventRecord(ev[e++], st));
+  GSR_MARK();
   GSR_CHECK(hipGetLastError());
   return GSR_OK;
 }
@@ -4566,7 +4543,7 @@ int gsr_backward(const GsrDims* dims, const GsrView* views, const float* means, 
                  void* scratch, float* dL_dmeans, float* dL_dcov6, float* dL_dopacities,
                  float* dL_dcolors, float* dL_dextra, float* dL_dmeans2D, void* stream_) {
   return backward_impl(dims, views, means, cov6, opacities, colors, extra, geom, bin, img, dL_dcolor, dL_dextra_img, scratch,
-                       dL_dmeans, dL_dcov6, dL_dopacities, dL_dcolors, dL_dextra, dL_dmeans2D, stream_, nullptr);
+                       dL_dmeans, dL_dcov6, dL_dopacities, dL_dcolors, dL_dextra, dL_dmeans2D, stream_, nullptr, nullptr);
 }
 
 int gsr_forward_scale_rot(const GsrDims* dims, const GsrView* views, const float* means, const float* scale_rot,
@@ -4585,7 +4562,7 @@ int gsr_backward_scale_rot(const GsrDims* dims, const GsrView* views, const floa
                            float* dL_dopacities, float* dL_dcolors, float* dL_dextra, float* dL_dmeans2D, void* stream_) {
   const SrArgs sr{frames, num_frames};
   return backward_impl(dims, views, means, scale_rot, opacities, colors, extra, geom, bin, img, dL_dcolor, dL_dextra_img,
-                       scratch, dL_dmeans, dL_dscale_rot, dL_dopacities, dL_dcolors, dL_dextra, dL_dmeans2D, stream_, &sr);
+                       scratch, dL_dmeans, dL_dscale_rot, dL_dopacities, dL_dcolors, dL_dextra, dL_dmeans2D, stream_, nullptr, &sr);
 }
 
 size_t gsr_pose_partials_bytes(const GsrDims* dims) {
@@ -4599,15 +4576,15 @@ int gsr_backward_ex(const GsrDims* dims, const GsrView* views, const float* mean
                     float* dL_dopacities, float* dL_dcolors, float* dL_dextra, float* dL_dmeans2D, const GsrBackwardOptions* opt,
                     void* stream_) {
   if (!opt) return backward_impl(dims, views, means, cov, opacities, colors, extra, geom, bin, img, dL_dcolor, dL_dextra_img, scratch,
-                                 dL_dmeans, dL_dcov, dL_dopacities, dL_dcolors, dL_dextra, dL_dmeans2D, stream_, nullptr);
+                                 dL_dmeans, dL_dcov, dL_dopacities, dL_dcolors, dL_dextra, dL_dmeans2D, stream_, nullptr, nullptr);
   const SrArgs sr{opt->frames, opt->num_frames};
   return backward_impl(dims, views, means, cov, opacities, colors, extra, geom, bin, img, dL_dcolor, dL_dextra_img, scratch,
-                       dL_dmeans, dL_dcov, dL_dopacities, dL_dcolors, dL_dextra, dL_dmeans2D, stream_, opt->scale_rot ? &sr : nullptr,
+                       dL_dmeans, dL_dcov, dL_dopacities, dL_dcolors, dL_dextra, dL_dmeans2D, stream_, nullptr, opt->scale_rot ? &sr : nullptr,
                        opt->dL_dviews, opt->pose_partials, opt->depth_term_only);
 }
 
 // Measurement aid (bench.py): gsr_backward with events between its two stages (blend backward, preprocess backward);
-// synchronises the stream.  Not thread-safe (uses a process-wide event slot); never used on the product path.
+// synchronises the stream.  Never used on the product path.
 int gsr_backward_profile(const GsrDims* dims, const GsrView* views, const float* means, const float* cov6,
                          const float* opacities, const float* colors, const float* extra, const void* geom,
                          const void* bin, const void* img, const float* dL_dcolor, const float* dL_dextra_img,
@@ -4617,10 +4594,8 @@ int gsr_backward_profile(const GsrDims* dims, const GsrView* views, const float*
   hipStream_t st = static_cast<hipStream_t>(stream_);
   hipEvent_t ev[GSR_BWD_STAGES + 1];
   for (int i = 0; i <= GSR_BWD_STAGES; ++i) GSR_CHECK(hipEventCreate(&ev[i]));
-  g_bwd_events = ev;
-  int rc = gsr_backward(dims, views, means, cov6, opacities, colors, extra, geom, bin, img, dL_dcolor, dL_dextra_img,
-                        scratch, dL_dmeans, dL_dcov6, dL_dopacities, dL_dcolors, dL_dextra, dL_dmeans2D, stream_);
-  g_bwd_events = nullptr;
+  int rc = backward_impl(dims, views, means, cov6, opacities, colors, extra, geom, bin, img, dL_dcolor, dL_dextra_img,
+                         scratch, dL_dmeans, dL_dcov6, dL_dopacities, dL_dcolors, dL_dextra, dL_dmeans2D, stream_, ev, nullptr);
   for (int i = 0; i < GSR_BWD_STAGES; ++i) stage_ms[i] = 0.f;
   if (rc == GSR_OK && dims->num_views > 0 && dims->num_gaussians > 0) {
     if (hipStreamSynchronize(st) != hipSuccess) rc = GSR_ERR_LAUNCH;

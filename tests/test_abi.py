@@ -30,6 +30,33 @@ def test_library_exports_every_declared_symbol():
     assert b"gfx950" in lib.gsr_build_info()
 
 
+def test_source_stamp_covers_every_file_the_library_is_built_from(tmp_path):
+    """One byte changed in gsr_hip.hip, in a header next to it or in include/gsr.h changes the stamp build() compares; the torch
+    binding, a library of its own, does not.  On a copy of the sources: nothing is written into the tree."""
+    import shutil
+
+    shutil.copytree(os.path.dirname(_lib.SRC), tmp_path / "csrc")
+    shutil.copy(_lib.HEADER, tmp_path / "gsr.h")
+
+    def stamp():
+        return _lib._source_stamp(csrc=str(tmp_path / "csrc"), header=str(tmp_path / "gsr.h"))
+
+    assert stamp() == _lib._source_stamp()  # the copy is the tree
+    before = stamp()
+    (tmp_path / "csrc" / "gsr_stage.h").write_bytes(b"// a header gsr_hip.hip would include\n")
+    assert stamp() != before, "a new file next to gsr_hip.hip does not make the library stale"
+    for path in [tmp_path / "csrc" / "gsr_hip.hip", tmp_path / "csrc" / "gsr_stage.h", tmp_path / "gsr.h"]:
+        before, data = stamp(), path.read_bytes()
+        path.write_bytes(data[:-1] + b" ")
+        assert stamp() != before, f"a change to {path.name} does not make the library stale"
+        path.write_bytes(data)
+        assert stamp() == before
+    with open(tmp_path / "csrc" / "gsr_torch.cpp", "ab") as f:
+        f.write(b"\n")
+    assert stamp() == before
+    assert {os.path.basename(s) for s in _lib.hip_sources()} == {"gsr_hip.hip", "gsr.h"}
+
+
 def test_struct_layouts_match_header():
     assert ctypes.sizeof(_lib.GsrDims) == 56  # 12 x int32 + int64
     assert rasterizer.VIEW_FLOATS * 4 == 192  # sizeof(GsrView)
