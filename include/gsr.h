@@ -16,7 +16,7 @@
  *
  * Conventions (all pointers are DEVICE pointers owned by the caller unless noted; the library
  * allocates nothing and keeps no state between calls, enqueues all work on `stream` as a plain chain of kernel launches
- * (capturable into a HIP graph), never synchronises the host (except in GSR_FLAG_DEBUG mode and in the *_profile aids), never
+ * (capturable into a HIP graph), never synchronises the host (except in GSR_FLAG_DEBUG mode and when an _ex call is given stage_ms), never
  * throws; every entry point returns GSR_OK or a negative error code):
  *   means     (num_sets, N, 3)   fp32 world-space centres                     (means3D)
  *   cov6      (num_sets, N, 6)   fp32 xx,xy,xz,yy,yz,zz                       (cov3D_precomp)
@@ -41,7 +41,7 @@ extern "C" {
 #define GSR_ERR_INVALID_ARGUMENT (-1)
 #define GSR_ERR_LAUNCH (-2)
 #define GSR_ERR_UNSUPPORTED (-3)
-#define GSR_ABI_VERSION 3
+#define GSR_ABI_VERSION 4
 /* GsrDims.flags input-layout bits: the arrays PF3plat's `Gaussians` record carries (src/model/types.py:7-18) can be passed
  * as they are, with no re-layout copy (the reference wrapper makes two per call: cuda_splatting.py:75 and :115,123). */
 #define GSR_FLAG_SH_PLANAR 0x4  /* colors are (num_sets, N, 3, M) "harmonics" instead of (num_sets, N, M, 3); grads likewise */
@@ -49,7 +49,7 @@ extern "C" {
                                    the gradient on the upper triangle only (as the reference's triu gather yields) */
 /* Harmonics in their group's frame (the encoder's adapter hands them over unrotated: gaussian_adapter.py:90-92 rotates them by
  * the source view's camera-to-world rotation F in torch).  GSR_FLAG_SH_IN_FRAME: the harmonics of Gaussian i of set s are in
- * the coordinates of frames[s, i / (N / F)] (the `frames` of gsr_forward_scale_rot), and the kernels evaluate them at the view
+ * the coordinates of frames[s, i / (N / F)] (the `frames` of GsrForwardOptions), and the kernels evaluate them at the view
  * direction d carried into that frame instead of rotating the coefficients.  With B the basis the kernels evaluate and
  * rotate_sh the rotation of pf3plat_amd/sh_rotation.py, for every rotation F and unit direction d:
  *   basis "rasterizer" (no second bit):     B(d) . rotate_sh(c, F) = B(F^T d) . c
@@ -57,7 +57,7 @@ extern "C" {
  *     P: (x, y, z) -> (z, x, y) (e3nn's polar axis is y), Z = diag(-1, -1, 1) (the (-1)^m phase: a half-turn about z).
  * The image and every gradient are those of the rotated coefficients; dL_dcolors comes back in the frame's coordinates, the
  * direction's gradient (dL_dmeans, and the camera centre of gsr_backward_ex) in world coordinates.  Frames get no gradient.
- * Valid only through gsr_forward_scale_rot, gsr_backward_scale_rot and gsr_backward_ex with opt->scale_rot != 0, with
+ * Valid only through gsr_forward_ex and gsr_backward_ex with opt->scale_rot != 0, with
  * non-NULL frames and sh_coeffs > 0 (GSR_FLAG_SH_FRAME_E3NN only together with GSR_FLAG_SH_IN_FRAME); anything else, and
  * gsr_workspace_sizes and the other helpers, return GSR_ERR_INVALID_ARGUMENT.  The bits do not change any workspace size:
  * size with the same dims without them.  At an evaluated degree of 0 they change nothing. */
@@ -192,45 +192,58 @@ int gsr_backward(const GsrDims* dims, const GsrView* views, const float* means, 
                  void* scratch, float* dL_dmeans, float* dL_dcov6, float* dL_dopacities,
                  float* dL_dcolors, float* dL_dextra, float* dL_dmeans2D, void* stream);
 
-/* The same two calls with the covariances in the form PF3plat's encoder produces them (reference
- * src/model/encoder/common/gaussian_adapter.py:63-83, gaussians.py:8-44): `scale_rot` (num_sets, N, 7) = scale x, y, z and a
+/* The extended calls: gsr_forward / gsr_backward with an options struct in front of `stream`.  opt == NULL: exactly the plain call.
+ *
+ * scale_rot != 0: the covariances in the form PF3plat's encoder produces them (reference
+ * src/model/encoder/common/gaussian_adapter.py:63-83, gaussians.py:8-44): `cov` is (num_sets, N, 7) = scale x, y, z and a
  * quaternion x, y, z, w; Sigma = M diag(scale^2) M^T with M = F Rq, Rq the rotation of the quaternion (normalised through
  * two_s = 2 / (|q|^2 + 1e-8), as quaternion_to_matrix does) and F an optional rotation into world space: `frames`
  * (num_sets, num_frames, 3, 3), the N Gaussians of a set being num_frames equal consecutive groups (one per source view:
  * the camera-to-world rotation of gaussian_adapter.py:81-83); NULL / 0 = no frame.  The covariance is built in registers
- * on load - no (N, 3, 3) array exists - and the backward returns dL_dscale_rot (num_sets, N, 7) directly.  GSR_FLAG_COV_3X3 does
- * not apply.  Everything else as in gsr_forward / gsr_backward. */
-int gsr_forward_scale_rot(const GsrDims* dims, const GsrView* views, const float* means, const float* scale_rot,
-                          const float* frames, int num_frames, const float* opacities, const float* colors,
-                          const float* extra, float* out_color, float* out_extra, int32_t* radii, void* geom, void* bin,
-                          void* img, void* stream);
-int gsr_backward_scale_rot(const GsrDims* dims, const GsrView* views, const float* means, const float* scale_rot,
-                           const float* frames, int num_frames, const float* opacities, const float* colors,
-                           const float* extra, const void* geom, const void* bin, const void* img, const float* dL_dcolor,
-                           const float* dL_dextra_img, void* scratch, float* dL_dmeans, float* dL_dscale_rot,
-                           float* dL_dopacities, float* dL_dcolors, float* dL_dextra, float* dL_dmeans2D, void* stream);
-
-/* gsr_backward with options (camera-pose gradients, opt-in - the reference gets none through the operator
- * although PF3plat learns poses).  opt == NULL: exactly gsr_backward.  scale_rot != 0: `cov` / `dL_dcov` are (S, N, 7) records
- * with `frames` / `num_frames` as in gsr_backward_scale_rot.  dL_dviews != NULL: (V, 48) floats laid out like GsrView receive
+ * on load - no (N, 3, 3) array exists - and the backward returns dL_dcov as (num_sets, N, 7) directly.  GSR_FLAG_COV_3X3 does
+ * not apply.  Without scale_rot, `frames` / `num_frames` are not read.
+ *
+ * stage_ms != NULL (measurement aid for bench.py, never on the product path): a host array of GSR_FWD_STAGES / GSR_BWD_STAGES
+ * floats.  The same launch chain with a HIP event recorded on `stream` between stages; the call synchronises the stream and
+ * returns per-stage milliseconds (zeros for an empty call).
+ * Forward stages, in launch order: 0 the colour pass when it is a launch of its own (gsr_colour_in_binning == 0; otherwise
+ * empty: it runs inside stage 1) 1 preprocess (geometry, hit masks and - images of up to 20 480 tiles - the whole binning)
+ * 2 count + tile scans and 3 emit (windowed binning path only: empty, i.e. one event gap each, otherwise) 4 the tile launch
+ * (per tile: gather + sort of its list, then its blend).
+ * Backward stages: 0 blend backward 1 preprocess backward.
+ *
+ * dL_dviews != NULL (camera-pose gradients, opt-in - the reference gets none through the operator although
+ * PF3plat learns poses): (V, 48) floats laid out like GsrView receive
  * dL/d viewmatrix [0, 16), dL/d projmatrix [16, 32), dL/d campos [32, 35) (zeros behind) - the two matrices as independent
  * inputs, the way the operator takes them; tan-fov, background and scale get none.  Every place the forward reads a camera
  * is differentiated (EWA covariance through t = V p and J Wr, projection to pixel coordinates, view direction of the
  * harmonics, depth of the built-in extra channel); depth ordering and culling are not, as for the Gaussians.  pose_partials:
  * gsr_pose_partials_bytes(dims) bytes of scratch (four rows per view and 64-Gaussian unit; reduced in a fixed order). */
+#define GSR_FWD_STAGES 5
+#define GSR_BWD_STAGES 2
+typedef struct GsrForwardOptions {
+  const float* frames;
+  int32_t num_frames;
+  int32_t scale_rot;
+  float* stage_ms; /* [GSR_FWD_STAGES] host, or NULL */
+} GsrForwardOptions;
+int gsr_forward_ex(const GsrDims* dims, const GsrView* views, const float* means, const float* cov, const float* opacities,
+                   const float* colors, const float* extra, float* out_color, float* out_extra, int32_t* radii, void* geom,
+                   void* bin, void* img, const GsrForwardOptions* opt, void* stream);
 typedef struct GsrBackwardOptions {
   const float* frames;
   int32_t num_frames;
   int32_t scale_rot;
   float* dL_dviews;
   float* pose_partials;
+  float* stage_ms; /* [GSR_BWD_STAGES] host, or NULL */
   int32_t depth_term_only; /* != 0: dL_dviews receives ONLY what the built-in depth channel (GSR_FLAG_EXTRA_MODE) sends to the
                               camera - floats 2, 6, 10, 14 of the view matrix, the row that forms z; zeros elsewhere.  This is the
                               one camera gradient the reference's own training graph carries: its depth render forms z with
                               extrinsics.inverse() in torch (cuda_splatting.py:239-242, extrinsics requiring grad at
                               model_wrapper.py:148-156) while nothing reaches a camera through the rasterizer.  Costs four wave
                               reductions in the backward preprocess instead of thirty-five and two small reduce launches. */
-  int32_t reserved_;
+  int32_t reserved_;       /* 0: spells the tail of the struct out (its size is a multiple of its pointers' alignment) */
 } GsrBackwardOptions;
 size_t gsr_pose_partials_bytes(const GsrDims* dims);
 int gsr_backward_ex(const GsrDims* dims, const GsrView* views, const float* means, const float* cov, const float* opacities,
@@ -239,9 +252,11 @@ int gsr_backward_ex(const GsrDims* dims, const GsrView* views, const float* mean
                     float* dL_dopacities, float* dL_dcolors, float* dL_dextra, float* dL_dmeans2D, const GsrBackwardOptions* opt,
                     void* stream);
 
-/* GSR_FLAG_DEBUG: the stage of the last failed call of this host thread (forward: 0 colour, 1 preprocess/binning,
- * 2 count + scans, 3 emit, 4 per-tile sort + blend; backward: 0 blend backward, 1 preprocess backward), or -1. */
+/* GSR_FLAG_DEBUG: the stage of the last failed call of this host thread (an index into the stages above), or -1; and the
+ * name of stage `stage` of the forward (backward == 0) or the backward - the one statement of the names every caller prints -
+ * or NULL outside [0, GSR_FWD_STAGES) / [0, GSR_BWD_STAGES). */
 int gsr_last_failed_stage(void);
+const char* gsr_stage_name(int backward, int stage);
 
 /* Bytes of the `scratch` buffer gsr_backward needs for these dims (V * N * 12 floats; twice that with
  * GSR_FLAG_DETERMINISTIC). */
@@ -320,12 +335,12 @@ int gsr_image_loss_finish(int num_images, int height, int width, const float* pa
  *        `raw_row_stride` floats apart (>= 7 + 3 M) - the encoder hands over the slice `gaussians[..., 2:]` of an 84-wide tensor
  *        (encoder_costvolume.py:535-538), which is read where it is (stride 84);
  *   means (G, P, 3) = t + depth R normalise(K^-1 (u, v, 1));
- *   scale_rot (G, P, 7), the record form gsr_forward_scale_rot takes: (scale_min + (scale_max - scale_min) sigmoid(r)) x depth x
+ *   scale_rot (G, P, 7), the record form gsr_forward_ex takes with scale_rot: (scale_min + (scale_max - scale_min) sigmoid(r)) x depth x
  *        0.1 sum(K[:2, :2]^-1 (1 / width, 1 / height)), and q / (|q| + eps);
  *   harmonics (G, P, 3, M) (GSR_FLAG_SH_PLANAR layout): the raw coefficients times 1 (DC) or 0.1 x 0.25^l (band l).
  * K^-1 and the multiplier are formed once per group.  Opacities do not pass through here.
  * gsr_adapt_backward takes the forward's inputs again (everything is recomputed: nothing is saved) and the cotangents dL_dmeans
- * (G, P, 3), dL_dscale_rot (G, P, 7) - the array gsr_backward_scale_rot writes - and dL_dharmonics (G, P, 3, M), each of which
+ * (G, P, 3), dL_dscale_rot (G, P, 7) - the array gsr_backward_ex writes with scale_rot - and dL_dharmonics (G, P, 3, M), each of which
  * may be NULL (zeros).  Outputs, all fully written: dL_draw (G, P, 7 + 3 M) contiguous, dL_ddepths (G, P), dL_dcoordinates (G, P, 2)
  * and dL_dextrinsics (G, 4, 4): rows 0-2 x columns 0-2 the sum over the group of dmean (x) (depth ray), column 3 the sum of
  * dmean, bottom row zero (PF3plat's extrinsics are learned poses: this is how the render loss reaches them through the means).
@@ -342,26 +357,6 @@ int gsr_adapt_backward(int num_groups, int gaussians_per_group, int sh_degree, c
                        float scale_max, int height, int width, float eps, const float* dL_dmeans, const float* dL_dscale_rot,
                        const float* dL_dharmonics, float* dL_draw, float* dL_ddepths, float* dL_dcoordinates, float* dL_dextrinsics,
                        float* partials, void* stream);
-
-/* Measurement aids for bench.py (never on the product path): the same launch chains with a HIP event recorded on
- * `stream` between stages; they synchronise the stream and return per-stage milliseconds.
- * Forward stages, in launch order: 0 the colour pass when it is a launch of its own (gsr_colour_in_binning == 0; otherwise
- * empty: it runs inside stage 1) 1 preprocess (geometry, hit masks and - images of up to 20 480 tiles - the whole binning)
- * 2 count + tile scans and 3 emit (windowed binning path only: empty, i.e. one event gap each, otherwise) 4 the tile launch
- * (per tile: gather + sort of its list, then its blend).
- * Backward stages: 0 blend backward 1 preprocess backward. */
-#define GSR_FWD_STAGES 5
-#define GSR_BWD_STAGES 2
-int gsr_forward_profile(const GsrDims* dims, const GsrView* views, const float* means, const float* cov6,
-                        const float* opacities, const float* colors, const float* extra, float* out_color,
-                        float* out_extra, int32_t* radii, void* geom, void* bin, void* img, void* stream,
-                        float* stage_ms /* [GSR_FWD_STAGES] host */);
-int gsr_backward_profile(const GsrDims* dims, const GsrView* views, const float* means, const float* cov6,
-                         const float* opacities, const float* colors, const float* extra, const void* geom,
-                         const void* bin, const void* img, const float* dL_dcolor, const float* dL_dextra_img,
-                         void* scratch, float* dL_dmeans, float* dL_dcov6, float* dL_dopacities,
-                         float* dL_dcolors, float* dL_dextra, float* dL_dmeans2D, void* stream,
-                         float* stage_ms /* [GSR_BWD_STAGES] host */);
 
 /* Measurement aid: 1 when gsr_forward runs the colour pass inside the binning launch for these dims (two launches: binning +
  * colour, per-tile sort + blend), 0 when the colour pass is a launch of its own (images of more than 4608 8x8 tiles, more than

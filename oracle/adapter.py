@@ -1,7 +1,7 @@
 """Oracle side of the scale / rotation input form: the covariance PF3plat's encoder builds between its raw outputs and the
 decoder, restated with differentiable CPU torch ops (float32 or float64).  TEST INFRASTRUCTURE - only tests/,
 __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this; the product builds the covariance inside its
-kernels (gsr_forward_scale_rot) and is compared with these functions by the tests.
+kernels (gsr_forward_ex with scale_rot) and is compared with these functions by the tests.
 
 Pinned to the reference by tests/golden/adapter_fixtures.npz (tests/test_adapter.py): covariances, scales, rotations and
 means recorded from the reference's own `GaussianAdapter.forward` / `build_covariance` for seeded inputs.

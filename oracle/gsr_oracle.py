@@ -21,15 +21,32 @@ _LIB_PATH = os.path.join(_HERE, "libgsr_oracle.so")
 _lib = None
 
 
+def _source_stamp(src) -> str:
+    import hashlib
+
+    h = hashlib.sha256()
+    for path in src:
+        with open(path, "rb") as f:
+            h.update(os.path.basename(path).encode() + b"\0" + f.read())
+    return h.hexdigest()
+
+
 def build_oracle(force: bool = False) -> str:
-    """Compile the oracle with gcc (a few seconds).  Building the checker is not using it."""
+    """Compile the oracle with gcc (a few seconds).  Building the checker is not using it.  Stale by CONTENT (a stamp file next
+    to the .so, as pf3plat_amd/_lib.py keeps for the product library), not by modification time: a copy of the tree keeps the files and
+    not the order of their times, and a twin built from another GSR_ABI_VERSION refuses every call."""
     src = [os.path.join(_HERE, f) for f in ("gsr_oracle.cpp", "gsr_oracle.hpp", "gsr_cpu.h", "Makefile")]
     src.append(os.path.join(os.path.dirname(_HERE), "include", "gsr.h"))  # the twin's signatures and GSR_ABI_VERSION live there
-    stale = (not os.path.exists(_LIB_PATH)) or any(
-        os.path.getmtime(s) > os.path.getmtime(_LIB_PATH) for s in src
-    )
+    stamp = _source_stamp(src)
+    try:
+        with open(_LIB_PATH + ".stamp") as f:
+            stale = not os.path.exists(_LIB_PATH) or f.read().strip() != stamp
+    except OSError:
+        stale = True
     if force or stale:
-        subprocess.run(["make", "-C", _HERE, "-B" if force else "-s"], check=True, capture_output=True)
+        subprocess.run(["make", "-C", _HERE, "-B", "-s"], check=True, capture_output=True)
+        with open(_LIB_PATH + ".stamp", "w") as f:
+            f.write(stamp + "\n")
     return _LIB_PATH
 
 

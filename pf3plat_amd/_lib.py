@@ -17,7 +17,7 @@ REPO_ROOT = os.path.dirname(_HERE)
 SRC = os.path.join(_HERE, "csrc", "gsr_hip.hip")
 HEADER = os.path.join(REPO_ROOT, "include", "gsr.h")
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "libgsr_hip.so")  # (override: tools/ablate.py's measurement build)
-GSR_ABI_VERSION = 3  # bump with include/gsr.h whenever a struct, a workspace layout or a signature changes
+GSR_ABI_VERSION = 4  # bump with include/gsr.h whenever a struct, a workspace layout or a signature changes
 SCREEN_GRAD_FLOATS = 12
 FLAG_PREFILTERED = 0x1  # accepted and ignored, as upstream with prefiltered = False
 FLAG_DEBUG = 0x2  # upstream's `debug`: synchronise + check after every stage
@@ -45,10 +45,15 @@ class GsrDims(ctypes.Structure):
     ]
 
 
+class GsrForwardOptions(ctypes.Structure):
+    _fields_ = [("frames", ctypes.c_void_p), ("num_frames", ctypes.c_int32), ("scale_rot", ctypes.c_int32),
+                ("stage_ms", ctypes.POINTER(ctypes.c_float))]
+
+
 class GsrBackwardOptions(ctypes.Structure):
     _fields_ = [("frames", ctypes.c_void_p), ("num_frames", ctypes.c_int32), ("scale_rot", ctypes.c_int32),
-                ("dL_dviews", ctypes.c_void_p), ("pose_partials", ctypes.c_void_p), ("depth_term_only", ctypes.c_int32),
-                ("reserved_", ctypes.c_int32)]
+                ("dL_dviews", ctypes.c_void_p), ("pose_partials", ctypes.c_void_p), ("stage_ms", ctypes.POINTER(ctypes.c_float)),
+                ("depth_term_only", ctypes.c_int32), ("reserved_", ctypes.c_int32)]
 
 
 def find_hipcc() -> str:
@@ -234,6 +239,8 @@ def load():
     lib.gsr_geom_layout.argtypes = [dp, i64p]
     lib.gsr_last_failed_stage.restype = ctypes.c_int
     lib.gsr_last_failed_stage.argtypes = []
+    lib.gsr_stage_name.restype = ctypes.c_char_p
+    lib.gsr_stage_name.argtypes = [ctypes.c_int, ctypes.c_int]
     lib.gsr_backward_scratch_bytes.restype = ctypes.c_size_t
     lib.gsr_backward_scratch_bytes.argtypes = [dp]
     lib.gsr_cov_from_scale_rot.restype = ctypes.c_int
@@ -246,16 +253,14 @@ def load():
     lib.gsr_forward.argtypes = [dp] + [vp] * 13
     lib.gsr_backward.restype = ctypes.c_int
     lib.gsr_backward.argtypes = [dp] + [vp] * 19
-    lib.gsr_forward_scale_rot.restype = ctypes.c_int
-    lib.gsr_forward_scale_rot.argtypes = [dp, vp, vp, vp, vp, ctypes.c_int] + [vp] * 10
+    lib.gsr_forward_ex.restype = ctypes.c_int
+    lib.gsr_forward_ex.argtypes = [dp] + [vp] * 12 + [ctypes.POINTER(GsrForwardOptions), vp]
     lib.gsr_colour_in_binning.restype = ctypes.c_int
     lib.gsr_colour_in_binning.argtypes = [dp]
     lib.gsr_backward_ex.restype = ctypes.c_int
     lib.gsr_backward_ex.argtypes = [dp] + [vp] * 18 + [ctypes.POINTER(GsrBackwardOptions), vp]
     lib.gsr_pose_partials_bytes.restype = ctypes.c_size_t
     lib.gsr_pose_partials_bytes.argtypes = [dp]
-    lib.gsr_backward_scale_rot.restype = ctypes.c_int
-    lib.gsr_backward_scale_rot.argtypes = [dp, vp, vp, vp, vp, ctypes.c_int] + [vp] * 16
     lib.gsr_image_loss_partials.restype = ctypes.c_size_t
     lib.gsr_image_loss_partials.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
     lib.gsr_image_loss.restype = ctypes.c_int
@@ -279,11 +284,6 @@ def load():
     lib.gsr_adapt.argtypes = adapt_head + [vp] * 4
     lib.gsr_adapt_backward.restype = ctypes.c_int
     lib.gsr_adapt_backward.argtypes = adapt_head + [vp] * 9
-    fp = ctypes.POINTER(ctypes.c_float)
-    lib.gsr_forward_profile.restype = ctypes.c_int
-    lib.gsr_forward_profile.argtypes = [dp] + [vp] * 13 + [fp]
-    lib.gsr_backward_profile.restype = ctypes.c_int
-    lib.gsr_backward_profile.argtypes = [dp] + [vp] * 19 + [fp]
     if lib.gsr_abi_version() != GSR_ABI_VERSION:
         raise RuntimeError(f"libgsr_hip.so ABI {lib.gsr_abi_version()} != expected {GSR_ABI_VERSION}; rebuild")
     _lib = lib
@@ -292,14 +292,14 @@ def load():
 
 EXPORTED_SYMBOLS = (
     "gsr_abi_version", "gsr_build_info", "gsr_workspace_sizes", "gsr_workspace_layout", "gsr_forward",
-    "gsr_backward", "gsr_mark_visible", "gsr_forward_profile", "gsr_backward_profile", "gsr_setup_views",
+    "gsr_backward", "gsr_mark_visible", "gsr_forward_ex", "gsr_stage_name", "gsr_setup_views",
     "gsr_capacity_for", "gsr_cov_from_scale_rot", "gsr_cov_from_scale_rot_backward", "gsr_last_failed_stage",
-    "gsr_colour_in_binning", "gsr_geom_layout", "gsr_backward_ex", "gsr_pose_partials_bytes", "gsr_backward_scratch_bytes", "gsr_setup_views_orthographic", "gsr_forward_scale_rot", "gsr_backward_scale_rot",
+    "gsr_colour_in_binning", "gsr_geom_layout", "gsr_backward_ex", "gsr_pose_partials_bytes", "gsr_backward_scratch_bytes", "gsr_setup_views_orthographic",
     "gsr_image_loss", "gsr_image_loss_partials", "gsr_image_loss_finish", "gsr_pack_view", "gsr_setup_views_backward",
     "gsr_adapt", "gsr_adapt_backward", "gsr_adapt_partials_bytes",
 )
-# gsr_forward_profile's stages.  On images of up to 20 480 tiles (the fused binning path) "preprocess" is the whole binning
+# The stages of GsrForwardOptions.stage_ms / GsrBackwardOptions.stage_ms as run_forward / run_backward(profile=True) key them (the
+# names a failed debug-mode stage is reported with are the library's: gsr_stage_name).  On images of up to 20 480 tiles (the fused binning path) "preprocess" is the whole binning
 # kernel and "count_scan" / "emit" have no launch (their entries are one empty event gap each).
 FWD_STAGES = ("color", "preprocess", "count_scan", "emit", "tiles")
-FWD_DEBUG_STAGES = ("colour", "preprocess/binning", "count + scans", "emit", "per-tile sort + blend")
 BWD_STAGES = ("blend_bwd", "preprocess_bwd")

@@ -3,7 +3,7 @@ front of the raster path.  Counterpart of the reference's `Gaus
 (src/model/encoder/common/gaussian_adapter.py:30-125; same constructor cfg, same `forward` arguments, `get_scale_multiplier`,
 `d_sh`, `d_in`) with one difference in what comes out: the (N, 3, 3) world-space covariances are NOT materialised.  The
 adapter returns scales, unit quaternions and the camera-to-world rotation of every source view; the raster library builds
-Sigma = (C R) diag(s^2) (C R)^T in registers as it loads a Gaussian (`gsr_forward_scale_rot`) and its backward returns
+Sigma = (C R) diag(s^2) (C R)^T in registers as it loads a Gaussian (`gsr_forward_ex`, `scale_rot`) and its backward returns
 dL/dscale and dL/dquaternion directly.  That removes the 36 bytes per Gaussian the covariance costs in each direction (written
 by the adapter, read by the forward, its gradient written by the backward and read by autograd) and six small torch
 kernels.  `AdaptedGaussians.covariances` still yields the matrices (as differentiable torch ops) for callers that want them.

@@ -220,7 +220,7 @@ struct Params {
   int chunk;  // Gaussians per binning workgroup (choose_chunk)
   const GsrView* views;
   const float *means, *cov6, *opac, *colors, *extra;
-  const float* frames;   // scale/rotation input form (gsr_forward_scale_rot): cov6 points at (S, N, 7) records, frames at
+  const float* frames;   // scale/rotation input form (GsrForwardOptions.scale_rot): cov6 points at (S, N, 7) records, frames at
   int num_frames;        // (S, F, 3, 3) rotations (nullable) applied to the Gaussians of each of the F equal groups of a set
   int scale_rot;         // 1: that form is in use
   float* out_color;
@@ -4182,15 +4182,53 @@ __global__ __launch_bounds__(256) void k_cov_from_scale_rot_bwd(long long n, con
   }
 }
 
+struct SrArgs {  // scale / rotation input form: cov6 is (S, N, 7); frames (S, F, 3, 3) or null
+  const float* frames;
+  int num_frames;
+};
+// the options of an _ex call as the launches take them: null unless the call is in the scale / rotation form
+template <class Options>
+static const SrArgs* sr_of(const Options* opt, SrArgs* sr) {
+  if (!opt || !opt->scale_rot) return nullptr;
+  *sr = {opt->frames, opt->num_frames};
+  return sr;
+}
+
+// opt->stage_ms of the _ex calls (measurement aid, never on the product path): `run` enqueues the launch chain with a HIP event
+// between its kStages stages; the stream is synchronised and the stage durations come back in milliseconds (zeros for an
+// empty call).  stage_ms == nullptr: just `run`, without events.
+template <int kStages, class Run>
+static int with_stage_events(const GsrDims* dims, hipStream_t st, float* stage_ms, Run&& run) {
+  if (!stage_ms) return run(nullptr);
+  hipEvent_t ev[kStages + 1];
+  for (int i = 0; i <= kStages; ++i) GSR_CHECK(hipEventCreate(&ev[i]));
+  int rc = run(ev);
+  for (int i = 0; i < kStages; ++i) stage_ms[i] = 0.f;
+  if (rc == GSR_OK && dims->num_views > 0 && dims->num_gaussians > 0) {
+    if (hipStreamSynchronize(st) != hipSuccess) rc = GSR_ERR_LAUNCH;
+    for (int i = 0; i < kStages && rc == GSR_OK; ++i)
+      if (hipEventElapsedTime(&stage_ms[i], ev[i], ev[i + 1]) != hipSuccess) rc = GSR_ERR_LAUNCH;
+  }
+  for (int i = 0; i <= kStages; ++i) (void)hipEventDestroy(ev[i]);
+  return rc;
+}
+
 extern "C" {
 
 int gsr_abi_version(void) { return GSR_ABI_VERSION; }
 
 const char* gsr_build_info(void) {
-  return "gsr_hip gfx950 wave64 tile8x8 binning+colour tile-sort+segment-blend single-stream abi3";
+  return "gsr_hip gfx950 wave64 tile8x8 binning+colour tile-sort+segment-blend single-stream abi4";
 }
 
 int gsr_last_failed_stage(void) { return g_failed_stage; }
+
+const char* gsr_stage_name(int backward, int stage) {
+  static const char* const fwd[GSR_FWD_STAGES] = {"colour", "preprocess/binning", "count + scans", "emit", "per-tile sort + blend"};
+  static const char* const bwd[GSR_BWD_STAGES] = {"blend_bwd", "preprocess_bwd"};
+  if (stage < 0 || stage >= (backward ? GSR_BWD_STAGES : GSR_FWD_STAGES)) return nullptr;
+  return backward ? bwd[stage] : fwd[stage];
+}
 
 // 1 when gsr_forward runs the colour pass inside the binning launch for these dims (k_preprocess_bin<true, .>: two launches),
 // 0 when it is a launch of its own (three or more), negative on bad dims.  Measurement aid (bench.py attributes bytes to launches).
@@ -4293,10 +4331,6 @@ int gsr_geom_layout(const GsrDims* dims, int64_t* offsets4) {
   return GSR_OK;
 }
 
-struct SrArgs {  // scale / rotation input form: cov6 is (S, N, 7); frames (S, F, 3, 3) or null
-  const float* frames;
-  int num_frames;
-};
 static bool sr_ok(const GsrDims* d, const SrArgs* sr) {
   if (!sr) return true;
   if (d->flags & GSR_FLAG_COV_3X3) return false;
@@ -4322,13 +4356,15 @@ static bool call_dims_ok(const GsrDims* d, const SrArgs* sr) {
       }                                                                                 \
     }                                                                                   \
   } while (0)
-// the profile entry points' events: one between every two stages (ev: null on the product path)
+// the events of with_stage_events: one between every two stages (ev: null on the product path)
 #define GSR_MARK() do { if (ev) GSR_CHECK(hipEventRecord(ev[e++], st)); } while (0)
+
+static_assert(sizeof(GsrForwardOptions) == 24 && sizeof(GsrBackwardOptions) == 48, "options structs as tests/test_abi.py mirrors them");
 
 static int forward_impl(const GsrDims* dims, const GsrView* views, const float* means, const float* cov6,
                         const float* opacities, const float* colors, const float* extra, float* out_color,
                         float* out_extra, int32_t* radii, void* geom, void* bin, void* img, hipStream_t st,
-                        hipEvent_t* ev, const SrArgs* sr = nullptr) {
+                        hipEvent_t* ev, const SrArgs* sr) {
   if (!call_dims_ok(dims, sr)) return GSR_ERR_INVALID_ARGUMENT;
   const GsrDims& d = *dims;
   const size_t V = d.num_views, N = d.num_gaussians, HW = (size_t)d.height * d.width;
@@ -4431,45 +4467,30 @@ static int forward_impl(const GsrDims* dims, const GsrView* views, const float* 
   return GSR_OK;
 }
 
-int gsr_forward(const GsrDims* dims, const GsrView* views, const float* means, const float* cov6,
-                const float* opacities, const float* colors, const float* extra, float* out_color,
-                float* out_extra, int32_t* radii, void* geom, void* bin, void* img, void* stream_) {
-  return forward_impl(dims, views, means, cov6, opacities, colors, extra, out_color, out_extra, radii, geom, bin, img,
-                      static_cast<hipStream_t>(stream_), nullptr);
+int gsr_forward_ex(const GsrDims* dims, const GsrView* views, const float* means, const float* cov, const float* opacities,
+                   const float* colors, const float* extra, float* out_color, float* out_extra, int32_t* radii, void* geom,
+                   void* bin, void* img, const GsrForwardOptions* opt, void* stream_) {
+  hipStream_t st = static_cast<hipStream_t>(stream_);
+  SrArgs sr_store;
+  const SrArgs* sr = sr_of(opt, &sr_store);
+  return with_stage_events<GSR_FWD_STAGES>(dims, st, opt ? opt->stage_ms : nullptr, [&](hipEvent_t* ev) {
+    return forward_impl(dims, views, means, cov, opacities, colors, extra, out_color, out_extra, radii, geom, bin, img, st, ev, sr);
+  });
 }
 
-// Measurement aid (bench.py): the same launch chain with a HIP event recorded on `stream` between its stages;
-// synchronises the stream and returns the GSR_FWD_STAGES stage durations in milliseconds (see include/gsr.h).
-// Never used on the product path.
-int gsr_forward_profile(const GsrDims* dims, const GsrView* views, const float* means, const float* cov6,
-                        const float* opacities, const float* colors, const float* extra, float* out_color,
-                        float* out_extra, int32_t* radii, void* geom, void* bin, void* img, void* stream_,
-                        float* stage_ms) {
-  if (!stage_ms) return GSR_ERR_INVALID_ARGUMENT;
-  hipStream_t st = static_cast<hipStream_t>(stream_);
-  hipEvent_t ev[GSR_FWD_STAGES + 1];
-  for (int i = 0; i <= GSR_FWD_STAGES; ++i) GSR_CHECK(hipEventCreate(&ev[i]));
-  int rc = forward_impl(dims, views, means, cov6, opacities, colors, extra, out_color, out_extra, radii, geom, bin, img,
-                        st, ev);
-  if (rc == GSR_OK && dims->num_views > 0 && dims->num_gaussians > 0) {
-    if (hipStreamSynchronize(st) != hipSuccess) rc = GSR_ERR_LAUNCH;
-    for (int i = 0; i < GSR_FWD_STAGES && rc == GSR_OK; ++i)
-      if (hipEventElapsedTime(&stage_ms[i], ev[i], ev[i + 1]) != hipSuccess) rc = GSR_ERR_LAUNCH;
-  } else {
-    for (int i = 0; i < GSR_FWD_STAGES; ++i) stage_ms[i] = 0.f;
-  }
-  for (int i = 0; i <= GSR_FWD_STAGES; ++i) (void)hipEventDestroy(ev[i]);
-  return rc;
+int gsr_forward(const GsrDims* dims, const GsrView* views, const float* means, const float* cov6,
+                const float* opacities, const float* colors, const float* extra, float* out_color,
+                float* out_extra, int32_t* radii, void* geom, void* bin, void* img, void* stream) {
+  return gsr_forward_ex(dims, views, means, cov6, opacities, colors, extra, out_color, out_extra, radii, geom, bin, img, nullptr, stream);
 }
 
 static int backward_impl(const GsrDims* dims, const GsrView* views, const float* means, const float* cov6,
                          const float* opacities, const float* colors, const float* extra, const void* geom,
                          const void* bin, const void* img, const float* dL_dcolor, const float* dL_dextra_img,
                          void* scratch, float* dL_dmeans, float* dL_dcov6, float* dL_dopacities,
-                         float* dL_dcolors, float* dL_dextra, float* dL_dmeans2D, void* stream_, hipEvent_t* ev,
-                         const SrArgs* sr, float* dL_dviews = nullptr, float* pose_partials = nullptr, int depth_term_only = 0) {
+                         float* dL_dcolors, float* dL_dextra, float* dL_dmeans2D, hipStream_t st, hipEvent_t* ev,
+                         const SrArgs* sr, float* dL_dviews, float* pose_partials, int depth_term_only) {
   if (!call_dims_ok(dims, sr)) return GSR_ERR_INVALID_ARGUMENT;
-  hipStream_t st = static_cast<hipStream_t>(stream_);
   const GsrDims& d = *dims;
   const size_t V = d.num_views, N = d.num_gaussians;
   if (V == 0 || N == 0) return GSR_OK;
@@ -4537,34 +4558,6 @@ static int backward_impl(const GsrDims* dims, const GsrView* views, const float*
   return GSR_OK;
 }
 
-int gsr_backward(const GsrDims* dims, const GsrView* views, const float* means, const float* cov6,
-                 const float* opacities, const float* colors, const float* extra, const void* geom,
-                 const void* bin, const void* img, const float* dL_dcolor, const float* dL_dextra_img,
-                 void* scratch, float* dL_dmeans, float* dL_dcov6, float* dL_dopacities,
-                 float* dL_dcolors, float* dL_dextra, float* dL_dmeans2D, void* stream_) {
-  return backward_impl(dims, views, means, cov6, opacities, colors, extra, geom, bin, img, dL_dcolor, dL_dextra_img, scratch,
-                       dL_dmeans, dL_dcov6, dL_dopacities, dL_dcolors, dL_dextra, dL_dmeans2D, stream_, nullptr, nullptr);
-}
-
-int gsr_forward_scale_rot(const GsrDims* dims, const GsrView* views, const float* means, const float* scale_rot,
-                          const float* frames, int num_frames, const float* opacities, const float* colors,
-                          const float* extra, float* out_color, float* out_extra, int32_t* radii, void* geom, void* bin,
-                          void* img, void* stream_) {
-  const SrArgs sr{frames, num_frames};
-  return forward_impl(dims, views, means, scale_rot, opacities, colors, extra, out_color, out_extra, radii, geom, bin, img,
-                      static_cast<hipStream_t>(stream_), nullptr, &sr);
-}
-
-int gsr_backward_scale_rot(const GsrDims* dims, const GsrView* views, const float* means, const float* scale_rot,
-                           const float* frames, int num_frames, const float* opacities, const float* colors,
-                           const float* extra, const void* geom, const void* bin, const void* img, const float* dL_dcolor,
-                           const float* dL_dextra_img, void* scratch, float* dL_dmeans, float* dL_dscale_rot,
-                           float* dL_dopacities, float* dL_dcolors, float* dL_dextra, float* dL_dmeans2D, void* stream_) {
-  const SrArgs sr{frames, num_frames};
-  return backward_impl(dims, views, means, scale_rot, opacities, colors, extra, geom, bin, img, dL_dcolor, dL_dextra_img,
-                       scratch, dL_dmeans, dL_dscale_rot, dL_dopacities, dL_dcolors, dL_dextra, dL_dmeans2D, stream_, nullptr, &sr);
-}
-
 size_t gsr_pose_partials_bytes(const GsrDims* dims) {
   if (!dims_ok(dims)) return 0;
   return (size_t)dims->num_views * ((size_t)((dims->num_gaussians + 63) / 64) * 4 + kPoseBlocks) * kPoseFloats * sizeof(float);
@@ -4575,35 +4568,23 @@ int gsr_backward_ex(const GsrDims* dims, const GsrView* views, const float* mean
                     const float* dL_dcolor, const float* dL_dextra_img, void* scratch, float* dL_dmeans, float* dL_dcov,
                     float* dL_dopacities, float* dL_dcolors, float* dL_dextra, float* dL_dmeans2D, const GsrBackwardOptions* opt,
                     void* stream_) {
-  if (!opt) return backward_impl(dims, views, means, cov, opacities, colors, extra, geom, bin, img, dL_dcolor, dL_dextra_img, scratch,
-                                 dL_dmeans, dL_dcov, dL_dopacities, dL_dcolors, dL_dextra, dL_dmeans2D, stream_, nullptr, nullptr);
-  const SrArgs sr{opt->frames, opt->num_frames};
-  return backward_impl(dims, views, means, cov, opacities, colors, extra, geom, bin, img, dL_dcolor, dL_dextra_img, scratch,
-                       dL_dmeans, dL_dcov, dL_dopacities, dL_dcolors, dL_dextra, dL_dmeans2D, stream_, nullptr, opt->scale_rot ? &sr : nullptr,
-                       opt->dL_dviews, opt->pose_partials, opt->depth_term_only);
+  hipStream_t st = static_cast<hipStream_t>(stream_);
+  SrArgs sr_store;
+  const SrArgs* sr = sr_of(opt, &sr_store);
+  return with_stage_events<GSR_BWD_STAGES>(dims, st, opt ? opt->stage_ms : nullptr, [&](hipEvent_t* ev) {
+    return backward_impl(dims, views, means, cov, opacities, colors, extra, geom, bin, img, dL_dcolor, dL_dextra_img, scratch, dL_dmeans, dL_dcov,
+                         dL_dopacities, dL_dcolors, dL_dextra, dL_dmeans2D, st, ev, sr, opt ? opt->dL_dviews : nullptr,
+                         opt ? opt->pose_partials : nullptr, opt ? opt->depth_term_only : 0);
+  });
 }
 
-// Measurement aid (bench.py): gsr_backward with events between its two stages (blend backward, preprocess backward);
-// synchronises the stream.  Never used on the product path.
-int gsr_backward_profile(const GsrDims* dims, const GsrView* views, const float* means, const float* cov6,
-                         const float* opacities, const float* colors, const float* extra, const void* geom,
-                         const void* bin, const void* img, const float* dL_dcolor, const float* dL_dextra_img,
-                         void* scratch, float* dL_dmeans, float* dL_dcov6, float* dL_dopacities,
-                         float* dL_dcolors, float* dL_dextra, float* dL_dmeans2D, void* stream_, float* stage_ms) {
-  if (!stage_ms) return GSR_ERR_INVALID_ARGUMENT;
-  hipStream_t st = static_cast<hipStream_t>(stream_);
-  hipEvent_t ev[GSR_BWD_STAGES + 1];
-  for (int i = 0; i <= GSR_BWD_STAGES; ++i) GSR_CHECK(hipEventCreate(&ev[i]));
-  int rc = backward_impl(dims, views, means, cov6, opacities, colors, extra, geom, bin, img, dL_dcolor, dL_dextra_img,
-                         scratch, dL_dmeans, dL_dcov6, dL_dopacities, dL_dcolors, dL_dextra, dL_dmeans2D, stream_, ev, nullptr);
-  for (int i = 0; i < GSR_BWD_STAGES; ++i) stage_ms[i] = 0.f;
-  if (rc == GSR_OK && dims->num_views > 0 && dims->num_gaussians > 0) {
-    if (hipStreamSynchronize(st) != hipSuccess) rc = GSR_ERR_LAUNCH;
-    for (int i = 0; i < GSR_BWD_STAGES && rc == GSR_OK; ++i)
-      if (hipEventElapsedTime(&stage_ms[i], ev[i], ev[i + 1]) != hipSuccess) rc = GSR_ERR_LAUNCH;
-  }
-  for (int i = 0; i <= GSR_BWD_STAGES; ++i) (void)hipEventDestroy(ev[i]);
-  return rc;
+int gsr_backward(const GsrDims* dims, const GsrView* views, const float* means, const float* cov6,
+                 const float* opacities, const float* colors, const float* extra, const void* geom,
+                 const void* bin, const void* img, const float* dL_dcolor, const float* dL_dextra_img,
+                 void* scratch, float* dL_dmeans, float* dL_dcov6, float* dL_dopacities,
+                 float* dL_dcolors, float* dL_dextra, float* dL_dmeans2D, void* stream) {
+  return gsr_backward_ex(dims, views, means, cov6, opacities, colors, extra, geom, bin, img, dL_dcolor, dL_dextra_img, scratch, dL_dmeans, dL_dcov6,
+                         dL_dopacities, dL_dcolors, dL_dextra, dL_dmeans2D, nullptr, stream);
 }
 
 int gsr_setup_views(int num_views, const float* extrinsics, const float* intrinsics, const float* near_, const float* far_,

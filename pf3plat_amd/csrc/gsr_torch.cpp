@@ -44,14 +44,12 @@ struct Abi {
   decltype(&gsr_abi_version) abi_version = nullptr;
   decltype(&gsr_workspace_sizes) workspace_sizes = nullptr;
   decltype(&gsr_capacity_for) capacity_for = nullptr;
-  decltype(&gsr_forward) forward = nullptr;
-  decltype(&gsr_backward) backward = nullptr;
-  decltype(&gsr_forward_scale_rot) forward_scale_rot = nullptr;
-  decltype(&gsr_backward_scale_rot) backward_scale_rot = nullptr;
+  decltype(&gsr_forward_ex) forward_ex = nullptr;
   decltype(&gsr_backward_ex) backward_ex = nullptr;
   decltype(&gsr_pose_partials_bytes) pose_partials_bytes = nullptr;
   decltype(&gsr_backward_scratch_bytes) backward_scratch_bytes = nullptr;
   decltype(&gsr_last_failed_stage) last_failed_stage = nullptr;
+  decltype(&gsr_stage_name) stage_name = nullptr;
   decltype(&gsr_pack_view) pack_view = nullptr;
   decltype(&gsr_setup_views) setup_views = nullptr;
   decltype(&gsr_setup_views_backward) setup_views_backward = nullptr;
@@ -77,14 +75,12 @@ void init(const std::string& path) {
   resolve(g_abi.abi_version, "gsr_abi_version");
   resolve(g_abi.workspace_sizes, "gsr_workspace_sizes");
   resolve(g_abi.capacity_for, "gsr_capacity_for");
-  resolve(g_abi.forward, "gsr_forward");
-  resolve(g_abi.backward, "gsr_backward");
-  resolve(g_abi.forward_scale_rot, "gsr_forward_scale_rot");
-  resolve(g_abi.backward_scale_rot, "gsr_backward_scale_rot");
+  resolve(g_abi.forward_ex, "gsr_forward_ex");
   resolve(g_abi.backward_ex, "gsr_backward_ex");
   resolve(g_abi.pose_partials_bytes, "gsr_pose_partials_bytes");
   resolve(g_abi.backward_scratch_bytes, "gsr_backward_scratch_bytes");
   resolve(g_abi.last_failed_stage, "gsr_last_failed_stage");
+  resolve(g_abi.stage_name, "gsr_stage_name");
   resolve(g_abi.pack_view, "gsr_pack_view");
   resolve(g_abi.setup_views, "gsr_setup_views");
   resolve(g_abi.setup_views_backward, "gsr_setup_views_backward");
@@ -100,8 +96,6 @@ void init(const std::string& path) {
 
 // ---- small helpers ----------------------------------------------------------------------------------------------------------
 constexpr int kViewFloats = 48;  // sizeof(GsrView) / 4
-const char* const kFwdStages[] = {"colour", "preprocess/binning", "tile scan", "emit", "tile sort + blend"};
-const char* const kBwdStages[] = {"blend_bwd", "preprocess_bwd"};
 
 void check_device(std::initializer_list<const Tensor*> ts) {
   for (const Tensor* t : ts)
@@ -115,12 +109,12 @@ const float* fptr(const Tensor& t) { return t.defined() ? t.data_ptr<float>() : 
 float* fptr_mut(Tensor& t) { return t.defined() ? t.data_ptr<float>() : nullptr; }
 hipStream_t stream_of(const at::Device& d) { return c10::hip::getCurrentHIPStream(d.index()).stream(); }
 
-void rc_check(int rc, const char* what, const char* const* stages, int n_stages) {
+void rc_check(int rc, const char* what, bool backward) {
   if (rc == 0) return;
   std::string msg = std::string(what) + " failed with code " + std::to_string(rc);
   if (rc == GSR_ERR_LAUNCH) {
-    const int st = g_abi.last_failed_stage();
-    if (st >= 0 && st < n_stages) msg += std::string(" (debug mode: stage '") + stages[st] + "' did not complete)";
+    const char* stage = g_abi.stage_name(backward, g_abi.last_failed_stage());
+    if (stage) msg += std::string(" (debug mode: stage '") + stage + "' did not complete)";
   }
   throw std::runtime_error(msg);
 }
@@ -175,6 +169,13 @@ Tensor frames_arg(const Cfg& cfg, const Tensor& frames) {
       cfg.num_gaussians % frames.size(1))
     throw pybind11::value_error("frames must be (sets, F, 3, 3) with F dividing the number of Gaussians");
   return frames.detach().to(at::kFloat).contiguous();  // (a QR factor, e.g., arrives column-major)
+}
+// The options of an _ex launch from the call shape and its checked frames (`fr`: frames_arg's result, alive until the call returns)
+template <class Options>
+Options launch_options(const Cfg& cfg, const Tensor& fr) {
+  Options opt{};
+  opt.frames = fptr(fr); opt.num_frames = fr.defined() ? (int)fr.size(1) : 0; opt.scale_rot = cfg.scale_rot;
+  return opt;
 }
 
 struct Status {
@@ -440,32 +441,21 @@ class Backend : public std::enable_shared_from_this<Backend> {
       Tensor g_extra;
       if (cfg.has_extra) g_extra = g_extra_in.defined() ? f32c(g_extra_in) : at::zeros({v, cfg.height, cfg.width}, f32);
       if (want_views) d_views = at::empty({v, kViewFloats}, f32);
-      int rc;
       const GsrView* vb = reinterpret_cast<const GsrView*>(viewbuf.data_ptr<float>());
+      const Tensor fr = cfg.scale_rot ? frames_arg(cfg, frames) : Tensor();
+      GsrBackwardOptions opt = launch_options<GsrBackwardOptions>(cfg, fr);
+      Tensor partials;
       if (want_views) {
-        Tensor fr = cfg.scale_rot ? frames_arg(cfg, frames) : Tensor();
         GsrDims sizing_dims = saved.dims;  // (the helpers take no GSR_FLAG_SH_IN_FRAME bits; they change no size)
         sizing_dims.flags &= ~Cfg::kShFrameBits;
-        Tensor partials = at::empty({(int64_t)std::max<size_t>(16, g_abi.pose_partials_bytes(&sizing_dims))}, f32.dtype(at::kByte));
-        GsrBackwardOptions opt;
-        opt.frames = fptr(fr); opt.num_frames = fr.defined() ? (int)fr.size(1) : 0; opt.scale_rot = cfg.scale_rot;
+        partials = at::empty({(int64_t)std::max<size_t>(16, g_abi.pose_partials_bytes(&sizing_dims))}, f32.dtype(at::kByte));
         opt.dL_dviews = d_views.data_ptr<float>(); opt.pose_partials = reinterpret_cast<float*>(partials.data_ptr()); opt.depth_term_only = want_views == 2;
-        opt.reserved_ = 0;
-        rc = g_abi.backward_ex(&saved.dims, vb, fptr(means), fptr(cov), fptr(opac), fptr(colors), fptr(extra), saved.geom.data_ptr(), saved.bin.data_ptr(),
-                               saved.img.data_ptr(), fptr(g_color), fptr(g_extra), scratch.defined() ? scratch.data_ptr() : nullptr, fptr_mut(d_means),
-                               fptr_mut(d_cov), fptr_mut(d_opac), fptr_mut(d_colors), fptr_mut(d_extra), fptr_mut(d_means2d), &opt, stream);
-      } else if (cfg.scale_rot) {
-        Tensor fr = frames_arg(cfg, frames);
-        rc = g_abi.backward_scale_rot(&saved.dims, vb, fptr(means), fptr(cov), fptr(fr), fr.defined() ? (int)fr.size(1) : 0, fptr(opac), fptr(colors),
-                                      fptr(extra), saved.geom.data_ptr(), saved.bin.data_ptr(), saved.img.data_ptr(), fptr(g_color), fptr(g_extra),
-                                      scratch.defined() ? scratch.data_ptr() : nullptr, fptr_mut(d_means), fptr_mut(d_cov), fptr_mut(d_opac),
-                                      fptr_mut(d_colors), fptr_mut(d_extra), fptr_mut(d_means2d), stream);
-      } else {
-        rc = g_abi.backward(&saved.dims, vb, fptr(means), fptr(cov), fptr(opac), fptr(colors), fptr(extra), saved.geom.data_ptr(), saved.bin.data_ptr(),
-                            saved.img.data_ptr(), fptr(g_color), fptr(g_extra), scratch.defined() ? scratch.data_ptr() : nullptr, fptr_mut(d_means),
-                            fptr_mut(d_cov), fptr_mut(d_opac), fptr_mut(d_colors), fptr_mut(d_extra), fptr_mut(d_means2d), stream);
       }
-      rc_check(rc, "gsr_backward", kBwdStages, 2);
+      const int rc = g_abi.backward_ex(&saved.dims, vb, fptr(means), fptr(cov), fptr(opac), fptr(colors), fptr(extra), saved.geom.data_ptr(),
+                                       saved.bin.data_ptr(), saved.img.data_ptr(), fptr(g_color), fptr(g_extra), scratch.defined() ? scratch.data_ptr() : nullptr,
+                                       fptr_mut(d_means), fptr_mut(d_cov), fptr_mut(d_opac), fptr_mut(d_colors), fptr_mut(d_extra), fptr_mut(d_means2d),
+                                       (cfg.scale_rot || want_views) ? &opt : nullptr, stream);
+      rc_check(rc, "gsr_backward", true);
     } else if (want_views) {
       d_views = at::zeros({v, kViewFloats}, f32);
     }
@@ -549,17 +539,12 @@ class Backend : public std::enable_shared_from_this<Backend> {
   void run_forward(Plan& p, const Cfg& cfg, const Tensor& viewbuf, const Tensor& means, const Tensor& cov, const Tensor& opac, const Tensor& colors,
                    const Tensor& extra, const Tensor& frames, hipStream_t stream) {
     const GsrView* vb = reinterpret_cast<const GsrView*>(viewbuf.data_ptr<float>());
-    int rc;
-    if (cfg.scale_rot) {
-      Tensor fr = frames_arg(cfg, frames);
-      rc = g_abi.forward_scale_rot(&p.dims, vb, fptr(means), fptr(cov), fptr(fr), fr.defined() ? (int)fr.size(1) : 0, fptr(opac), fptr(colors), fptr(extra),
-                                   p.color.data_ptr<float>(), fptr_mut(p.extra_img), p.radii.data_ptr<int32_t>(), p.geom.data_ptr(), p.bin.data_ptr(),
-                                   p.img.data_ptr(), stream);
-    } else {
-      rc = g_abi.forward(&p.dims, vb, fptr(means), fptr(cov), fptr(opac), fptr(colors), fptr(extra), p.color.data_ptr<float>(), fptr_mut(p.extra_img),
-                         p.radii.data_ptr<int32_t>(), p.geom.data_ptr(), p.bin.data_ptr(), p.img.data_ptr(), stream);
-    }
-    rc_check(rc, "gsr_forward", kFwdStages, 5);
+    const Tensor fr = cfg.scale_rot ? frames_arg(cfg, frames) : Tensor();
+    const GsrForwardOptions opt = launch_options<GsrForwardOptions>(cfg, fr);
+    const int rc = g_abi.forward_ex(&p.dims, vb, fptr(means), fptr(cov), fptr(opac), fptr(colors), fptr(extra), p.color.data_ptr<float>(),
+                                    fptr_mut(p.extra_img), p.radii.data_ptr<int32_t>(), p.geom.data_ptr(), p.bin.data_ptr(), p.img.data_ptr(),
+                                    cfg.scale_rot ? &opt : nullptr, stream);
+    rc_check(rc, "gsr_forward", false);
   }
 
   Pinned status_copy(const Tensor& bin, hipStream_t stream) {

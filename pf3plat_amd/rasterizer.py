@@ -54,7 +54,7 @@ class RasterConfig:
     max_sh_eval: int = 4
     has_extra: bool = False
     flags: int = 0  # _lib.FLAG_SH_PLANAR | _lib.FLAG_COV_3X3 (input layouts)
-    scale_rot: bool = False  # the covariance argument is (S, N, 7) scale + quaternion (x, y, z, w) records (gsr_forward_scale_rot)
+    scale_rot: bool = False  # the covariance argument is (S, N, 7) scale + quaternion (x, y, z, w) records (GsrForwardOptions.scale_rot)
 
 
 def pack_views(viewmatrix: Tensor, projmatrix: Tensor, campos: Tensor, tanfovx: Tensor, tanfovy: Tensor,
@@ -178,14 +178,14 @@ class HipBackend:
         """The head-room factor the next deferred / lazy call of shape (views, N, H, W) is sized with."""
         return float(self._c.headroom_for(tuple(int(k) for k in key)))
 
-    def _rc(self, rc: int, what: str, stages=None):
+    def _rc(self, rc: int, what: str, backward: bool = False):
         if rc == 0:
             return
         msg = f"{what} failed with code {rc}"
         if rc == -2:  # GSR_ERR_LAUNCH
-            st = self.lib.gsr_last_failed_stage()
-            if stages is not None and 0 <= st < len(stages):
-                msg += f" (debug mode: stage '{stages[st]}' did not complete)"
+            stage = self.lib.gsr_stage_name(int(backward), self.lib.gsr_last_failed_stage())
+            if stage is not None:
+                msg += f" (debug mode: stage '{stage.decode()}' did not complete)"
         raise RuntimeError(msg)
 
     @staticmethod
@@ -279,28 +279,24 @@ class HipBackend:
 
     def run_forward(self, plan: dict, viewbuf, means, cov6, opac, colors, extra=None, profile: bool = False, out_color=None,
                     frames=None):
-        """Enqueue one forward launch chain on the current stream.  profile=True returns per-stage ms (synchronises).
+        """Enqueue one forward launch chain on the current stream (gsr_forward_ex).  profile=True returns per-stage ms
+        (synchronises), in the scale / rotation form too.
         out_color: render into this contiguous (V, 3, H, W) fp32 tensor instead of the plan's own image (e.g. a slot of a
         buffer that is all-gathered later: no copy)."""
         stream = _stream_ptr(plan["device"])
         color = plan["color"] if out_color is None else out_color
         if color.shape != plan["color"].shape or color.dtype != torch.float32 or not color.is_contiguous():
             raise ValueError("out_color must be a contiguous fp32 tensor of the plan's image shape")
-        args = (ctypes.byref(plan["dims"]), _ptr(viewbuf), _ptr(means), _ptr(cov6), _ptr(opac), _ptr(colors), _ptr(extra),
-                _ptr(color), _ptr(plan["extra_img"]), _ptr(plan["radii"]), _ptr(plan["geom"]), _ptr(plan["bin"]),
-                _ptr(plan["img"]), stream)
+        cfg = plan["cfg"]
+        fr, nf = self._ext.frames_arg(_cfg_vec(cfg), frames) if cfg.scale_rot else (None, 0)
+        ms = (ctypes.c_float * len(_lib.FWD_STAGES))() if profile else None
+        # (nothing asked for: NULL options, the plain call)
+        opt = ctypes.byref(_lib.GsrForwardOptions(_ptr(fr), nf, int(cfg.scale_rot), ms)) if cfg.scale_rot or profile else None
         with _on_device(plan["device"]):  # kernels launch on the process's current device: make it the tensors' device
-            if plan["cfg"].scale_rot:
-                fr, nf = self._ext.frames_arg(_cfg_vec(plan["cfg"]), frames)
-                ms = None
-                rc = self.lib.gsr_forward_scale_rot(*args[:4], _ptr(fr), nf, *args[4:])
-            elif profile:
-                ms = (ctypes.c_float * len(_lib.FWD_STAGES))()
-                rc = self.lib.gsr_forward_profile(*args, ms)
-            else:
-                ms = None
-                rc = self.lib.gsr_forward(*args)
-        self._rc(rc, "gsr_forward", _lib.FWD_DEBUG_STAGES)
+            rc = self.lib.gsr_forward_ex(ctypes.byref(plan["dims"]), _ptr(viewbuf), _ptr(means), _ptr(cov6), _ptr(opac), _ptr(colors),
+                                         _ptr(extra), _ptr(color), _ptr(plan["extra_img"]), _ptr(plan["radii"]), _ptr(plan["geom"]),
+                                         _ptr(plan["bin"]), _ptr(plan["img"]), opt, stream)
+        self._rc(rc, "gsr_forward")
         return None if ms is None else dict(zip(_lib.FWD_STAGES, [float(x) for x in ms]))
 
     def bind_forward(self, plan: dict, viewbuf, means, cov6, opac, colors, extra=None, out_color=None):
@@ -327,43 +323,38 @@ class HipBackend:
             else:
                 rc = fn(*args, _raw_stream(idx) if _raw_stream is not None else torch.cuda.current_stream(dev).cuda_stream)
             if rc:
-                rc_check(rc, "gsr_forward", _lib.FWD_DEBUG_STAGES)
+                rc_check(rc, "gsr_forward")
 
         return call
 
     def run_backward(self, plan: dict, viewbuf, means, cov6, opac, colors, extra, g_color, g_extra_img=None,
                      want_means2d: bool = True, profile: bool = False, frames=None, d_views=None, depth_term_only: bool = False):
-        """d_views: a (V, 48) fp32 tensor that receives the camera gradients (gsr_backward_ex); depth_term_only: only
-        what the built-in depth channel sends to the camera (the z row of the view matrix), the gradient of the reference's graph."""
+        """Enqueue one backward launch chain on the current stream (gsr_backward_ex).  profile=True returns per-stage ms
+        (synchronises), in the scale / rotation form and together with d_views too.
+        d_views: a (V, 48) fp32 tensor that receives the camera gradients; depth_term_only: only what the built-in
+        depth channel sends to the camera (the z row of the view matrix), the gradient of the reference's graph."""
         cfg = plan["cfg"]
         stream = _stream_ptr(plan["device"])
-        args = (ctypes.byref(plan["dims"]), _ptr(viewbuf), _ptr(means), _ptr(cov6), _ptr(opac), _ptr(colors), _ptr(extra),
-                _ptr(plan["geom"]), _ptr(plan["bin"]), _ptr(plan["img"]), _ptr(g_color),
-                _ptr(g_extra_img if cfg.has_extra else None), _ptr(plan["scratch"]), _ptr(plan["d_means"]),
-                _ptr(plan["d_cov6"]), _ptr(plan["d_opac"]), _ptr(plan["d_colors"]), _ptr(plan["d_extra"]),
-                _ptr(plan["d_means2d"] if want_means2d else None), stream)
+        fr, nf = self._ext.frames_arg(_cfg_vec(cfg), frames) if cfg.scale_rot else (None, 0)
+        ms = (ctypes.c_float * len(_lib.BWD_STAGES))() if profile else None
+        partials = None
+        if d_views is not None:
+            partials = plan.get("pose_partials")
+            if partials is None:
+                partials = plan["pose_partials"] = torch.empty(
+                    max(16, int(self.lib.gsr_pose_partials_bytes(ctypes.byref(self._sizing_dims(plan["dims"]))))), dtype=torch.uint8,
+                    device=plan["device"])
+        opt = None  # (nothing asked for: NULL options, the plain call)
+        if cfg.scale_rot or profile or d_views is not None:
+            opt = ctypes.byref(_lib.GsrBackwardOptions(_ptr(fr), nf, int(cfg.scale_rot), _ptr(d_views), _ptr(partials), ms,
+                                                       int(d_views is not None and bool(depth_term_only))))
         with _on_device(plan["device"]):
-            if d_views is not None:
-                fr, nf = self._ext.frames_arg(_cfg_vec(cfg), frames) if cfg.scale_rot else (None, 0)
-                partials = plan.get("pose_partials")
-                if partials is None:
-                    partials = plan["pose_partials"] = torch.empty(
-                        max(16, int(self.lib.gsr_pose_partials_bytes(ctypes.byref(self._sizing_dims(plan["dims"]))))), dtype=torch.uint8,
-                        device=plan["device"])
-                opt = _lib.GsrBackwardOptions(_ptr(fr), nf, int(cfg.scale_rot), _ptr(d_views), _ptr(partials), int(bool(depth_term_only)), 0)
-                ms = None
-                rc = self.lib.gsr_backward_ex(*args[:-1], ctypes.byref(opt), stream)
-            elif cfg.scale_rot:
-                fr, nf = self._ext.frames_arg(_cfg_vec(cfg), frames)
-                ms = None
-                rc = self.lib.gsr_backward_scale_rot(*args[:4], _ptr(fr), nf, *args[4:])
-            elif profile:
-                ms = (ctypes.c_float * len(_lib.BWD_STAGES))()
-                rc = self.lib.gsr_backward_profile(*args, ms)
-            else:
-                ms = None
-                rc = self.lib.gsr_backward(*args)
-        self._rc(rc, "gsr_backward", _lib.BWD_STAGES)
+            rc = self.lib.gsr_backward_ex(ctypes.byref(plan["dims"]), _ptr(viewbuf), _ptr(means), _ptr(cov6), _ptr(opac), _ptr(colors),
+                                          _ptr(extra), _ptr(plan["geom"]), _ptr(plan["bin"]), _ptr(plan["img"]), _ptr(g_color),
+                                          _ptr(g_extra_img if cfg.has_extra else None), _ptr(plan["scratch"]), _ptr(plan["d_means"]),
+                                          _ptr(plan["d_cov6"]), _ptr(plan["d_opac"]), _ptr(plan["d_colors"]), _ptr(plan["d_extra"]),
+                                          _ptr(plan["d_means2d"] if want_means2d else None), opt, stream)
+        self._rc(rc, "gsr_backward", backward=True)
         return None if ms is None else dict(zip(_lib.BWD_STAGES, [float(x) for x in ms]))
 
     def read_status(self, plan: dict) -> dict:

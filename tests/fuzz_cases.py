@@ -91,7 +91,7 @@ def named_case(seed: int, index: int):
 WORST_CASES = ((8, 275), (8, 886), (7, 151), (7, 332), (7, 885), (7, 844), (8, 75), (7, 695), (4, 363))
 
 
-# ---- the scale / rotation form (gsr_forward_scale_rot / gsr_backward_scale_rot / gsr_backward_ex with scale_rot): a sequence of its
+# ---- the scale / rotation form (gsr_forward_ex / gsr_backward_ex with scale_rot): a sequence of its
 # own, so that draw_case's sequence - and every (seed, index) named above and in profiles/ - stays where it is
 SR_SH_FRAMES = (None, "rasterizer", "e3nn")
 

@@ -127,7 +127,7 @@ def test_decoder_renders_scale_rotation_records_like_materialised_covariances(or
 
 @pytest.mark.gpu
 def test_hip_scale_rotation_form_matches_the_oracle_forward_and_backward():
-    """gsr_forward_scale_rot / gsr_backward_scale_rot (covariance built in registers on load, dL/dscale and dL/dquaternion
+    """gsr_forward_ex / gsr_backward_ex with scale_rot (covariance built in registers on load, dL/dscale and dL/dquaternion
     returned directly) against the oracle rasterizer fed with the oracle's materialised covariances, through the same decoder."""
     from pf3plat_amd import rasterizer
     from tests.oracle_backend import OracleBackend

@@ -107,7 +107,7 @@ import pytest  # noqa: E402
 @pytest.mark.gpu
 def test_hip_renders_an_exported_ply_like_the_scene_it_came_from(tmp_path):
     """SURVEY 8f-4 on the device: export_ply -> read_ply -> gaussians_from_ply -> DecoderSplattingCUDA on the HIP library (the
-    scale + quaternion form, gsr_forward_scale_rot) gives the image and the depth of the original Gaussians seen through the
+    scale + quaternion form, gsr_forward_ex with scale_rot) gives the image and the depth of the original Gaussians seen through the
     correspondingly transformed camera - and both agree with the oracle-driven CPU run of the same code."""
     from tests.oracle_backend import OracleBackend
     from tests.util import install_backend

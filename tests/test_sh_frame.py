@@ -152,6 +152,14 @@ def test_c_entry_points_reject_the_bits_outside_the_scale_rotation_form():
     z = ctypes.c_size_t()
     frame, e3nn = _lib.FLAG_SH_IN_FRAME, _lib.FLAG_SH_FRAME_E3NN
     sizes = lambda d: lib.gsr_workspace_sizes(ctypes.byref(d), ctypes.byref(z), ctypes.byref(z), ctypes.byref(z))
+    fake = ctypes.cast(ctypes.create_string_buffer(64), ctypes.c_void_p).value
+
+    def forward_ex(d, *opt):  # opt: frames, num_frames, scale_rot; nothing = NULL options
+        return lib.gsr_forward_ex(ctypes.byref(d), *([None] * 12), ctypes.byref(_lib.GsrForwardOptions(*opt)) if opt else None, None)
+
+    def backward_ex(d, *opt):
+        return lib.gsr_backward_ex(ctypes.byref(d), *([None] * 18), ctypes.byref(_lib.GsrBackwardOptions(*opt)) if opt else None, None)
+
     assert sizes(_dims(0)) == 0
     for bits in (frame, frame | e3nn, e3nn):
         d = _dims(bits)
@@ -159,16 +167,11 @@ def test_c_entry_points_reject_the_bits_outside_the_scale_rotation_form():
         assert lib.gsr_backward_scratch_bytes(ctypes.byref(d)) == 0 and lib.gsr_pose_partials_bytes(ctypes.byref(d)) == 0
         assert lib.gsr_forward(ctypes.byref(d), *([None] * 13)) == -1
         assert lib.gsr_backward(ctypes.byref(d), *([None] * 19)) == -1
-        # scale / rotation form without frames
-        assert lib.gsr_forward_scale_rot(ctypes.byref(d), None, None, None, None, 0, *([None] * 10)) == -1
-        assert lib.gsr_backward_scale_rot(ctypes.byref(d), None, None, None, None, 0, *([None] * 16)) == -1
-        # gsr_backward_ex: without options, with options but not the scale / rotation form, and without frames
-        assert lib.gsr_backward_ex(ctypes.byref(d), *([None] * 18), None, None) == -1
-        fake = ctypes.cast(ctypes.create_string_buffer(64), ctypes.c_void_p).value
-        for opt in (_lib.GsrBackwardOptions(fake, 2, 0, None, None, 0, 0), _lib.GsrBackwardOptions(None, 0, 1, None, None, 0, 0)):
-            assert lib.gsr_backward_ex(ctypes.byref(d), *([None] * 18), ctypes.byref(opt), None) == -1
+        for ex in (forward_ex, backward_ex):
+            assert ex(d) == -1  # without options
+            assert ex(d, None, 0, 1) == -1  # scale / rotation form without frames
+            assert ex(d, fake, 2, 0) == -1  # options, frames even, but not the scale / rotation form
     # the e3nn bit alone, and the bits on colours that are not harmonics, even with frames
-    fake = ctypes.cast(ctypes.create_string_buffer(64), ctypes.c_void_p).value
     for d in (_dims(e3nn), _dims(frame, sh_coeffs=0)):
-        assert lib.gsr_forward_scale_rot(ctypes.byref(d), None, None, None, fake, 2, *([None] * 10)) == -1
-        assert lib.gsr_backward_scale_rot(ctypes.byref(d), None, None, None, fake, 2, *([None] * 16)) == -1
+        assert forward_ex(d, fake, 2, 1) == -1
+        assert backward_ex(d, fake, 2, 1) == -1
