@@ -252,6 +252,28 @@ int gsr_backward_ex(const GsrDims* dims, const GsrView* views, const float* mean
                     float* dL_dopacities, float* dL_dcolors, float* dL_dextra, float* dL_dmeans2D, const GsrBackwardOptions* opt,
                     void* stream);
 
+/* Accumulated alpha.  gsr_forward_alpha is gsr_forward_ex with one more output, out_alpha (V, H, W) or NULL (= gsr_forward_ex):
+ *   A = sum_j alpha_j T_j = 1 - T_final,   T_j = prod_{i < j} (1 - alpha_i),
+ * over the splats the pixel blends, in the same pass and from the transmittance the colour pass keeps anyway (`img`): what the
+ * extra channel blends for an `extra` array of ones, without spending that channel.  A pixel no splat reaches has A = 0 exactly.
+ * A pixel that stops early (the next splat would leave T (1 - alpha) < 1e-4) reports the T in front of the rejected splat - the
+ * value the background is weighted with - so colour = sum + (1 - A) bg holds exactly and A never reaches 1.  An empty call
+ * (num_gaussians == 0) writes zeros; an overflowed one (GsrStatus.overflow) NaN, as for the colour.  The expected depth of a
+ * pixel is out_extra / A with GSR_EXTRA_DEPTH, one pass; the clamp for small A is the caller's (no normalised mode exists).
+ * gsr_backward_alpha is gsr_backward_ex with one more cotangent, dL_dalpha_img (V, H, W) or NULL (= gsr_backward_ex): with
+ * dA / dalpha_j = T_final / (1 - alpha_j) it enters the blend's backward where the background does and reaches every output
+ * (dL_dviews included) through the splats' alphas.  dL_dcolor stays required: a caller with a loss on A alone passes zeros.
+ * Neither call changes a workspace size or layout: size with gsr_workspace_sizes as usual, and either backward may follow
+ * either forward. */
+int gsr_forward_alpha(const GsrDims* dims, const GsrView* views, const float* means, const float* cov, const float* opacities,
+                      const float* colors, const float* extra, float* out_color, float* out_extra, float* out_alpha,
+                      int32_t* radii, void* geom, void* bin, void* img, const GsrForwardOptions* opt, void* stream);
+int gsr_backward_alpha(const GsrDims* dims, const GsrView* views, const float* means, const float* cov, const float* opacities,
+                       const float* colors, const float* extra, const void* geom, const void* bin, const void* img,
+                       const float* dL_dcolor, const float* dL_dextra_img, const float* dL_dalpha_img, void* scratch, float* dL_dmeans,
+                       float* dL_dcov, float* dL_dopacities, float* dL_dcolors, float* dL_dextra, float* dL_dmeans2D,
+                       const GsrBackwardOptions* opt, void* stream);
+
 /* GSR_FLAG_DEBUG: the stage of the last failed call of this host thread (an index into the stages above), or -1; and the
  * name of stage `stage` of the forward (backward == 0) or the backward - the one statement of the names every caller prints -
  * or NULL outside [0, GSR_FWD_STAGES) / [0, GSR_BWD_STAGES). */

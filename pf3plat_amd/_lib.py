@@ -259,6 +259,10 @@ def load():
     lib.gsr_colour_in_binning.argtypes = [dp]
     lib.gsr_backward_ex.restype = ctypes.c_int
     lib.gsr_backward_ex.argtypes = [dp] + [vp] * 18 + [ctypes.POINTER(GsrBackwardOptions), vp]
+    lib.gsr_forward_alpha.restype = ctypes.c_int  # gsr_forward_ex + out_alpha behind out_extra
+    lib.gsr_forward_alpha.argtypes = [dp] + [vp] * 13 + [ctypes.POINTER(GsrForwardOptions), vp]
+    lib.gsr_backward_alpha.restype = ctypes.c_int  # gsr_backward_ex + dL_dalpha_img behind dL_dextra_img
+    lib.gsr_backward_alpha.argtypes = [dp] + [vp] * 19 + [ctypes.POINTER(GsrBackwardOptions), vp]
     lib.gsr_pose_partials_bytes.restype = ctypes.c_size_t
     lib.gsr_pose_partials_bytes.argtypes = [dp]
     lib.gsr_image_loss_partials.restype = ctypes.c_size_t
@@ -296,7 +300,7 @@ EXPORTED_SYMBOLS = (
     "gsr_capacity_for", "gsr_cov_from_scale_rot", "gsr_cov_from_scale_rot_backward", "gsr_last_failed_stage",
     "gsr_colour_in_binning", "gsr_geom_layout", "gsr_backward_ex", "gsr_pose_partials_bytes", "gsr_backward_scratch_bytes", "gsr_setup_views_orthographic",
     "gsr_image_loss", "gsr_image_loss_partials", "gsr_image_loss_finish", "gsr_pack_view", "gsr_setup_views_backward",
-    "gsr_adapt", "gsr_adapt_backward", "gsr_adapt_partials_bytes",
+    "gsr_adapt", "gsr_adapt_backward", "gsr_adapt_partials_bytes", "gsr_forward_alpha", "gsr_backward_alpha",
 )
 # The stages of GsrForwardOptions.stage_ms / GsrBackwardOptions.stage_ms as run_forward / run_backward(profile=True) key them (the
 # names a failed debug-mode stage is reported with are the library's: gsr_stage_name).  On images of up to 20 480 tiles (the fused binning path) "preprocess" is the whole binning

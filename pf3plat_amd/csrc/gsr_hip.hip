@@ -225,7 +225,10 @@ struct Params {
   int scale_rot;         // 1: that form is in use
   float* out_color;
   float* out_extra;
-  int32_t* radii;
+  union {
+    int32_t* radii;              // forward
+    const float* dL_dalpha_img;  // backward - (V, H, W), or null (shares the forward-only pointer's storage: see out_alpha)
+  };
   GeomRec* geom;
   float4* aux;  // footprint words of the windowed binning chain (null on the fused path)
   float4* rgbc;
@@ -257,8 +260,16 @@ struct Params {
   const float *dL_dcolor, *dL_dextra_img;
   float* scratch;
   float *dL_dmeans, *dL_dcov6, *dL_dopac, *dL_dcolors, *dL_dextra, *dL_dmeans2D;  // (scale_rot: dL_dcov6 is (S, N, 7))
-  float* pose_partials;  // camera gradients requested: [view][preprocess_bwd workgroup][DPP row 0..3][kPoseFloats]
+  // accumulated alpha (gsr_forward_alpha / gsr_backward_alpha; read by the kAlpha instances only).  The struct keeps its size and
+  // every field its offset - kernels that take their arguments from it, copy it or carry an argument behind it are then the code
+  // they were - so the two pointers share the storage of one that only the OTHER direction's kernels read.  (A backward kernel that
+  // ever needs `radii`, or a forward kernel `pose_partials`, takes that pointer out of its union first.)
+  union {
+    float* pose_partials;  // backward - camera gradients requested: [view][preprocess_bwd workgroup][DPP row 0..3][kPoseFloats]
+    float* out_alpha;      // forward - (V, H, W) 1 - final_T, or null
+  };
 };
+static_assert(sizeof(Params) == 464, "Params as the kernels without kAlpha were built around it");
 
 // ------------------------------------------------------------------------------------------------
 // small device helpers
@@ -2445,7 +2456,7 @@ __device__ __forceinline__ bool blend_range(const GeomRec* geom, const float4* r
 
 // Pair workspace too small (status->overflow): nothing was binned.  Poison the outputs so the condition cannot go unnoticed
 // even when the caller defers reading the status block.  Workgroup-uniform result: true = poisoned, nothing to blend.
-template <bool kExtra>
+template <bool kExtra, bool kAlpha = false>
 __device__ __forceinline__ bool blend_poisoned(const Params& p, const int v, const int pxi, const int pyi, const bool inside,
                                                const bool known = false) {
   // (the flag may be raised by another tile while this workgroup's waves read it: the decision is taken once for the workgroup)
@@ -2458,6 +2469,7 @@ __device__ __forceinline__ bool blend_poisoned(const Params& p, const int v, con
     float* oc = p.out_color + (size_t)v * 3 * HW;
     oc[pix] = qnan; oc[HW + pix] = qnan; oc[2 * HW + pix] = qnan;
     if (kExtra) p.out_extra[(size_t)v * HW + pix] = qnan;
+    if (kAlpha) p.out_alpha[(size_t)v * HW + pix] = qnan;
     p.final_T[(size_t)v * HW + pix] = 1.f;
     p.n_contrib[(size_t)v * HW + pix] = 0u;
   }
@@ -2465,7 +2477,9 @@ __device__ __forceinline__ bool blend_poisoned(const Params& p, const int v, con
 }
 
 // The four waves' partial results -> the pixel: image, final transmittance, contributor count; the entries the tile walked.
-template <bool kExtra>
+// kAlpha (gsr_forward_alpha): also the accumulated alpha A = 1 - final_T, from the value that is stored - one subtraction and
+// one store per pixel in instances of their own; the kAlpha = false instances are the code they were.
+template <bool kExtra, bool kAlpha = false>
 __device__ __forceinline__ void blend_finish(const Params& p, const int v, const int t, const uint32_t n, BlendFin& lds, const BlendAcc& s,
                                              const int pxi, const int pyi, const bool inside, const float bg0, const float bg1,
                                              const float bg2) {
@@ -2492,6 +2506,7 @@ __device__ __forceinline__ void blend_finish(const Params& p, const int v, const
       }
       const size_t HW = (size_t)g.H * g.W, pix = (size_t)pyi * g.W + pxi;
       p.final_T[(size_t)v * HW + pix] = T;
+      if (kAlpha) p.out_alpha[(size_t)v * HW + pix] = 1.f - T;
       // the pixel's loop ran through `last` entries before it stopped (every splat it blended has a smaller index; the reference
       // stores the index of the last one it blended - the entries in between are skipped by the alpha < 1/255 test either way)
       p.n_contrib[(size_t)v * HW + pix] = min(last, n);  // (the padding of the last batch counts as alive)
@@ -2505,7 +2520,7 @@ __device__ __forceinline__ void blend_finish(const Params& p, const int v, const
 }
 
 // The blend of tile t of view v over the index-list range rg (256 threads; `lds` may alias anything the workgroup is done with)
-template <bool kExtra>
+template <bool kExtra, bool kAlpha = false>
 __device__ __forceinline__ void blend_tile(const Params& p, const int v, const int t, const uint2 rg, BlendLds& lds) {
   const Grid& g = p.g;
   const int lane = threadIdx.x & 63;
@@ -2518,7 +2533,7 @@ __device__ __forceinline__ void blend_tile(const Params& p, const int v, const i
   typedef const __attribute__((address_space(4))) float* cfptr;
   cfptr camc = reinterpret_cast<cfptr>(reinterpret_cast<uintptr_t>(p.views + __builtin_amdgcn_readfirstlane(v)));
   const float bg0 = camc[37], bg1 = camc[38], bg2 = camc[39];  // GsrView::bg
-  if (blend_poisoned<kExtra>(p, v, pxi, pyi, inside)) return;
+  if (blend_poisoned<kExtra, kAlpha>(p, v, pxi, pyi, inside)) return;
   const bool dbg = GSR_ABL(p.d.flags, GSR_FLAG_DEBUG_TIMING);
   unsigned long long tm0 = 0, rt0 = 0;
   if (dbg) { tm0 = __builtin_readcyclecounter(); rt0 = __builtin_amdgcn_s_memrealtime(); }
@@ -2537,7 +2552,7 @@ __device__ __forceinline__ void blend_tile(const Params& p, const int v, const i
     o[0] = tm0; o[1] = ((unsigned long long)hw << 32); o[2] = __builtin_readcyclecounter();
     o[3] = (rt0 << 32) | (__builtin_amdgcn_s_memrealtime() & 0xffffffffull);  // 100 MHz wall clock: start | end
   }
-  blend_finish<kExtra>(p, v, t, n, *reinterpret_cast<BlendFin*>(&lds + 1), acc, pxi, pyi, inside, bg0, bg1, bg2);
+  blend_finish<kExtra, kAlpha>(p, v, t, n, *reinterpret_cast<BlendFin*>(&lds + 1), acc, pxi, pyi, inside, bg0, bg1, bg2);
 }
 
 // One launch per tile for both: the tile's sort (its gather latency under the blend arithmetic of the other tiles of the CU),
@@ -2548,7 +2563,7 @@ __device__ __forceinline__ void blend_tile(const Params& p, const int v, const i
 #ifndef GSR_WINDOWED_SHORT
 #define GSR_WINDOWED_SHORT 600  // pair capacity per tile up to which the windowed chain sorts with the 2048-key variant
 #endif
-template <bool kGather, int kLds, bool kExtra>
+template <bool kGather, int kLds, bool kExtra, bool kAlpha = false>
 __global__ __launch_bounds__(kFwdThreads, (kLds == 2048 && kGather && !kExtra) ? GSR_TF_WAVES : 4) void k_tile_fwd(const Params p) {
   static_assert(kSortThreads == kFwdThreads, "one workgroup shape for the two phases");
   constexpr int kSortWords = SortLds<kLds>::kWords, kBlendWords = (int)((sizeof(BlendLds) + sizeof(BlendFin) + 7) / 8);
@@ -2566,7 +2581,7 @@ __global__ __launch_bounds__(kFwdThreads, (kLds == 2048 && kGather && !kExtra) ?
   __syncthreads();  // the list is this workgroup's own: its stores are visible to its waves from here on; the keys are dead
   const int tg = kGather ? xcd_remap((int)bid, (int)p.sort_blocks) : (int)bid;
   const int v = tg / p.g.T;
-  blend_tile<kExtra>(p, v, tg - v * p.g.T, rg, *reinterpret_cast<BlendLds*>(smem));
+  blend_tile<kExtra, kAlpha>(p, v, tg - v * p.g.T, rg, *reinterpret_cast<BlendLds*>(smem));
   if (kGather && threadIdx.x == 64 && rg.y - rg.x > p.status->max_list) atomicMax(&p.status->max_list, rg.y - rg.x);
 }
 
@@ -2620,7 +2635,7 @@ __device__ __forceinline__ void bitonic_whole_list(unsigned long long* sk, uint3
 // cursors packed two to a 32-bit word (a cursor is at most 2048: sixteen bits; the LDS atomic adds 1 or 1 << 16) - 25.7 KB of LDS
 // instead of 31.9, and the instance is built for six waves per SIMD (80 VGPRs): SIX workgroups per CU instead of five.  The single
 // view (1024 tiles = four per CU) has nothing to gain from that and keeps its instance untouched.
-template <bool kExtra, bool kCompact>
+template <bool kExtra, bool kCompact, bool kAlpha = false>
 __global__ __launch_bounds__(kFwdThreads, kCompact ? 6 : 4) void k_tile_fwd_prefix(const Params p) {
   constexpr int kLds = 2048;
   constexpr int kBk = kCompact ? 1024 : SortLds<kLds>::kBuckets, kBkBits = kCompact ? 10 : SortLds<kLds>::kBucketBits, kBpt = kBk / kSortThreads;
@@ -2903,8 +2918,8 @@ __global__ __launch_bounds__(kFwdThreads, kCompact ? 6 : 4) void k_tile_fwd_pref
     }
   };
   // (usual path: the flag as thread 0 read it at the kernel's start, handed round through LDS - the same value in every wave)
-  if (fast_path ? (sInfo[3] != 0u && blend_poisoned<kExtra>(p, v, pxi, pyi, inside, true))
-                                          : blend_poisoned<kExtra>(p, v, pxi, pyi, inside)) {
+  if (fast_path ? (sInfo[3] != 0u && blend_poisoned<kExtra, kAlpha>(p, v, pxi, pyi, inside, true))
+                                          : blend_poisoned<kExtra, kAlpha>(p, v, pxi, pyi, inside)) {
     report_length();
     return;
   }
@@ -2947,9 +2962,9 @@ __global__ __launch_bounds__(kFwdThreads, kCompact ? 6 : 4) void k_tile_fwd_pref
     int ln = lane;
     asm volatile("" : "+v"(ln));
     const int qx = tx * 8 + (ln & 7), qy = ty * 8 + (ln >> 3);
-    blend_finish<kExtra>(p, v, t, n, *reinterpret_cast<BlendFin*>(smem), acc, qx, qy, qx < g.W && qy < g.H, bg0, bg1, bg2);
+    blend_finish<kExtra, kAlpha>(p, v, t, n, *reinterpret_cast<BlendFin*>(smem), acc, qx, qy, qx < g.W && qy < g.H, bg0, bg1, bg2);
   } else {
-    blend_finish<kExtra>(p, v, t, n, *reinterpret_cast<BlendFin*>(smem), acc, pxi, pyi, inside, bg0, bg1, bg2);
+    blend_finish<kExtra, kAlpha>(p, v, t, n, *reinterpret_cast<BlendFin*>(smem), acc, pxi, pyi, inside, bg0, bg1, bg2);
   }
   report_length();
   (void)sInfo;
@@ -3024,7 +3039,9 @@ __device__ __forceinline__ float from_fixed(long long x) { return (float)x * kFi
 // walked (Params::tile_total); every workgroup finds its own tile: a selection by bisection over the <= 256 keys of its XCD, one wave, ballots only.
 constexpr int kBalanceMax = 256;  // tiles per XCD up to which the deal is computed (more: image order; later rounds balance themselves)
 
-template <bool kExtra, bool kDet>
+// kAlpha (gsr_backward_alpha): a loss on the accumulated alpha A = 1 - T_final.  dA/dalpha_j = T_final / (1 - alpha_j) is the
+// background term's derivative with the sign turned, so dL/dA enters where the background does: Q starts from bg.g - g_A.
+template <bool kExtra, bool kDet, bool kAlpha = false>
 __global__ __launch_bounds__(kBwdThreads, 4) void k_blend_bwd(const Params p) {
   __shared__ __attribute__((aligned(16))) float sW[kBwdWaves][kBS][64];  // A -> R, per wave: blend weight w
   __shared__ __attribute__((aligned(16))) float sQ[kBwdWaves][kBS][64];  // A -> R, per wave: G dL/dalpha
@@ -3341,6 +3358,10 @@ __global__ __launch_bounds__(kBwdThreads, 4) void k_blend_bwd(const Params p) {
   const float T_final = inside ? p.final_T[(size_t)v * HW + pix] : 0.f;
   float Tb = T_final;                                              // (T, Q) at the back end of the batch: the same in all four
   float Qb = cam.bg[0] * g0 + cam.bg[1] * g1 + cam.bg[2] * g2;    // waves (behind the last splat Q = Bg / T_final = bg.g)
+  if (kAlpha) {
+    Qb -= inside ? p.dL_dalpha_img[(size_t)v * HW + pix] : 0.f;
+    asm volatile("" : "+v"(Qb));  // (arrived before the loop, like T_final below)
+  }
   if (dbg) stamp[1] = __builtin_amdgcn_s_memrealtime();
   // T_final has to have ARRIVED before the loop: a load still counted as pending at the loop's entry makes the compiler wait
   // for "everything" at the first use of Tb inside the loop - on every iteration, right behind the gather just issued
@@ -4364,7 +4385,7 @@ static_assert(sizeof(GsrForwardOptions) == 24 && sizeof(GsrBackwardOptions) == 4
 static int forward_impl(const GsrDims* dims, const GsrView* views, const float* means, const float* cov6,
                         const float* opacities, const float* colors, const float* extra, float* out_color,
                         float* out_extra, int32_t* radii, void* geom, void* bin, void* img, hipStream_t st,
-                        hipEvent_t* ev, const SrArgs* sr) {
+                        hipEvent_t* ev, const SrArgs* sr, float* out_alpha = nullptr) {
   if (!call_dims_ok(dims, sr)) return GSR_ERR_INVALID_ARGUMENT;
   const GsrDims& d = *dims;
   const size_t V = d.num_views, N = d.num_gaussians, HW = (size_t)d.height * d.width;
@@ -4373,7 +4394,7 @@ static int forward_impl(const GsrDims* dims, const GsrView* views, const float* 
   if (d.has_extra && !out_extra) return GSR_ERR_INVALID_ARGUMENT;
   if (d.has_extra && N > 0 && !extra && ((d.flags >> 4) & 7) == 0) return GSR_ERR_INVALID_ARGUMENT;  // (an empty array has no address)
   Params p = base_params(dims, views, means, cov6, opacities, colors, extra, geom, bin, img);
-  p.out_color = out_color; p.out_extra = out_extra; p.radii = radii;
+  p.out_color = out_color; p.out_extra = out_extra; p.radii = radii; p.out_alpha = out_alpha;
   if (sr) { p.scale_rot = 1; p.frames = sr->frames; p.num_frames = sr->frames ? sr->num_frames : 1; }
   static std::atomic<uint32_t> call_counter{1u};
   p.call_tag = call_counter.fetch_add(1u, std::memory_order_relaxed);
@@ -4381,6 +4402,7 @@ static int forward_impl(const GsrDims* dims, const GsrView* views, const float* 
   if (N == 0) {  // upstream returns an all-zero image when there is nothing to rasterize
     GSR_CHECK(hipMemsetAsync(out_color, 0, V * 3 * HW * sizeof(float), st));
     if (d.has_extra) GSR_CHECK(hipMemsetAsync(out_extra, 0, V * HW * sizeof(float), st));
+    if (out_alpha) GSR_CHECK(hipMemsetAsync(out_alpha, 0, V * HW * sizeof(float), st));
     GSR_CHECK(hipMemsetAsync(bin, 0, L.o_counts, st));
     GSR_CHECK(hipMemsetAsync(img, 0, L.img_bytes, st));
     return GSR_OK;
@@ -4440,13 +4462,13 @@ static int forward_impl(const GsrDims* dims, const GsrView* views, const float* 
   p.sort_blocks = (uint32_t)VT;
   {
     const dim3 tgrid((unsigned)VT);
-    const bool extra = d.has_extra != 0;
+    const bool extra = d.has_extra != 0, alpha = out_alpha != nullptr;  // (alpha: the kAlpha instances, which also store 1 - final_T)
     // every list that sits in its slot is at most `stride` long: a small slot means short lists, and the 2048-key variant
     // (windowed chain: lists are contiguous ranges of any length; short ones on average - a large image - sort in the 2048-key
     // variant, whose smaller LDS footprint lets six workgroups share a CU; a list longer than the LDS array sorts in memory either way)
     auto tiles = [&](auto gather, bool short_lists) {
-      dispatch_bools([&](auto sh, auto x) { hipLaunchKernelGGL((k_tile_fwd<decltype(gather)::value, sh.value ? 2048 : 4096, x.value>), tgrid, dim3(kFwdThreads), 0, st, p); },
-                     short_lists, extra);
+      dispatch_bools([&](auto a, auto sh, auto x) { hipLaunchKernelGGL((k_tile_fwd<decltype(gather)::value, sh.value ? 2048 : 4096, x.value, a.value>), tgrid, dim3(kFwdThreads), 0, st, p); },
+                     alpha, short_lists, extra);
     };
     // (more tiles than five workgroups per CU hold at once: the compact instance, six per CU.  Round 5: with the extra channel too - until
     // stage A formed its weights after the death decision (blend_range) that instance spilled the record in flight at 80 registers)
@@ -4458,7 +4480,7 @@ static int forward_impl(const GsrDims* dims, const GsrView* views, const float* 
     // instance (25.8 KB, 80 registers: six workgroups per CU, like k_tile_fwd's) keeps its cheaper gather - no scan over the rows,
     // four barriers fewer - and takes them when the call has more tiles than the chip holds at once: that view 174.3 -> 167.3 us.
     else if (p.stride <= 2048u && (p.stride > (uint32_t)(kPrefix + kPrefix / 4) || compact) && p.rows <= kSortThreads)
-      dispatch_bools([&](auto x, auto c) { hipLaunchKernelGGL((k_tile_fwd_prefix<x.value, c.value>), tgrid, dim3(kFwdThreads), 0, st, p); }, extra, compact);
+      dispatch_bools([&](auto a, auto x, auto c) { hipLaunchKernelGGL((k_tile_fwd_prefix<x.value, c.value, a.value>), tgrid, dim3(kFwdThreads), 0, st, p); }, alpha, extra, compact);
     else tiles(std::true_type{}, p.stride <= 2048u);
   }
   GSR_STAGE_DONE(4);
@@ -4467,15 +4489,21 @@ static int forward_impl(const GsrDims* dims, const GsrView* views, const float* 
   return GSR_OK;
 }
 
-int gsr_forward_ex(const GsrDims* dims, const GsrView* views, const float* means, const float* cov, const float* opacities,
-                   const float* colors, const float* extra, float* out_color, float* out_extra, int32_t* radii, void* geom,
-                   void* bin, void* img, const GsrForwardOptions* opt, void* stream_) {
+int gsr_forward_alpha(const GsrDims* dims, const GsrView* views, const float* means, const float* cov, const float* opacities,
+                      const float* colors, const float* extra, float* out_color, float* out_extra, float* out_alpha,
+                      int32_t* radii, void* geom, void* bin, void* img, const GsrForwardOptions* opt, void* stream_) {
   hipStream_t st = static_cast<hipStream_t>(stream_);
   SrArgs sr_store;
   const SrArgs* sr = sr_of(opt, &sr_store);
   return with_stage_events<GSR_FWD_STAGES>(dims, st, opt ? opt->stage_ms : nullptr, [&](hipEvent_t* ev) {
-    return forward_impl(dims, views, means, cov, opacities, colors, extra, out_color, out_extra, radii, geom, bin, img, st, ev, sr);
+    return forward_impl(dims, views, means, cov, opacities, colors, extra, out_color, out_extra, radii, geom, bin, img, st, ev, sr, out_alpha);
   });
+}
+
+int gsr_forward_ex(const GsrDims* dims, const GsrView* views, const float* means, const float* cov, const float* opacities,
+                   const float* colors, const float* extra, float* out_color, float* out_extra, int32_t* radii, void* geom,
+                   void* bin, void* img, const GsrForwardOptions* opt, void* stream) {
+  return gsr_forward_alpha(dims, views, means, cov, opacities, colors, extra, out_color, out_extra, nullptr, radii, geom, bin, img, opt, stream);
 }
 
 int gsr_forward(const GsrDims* dims, const GsrView* views, const float* means, const float* cov6,
@@ -4489,7 +4517,8 @@ static int backward_impl(const GsrDims* dims, const GsrView* views, const float*
                          const void* bin, const void* img, const float* dL_dcolor, const float* dL_dextra_img,
                          void* scratch, float* dL_dmeans, float* dL_dcov6, float* dL_dopacities,
                          float* dL_dcolors, float* dL_dextra, float* dL_dmeans2D, hipStream_t st, hipEvent_t* ev,
-                         const SrArgs* sr, float* dL_dviews, float* pose_partials, int depth_term_only) {
+                         const SrArgs* sr, float* dL_dviews, float* pose_partials, int depth_term_only,
+                         const float* dL_dalpha_img = nullptr) {
   if (!call_dims_ok(dims, sr)) return GSR_ERR_INVALID_ARGUMENT;
   const GsrDims& d = *dims;
   const size_t V = d.num_views, N = d.num_gaussians;
@@ -4500,7 +4529,7 @@ static int backward_impl(const GsrDims* dims, const GsrView* views, const float*
     return GSR_ERR_INVALID_ARGUMENT;
   Params p = base_params(dims, views, means, cov6, opacities, colors, extra, const_cast<void*>(geom),
                          const_cast<void*>(bin), const_cast<void*>(img));
-  p.dL_dcolor = dL_dcolor; p.dL_dextra_img = d.has_extra ? dL_dextra_img : nullptr;
+  p.dL_dcolor = dL_dcolor; p.dL_dextra_img = d.has_extra ? dL_dextra_img : nullptr; p.dL_dalpha_img = dL_dalpha_img;
   if (sr) { p.scale_rot = 1; p.frames = sr->frames; p.num_frames = sr->frames ? sr->num_frames : 1; }
   p.scratch = own_rows ? reinterpret_cast<float*>(p.grad_rows) : static_cast<float*>(scratch);
   p.dL_dmeans = dL_dmeans; p.dL_dcov6 = dL_dcov6; p.dL_dopac = dL_dopacities; p.dL_dcolors = dL_dcolors;
@@ -4510,8 +4539,8 @@ static int backward_impl(const GsrDims* dims, const GsrView* views, const float*
   const bool det = (d.flags & GSR_FLAG_DETERMINISTIC) != 0;
   if (!own_rows) GSR_CHECK(hipMemsetAsync(scratch, 0, scratch_bytes_of(d), st));
   const dim3 bgrid((unsigned)p.g.T, (unsigned)V);
-  dispatch_bools([&](auto x, auto dt) { hipLaunchKernelGGL((k_blend_bwd<x.value, dt.value>), bgrid, dim3(kBwdThreads), 0, st, p); },
-                 p.dL_dextra_img != nullptr, det);
+  dispatch_bools([&](auto a, auto x, auto dt) { hipLaunchKernelGGL((k_blend_bwd<x.value, dt.value, a.value>), bgrid, dim3(kBwdThreads), 0, st, p); },
+                 dL_dalpha_img != nullptr, p.dL_dextra_img != nullptr, det);
   GSR_STAGE_DONE(0);
   GSR_MARK();
   const int rowf = 3 * d.sh_coeffs, ldstride = rowf | 1;
@@ -4567,14 +4596,23 @@ int gsr_backward_ex(const GsrDims* dims, const GsrView* views, const float* mean
                     const float* colors, const float* extra, const void* geom, const void* bin, const void* img,
                     const float* dL_dcolor, const float* dL_dextra_img, void* scratch, float* dL_dmeans, float* dL_dcov,
                     float* dL_dopacities, float* dL_dcolors, float* dL_dextra, float* dL_dmeans2D, const GsrBackwardOptions* opt,
-                    void* stream_) {
+                    void* stream) {
+  return gsr_backward_alpha(dims, views, means, cov, opacities, colors, extra, geom, bin, img, dL_dcolor, dL_dextra_img, nullptr, scratch, dL_dmeans,
+                            dL_dcov, dL_dopacities, dL_dcolors, dL_dextra, dL_dmeans2D, opt, stream);
+}
+
+int gsr_backward_alpha(const GsrDims* dims, const GsrView* views, const float* means, const float* cov, const float* opacities,
+                       const float* colors, const float* extra, const void* geom, const void* bin, const void* img,
+                       const float* dL_dcolor, const float* dL_dextra_img, const float* dL_dalpha_img, void* scratch, float* dL_dmeans,
+                       float* dL_dcov, float* dL_dopacities, float* dL_dcolors, float* dL_dextra, float* dL_dmeans2D,
+                       const GsrBackwardOptions* opt, void* stream_) {
   hipStream_t st = static_cast<hipStream_t>(stream_);
   SrArgs sr_store;
   const SrArgs* sr = sr_of(opt, &sr_store);
   return with_stage_events<GSR_BWD_STAGES>(dims, st, opt ? opt->stage_ms : nullptr, [&](hipEvent_t* ev) {
     return backward_impl(dims, views, means, cov, opacities, colors, extra, geom, bin, img, dL_dcolor, dL_dextra_img, scratch, dL_dmeans, dL_dcov,
                          dL_dopacities, dL_dcolors, dL_dextra, dL_dmeans2D, st, ev, sr, opt ? opt->dL_dviews : nullptr,
-                         opt ? opt->pose_partials : nullptr, opt ? opt->depth_term_only : 0);
+                         opt ? opt->pose_partials : nullptr, opt ? opt->depth_term_only : 0, dL_dalpha_img);
   });
 }
 

@@ -46,6 +46,8 @@ struct Abi {
   decltype(&gsr_capacity_for) capacity_for = nullptr;
   decltype(&gsr_forward_ex) forward_ex = nullptr;
   decltype(&gsr_backward_ex) backward_ex = nullptr;
+  decltype(&gsr_forward_alpha) forward_alpha = nullptr;
+  decltype(&gsr_backward_alpha) backward_alpha = nullptr;
   decltype(&gsr_pose_partials_bytes) pose_partials_bytes = nullptr;
   decltype(&gsr_backward_scratch_bytes) backward_scratch_bytes = nullptr;
   decltype(&gsr_last_failed_stage) last_failed_stage = nullptr;
@@ -77,6 +79,8 @@ void init(const std::string& path) {
   resolve(g_abi.capacity_for, "gsr_capacity_for");
   resolve(g_abi.forward_ex, "gsr_forward_ex");
   resolve(g_abi.backward_ex, "gsr_backward_ex");
+  resolve(g_abi.forward_alpha, "gsr_forward_alpha");
+  resolve(g_abi.backward_alpha, "gsr_backward_alpha");
   resolve(g_abi.pose_partials_bytes, "gsr_pose_partials_bytes");
   resolve(g_abi.backward_scratch_bytes, "gsr_backward_scratch_bytes");
   resolve(g_abi.last_failed_stage, "gsr_last_failed_stage");
@@ -123,7 +127,8 @@ void rc_check(int rc, const char* what, bool backward) {
 struct Cfg {
   int num_views = 0, num_sets = 0, views_per_set = 0, num_gaussians = 0, height = 0, width = 0, sh_degree = 0, sh_coeffs = 0, max_sh_eval = 4;
   int has_extra = 0, flags = 0, scale_rot = 0;
-  auto tie() const { return std::tie(num_views, num_sets, views_per_set, num_gaussians, height, width, sh_degree, sh_coeffs, max_sh_eval, has_extra, flags, scale_rot); }
+  int alpha = 0;  // the accumulated-alpha image is wanted (gsr_forward_alpha / gsr_backward_alpha); not part of the dims: it sizes nothing
+  auto tie() const { return std::tie(num_views, num_sets, views_per_set, num_gaussians, height, width, sh_degree, sh_coeffs, max_sh_eval, has_extra, flags, scale_rot, alpha); }
   bool operator<(const Cfg& o) const { return tie() < o.tie(); }
   // the dims of the sizing helpers: without the GSR_FLAG_SH_IN_FRAME bits, which only the launches take (they size nothing)
   GsrDims dims(int64_t capacity) const {
@@ -142,11 +147,11 @@ struct Cfg {
   int extra_mode() const { return (flags >> 4) & 7; }
 };
 Cfg cfg_from(const std::vector<int64_t>& v) {
-  TORCH_CHECK(v.size() == 12, "cfg: 12 integers expected");
+  TORCH_CHECK(v.size() == 12 || v.size() == 13, "cfg: 12 integers expected (a 13th: accumulated alpha wanted)");
   Cfg c;
   c.num_views = (int)v[0]; c.num_sets = (int)v[1]; c.views_per_set = (int)v[2]; c.num_gaussians = (int)v[3]; c.height = (int)v[4];
   c.width = (int)v[5]; c.sh_degree = (int)v[6]; c.sh_coeffs = (int)v[7]; c.max_sh_eval = (int)v[8]; c.has_extra = (int)v[9];
-  c.flags = (int)v[10]; c.scale_rot = (int)v[11];
+  c.flags = (int)v[10]; c.scale_rot = (int)v[11]; c.alpha = v.size() > 12 && v[12] != 0;
   return c;
 }
 std::vector<int64_t> dims_vec(const GsrDims& d) {
@@ -214,11 +219,13 @@ struct Saved {  // what a differentiated forward hands its backward
 struct ForwardOut {
   Tensor color, extra_img, radii;
   Saved saved;
+  Tensor alpha_img;  // (V, H, W), only when the call shape asks for it (Cfg::alpha)
 };
 
 struct Plan {
   GsrDims dims;
   Tensor color, extra_img, radii, geom, bin, img;
+  Tensor alpha_img;
 };
 
 struct Sizes { size_t geom = 0, bin = 0, img = 0, scratch = 0; };
@@ -307,7 +314,7 @@ class Backend : public std::enable_shared_from_this<Backend> {
       TORCH_CHECK(capacity > 0 || known, "gsr_forward under stream capture: pass `capacity` (or run the shape once outside the capture)");
       Plan plan = make_plan(cfg, dev, capacity > 0 ? capacity : default_capacity(cfg), false, one_view);
       run_forward(plan, cfg, viewbuf, means, cov, opac, colors, extra, frames, stream);
-      ForwardOut o{plan.color, plan.extra_img, plan.radii, {}};
+      ForwardOut o{plan.color, plan.extra_img, plan.radii, {}, plan.alpha_img};
       o.saved = Saved{true, plan.dims, plan.geom, plan.bin, plan.img, 0};
       return o;
     }
@@ -328,7 +335,7 @@ class Backend : public std::enable_shared_from_this<Backend> {
         std::lock_guard<std::mutex> g(mu_);
         token = ++token_;
       }
-      ForwardOut out{plan.color, plan.extra_img, plan.radii, {}};
+      ForwardOut out{plan.color, plan.extra_img, plan.radii, {}, plan.alpha_img};
       if (!reuse_workspaces) out.saved = Saved{true, plan.dims, plan.geom, plan.bin, plan.img, token};
       if (cfg.num_gaussians == 0 || cfg.num_views == 0) return out;
       if (lazy) {
@@ -418,7 +425,8 @@ class Backend : public std::enable_shared_from_this<Backend> {
   // -> d_means, d_cov, d_opac, d_colors, d_extra, d_means2d, d_views (undefined where not asked for)
   std::vector<Tensor> backward(const Cfg& cfg, const Saved& saved, const Tensor& viewbuf, const Tensor& means, const Tensor& cov, const Tensor& opac,
                                const Tensor& colors, const Tensor& extra_in, const Tensor& g_color_in, const Tensor& g_extra_in, bool want_means2d,
-                               bool rows_in_workspace, const Tensor& frames, int want_views /* 0 none, 1 all, 2 depth term */) {
+                               bool rows_in_workspace, const Tensor& frames, int want_views /* 0 none, 1 all, 2 depth term */,
+                               const Tensor& g_alpha_in = Tensor() /* dL/d accumulated alpha (V, H, W); undefined: none */) {
     TORCH_CHECK(saved.valid, "this forward ran with reuse_workspaces=True (nothing was to be differentiated): it has no backward");
     const at::Device dev = viewbuf.device();
     c10::hip::HIPGuard guard(dev.index());
@@ -451,10 +459,17 @@ class Backend : public std::enable_shared_from_this<Backend> {
         partials = at::empty({(int64_t)std::max<size_t>(16, g_abi.pose_partials_bytes(&sizing_dims))}, f32.dtype(at::kByte));
         opt.dL_dviews = d_views.data_ptr<float>(); opt.pose_partials = reinterpret_cast<float*>(partials.data_ptr()); opt.depth_term_only = want_views == 2;
       }
-      const int rc = g_abi.backward_ex(&saved.dims, vb, fptr(means), fptr(cov), fptr(opac), fptr(colors), fptr(extra), saved.geom.data_ptr(),
-                                       saved.bin.data_ptr(), saved.img.data_ptr(), fptr(g_color), fptr(g_extra), scratch.defined() ? scratch.data_ptr() : nullptr,
-                                       fptr_mut(d_means), fptr_mut(d_cov), fptr_mut(d_opac), fptr_mut(d_colors), fptr_mut(d_extra), fptr_mut(d_means2d),
-                                       (cfg.scale_rot || want_views) ? &opt : nullptr, stream);
+      const Tensor g_alpha = f32c(g_alpha_in);
+      if (g_alpha.defined()) TORCH_CHECK(g_alpha.numel() == (int64_t)v * cfg.height * cfg.width, "dL/dalpha must be (views, H, W)");
+      const GsrBackwardOptions* optp = (cfg.scale_rot || want_views) ? &opt : nullptr;
+      void* const scr = scratch.defined() ? scratch.data_ptr() : nullptr;
+      const int rc = g_alpha.defined()
+          ? g_abi.backward_alpha(&saved.dims, vb, fptr(means), fptr(cov), fptr(opac), fptr(colors), fptr(extra), saved.geom.data_ptr(), saved.bin.data_ptr(),
+                                 saved.img.data_ptr(), fptr(g_color), fptr(g_extra), fptr(g_alpha), scr, fptr_mut(d_means), fptr_mut(d_cov), fptr_mut(d_opac),
+                                 fptr_mut(d_colors), fptr_mut(d_extra), fptr_mut(d_means2d), optp, stream)
+          : g_abi.backward_ex(&saved.dims, vb, fptr(means), fptr(cov), fptr(opac), fptr(colors), fptr(extra), saved.geom.data_ptr(), saved.bin.data_ptr(),
+                              saved.img.data_ptr(), fptr(g_color), fptr(g_extra), scr, fptr_mut(d_means), fptr_mut(d_cov), fptr_mut(d_opac), fptr_mut(d_colors),
+                              fptr_mut(d_extra), fptr_mut(d_means2d), optp, stream);
       rc_check(rc, "gsr_backward", true);
     } else if (want_views) {
       d_views = at::zeros({v, kViewFloats}, f32);
@@ -516,13 +531,14 @@ class Backend : public std::enable_shared_from_this<Backend> {
     p.bin = whole.narrow(0, 0, (int64_t)sz.bin);
     p.geom = whole.narrow(0, o_g, (int64_t)sz.geom);
     p.img = whole.narrow(0, o_i, (int64_t)sz.img);
-    if (one_view && cfg.num_views == 1 && !cfg.has_extra) {
+    if (one_view && cfg.num_views == 1 && !cfg.has_extra && !cfg.alpha) {
       p.color = at::empty({3, cfg.height, cfg.width}, f32);
       p.radii = at::empty({cfg.num_gaussians}, u8.dtype(at::kInt));
       return p;
     }
     p.color = at::empty({cfg.num_views, 3, cfg.height, cfg.width}, f32);
     if (cfg.has_extra) p.extra_img = at::empty({cfg.num_views, cfg.height, cfg.width}, f32);
+    if (cfg.alpha) p.alpha_img = at::empty({cfg.num_views, cfg.height, cfg.width}, f32);
     p.radii = at::empty({cfg.num_views, cfg.num_gaussians}, u8.dtype(at::kInt));
     return p;
   }
@@ -541,9 +557,12 @@ class Backend : public std::enable_shared_from_this<Backend> {
     const GsrView* vb = reinterpret_cast<const GsrView*>(viewbuf.data_ptr<float>());
     const Tensor fr = cfg.scale_rot ? frames_arg(cfg, frames) : Tensor();
     const GsrForwardOptions opt = launch_options<GsrForwardOptions>(cfg, fr);
-    const int rc = g_abi.forward_ex(&p.dims, vb, fptr(means), fptr(cov), fptr(opac), fptr(colors), fptr(extra), p.color.data_ptr<float>(),
-                                    fptr_mut(p.extra_img), p.radii.data_ptr<int32_t>(), p.geom.data_ptr(), p.bin.data_ptr(), p.img.data_ptr(),
-                                    cfg.scale_rot ? &opt : nullptr, stream);
+    const GsrForwardOptions* optp = cfg.scale_rot ? &opt : nullptr;
+    const int rc = p.alpha_img.defined()
+        ? g_abi.forward_alpha(&p.dims, vb, fptr(means), fptr(cov), fptr(opac), fptr(colors), fptr(extra), p.color.data_ptr<float>(), fptr_mut(p.extra_img),
+                              fptr_mut(p.alpha_img), p.radii.data_ptr<int32_t>(), p.geom.data_ptr(), p.bin.data_ptr(), p.img.data_ptr(), optp, stream)
+        : g_abi.forward_ex(&p.dims, vb, fptr(means), fptr(cov), fptr(opac), fptr(colors), fptr(extra), p.color.data_ptr<float>(), fptr_mut(p.extra_img),
+                           p.radii.data_ptr<int32_t>(), p.geom.data_ptr(), p.bin.data_ptr(), p.img.data_ptr(), optp, stream);
     rc_check(rc, "gsr_forward", false);
   }
 
@@ -683,6 +702,12 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
       extra_img = at::empty({0}, o.color.options());
       ctx->mark_non_differentiable({extra_img});
     }
+    if (cfg.alpha) {  // a third differentiable output, only when asked for
+      // an output the loss does not use arrives in backward() as an undefined tensor instead of a materialised image of zeros: an alpha
+      // image that was only looked at then costs the backward nothing (gsr_backward_ex, the instances without alpha)
+      ctx->set_materialize_grads(false);
+      return {o.color, extra_img, o.radii, o.alpha_img};
+    }
     return {o.color, extra_img, o.radii};
   }
 
@@ -706,7 +731,8 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
     const int want_views = cam ? (ctx->saved_data["camera_gradient"].toInt() == 2 ? 2 : 1) : 0;
     const c10::IValue& fr = ctx->saved_data["frames"];
     std::vector<Tensor> g = holder->be->backward(cfg, ws, viewbuf, means, cov, opac, colors, extra, g_color, g_extra, ctx->saved_data["want_means2d"].toBool(),
-                                                 ctx->saved_data["rows_fresh"].toBool(), fr.isTensor() ? fr.toTensor() : Tensor(), want_views);
+                                                 ctx->saved_data["rows_fresh"].toBool(), fr.isTensor() ? fr.toTensor() : Tensor(), want_views,
+                                                 (cfg.alpha && grads.size() > 3) ? grads[3] : Tensor());
     ctx->saved_data["rows_fresh"] = false;
     // the workspaces stay with ctx (freed with the graph): a second backward (retain_graph=True, several autograd.grad calls over one
     // render) runs on them again, as upstream's Function can
@@ -932,7 +958,7 @@ pybind11::dict status_dict(const Status& st) {
 // announces a backward.  Runs WITHOUT the GIL (the callers below release it around their work and take it back to build the result):
 // a blocking forward polls its status block for as long as its kernels run, and other Python threads - a data loader's pin-memory
 // thread - must not stand still meanwhile.
-struct RasterOut { Tensor color, extra_img, radii; };
+struct RasterOut { Tensor color, extra_img, radii, alpha_img; };
 RasterOut rasterize_impl(PyBackend& pb, const Tensor& means, const Tensor& cov, const Tensor& opac, const Tensor& colors, const c10::optional<Tensor>& extra,
                          const c10::optional<Tensor>& means2d, const Tensor& viewbuf, const std::vector<int64_t>& cfgv, const c10::optional<Tensor>& frames,
                          int64_t camera_gradient) {
@@ -941,16 +967,18 @@ RasterOut rasterize_impl(PyBackend& pb, const Tensor& means, const Tensor& cov, 
   RasterOut r;
   if (!(cfg.flags & GSR_FLAG_BACKWARD_FOLLOWS)) {  // nothing here can be differentiated: no autograd node, no saved workspaces
     ForwardOut o = pb.be().forward(cfg, viewbuf, means, cov, opac, colors, ex, fr, -1, true);
-    r.color = o.color; r.extra_img = o.extra_img; r.radii = o.radii;
+    r.color = o.color; r.extra_img = o.extra_img; r.radii = o.radii; r.alpha_img = o.alpha_img;
   } else {
     auto out = RasterizeFn::apply(means, cov, opac, colors, extra, means2d, viewbuf, frames, pb.holder, cfgv, camera_gradient);
     r.color = out[0]; r.radii = out[2];
     if (cfg.has_extra) r.extra_img = out[1];
+    if (cfg.alpha) r.alpha_img = out[3];
   }
   return r;
 }
 pybind11::tuple raster_tuple(const RasterOut& r) {
   pybind11::object e = r.extra_img.defined() ? pybind11::cast(r.extra_img) : pybind11::none();
+  if (r.alpha_img.defined()) return pybind11::make_tuple(r.color, e, r.radii, r.alpha_img);  // (only a call that asked for alpha gets four)
   return pybind11::make_tuple(r.color, e, r.radii);
 }
 pybind11::tuple rasterize(PyBackend& pb, const Tensor& means, const Tensor& cov, const Tensor& opac, const Tensor& colors, const c10::optional<Tensor>& extra,
@@ -1025,12 +1053,13 @@ pybind11::tuple rasterize_views(PyBackend& pb, const Tensor& means_in, const Ten
                                 int64_t h, int64_t w, int64_t sh_degree, bool use_sh, int64_t views_per_set, const c10::optional<Tensor>& extra_in,
                                 const c10::optional<Tensor>& means2d, int64_t max_sh_eval, bool sh_planar, bool cov_3x3, int64_t extra_mode, bool debug,
                                 bool prefiltered, int64_t deterministic, bool scale_rot, const c10::optional<Tensor>& frames_in, int64_t camera_gradient,
-                                int64_t sh_frame) {
+                                int64_t sh_frame, bool return_alpha) {
   RasterOut result;
   {
   pybind11::gil_scoped_release nogil;
-  const Prepared p = prepare_call(means_in, cov_in, opac_in, colors_in, viewbuf_in, h, w, sh_degree, use_sh, views_per_set, extra_in, means2d, max_sh_eval, sh_planar,
+  Prepared p = prepare_call(means_in, cov_in, opac_in, colors_in, viewbuf_in, h, w, sh_degree, use_sh, views_per_set, extra_in, means2d, max_sh_eval, sh_planar,
                                   cov_3x3, extra_mode, debug, prefiltered, deterministic, scale_rot, frames_in, camera_gradient, sh_frame);
+  if (return_alpha) p.cfgv.push_back(1);  // (Cfg::alpha: the thirteenth integer of a call shape that wants the accumulated alpha)
   result = rasterize_impl(pb, p.means, p.cov, p.opac, p.colors, p.extra, means2d, p.viewbuf, p.cfgv, p.frames, camera_gradient);
   }
   return raster_tuple(result);
@@ -1121,10 +1150,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              return status_dict(st);
            })
       .def("make_plan", [](PyBackend& b, const std::vector<int64_t>& cfgv, const at::Device& device, int64_t capacity) {
-             // the plan API's outputs and workspaces: (dims (13 ints), color, extra_img | None, radii, geom, bin, img, backward-scratch bytes)
+             // the plan API's outputs and workspaces: (dims (13 ints), color, extra_img | None, radii, geom, bin, img, backward-scratch bytes
+             // [, alpha_img: a call shape that wants the accumulated alpha])
              const Cfg cfg = cfg_from(cfgv);
              const Plan p = b.be().make_plan(cfg, device, capacity, false);
              pybind11::object e = p.extra_img.defined() ? pybind11::cast(p.extra_img) : pybind11::none();
+             if (cfg.alpha)
+               return pybind11::make_tuple(dims_vec(p.dims), p.color, e, p.radii, p.geom, p.bin, p.img, b.be().sized(cfg, capacity).scratch, p.alpha_img);
              return pybind11::make_tuple(dims_vec(p.dims), p.color, e, p.radii, p.geom, p.bin, p.img, b.be().sized(cfg, capacity).scratch);
            })
       .def("check_pending", [](PyBackend& b, bool wait, int64_t only_token) { pybind11::gil_scoped_release nogil; b.be().check_pending(wait, only_token); },
@@ -1142,25 +1174,30 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              pybind11::object saved = pybind11::none();
              if (o.saved.valid) saved = pybind11::make_tuple(dims_vec(o.saved.dims), o.saved.geom, o.saved.bin, o.saved.img, o.saved.token);
              pybind11::object e = o.extra_img.defined() ? pybind11::cast(o.extra_img) : pybind11::none();
+             if (o.alpha_img.defined()) return pybind11::make_tuple(o.color, e, o.radii, saved, o.alpha_img);
              return pybind11::make_tuple(o.color, e, o.radii, saved);
            }, pybind11::arg("cfg"), pybind11::arg("viewbuf"), pybind11::arg("means"), pybind11::arg("cov"), pybind11::arg("opac"), pybind11::arg("colors"),
            pybind11::arg("extra"), pybind11::arg("frames"), pybind11::arg("capacity") = -1, pybind11::arg("reuse_workspaces") = false)
       .def("backward", [](PyBackend& b, const std::vector<int64_t>& cfgv, const std::vector<int64_t>& dimsv, const Tensor& geom, const Tensor& bin, const Tensor& img,
                           int64_t token, const Tensor& viewbuf, const Tensor& means, const Tensor& cov, const Tensor& opac, const Tensor& colors,
                           const c10::optional<Tensor>& extra, const Tensor& g_color, const c10::optional<Tensor>& g_extra, bool want_means2d, bool rows_in_workspace,
-                          const c10::optional<Tensor>& frames, int want_views) {
+                          const c10::optional<Tensor>& frames, int want_views, const c10::optional<Tensor>& g_alpha) {
              Saved ws;
              ws.valid = true; ws.dims = dims_from(dimsv); ws.geom = geom; ws.bin = bin; ws.img = img; ws.token = token;
              std::vector<Tensor> g;
              {
                pybind11::gil_scoped_release nogil;
                g = b.be().backward(cfg_from(cfgv), ws, viewbuf, means, cov, opac, colors, extra.has_value() ? *extra : Tensor(), g_color,
-                                   g_extra.has_value() ? *g_extra : Tensor(), want_means2d, rows_in_workspace, frames.has_value() ? *frames : Tensor(), want_views);
+                                   g_extra.has_value() ? *g_extra : Tensor(), want_means2d, rows_in_workspace, frames.has_value() ? *frames : Tensor(), want_views,
+                                   g_alpha.has_value() ? *g_alpha : Tensor());
              }
              pybind11::list out;
              for (size_t k = 0; k < (want_views ? 7u : 6u); ++k) out.append(g[k].defined() ? pybind11::cast(g[k]) : pybind11::none());
              return pybind11::tuple(out);
-           });
+           }, pybind11::arg("cfg"), pybind11::arg("dims"), pybind11::arg("geom"), pybind11::arg("bin"), pybind11::arg("img"), pybind11::arg("token"),
+           pybind11::arg("viewbuf"), pybind11::arg("means"), pybind11::arg("cov"), pybind11::arg("opac"), pybind11::arg("colors"), pybind11::arg("extra"),
+           pybind11::arg("g_color"), pybind11::arg("g_extra"), pybind11::arg("want_means2d"), pybind11::arg("rows_in_workspace"), pybind11::arg("frames"),
+           pybind11::arg("want_views"), pybind11::arg("g_alpha") = pybind11::none());
   m.def("rasterize", &rasterize, pybind11::arg("backend"), pybind11::arg("means"), pybind11::arg("cov"), pybind11::arg("opac"), pybind11::arg("colors"),
         pybind11::arg("extra"), pybind11::arg("means2d"), pybind11::arg("viewbuf"), pybind11::arg("cfg"), pybind11::arg("frames"), pybind11::arg("camera_gradient"));
   m.def("rasterize_views", &rasterize_views);

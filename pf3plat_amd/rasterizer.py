@@ -55,6 +55,7 @@ class RasterConfig:
     has_extra: bool = False
     flags: int = 0  # _lib.FLAG_SH_PLANAR | _lib.FLAG_COV_3X3 (input layouts)
     scale_rot: bool = False  # the covariance argument is (S, N, 7) scale + quaternion (x, y, z, w) records (GsrForwardOptions.scale_rot)
+    alpha: bool = False  # the call also returns the accumulated alpha image (V, H, W) (gsr_forward_alpha / gsr_backward_alpha); sizes nothing
 
 
 def pack_views(viewmatrix: Tensor, projmatrix: Tensor, campos: Tensor, tanfovx: Tensor, tanfovy: Tensor,
@@ -256,8 +257,9 @@ class HipBackend:
         backward=True adds the gradient outputs and the backward's scratch."""
         v, n, s = cfg.num_views, cfg.num_gaussians, cfg.num_sets
         f32, u8 = torch.float32, torch.uint8
-        dims, color, extra_img, radii, geom, binb, img, scratch_bytes = self._c.make_plan(_cfg_vec(cfg), torch.device(device), int(capacity))
-        plan = dict(cfg=cfg, dims=_lib.GsrDims(*dims), device=device, color=color, extra_img=extra_img, radii=radii, geom=geom, bin=binb, img=img)
+        dims, color, extra_img, radii, geom, binb, img, scratch_bytes, *acc = self._c.make_plan(_cfg_vec(cfg), torch.device(device), int(capacity))
+        plan = dict(cfg=cfg, dims=_lib.GsrDims(*dims), device=device, color=color, extra_img=extra_img, radii=radii, geom=geom, bin=binb, img=img,
+                    alpha_img=acc[0] if acc else None)  # (cfg.alpha: the accumulated alpha image, written by run_forward)
         if backward:
             if colors_shape is None:
                 if cfg.sh_coeffs > 0:
@@ -279,8 +281,9 @@ class HipBackend:
 
     def run_forward(self, plan: dict, viewbuf, means, cov6, opac, colors, extra=None, profile: bool = False, out_color=None,
                     frames=None):
-        """Enqueue one forward launch chain on the current stream (gsr_forward_ex).  profile=True returns per-stage ms
-        (synchronises), in the scale / rotation form too.
+        """Enqueue one forward launch chain on the current stream (gsr_forward_ex; gsr_forward_alpha, which also fills
+        plan["alpha_img"], for a plan of a cfg with alpha=True).  profile=True returns per-stage ms (synchronises), in the
+        scale / rotation form too.
         out_color: render into this contiguous (V, 3, H, W) fp32 tensor instead of the plan's own image (e.g. a slot of a
         buffer that is all-gathered later: no copy)."""
         stream = _stream_ptr(plan["device"])
@@ -292,10 +295,13 @@ class HipBackend:
         ms = (ctypes.c_float * len(_lib.FWD_STAGES))() if profile else None
         # (nothing asked for: NULL options, the plain call)
         opt = ctypes.byref(_lib.GsrForwardOptions(_ptr(fr), nf, int(cfg.scale_rot), ms)) if cfg.scale_rot or profile else None
+        head = (ctypes.byref(plan["dims"]), _ptr(viewbuf), _ptr(means), _ptr(cov6), _ptr(opac), _ptr(colors), _ptr(extra), _ptr(color), _ptr(plan["extra_img"]))
+        tail = (_ptr(plan["radii"]), _ptr(plan["geom"]), _ptr(plan["bin"]), _ptr(plan["img"]), opt, stream)
         with _on_device(plan["device"]):  # kernels launch on the process's current device: make it the tensors' device
-            rc = self.lib.gsr_forward_ex(ctypes.byref(plan["dims"]), _ptr(viewbuf), _ptr(means), _ptr(cov6), _ptr(opac), _ptr(colors),
-                                         _ptr(extra), _ptr(color), _ptr(plan["extra_img"]), _ptr(plan["radii"]), _ptr(plan["geom"]),
-                                         _ptr(plan["bin"]), _ptr(plan["img"]), opt, stream)
+            if cfg.alpha:
+                rc = self.lib.gsr_forward_alpha(*head, _ptr(plan["alpha_img"]), *tail)
+            else:
+                rc = self.lib.gsr_forward_ex(*head, *tail)
         self._rc(rc, "gsr_forward")
         return None if ms is None else dict(zip(_lib.FWD_STAGES, [float(x) for x in ms]))
 
@@ -304,8 +310,8 @@ class HipBackend:
         current stream every time it is called (the tensors must stay alive and in place; plain forward only: no scale / rotation form,
         no profiling).  A loop over one plan then costs the host the C call and the stream lookup, not thirteen pointer conversions -
         what `bench.py`'s timed loop and the tools use, so that a busy host does not show in a 20-step window."""
-        if plan["cfg"].scale_rot:
-            raise ValueError("bind_forward: plain covariance form only")
+        if plan["cfg"].scale_rot or plan["cfg"].alpha:
+            raise ValueError("bind_forward: plain covariance form only, without the alpha image")
         color = plan["color"] if out_color is None else out_color
         if color.shape != plan["color"].shape or color.dtype != torch.float32 or not color.is_contiguous():
             raise ValueError("out_color must be a contiguous fp32 tensor of the plan's image shape")
@@ -328,8 +334,10 @@ class HipBackend:
         return call
 
     def run_backward(self, plan: dict, viewbuf, means, cov6, opac, colors, extra, g_color, g_extra_img=None,
-                     want_means2d: bool = True, profile: bool = False, frames=None, d_views=None, depth_term_only: bool = False):
-        """Enqueue one backward launch chain on the current stream (gsr_backward_ex).  profile=True returns per-stage ms
+                     want_means2d: bool = True, profile: bool = False, frames=None, d_views=None, depth_term_only: bool = False,
+                     g_alpha_img=None):
+        """Enqueue one backward launch chain on the current stream (gsr_backward_ex; gsr_backward_alpha when g_alpha_img, the
+        (V, H, W) gradient of the accumulated alpha, is given).  profile=True returns per-stage ms
         (synchronises), in the scale / rotation form and together with d_views too.
         d_views: a (V, 48) fp32 tensor that receives the camera gradients; depth_term_only: only what the built-in
         depth channel sends to the camera (the z row of the view matrix), the gradient of the reference's graph."""
@@ -348,12 +356,15 @@ class HipBackend:
         if cfg.scale_rot or profile or d_views is not None:
             opt = ctypes.byref(_lib.GsrBackwardOptions(_ptr(fr), nf, int(cfg.scale_rot), _ptr(d_views), _ptr(partials), ms,
                                                        int(d_views is not None and bool(depth_term_only))))
+        head = (ctypes.byref(plan["dims"]), _ptr(viewbuf), _ptr(means), _ptr(cov6), _ptr(opac), _ptr(colors), _ptr(extra), _ptr(plan["geom"]),
+                _ptr(plan["bin"]), _ptr(plan["img"]), _ptr(g_color), _ptr(g_extra_img if cfg.has_extra else None))
+        tail = (_ptr(plan["scratch"]), _ptr(plan["d_means"]), _ptr(plan["d_cov6"]), _ptr(plan["d_opac"]), _ptr(plan["d_colors"]), _ptr(plan["d_extra"]),
+                _ptr(plan["d_means2d"] if want_means2d else None), opt, stream)
         with _on_device(plan["device"]):
-            rc = self.lib.gsr_backward_ex(ctypes.byref(plan["dims"]), _ptr(viewbuf), _ptr(means), _ptr(cov6), _ptr(opac), _ptr(colors),
-                                          _ptr(extra), _ptr(plan["geom"]), _ptr(plan["bin"]), _ptr(plan["img"]), _ptr(g_color),
-                                          _ptr(g_extra_img if cfg.has_extra else None), _ptr(plan["scratch"]), _ptr(plan["d_means"]),
-                                          _ptr(plan["d_cov6"]), _ptr(plan["d_opac"]), _ptr(plan["d_colors"]), _ptr(plan["d_extra"]),
-                                          _ptr(plan["d_means2d"] if want_means2d else None), opt, stream)
+            if g_alpha_img is not None:
+                rc = self.lib.gsr_backward_alpha(*head, _ptr(g_alpha_img), *tail)
+            else:
+                rc = self.lib.gsr_backward_ex(*head, *tail)
         self._rc(rc, "gsr_backward", backward=True)
         return None if ms is None else dict(zip(_lib.BWD_STAGES, [float(x) for x in ms]))
 
@@ -367,7 +378,8 @@ class HipBackend:
     # tools call them directly; `rasterize_views` goes through the compiled autograd function, which calls the same C++).
     def forward(self, cfg: RasterConfig, viewbuf, means, cov6, opac, colors, extra, capacity: Optional[int] = None,
                 frames=None, reuse_workspaces: bool = False):
-        """-> (color, extra_img, radii, saved).  `saved` = (dims, geom, bin, img, token) for `backward`, or None with reuse_workspaces.
+        """-> (color, extra_img, radii, saved) and, for a cfg with alpha=True, a fifth element: the accumulated alpha image (V, H, W).
+        `saved` = (dims, geom, bin, img, token) for `backward`, or None with reuse_workspaces.
 
         reuse_workspaces: the caller will not differentiate this call (rasterize_views' no-autograd branch): geom / bin / img
         come from a per-(shape, device, stream) cache that the next call of the same shape overwrites, and nothing is handed
@@ -389,11 +401,11 @@ class HipBackend:
                   and verify it at the next call, at `check_pending()`, and - for a call that is differentiated - at the
                   end of its backward.  A workspace that turns out too small poisons that call's image with NaN
                   (k_tile_fwd) and raises at verification - it cannot pass silently."""
-        color, extra_img, radii, saved = self._c.forward(_cfg_vec(cfg), viewbuf, means, cov6, opac, colors, extra, frames,
-                                                         -1 if capacity is None else int(capacity), bool(reuse_workspaces))
+        color, extra_img, radii, saved, *acc = self._c.forward(_cfg_vec(cfg), viewbuf, means, cov6, opac, colors, extra, frames,
+                                                               -1 if capacity is None else int(capacity), bool(reuse_workspaces))
         if saved is not None:
             saved = (_lib.GsrDims(*saved[0]),) + tuple(saved[1:])
-        return color, extra_img, radii, saved
+        return (color, extra_img, radii, saved, *acc)
 
     def check_pending(self, wait: bool = False, only_token: Optional[int] = None):
         """Verify the status blocks of earlier lazy / deferred forwards (those whose async copy has landed; all if `wait`;
@@ -403,8 +415,9 @@ class HipBackend:
         self._c.check_pending(bool(wait), -1 if only_token is None else int(only_token))
 
     def backward(self, cfg: RasterConfig, saved, viewbuf, means, cov6, opac, colors, extra, g_color, g_extra_img,
-                 want_means2d: bool, rows_in_workspace: bool = False, frames=None, want_views=False):
-        """rows_in_workspace: the forward ran with FLAG_BACKWARD_FOLLOWS and this is the first backward over it - accumulate
+                 want_means2d: bool, rows_in_workspace: bool = False, frames=None, want_views=False, g_alpha_img=None):
+        """g_alpha_img: the (V, H, W) gradient of the accumulated alpha image (any forward's workspaces will do), or None.
+        rows_in_workspace: the forward ran with FLAG_BACKWARD_FOLLOWS and this is the first backward over it - accumulate
         into the rows it zero-filled inside geom (no scratch, no zero-fill pass).  want_views: a seventh result, the (V, 48)
         gradient of the camera records - True: all of it (view matrix, projection matrix, camera centre); "depth": only what
         the built-in depth channel contributes (the z row of the view matrix: the reference graph's camera gradient)."""
@@ -414,7 +427,7 @@ class HipBackend:
         dimsv = [getattr(dims, n) for n, _ in dims._fields_]
         return self._c.backward(_cfg_vec(cfg), dimsv, geom, binb, img, int(token), viewbuf, means, cov6, opac, colors, extra, g_color,
                                 g_extra_img if cfg.has_extra else None, bool(want_means2d), bool(rows_in_workspace), frames,
-                                2 if want_views == "depth" else (1 if want_views else 0))
+                                2 if want_views == "depth" else (1 if want_views else 0), g_alpha_img)
 
     def setup_views(self, extrinsics, intrinsics, near, far, background, scale_invariant: bool = True) -> Tensor:
         """(V,4,4) c2w, (V,3,3), (V,), (V,), (3,) or (V,3) -> (V,48) camera records, one kernel launch (gsr_setup_views)."""
@@ -442,9 +455,9 @@ class HipBackend:
 
 
 def _cfg_vec(cfg: RasterConfig):
-    """RasterConfig as the twelve integers the compiled backend takes."""
+    """RasterConfig as the twelve integers the compiled backend takes (a thirteenth, 1, when the alpha image is wanted)."""
     return [cfg.num_views, cfg.num_sets, cfg.views_per_set, cfg.num_gaussians, cfg.height, cfg.width, cfg.sh_degree, cfg.sh_coeffs,
-            cfg.max_sh_eval, int(cfg.has_extra), int(cfg.flags), int(cfg.scale_rot)]
+            cfg.max_sh_eval, int(cfg.has_extra), int(cfg.flags), int(cfg.scale_rot)] + ([1] if cfg.alpha else [])
 
 
 def cfg_repr(dims) -> str:
@@ -529,14 +542,17 @@ def rasterize_views(means: Tensor, cov6: Tensor, opacities: Tensor, colors: Tens
                     means2d: Optional[Tensor] = None, max_sh_eval: int = 4, sh_planar: bool = False, cov_3x3: bool = False,
                     extra_mode: Optional[str] = None, debug: bool = False, prefiltered: bool = False,
                     deterministic: Optional[bool] = None, scale_rot: bool = False, frames: Optional[Tensor] = None,
-                    camera_gradient: str = "full", sh_frame: Optional[str] = None):
+                    camera_gradient: str = "full", sh_frame: Optional[str] = None, return_alpha: bool = False):
     """Render V = num_sets * views_per_set views in one launch chain.
 
     means (S,N,3); cov6 (S,N,6) or, with cov_3x3, the full symmetric (S,N,3,3); opacities (S,N); colors (S,N,M,3) or, with
     sh_planar, PF3plat's harmonics layout (S,N,3,M) if use_sh else (S,N,3); viewbuf (V,48) from `pack_views` / the backend's
     `setup_views` (set-major); extra (V,N) optional 4th blended channel, or extra_mode in {"depth", "disparity",
     "relative_disparity", "log"} to blend the reference's depth-render scalar f(z) computed inside the kernels.
-    Returns (color (V,3,H,W), extra_img (V,H,W) | None, radii (V,N) int32).  Differentiable w.r.t. means, cov6, opacities,
+    Returns (color (V,3,H,W), extra_img (V,H,W) | None, radii (V,N) int32) and, with return_alpha=True, a fourth element: the
+    accumulated alpha A = sum_j alpha_j T_j = 1 - T_final (V,H,W) of every pixel, from the same pass (exactly 0 where no splat
+    reaches; a pixel that stops early keeps the T in front of the splat it rejected, so color = blended + (1 - A) bg holds) - a third
+    differentiable output; with extra_mode="depth" the expected depth is extra_img / A.  Differentiable w.r.t. means, cov6, opacities,
     colors, extra (gradients come back in the layouts given; means2d receives the screen-space gradient); cameras get none,
     like the reference operator.
     scale_rot: `cov6` is (S,N,7) = scale (x,y,z) + quaternion (x,y,z,w), the form PF3plat's encoder emits (reference
@@ -567,7 +583,9 @@ def rasterize_views(means: Tensor, cov6: Tensor, opacities: Tensor, colors: Tens
             backend._c, means, cov6, opacities, colors, viewbuf, int(image_shape[0]), int(image_shape[1]), int(sh_degree), bool(use_sh),
             int(views_per_set), extra, means2d, int(max_sh_eval), bool(sh_planar), bool(cov_3x3), EXTRA_MODES[extra_mode] if extra_mode is not None else 0,
             bool(debug), bool(prefiltered), -1 if deterministic is None else int(bool(deterministic)), bool(scale_rot), frames,
-            2 if camera_gradient == "depth" else 1, sh_code)
+            2 if camera_gradient == "depth" else 1, sh_code, bool(return_alpha))
+    if return_alpha:
+        raise NotImplementedError("return_alpha needs the HIP backend (gsr_forward_alpha)")
     # any other backend object (tests slide the CPU oracle under the host wrappers): the SAME statement of the call shape - the
     # compiled `prepare_call` (csrc/gsr_torch.cpp: checks, normalisation, flags; it touches no device) - then that backend's forward
     if camera_gradient not in ("full", "depth"):

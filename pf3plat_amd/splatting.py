@@ -207,10 +207,13 @@ def render_views(
     frames: Optional[Tensor] = None,  # (scene, F, 3, 3) world rotation per group of gaussian / F consecutive Gaussians
     pose_gradients: bool = False,  # opt-in: the render's gradient reaches `extrinsics` (the reference's does not)
     sh_frame: Optional[str] = None,  # "e3nn" | "rasterizer": the harmonics are in the coordinates of `frames` (rasterize_views)
+    alpha: bool = False,  # also return the accumulated opacity A = 1 - T_final of every pixel (rasterize_views(return_alpha=True))
 ):
     """Fused decoder path: all views of all scenes in one launch chain, Gaussians read once per scene
     (no V-fold `repeat`, reference decoder_splatting_cuda.py:52-56), depth as a 4th blended channel.
-    Returns (color (scene, view, 3, h, w), depth (scene, view, h, w) | None)."""
+    Returns (color (scene, view, 3, h, w), depth (scene, view, h, w) | None) and, with alpha=True, a third element: the accumulated
+    opacity (scene, view, h, w), differentiable like the other two.  The depth the reference blends is un-normalised (sum z alpha T);
+    the expected depth of a pixel is depth / alpha, from this one pass - how to clamp a small alpha is the caller's choice."""
     s, v = extrinsics.shape[:2]
     ext = extrinsics.reshape(s * v, 4, 4)
     intr = intrinsics.reshape(s * v, 3, 3)
@@ -223,14 +226,14 @@ def render_views(
     # that term (GsrBackwardOptions.depth_term_only), carried to `extrinsics` by the closed-form backward of the camera set-up.
     depth_cam = depth_mode is not None and not pose_gradients and _camera_wants_depth_gradient(extrinsics)
     viewbuf = _viewbuf(ext, intr, nr, fr, background_color.reshape(3), scale_invariant, pose_gradients or depth_cam)
-    channel = dict(extra_mode=depth_mode, camera_gradient="depth" if depth_cam else "full")
+    channel = dict(extra_mode=depth_mode, camera_gradient="depth" if depth_cam else "full", return_alpha=alpha)
     if gaussian_covariances is None:  # scale + quaternion records, as the encoder's adapter emits them
         records = _scale_rot_records(gaussian_scales, gaussian_rotations)
-        color, depth, _ = rasterize_views(
+        color, depth, _, *acc = rasterize_views(
             gaussian_means, records, gaussian_opacities, gaussian_sh_coefficients, viewbuf, image_shape=image_shape,
             sh_degree=degree, use_sh=True, views_per_set=v, sh_planar=True, scale_rot=True, frames=frames, sh_frame=sh_frame, **channel)
     else:
-        color, depth, _ = rasterize_views(
+        color, depth, _, *acc = rasterize_views(
             gaussian_means, gaussian_covariances, gaussian_opacities, gaussian_sh_coefficients, viewbuf,
             image_shape=image_shape, sh_degree=degree, use_sh=True, views_per_set=v, sh_planar=True, cov_3x3=True, sh_frame=sh_frame,
             **channel)
@@ -238,4 +241,6 @@ def render_views(
     color = color.reshape(s, v, 3, h, w)
     if depth is not None:
         depth = depth.reshape(s, v, h, w)
+    if alpha:
+        return color, depth, acc[0].reshape(s, v, h, w)
     return color, depth

@@ -38,3 +38,4 @@ class Gaussians:
 class DecoderOutput:
     color: Tensor  # (scene, view, 3, height, width)
     depth: Optional[Tensor]  # (scene, view, height, width), or None when no depth mode was asked for
+    alpha: Optional[Tensor] = None  # (scene, view, height, width) accumulated opacity 1 - T_final, only with forward(alpha=True)
