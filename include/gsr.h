@@ -41,7 +41,7 @@ extern "C" {
 #define GSR_ERR_INVALID_ARGUMENT (-1)
 #define GSR_ERR_LAUNCH (-2)
 #define GSR_ERR_UNSUPPORTED (-3)
-#define GSR_ABI_VERSION 4
+#define GSR_ABI_VERSION 5
 /* GsrDims.flags input-layout bits: the arrays PF3plat's `Gaussians` record carries (src/model/types.py:7-18) can be passed
  * as they are, with no re-layout copy (the reference wrapper makes two per call: cuda_splatting.py:75 and :115,123). */
 #define GSR_FLAG_SH_PLANAR 0x4  /* colors are (num_sets, N, 3, M) "harmonics" instead of (num_sets, N, M, 3); grads likewise */
@@ -192,7 +192,9 @@ int gsr_backward(const GsrDims* dims, const GsrView* views, const float* means, 
                  void* scratch, float* dL_dmeans, float* dL_dcov6, float* dL_dopacities,
                  float* dL_dcolors, float* dL_dextra, float* dL_dmeans2D, void* stream);
 
-/* The extended calls: gsr_forward / gsr_backward with an options struct in front of `stream`.  opt == NULL: exactly the plain call.
+/* The extended calls: gsr_forward / gsr_backward with an options struct in front of `stream`.  opt == NULL: exactly the plain call,
+ * and so is a zero-filled struct (every field opts in by being non-zero).  An optional image output or cotangent is a field of
+ * these structs, appended behind the existing ones; it never gets an entry point of its own.
  *
  * scale_rot != 0: the covariances in the form PF3plat's encoder produces them (reference
  * src/model/encoder/common/gaussian_adapter.py:63-83, gaussians.py:8-44): `cov` is (num_sets, N, 7) = scale x, y, z and a
@@ -226,6 +228,7 @@ typedef struct GsrForwardOptions {
   int32_t num_frames;
   int32_t scale_rot;
   float* stage_ms; /* [GSR_FWD_STAGES] host, or NULL */
+  float* out_alpha; /* (V, H, W) accumulated alpha, or NULL: see below */
 } GsrForwardOptions;
 int gsr_forward_ex(const GsrDims* dims, const GsrView* views, const float* means, const float* cov, const float* opacities,
                    const float* colors, const float* extra, float* out_color, float* out_extra, int32_t* radii, void* geom,
@@ -243,7 +246,8 @@ typedef struct GsrBackwardOptions {
                               extrinsics.inverse() in torch (cuda_splatting.py:239-242, extrinsics requiring grad at
                               model_wrapper.py:148-156) while nothing reaches a camera through the rasterizer.  Costs four wave
                               reductions in the backward preprocess instead of thirty-five and two small reduce launches. */
-  int32_t reserved_;       /* 0: spells the tail of the struct out (its size is a multiple of its pointers' alignment) */
+  int32_t reserved_;       /* 0: spells the padding in front of the next pointer out */
+  const float* dL_dalpha_img; /* (V, H, W) cotangent of the accumulated alpha, or NULL: see below */
 } GsrBackwardOptions;
 size_t gsr_pose_partials_bytes(const GsrDims* dims);
 int gsr_backward_ex(const GsrDims* dims, const GsrView* views, const float* means, const float* cov, const float* opacities,
@@ -252,7 +256,7 @@ int gsr_backward_ex(const GsrDims* dims, const GsrView* views, const float* mean
                     float* dL_dopacities, float* dL_dcolors, float* dL_dextra, float* dL_dmeans2D, const GsrBackwardOptions* opt,
                     void* stream);
 
-/* Accumulated alpha.  gsr_forward_alpha is gsr_forward_ex with one more output, out_alpha (V, H, W) or NULL (= gsr_forward_ex):
+/* Accumulated alpha.  GsrForwardOptions.out_alpha != NULL: one more output, (V, H, W),
  *   A = sum_j alpha_j T_j = 1 - T_final,   T_j = prod_{i < j} (1 - alpha_i),
  * over the splats the pixel blends, in the same pass and from the transmittance the colour pass keeps anyway (`img`): what the
  * extra channel blends for an `extra` array of ones, without spending that channel.  A pixel no splat reaches has A = 0 exactly.
@@ -260,19 +264,11 @@ int gsr_backward_ex(const GsrDims* dims, const GsrView* views, const float* mean
  * value the background is weighted with - so colour = sum + (1 - A) bg holds exactly and A never reaches 1.  An empty call
  * (num_gaussians == 0) writes zeros; an overflowed one (GsrStatus.overflow) NaN, as for the colour.  The expected depth of a
  * pixel is out_extra / A with GSR_EXTRA_DEPTH, one pass; the clamp for small A is the caller's (no normalised mode exists).
- * gsr_backward_alpha is gsr_backward_ex with one more cotangent, dL_dalpha_img (V, H, W) or NULL (= gsr_backward_ex): with
+ * GsrBackwardOptions.dL_dalpha_img != NULL: one more cotangent, (V, H, W): with
  * dA / dalpha_j = T_final / (1 - alpha_j) it enters the blend's backward where the background does and reaches every output
  * (dL_dviews included) through the splats' alphas.  dL_dcolor stays required: a caller with a loss on A alone passes zeros.
- * Neither call changes a workspace size or layout: size with gsr_workspace_sizes as usual, and either backward may follow
- * either forward. */
-int gsr_forward_alpha(const GsrDims* dims, const GsrView* views, const float* means, const float* cov, const float* opacities,
-                      const float* colors, const float* extra, float* out_color, float* out_extra, float* out_alpha,
-                      int32_t* radii, void* geom, void* bin, void* img, const GsrForwardOptions* opt, void* stream);
-int gsr_backward_alpha(const GsrDims* dims, const GsrView* views, const float* means, const float* cov, const float* opacities,
-                       const float* colors, const float* extra, const void* geom, const void* bin, const void* img,
-                       const float* dL_dcolor, const float* dL_dextra_img, const float* dL_dalpha_img, void* scratch, float* dL_dmeans,
-                       float* dL_dcov, float* dL_dopacities, float* dL_dcolors, float* dL_dextra, float* dL_dmeans2D,
-                       const GsrBackwardOptions* opt, void* stream);
+ * Neither field changes a workspace size or layout: size with gsr_workspace_sizes as usual, and either backward may follow
+ * either forward (a backward with the cotangent after a forward without the image, and the other way round). */
 
 /* GSR_FLAG_DEBUG: the stage of the last failed call of this host thread (an index into the stages above), or -1; and the
  * name of stage `stage` of the forward (backward == 0) or the backward - the one statement of the names every caller prints -

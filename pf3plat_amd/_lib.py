@@ -17,7 +17,7 @@ REPO_ROOT = os.path.dirname(_HERE)
 SRC = os.path.join(_HERE, "csrc", "gsr_hip.hip")
 HEADER = os.path.join(REPO_ROOT, "include", "gsr.h")
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "libgsr_hip.so")  # (override: tools/ablate.py's measurement build)
-GSR_ABI_VERSION = 4  # bump with include/gsr.h whenever a struct, a workspace layout or a signature changes
+GSR_ABI_VERSION = 5  # bump with include/gsr.h whenever a struct, a workspace layout or a signature changes
 SCREEN_GRAD_FLOATS = 12
 FLAG_PREFILTERED = 0x1  # accepted and ignored, as upstream with prefiltered = False
 FLAG_DEBUG = 0x2  # upstream's `debug`: synchronise + check after every stage
@@ -47,13 +47,13 @@ class GsrDims(ctypes.Structure):
 
 class GsrForwardOptions(ctypes.Structure):
     _fields_ = [("frames", ctypes.c_void_p), ("num_frames", ctypes.c_int32), ("scale_rot", ctypes.c_int32),
-                ("stage_ms", ctypes.POINTER(ctypes.c_float))]
+                ("stage_ms", ctypes.POINTER(ctypes.c_float)), ("out_alpha", ctypes.c_void_p)]
 
 
 class GsrBackwardOptions(ctypes.Structure):
     _fields_ = [("frames", ctypes.c_void_p), ("num_frames", ctypes.c_int32), ("scale_rot", ctypes.c_int32),
                 ("dL_dviews", ctypes.c_void_p), ("pose_partials", ctypes.c_void_p), ("stage_ms", ctypes.POINTER(ctypes.c_float)),
-                ("depth_term_only", ctypes.c_int32), ("reserved_", ctypes.c_int32)]
+                ("depth_term_only", ctypes.c_int32), ("reserved_", ctypes.c_int32), ("dL_dalpha_img", ctypes.c_void_p)]
 
 
 def find_hipcc() -> str:
@@ -259,10 +259,6 @@ def load():
     lib.gsr_colour_in_binning.argtypes = [dp]
     lib.gsr_backward_ex.restype = ctypes.c_int
     lib.gsr_backward_ex.argtypes = [dp] + [vp] * 18 + [ctypes.POINTER(GsrBackwardOptions), vp]
-    lib.gsr_forward_alpha.restype = ctypes.c_int  # gsr_forward_ex + out_alpha behind out_extra
-    lib.gsr_forward_alpha.argtypes = [dp] + [vp] * 13 + [ctypes.POINTER(GsrForwardOptions), vp]
-    lib.gsr_backward_alpha.restype = ctypes.c_int  # gsr_backward_ex + dL_dalpha_img behind dL_dextra_img
-    lib.gsr_backward_alpha.argtypes = [dp] + [vp] * 19 + [ctypes.POINTER(GsrBackwardOptions), vp]
     lib.gsr_pose_partials_bytes.restype = ctypes.c_size_t
     lib.gsr_pose_partials_bytes.argtypes = [dp]
     lib.gsr_image_loss_partials.restype = ctypes.c_size_t
@@ -300,7 +296,7 @@ EXPORTED_SYMBOLS = (
     "gsr_capacity_for", "gsr_cov_from_scale_rot", "gsr_cov_from_scale_rot_backward", "gsr_last_failed_stage",
     "gsr_colour_in_binning", "gsr_geom_layout", "gsr_backward_ex", "gsr_pose_partials_bytes", "gsr_backward_scratch_bytes", "gsr_setup_views_orthographic",
     "gsr_image_loss", "gsr_image_loss_partials", "gsr_image_loss_finish", "gsr_pack_view", "gsr_setup_views_backward",
-    "gsr_adapt", "gsr_adapt_backward", "gsr_adapt_partials_bytes", "gsr_forward_alpha", "gsr_backward_alpha",
+    "gsr_adapt", "gsr_adapt_backward", "gsr_adapt_partials_bytes",
 )
 # The stages of GsrForwardOptions.stage_ms / GsrBackwardOptions.stage_ms as run_forward / run_backward(profile=True) key them (the
 # names a failed debug-mode stage is reported with are the library's: gsr_stage_name).  On images of up to 20 480 tiles (the fused binning path) "preprocess" is the whole binning

@@ -260,7 +260,7 @@ struct Params {
   const float *dL_dcolor, *dL_dextra_img;
   float* scratch;
   float *dL_dmeans, *dL_dcov6, *dL_dopac, *dL_dcolors, *dL_dextra, *dL_dmeans2D;  // (scale_rot: dL_dcov6 is (S, N, 7))
-  // accumulated alpha (gsr_forward_alpha / gsr_backward_alpha; read by the kAlpha instances only).  The struct keeps its size and
+  // accumulated alpha (GsrForwardOptions.out_alpha / GsrBackwardOptions.dL_dalpha_img; read by the kAlpha instances only).  The struct keeps its size and
   // every field its offset - kernels that take their arguments from it, copy it or carry an argument behind it are then the code
   // they were - so the two pointers share the storage of one that only the OTHER direction's kernels read.  (A backward kernel that
   // ever needs `radii`, or a forward kernel `pose_partials`, takes that pointer out of its union first.)
@@ -2477,7 +2477,7 @@ __device__ __forceinline__ bool blend_poisoned(const Params& p, const int v, con
 }
 
 // The four waves' partial results -> the pixel: image, final transmittance, contributor count; the entries the tile walked.
-// kAlpha (gsr_forward_alpha): also the accumulated alpha A = 1 - final_T, from the value that is stored - one subtraction and
+// kAlpha (GsrForwardOptions.out_alpha): also the accumulated alpha A = 1 - final_T, from the value that is stored - one subtraction and
 // one store per pixel in instances of their own; the kAlpha = false instances are the code they were.
 template <bool kExtra, bool kAlpha = false>
 __device__ __forceinline__ void blend_finish(const Params& p, const int v, const int t, const uint32_t n, BlendFin& lds, const BlendAcc& s,
@@ -3039,7 +3039,7 @@ __device__ __forceinline__ float from_fixed(long long x) { return (float)x * kFi
 // walked (Params::tile_total); every workgroup finds its own tile: a selection by bisection over the <= 256 keys of its XCD, one wave, ballots only.
 constexpr int kBalanceMax = 256;  // tiles per XCD up to which the deal is computed (more: image order; later rounds balance themselves)
 
-// kAlpha (gsr_backward_alpha): a loss on the accumulated alpha A = 1 - T_final.  dA/dalpha_j = T_final / (1 - alpha_j) is the
+// kAlpha (GsrBackwardOptions.dL_dalpha_img): a loss on the accumulated alpha A = 1 - T_final.  dA/dalpha_j = T_final / (1 - alpha_j) is the
 // background term's derivative with the sign turned, so dL/dA enters where the background does: Q starts from bg.g - g_A.
 template <bool kExtra, bool kDet, bool kAlpha = false>
 __global__ __launch_bounds__(kBwdThreads, 4) void k_blend_bwd(const Params p) {
@@ -4239,7 +4239,7 @@ extern "C" {
 int gsr_abi_version(void) { return GSR_ABI_VERSION; }
 
 const char* gsr_build_info(void) {
-  return "gsr_hip gfx950 wave64 tile8x8 binning+colour tile-sort+segment-blend single-stream abi4";
+  return "gsr_hip gfx950 wave64 tile8x8 binning+colour tile-sort+segment-blend single-stream abi5";
 }
 
 int gsr_last_failed_stage(void) { return g_failed_stage; }
@@ -4380,12 +4380,12 @@ static bool call_dims_ok(const GsrDims* d, const SrArgs* sr) {
 // the events of with_stage_events: one between every two stages (ev: null on the product path)
 #define GSR_MARK() do { if (ev) GSR_CHECK(hipEventRecord(ev[e++], st)); } while (0)
 
-static_assert(sizeof(GsrForwardOptions) == 24 && sizeof(GsrBackwardOptions) == 48, "options structs as tests/test_abi.py mirrors them");
+static_assert(sizeof(GsrForwardOptions) == 32 && sizeof(GsrBackwardOptions) == 56, "options structs as tests/test_abi.py mirrors them");
 
 static int forward_impl(const GsrDims* dims, const GsrView* views, const float* means, const float* cov6,
                         const float* opacities, const float* colors, const float* extra, float* out_color,
                         float* out_extra, int32_t* radii, void* geom, void* bin, void* img, hipStream_t st,
-                        hipEvent_t* ev, const SrArgs* sr, float* out_alpha = nullptr) {
+                        hipEvent_t* ev, const SrArgs* sr, float* out_alpha) {
   if (!call_dims_ok(dims, sr)) return GSR_ERR_INVALID_ARGUMENT;
   const GsrDims& d = *dims;
   const size_t V = d.num_views, N = d.num_gaussians, HW = (size_t)d.height * d.width;
@@ -4489,21 +4489,16 @@ static int forward_impl(const GsrDims* dims, const GsrView* views, const float* 
   return GSR_OK;
 }
 
-int gsr_forward_alpha(const GsrDims* dims, const GsrView* views, const float* means, const float* cov, const float* opacities,
-                      const float* colors, const float* extra, float* out_color, float* out_extra, float* out_alpha,
-                      int32_t* radii, void* geom, void* bin, void* img, const GsrForwardOptions* opt, void* stream_) {
+int gsr_forward_ex(const GsrDims* dims, const GsrView* views, const float* means, const float* cov, const float* opacities,
+                   const float* colors, const float* extra, float* out_color, float* out_extra, int32_t* radii, void* geom,
+                   void* bin, void* img, const GsrForwardOptions* opt, void* stream_) {
   hipStream_t st = static_cast<hipStream_t>(stream_);
   SrArgs sr_store;
   const SrArgs* sr = sr_of(opt, &sr_store);
   return with_stage_events<GSR_FWD_STAGES>(dims, st, opt ? opt->stage_ms : nullptr, [&](hipEvent_t* ev) {
-    return forward_impl(dims, views, means, cov, opacities, colors, extra, out_color, out_extra, radii, geom, bin, img, st, ev, sr, out_alpha);
+    return forward_impl(dims, views, means, cov, opacities, colors, extra, out_color, out_extra, radii, geom, bin, img, st, ev, sr,
+                        opt ? opt->out_alpha : nullptr);
   });
-}
-
-int gsr_forward_ex(const GsrDims* dims, const GsrView* views, const float* means, const float* cov, const float* opacities,
-                   const float* colors, const float* extra, float* out_color, float* out_extra, int32_t* radii, void* geom,
-                   void* bin, void* img, const GsrForwardOptions* opt, void* stream) {
-  return gsr_forward_alpha(dims, views, means, cov, opacities, colors, extra, out_color, out_extra, nullptr, radii, geom, bin, img, opt, stream);
 }
 
 int gsr_forward(const GsrDims* dims, const GsrView* views, const float* means, const float* cov6,
@@ -4518,7 +4513,7 @@ static int backward_impl(const GsrDims* dims, const GsrView* views, const float*
                          void* scratch, float* dL_dmeans, float* dL_dcov6, float* dL_dopacities,
                          float* dL_dcolors, float* dL_dextra, float* dL_dmeans2D, hipStream_t st, hipEvent_t* ev,
                          const SrArgs* sr, float* dL_dviews, float* pose_partials, int depth_term_only,
-                         const float* dL_dalpha_img = nullptr) {
+                         const float* dL_dalpha_img) {
   if (!call_dims_ok(dims, sr)) return GSR_ERR_INVALID_ARGUMENT;
   const GsrDims& d = *dims;
   const size_t V = d.num_views, N = d.num_gaussians;
@@ -4596,23 +4591,14 @@ int gsr_backward_ex(const GsrDims* dims, const GsrView* views, const float* mean
                     const float* colors, const float* extra, const void* geom, const void* bin, const void* img,
                     const float* dL_dcolor, const float* dL_dextra_img, void* scratch, float* dL_dmeans, float* dL_dcov,
                     float* dL_dopacities, float* dL_dcolors, float* dL_dextra, float* dL_dmeans2D, const GsrBackwardOptions* opt,
-                    void* stream) {
-  return gsr_backward_alpha(dims, views, means, cov, opacities, colors, extra, geom, bin, img, dL_dcolor, dL_dextra_img, nullptr, scratch, dL_dmeans,
-                            dL_dcov, dL_dopacities, dL_dcolors, dL_dextra, dL_dmeans2D, opt, stream);
-}
-
-int gsr_backward_alpha(const GsrDims* dims, const GsrView* views, const float* means, const float* cov, const float* opacities,
-                       const float* colors, const float* extra, const void* geom, const void* bin, const void* img,
-                       const float* dL_dcolor, const float* dL_dextra_img, const float* dL_dalpha_img, void* scratch, float* dL_dmeans,
-                       float* dL_dcov, float* dL_dopacities, float* dL_dcolors, float* dL_dextra, float* dL_dmeans2D,
-                       const GsrBackwardOptions* opt, void* stream_) {
+                    void* stream_) {
   hipStream_t st = static_cast<hipStream_t>(stream_);
   SrArgs sr_store;
   const SrArgs* sr = sr_of(opt, &sr_store);
   return with_stage_events<GSR_BWD_STAGES>(dims, st, opt ? opt->stage_ms : nullptr, [&](hipEvent_t* ev) {
     return backward_impl(dims, views, means, cov, opacities, colors, extra, geom, bin, img, dL_dcolor, dL_dextra_img, scratch, dL_dmeans, dL_dcov,
                          dL_dopacities, dL_dcolors, dL_dextra, dL_dmeans2D, st, ev, sr, opt ? opt->dL_dviews : nullptr,
-                         opt ? opt->pose_partials : nullptr, opt ? opt->depth_term_only : 0, dL_dalpha_img);
+                         opt ? opt->pose_partials : nullptr, opt ? opt->depth_term_only : 0, opt ? opt->dL_dalpha_img : nullptr);
   });
 }
 

@@ -30,6 +30,7 @@
 #include <set>
 #include <sstream>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/gsr.h"
@@ -46,8 +47,6 @@ struct Abi {
   decltype(&gsr_capacity_for) capacity_for = nullptr;
   decltype(&gsr_forward_ex) forward_ex = nullptr;
   decltype(&gsr_backward_ex) backward_ex = nullptr;
-  decltype(&gsr_forward_alpha) forward_alpha = nullptr;
-  decltype(&gsr_backward_alpha) backward_alpha = nullptr;
   decltype(&gsr_pose_partials_bytes) pose_partials_bytes = nullptr;
   decltype(&gsr_backward_scratch_bytes) backward_scratch_bytes = nullptr;
   decltype(&gsr_last_failed_stage) last_failed_stage = nullptr;
@@ -79,8 +78,6 @@ void init(const std::string& path) {
   resolve(g_abi.capacity_for, "gsr_capacity_for");
   resolve(g_abi.forward_ex, "gsr_forward_ex");
   resolve(g_abi.backward_ex, "gsr_backward_ex");
-  resolve(g_abi.forward_alpha, "gsr_forward_alpha");
-  resolve(g_abi.backward_alpha, "gsr_backward_alpha");
   resolve(g_abi.pose_partials_bytes, "gsr_pose_partials_bytes");
   resolve(g_abi.backward_scratch_bytes, "gsr_backward_scratch_bytes");
   resolve(g_abi.last_failed_stage, "gsr_last_failed_stage");
@@ -127,7 +124,7 @@ void rc_check(int rc, const char* what, bool backward) {
 struct Cfg {
   int num_views = 0, num_sets = 0, views_per_set = 0, num_gaussians = 0, height = 0, width = 0, sh_degree = 0, sh_coeffs = 0, max_sh_eval = 4;
   int has_extra = 0, flags = 0, scale_rot = 0;
-  int alpha = 0;  // the accumulated-alpha image is wanted (gsr_forward_alpha / gsr_backward_alpha); not part of the dims: it sizes nothing
+  int alpha = 0;  // the accumulated-alpha image is wanted (GsrForwardOptions.out_alpha / GsrBackwardOptions.dL_dalpha_img); not part of the dims: it sizes nothing
   auto tie() const { return std::tie(num_views, num_sets, views_per_set, num_gaussians, height, width, sh_degree, sh_coeffs, max_sh_eval, has_extra, flags, scale_rot, alpha); }
   bool operator<(const Cfg& o) const { return tie() < o.tie(); }
   // the dims of the sizing helpers: without the GSR_FLAG_SH_IN_FRAME bits, which only the launches take (they size nothing)
@@ -147,11 +144,11 @@ struct Cfg {
   int extra_mode() const { return (flags >> 4) & 7; }
 };
 Cfg cfg_from(const std::vector<int64_t>& v) {
-  TORCH_CHECK(v.size() == 12 || v.size() == 13, "cfg: 12 integers expected (a 13th: accumulated alpha wanted)");
+  TORCH_CHECK(v.size() == 13, "cfg: 13 integers expected");
   Cfg c;
   c.num_views = (int)v[0]; c.num_sets = (int)v[1]; c.views_per_set = (int)v[2]; c.num_gaussians = (int)v[3]; c.height = (int)v[4];
   c.width = (int)v[5]; c.sh_degree = (int)v[6]; c.sh_coeffs = (int)v[7]; c.max_sh_eval = (int)v[8]; c.has_extra = (int)v[9];
-  c.flags = (int)v[10]; c.scale_rot = (int)v[11]; c.alpha = v.size() > 12 && v[12] != 0;
+  c.flags = (int)v[10]; c.scale_rot = (int)v[11]; c.alpha = v[12] != 0;
   return c;
 }
 std::vector<int64_t> dims_vec(const GsrDims& d) {
@@ -175,11 +172,15 @@ Tensor frames_arg(const Cfg& cfg, const Tensor& frames) {
     throw pybind11::value_error("frames must be (sets, F, 3, 3) with F dividing the number of Gaussians");
   return frames.detach().to(at::kFloat).contiguous();  // (a QR factor, e.g., arrives column-major)
 }
-// The options of an _ex launch from the call shape and its checked frames (`fr`: frames_arg's result, alive until the call returns)
+// The options of an _ex launch from the call shape, its checked frames (`fr`: frames_arg's result) and its alpha image - the forward's
+// output, the backward's cotangent; undefined: a NULL field, the launch without alpha.  Both tensors stay alive until the call returns.
 template <class Options>
-Options launch_options(const Cfg& cfg, const Tensor& fr) {
+Options launch_options(const Cfg& cfg, const Tensor& fr, const Tensor& alpha) {
   Options opt{};
   opt.frames = fptr(fr); opt.num_frames = fr.defined() ? (int)fr.size(1) : 0; opt.scale_rot = cfg.scale_rot;
+  float* const a = alpha.defined() ? alpha.data_ptr<float>() : nullptr;
+  if constexpr (std::is_same_v<Options, GsrForwardOptions>) opt.out_alpha = a;
+  else opt.dL_dalpha_img = a;
   return opt;
 }
 
@@ -451,7 +452,9 @@ class Backend : public std::enable_shared_from_this<Backend> {
       if (want_views) d_views = at::empty({v, kViewFloats}, f32);
       const GsrView* vb = reinterpret_cast<const GsrView*>(viewbuf.data_ptr<float>());
       const Tensor fr = cfg.scale_rot ? frames_arg(cfg, frames) : Tensor();
-      GsrBackwardOptions opt = launch_options<GsrBackwardOptions>(cfg, fr);
+      const Tensor g_alpha = f32c(g_alpha_in);
+      if (g_alpha.defined()) TORCH_CHECK(g_alpha.numel() == (int64_t)v * cfg.height * cfg.width, "dL/dalpha must be (views, H, W)");
+      GsrBackwardOptions opt = launch_options<GsrBackwardOptions>(cfg, fr, g_alpha);
       Tensor partials;
       if (want_views) {
         GsrDims sizing_dims = saved.dims;  // (the helpers take no GSR_FLAG_SH_IN_FRAME bits; they change no size)
@@ -459,17 +462,10 @@ class Backend : public std::enable_shared_from_this<Backend> {
         partials = at::empty({(int64_t)std::max<size_t>(16, g_abi.pose_partials_bytes(&sizing_dims))}, f32.dtype(at::kByte));
         opt.dL_dviews = d_views.data_ptr<float>(); opt.pose_partials = reinterpret_cast<float*>(partials.data_ptr()); opt.depth_term_only = want_views == 2;
       }
-      const Tensor g_alpha = f32c(g_alpha_in);
-      if (g_alpha.defined()) TORCH_CHECK(g_alpha.numel() == (int64_t)v * cfg.height * cfg.width, "dL/dalpha must be (views, H, W)");
-      const GsrBackwardOptions* optp = (cfg.scale_rot || want_views) ? &opt : nullptr;
       void* const scr = scratch.defined() ? scratch.data_ptr() : nullptr;
-      const int rc = g_alpha.defined()
-          ? g_abi.backward_alpha(&saved.dims, vb, fptr(means), fptr(cov), fptr(opac), fptr(colors), fptr(extra), saved.geom.data_ptr(), saved.bin.data_ptr(),
-                                 saved.img.data_ptr(), fptr(g_color), fptr(g_extra), fptr(g_alpha), scr, fptr_mut(d_means), fptr_mut(d_cov), fptr_mut(d_opac),
-                                 fptr_mut(d_colors), fptr_mut(d_extra), fptr_mut(d_means2d), optp, stream)
-          : g_abi.backward_ex(&saved.dims, vb, fptr(means), fptr(cov), fptr(opac), fptr(colors), fptr(extra), saved.geom.data_ptr(), saved.bin.data_ptr(),
-                              saved.img.data_ptr(), fptr(g_color), fptr(g_extra), scr, fptr_mut(d_means), fptr_mut(d_cov), fptr_mut(d_opac), fptr_mut(d_colors),
-                              fptr_mut(d_extra), fptr_mut(d_means2d), optp, stream);
+      const int rc = g_abi.backward_ex(&saved.dims, vb, fptr(means), fptr(cov), fptr(opac), fptr(colors), fptr(extra), saved.geom.data_ptr(), saved.bin.data_ptr(),
+                                       saved.img.data_ptr(), fptr(g_color), fptr(g_extra), scr, fptr_mut(d_means), fptr_mut(d_cov), fptr_mut(d_opac),
+                                       fptr_mut(d_colors), fptr_mut(d_extra), fptr_mut(d_means2d), &opt, stream);
       rc_check(rc, "gsr_backward", true);
     } else if (want_views) {
       d_views = at::zeros({v, kViewFloats}, f32);
@@ -556,13 +552,9 @@ class Backend : public std::enable_shared_from_this<Backend> {
                    const Tensor& extra, const Tensor& frames, hipStream_t stream) {
     const GsrView* vb = reinterpret_cast<const GsrView*>(viewbuf.data_ptr<float>());
     const Tensor fr = cfg.scale_rot ? frames_arg(cfg, frames) : Tensor();
-    const GsrForwardOptions opt = launch_options<GsrForwardOptions>(cfg, fr);
-    const GsrForwardOptions* optp = cfg.scale_rot ? &opt : nullptr;
-    const int rc = p.alpha_img.defined()
-        ? g_abi.forward_alpha(&p.dims, vb, fptr(means), fptr(cov), fptr(opac), fptr(colors), fptr(extra), p.color.data_ptr<float>(), fptr_mut(p.extra_img),
-                              fptr_mut(p.alpha_img), p.radii.data_ptr<int32_t>(), p.geom.data_ptr(), p.bin.data_ptr(), p.img.data_ptr(), optp, stream)
-        : g_abi.forward_ex(&p.dims, vb, fptr(means), fptr(cov), fptr(opac), fptr(colors), fptr(extra), p.color.data_ptr<float>(), fptr_mut(p.extra_img),
-                           p.radii.data_ptr<int32_t>(), p.geom.data_ptr(), p.bin.data_ptr(), p.img.data_ptr(), optp, stream);
+    const GsrForwardOptions opt = launch_options<GsrForwardOptions>(cfg, fr, p.alpha_img);
+    const int rc = g_abi.forward_ex(&p.dims, vb, fptr(means), fptr(cov), fptr(opac), fptr(colors), fptr(extra), p.color.data_ptr<float>(), fptr_mut(p.extra_img),
+                                    p.radii.data_ptr<int32_t>(), p.geom.data_ptr(), p.bin.data_ptr(), p.img.data_ptr(), &opt, stream);
     rc_check(rc, "gsr_forward", false);
   }
 
@@ -704,7 +696,7 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
     }
     if (cfg.alpha) {  // a third differentiable output, only when asked for
       // an output the loss does not use arrives in backward() as an undefined tensor instead of a materialised image of zeros: an alpha
-      // image that was only looked at then costs the backward nothing (gsr_backward_ex, the instances without alpha)
+      // image that was only looked at then costs the backward nothing (a NULL dL_dalpha_img: the instances without alpha)
       ctx->set_materialize_grads(false);
       return {o.color, extra_img, o.radii, o.alpha_img};
     }
@@ -976,10 +968,10 @@ RasterOut rasterize_impl(PyBackend& pb, const Tensor& means, const Tensor& cov, 
   }
   return r;
 }
+pybind11::object or_none(const Tensor& t) { return t.defined() ? pybind11::cast(t) : pybind11::none(); }
 pybind11::tuple raster_tuple(const RasterOut& r) {
-  pybind11::object e = r.extra_img.defined() ? pybind11::cast(r.extra_img) : pybind11::none();
-  if (r.alpha_img.defined()) return pybind11::make_tuple(r.color, e, r.radii, r.alpha_img);  // (only a call that asked for alpha gets four)
-  return pybind11::make_tuple(r.color, e, r.radii);
+  if (r.alpha_img.defined()) return pybind11::make_tuple(r.color, or_none(r.extra_img), r.radii, r.alpha_img);  // (only a call that asked for alpha gets four)
+  return pybind11::make_tuple(r.color, or_none(r.extra_img), r.radii);
 }
 pybind11::tuple rasterize(PyBackend& pb, const Tensor& means, const Tensor& cov, const Tensor& opac, const Tensor& colors, const c10::optional<Tensor>& extra,
                           const c10::optional<Tensor>& means2d, const Tensor& viewbuf, const std::vector<int64_t>& cfgv, const c10::optional<Tensor>& frames,
@@ -993,7 +985,7 @@ pybind11::tuple rasterize(PyBackend& pb, const Tensor& means, const Tensor& cov,
 }
 
 // The call shape of `rasterize_views`, stated ONCE: argument checks (message for message what the Python surface documents), dtype /
-// contiguity normalisation, the twelve integers of the call shape and its flags (GSR_FLAG_BACKWARD_FOLLOWS when something can be
+// contiguity normalisation, the thirteen integers of the call shape and its flags (GSR_FLAG_BACKWARD_FOLLOWS when something can be
 // differentiated).  Touches no device: `rasterize_views` below runs it in front of the operator, and `pf3plat_amd.rasterizer` runs the
 // SAME function (bound as `prepare_call`) in front of any other backend object - the tests slide the CPU oracle under the host wrappers
 // that way - so the two paths cannot drift apart.
@@ -1043,7 +1035,7 @@ Prepared prepare_call(const Tensor& means_in, const Tensor& cov_in, const Tensor
     if (!use_sh) throw pybind11::value_error("sh_frame needs use_sh=True (harmonics)");
     flags |= GSR_FLAG_SH_IN_FRAME | (sh_frame == 2 ? GSR_FLAG_SH_FRAME_E3NN : 0);
   }
-  p.cfgv = {v, s, views_per_set, n, h, w, sh_degree, m, max_sh_eval, has_extra ? 1 : 0, flags, scale_rot ? 1 : 0};
+  p.cfgv = {v, s, views_per_set, n, h, w, sh_degree, m, max_sh_eval, has_extra ? 1 : 0, flags, scale_rot ? 1 : 0, 0 /* Cfg::alpha: the caller's to set */};
   p.viewbuf = f32c(viewbuf_in);
   return p;
 }
@@ -1059,7 +1051,7 @@ pybind11::tuple rasterize_views(PyBackend& pb, const Tensor& means_in, const Ten
   pybind11::gil_scoped_release nogil;
   Prepared p = prepare_call(means_in, cov_in, opac_in, colors_in, viewbuf_in, h, w, sh_degree, use_sh, views_per_set, extra_in, means2d, max_sh_eval, sh_planar,
                                   cov_3x3, extra_mode, debug, prefiltered, deterministic, scale_rot, frames_in, camera_gradient, sh_frame);
-  if (return_alpha) p.cfgv.push_back(1);  // (Cfg::alpha: the thirteenth integer of a call shape that wants the accumulated alpha)
+  p.cfgv[12] = return_alpha;  // (Cfg::alpha)
   result = rasterize_impl(pb, p.means, p.cov, p.opac, p.colors, p.extra, means2d, p.viewbuf, p.cfgv, p.frames, camera_gradient);
   }
   return raster_tuple(result);
@@ -1089,7 +1081,7 @@ pybind11::tuple rasterize_one_view(PyBackend& pb, int64_t height, int64_t width,
   if (!grad) {
     // nothing can be differentiated (the reference's inference loop): the arrays go to the library as they are - the call shape says
     // V = 1, S = 1 - and the image / radii are allocated in the shapes the operator returns: no view op on either side of the call
-    const std::vector<int64_t> cfgv{1, 1, 1, n, height, width, sh_degree, use_sh ? col_in.size(1) : 0, 4, 0, flags, 0};
+    const std::vector<int64_t> cfgv{1, 1, 1, n, height, width, sh_degree, use_sh ? col_in.size(1) : 0, 4, 0, flags, 0, 0};
     ForwardOut o = pb.be().forward(cfg_from(cfgv), viewbuf, f32c(means3d), f32c(cov3d), f32c(opacities), f32c(col_in), Tensor(), Tensor(), -1, true, true);
     out_color = o.color; out_radii = o.radii;
   } else {
@@ -1098,7 +1090,7 @@ pybind11::tuple rasterize_one_view(PyBackend& pb, int64_t height, int64_t width,
   const Tensor colors = f32c(col_in.unsqueeze(0));
   c10::optional<Tensor> m2;
   if (means2d.has_value() && means2d->defined()) m2 = means2d->unsqueeze(0);
-  const std::vector<int64_t> cfgv{1, 1, 1, n, height, width, sh_degree, use_sh ? colors.size(2) : 0, 4, 0, flags, 0};
+  const std::vector<int64_t> cfgv{1, 1, 1, n, height, width, sh_degree, use_sh ? colors.size(2) : 0, 4, 0, flags, 0, 0};
   RasterOut r = rasterize_impl(pb, means, cov, opac, colors, c10::nullopt, m2, viewbuf, cfgv, c10::nullopt, 1);
   out_color = r.color.select(0, 0); out_radii = r.radii.select(0, 0);
   }
@@ -1150,14 +1142,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              return status_dict(st);
            })
       .def("make_plan", [](PyBackend& b, const std::vector<int64_t>& cfgv, const at::Device& device, int64_t capacity) {
-             // the plan API's outputs and workspaces: (dims (13 ints), color, extra_img | None, radii, geom, bin, img, backward-scratch bytes
-             // [, alpha_img: a call shape that wants the accumulated alpha])
+             // the plan API's outputs and workspaces: (dims (13 ints), color, extra_img | None, radii, geom, bin, img, backward-scratch bytes,
+             // alpha_img | None)
              const Cfg cfg = cfg_from(cfgv);
              const Plan p = b.be().make_plan(cfg, device, capacity, false);
-             pybind11::object e = p.extra_img.defined() ? pybind11::cast(p.extra_img) : pybind11::none();
-             if (cfg.alpha)
-               return pybind11::make_tuple(dims_vec(p.dims), p.color, e, p.radii, p.geom, p.bin, p.img, b.be().sized(cfg, capacity).scratch, p.alpha_img);
-             return pybind11::make_tuple(dims_vec(p.dims), p.color, e, p.radii, p.geom, p.bin, p.img, b.be().sized(cfg, capacity).scratch);
+             return pybind11::make_tuple(dims_vec(p.dims), p.color, or_none(p.extra_img), p.radii, p.geom, p.bin, p.img, b.be().sized(cfg, capacity).scratch,
+                                         or_none(p.alpha_img));
            })
       .def("check_pending", [](PyBackend& b, bool wait, int64_t only_token) { pybind11::gil_scoped_release nogil; b.be().check_pending(wait, only_token); },
            pybind11::arg("wait") = false,
@@ -1173,9 +1163,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              }
              pybind11::object saved = pybind11::none();
              if (o.saved.valid) saved = pybind11::make_tuple(dims_vec(o.saved.dims), o.saved.geom, o.saved.bin, o.saved.img, o.saved.token);
-             pybind11::object e = o.extra_img.defined() ? pybind11::cast(o.extra_img) : pybind11::none();
-             if (o.alpha_img.defined()) return pybind11::make_tuple(o.color, e, o.radii, saved, o.alpha_img);
-             return pybind11::make_tuple(o.color, e, o.radii, saved);
+             return pybind11::make_tuple(o.color, or_none(o.extra_img), o.radii, saved, or_none(o.alpha_img));
            }, pybind11::arg("cfg"), pybind11::arg("viewbuf"), pybind11::arg("means"), pybind11::arg("cov"), pybind11::arg("opac"), pybind11::arg("colors"),
            pybind11::arg("extra"), pybind11::arg("frames"), pybind11::arg("capacity") = -1, pybind11::arg("reuse_workspaces") = false)
       .def("backward", [](PyBackend& b, const std::vector<int64_t>& cfgv, const std::vector<int64_t>& dimsv, const Tensor& geom, const Tensor& bin, const Tensor& img,

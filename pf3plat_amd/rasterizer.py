@@ -55,7 +55,7 @@ class RasterConfig:
     has_extra: bool = False
     flags: int = 0  # _lib.FLAG_SH_PLANAR | _lib.FLAG_COV_3X3 (input layouts)
     scale_rot: bool = False  # the covariance argument is (S, N, 7) scale + quaternion (x, y, z, w) records (GsrForwardOptions.scale_rot)
-    alpha: bool = False  # the call also returns the accumulated alpha image (V, H, W) (gsr_forward_alpha / gsr_backward_alpha); sizes nothing
+    alpha: bool = False  # the call also returns the accumulated alpha image (V, H, W) (GsrForwardOptions.out_alpha); sizes nothing
 
 
 def pack_views(viewmatrix: Tensor, projmatrix: Tensor, campos: Tensor, tanfovx: Tensor, tanfovy: Tensor,
@@ -257,9 +257,9 @@ class HipBackend:
         backward=True adds the gradient outputs and the backward's scratch."""
         v, n, s = cfg.num_views, cfg.num_gaussians, cfg.num_sets
         f32, u8 = torch.float32, torch.uint8
-        dims, color, extra_img, radii, geom, binb, img, scratch_bytes, *acc = self._c.make_plan(_cfg_vec(cfg), torch.device(device), int(capacity))
+        dims, color, extra_img, radii, geom, binb, img, scratch_bytes, alpha_img = self._c.make_plan(_cfg_vec(cfg), torch.device(device), int(capacity))
         plan = dict(cfg=cfg, dims=_lib.GsrDims(*dims), device=device, color=color, extra_img=extra_img, radii=radii, geom=geom, bin=binb, img=img,
-                    alpha_img=acc[0] if acc else None)  # (cfg.alpha: the accumulated alpha image, written by run_forward)
+                    alpha_img=alpha_img)  # (cfg.alpha: the accumulated alpha image, written by run_forward; None otherwise)
         if backward:
             if colors_shape is None:
                 if cfg.sh_coeffs > 0:
@@ -281,8 +281,8 @@ class HipBackend:
 
     def run_forward(self, plan: dict, viewbuf, means, cov6, opac, colors, extra=None, profile: bool = False, out_color=None,
                     frames=None):
-        """Enqueue one forward launch chain on the current stream (gsr_forward_ex; gsr_forward_alpha, which also fills
-        plan["alpha_img"], for a plan of a cfg with alpha=True).  profile=True returns per-stage ms (synchronises), in the
+        """Enqueue one forward launch chain on the current stream (gsr_forward_ex; it also fills plan["alpha_img"] for a plan of
+        a cfg with alpha=True).  profile=True returns per-stage ms (synchronises), in the
         scale / rotation form too.
         out_color: render into this contiguous (V, 3, H, W) fp32 tensor instead of the plan's own image (e.g. a slot of a
         buffer that is all-gathered later: no copy)."""
@@ -294,14 +294,12 @@ class HipBackend:
         fr, nf = self._ext.frames_arg(_cfg_vec(cfg), frames) if cfg.scale_rot else (None, 0)
         ms = (ctypes.c_float * len(_lib.FWD_STAGES))() if profile else None
         # (nothing asked for: NULL options, the plain call)
-        opt = ctypes.byref(_lib.GsrForwardOptions(_ptr(fr), nf, int(cfg.scale_rot), ms)) if cfg.scale_rot or profile else None
-        head = (ctypes.byref(plan["dims"]), _ptr(viewbuf), _ptr(means), _ptr(cov6), _ptr(opac), _ptr(colors), _ptr(extra), _ptr(color), _ptr(plan["extra_img"]))
-        tail = (_ptr(plan["radii"]), _ptr(plan["geom"]), _ptr(plan["bin"]), _ptr(plan["img"]), opt, stream)
+        opt = None
+        if cfg.scale_rot or profile or cfg.alpha:
+            opt = ctypes.byref(_lib.GsrForwardOptions(_ptr(fr), nf, int(cfg.scale_rot), ms, _ptr(plan["alpha_img"])))
         with _on_device(plan["device"]):  # kernels launch on the process's current device: make it the tensors' device
-            if cfg.alpha:
-                rc = self.lib.gsr_forward_alpha(*head, _ptr(plan["alpha_img"]), *tail)
-            else:
-                rc = self.lib.gsr_forward_ex(*head, *tail)
+            rc = self.lib.gsr_forward_ex(ctypes.byref(plan["dims"]), _ptr(viewbuf), _ptr(means), _ptr(cov6), _ptr(opac), _ptr(colors), _ptr(extra), _ptr(color),
+                                         _ptr(plan["extra_img"]), _ptr(plan["radii"]), _ptr(plan["geom"]), _ptr(plan["bin"]), _ptr(plan["img"]), opt, stream)
         self._rc(rc, "gsr_forward")
         return None if ms is None else dict(zip(_lib.FWD_STAGES, [float(x) for x in ms]))
 
@@ -336,8 +334,8 @@ class HipBackend:
     def run_backward(self, plan: dict, viewbuf, means, cov6, opac, colors, extra, g_color, g_extra_img=None,
                      want_means2d: bool = True, profile: bool = False, frames=None, d_views=None, depth_term_only: bool = False,
                      g_alpha_img=None):
-        """Enqueue one backward launch chain on the current stream (gsr_backward_ex; gsr_backward_alpha when g_alpha_img, the
-        (V, H, W) gradient of the accumulated alpha, is given).  profile=True returns per-stage ms
+        """Enqueue one backward launch chain on the current stream (gsr_backward_ex; g_alpha_img: the (V, H, W) gradient of the
+        accumulated alpha, or None).  profile=True returns per-stage ms
         (synchronises), in the scale / rotation form and together with d_views too.
         d_views: a (V, 48) fp32 tensor that receives the camera gradients; depth_term_only: only what the built-in
         depth channel sends to the camera (the z row of the view matrix), the gradient of the reference's graph."""
@@ -353,18 +351,14 @@ class HipBackend:
                     max(16, int(self.lib.gsr_pose_partials_bytes(ctypes.byref(self._sizing_dims(plan["dims"]))))), dtype=torch.uint8,
                     device=plan["device"])
         opt = None  # (nothing asked for: NULL options, the plain call)
-        if cfg.scale_rot or profile or d_views is not None:
+        if cfg.scale_rot or profile or d_views is not None or g_alpha_img is not None:
             opt = ctypes.byref(_lib.GsrBackwardOptions(_ptr(fr), nf, int(cfg.scale_rot), _ptr(d_views), _ptr(partials), ms,
-                                                       int(d_views is not None and bool(depth_term_only))))
-        head = (ctypes.byref(plan["dims"]), _ptr(viewbuf), _ptr(means), _ptr(cov6), _ptr(opac), _ptr(colors), _ptr(extra), _ptr(plan["geom"]),
-                _ptr(plan["bin"]), _ptr(plan["img"]), _ptr(g_color), _ptr(g_extra_img if cfg.has_extra else None))
-        tail = (_ptr(plan["scratch"]), _ptr(plan["d_means"]), _ptr(plan["d_cov6"]), _ptr(plan["d_opac"]), _ptr(plan["d_colors"]), _ptr(plan["d_extra"]),
-                _ptr(plan["d_means2d"] if want_means2d else None), opt, stream)
+                                                       int(d_views is not None and bool(depth_term_only)), 0, _ptr(g_alpha_img)))
         with _on_device(plan["device"]):
-            if g_alpha_img is not None:
-                rc = self.lib.gsr_backward_alpha(*head, _ptr(g_alpha_img), *tail)
-            else:
-                rc = self.lib.gsr_backward_ex(*head, *tail)
+            rc = self.lib.gsr_backward_ex(ctypes.byref(plan["dims"]), _ptr(viewbuf), _ptr(means), _ptr(cov6), _ptr(opac), _ptr(colors), _ptr(extra),
+                                          _ptr(plan["geom"]), _ptr(plan["bin"]), _ptr(plan["img"]), _ptr(g_color), _ptr(g_extra_img if cfg.has_extra else None),
+                                          _ptr(plan["scratch"]), _ptr(plan["d_means"]), _ptr(plan["d_cov6"]), _ptr(plan["d_opac"]), _ptr(plan["d_colors"]),
+                                          _ptr(plan["d_extra"]), _ptr(plan["d_means2d"] if want_means2d else None), opt, stream)
         self._rc(rc, "gsr_backward", backward=True)
         return None if ms is None else dict(zip(_lib.BWD_STAGES, [float(x) for x in ms]))
 
@@ -401,11 +395,11 @@ class HipBackend:
                   and verify it at the next call, at `check_pending()`, and - for a call that is differentiated - at the
                   end of its backward.  A workspace that turns out too small poisons that call's image with NaN
                   (k_tile_fwd) and raises at verification - it cannot pass silently."""
-        color, extra_img, radii, saved, *acc = self._c.forward(_cfg_vec(cfg), viewbuf, means, cov6, opac, colors, extra, frames,
-                                                               -1 if capacity is None else int(capacity), bool(reuse_workspaces))
+        color, extra_img, radii, saved, alpha_img = self._c.forward(_cfg_vec(cfg), viewbuf, means, cov6, opac, colors, extra, frames,
+                                                                    -1 if capacity is None else int(capacity), bool(reuse_workspaces))
         if saved is not None:
             saved = (_lib.GsrDims(*saved[0]),) + tuple(saved[1:])
-        return (color, extra_img, radii, saved, *acc)
+        return (color, extra_img, radii, saved, alpha_img) if cfg.alpha else (color, extra_img, radii, saved)
 
     def check_pending(self, wait: bool = False, only_token: Optional[int] = None):
         """Verify the status blocks of earlier lazy / deferred forwards (those whose async copy has landed; all if `wait`;
@@ -455,9 +449,9 @@ class HipBackend:
 
 
 def _cfg_vec(cfg: RasterConfig):
-    """RasterConfig as the twelve integers the compiled backend takes (a thirteenth, 1, when the alpha image is wanted)."""
+    """RasterConfig as the thirteen integers the compiled backend takes."""
     return [cfg.num_views, cfg.num_sets, cfg.views_per_set, cfg.num_gaussians, cfg.height, cfg.width, cfg.sh_degree, cfg.sh_coeffs,
-            cfg.max_sh_eval, int(cfg.has_extra), int(cfg.flags), int(cfg.scale_rot)] + ([1] if cfg.alpha else [])
+            cfg.max_sh_eval, int(cfg.has_extra), int(cfg.flags), int(cfg.scale_rot), int(cfg.alpha)]
 
 
 def cfg_repr(dims) -> str:
@@ -585,7 +579,7 @@ def rasterize_views(means: Tensor, cov6: Tensor, opacities: Tensor, colors: Tens
             bool(debug), bool(prefiltered), -1 if deterministic is None else int(bool(deterministic)), bool(scale_rot), frames,
             2 if camera_gradient == "depth" else 1, sh_code, bool(return_alpha))
     if return_alpha:
-        raise NotImplementedError("return_alpha needs the HIP backend (gsr_forward_alpha)")
+        raise NotImplementedError("return_alpha needs the HIP backend")
     # any other backend object (tests slide the CPU oracle under the host wrappers): the SAME statement of the call shape - the
     # compiled `prepare_call` (csrc/gsr_torch.cpp: checks, normalisation, flags; it touches no device) - then that backend's forward
     if camera_gradient not in ("full", "depth"):

@@ -26,11 +26,13 @@ def test_library_exports_every_declared_symbol():
     for n in names:
         assert hasattr(lib, n), f"{n} declared in include/gsr.h but not exported by libgsr_hip.so"
     assert set(_lib.EXPORTED_SYMBOLS) <= set(names)
-    assert lib.gsr_abi_version() == _lib.GSR_ABI_VERSION == 4
-    assert b"gfx950" in lib.gsr_build_info()
-    # ABI 4: one extended launch entry point each way; the per-feature variants of ABI 3 are neither declared nor exported
+    assert lib.gsr_abi_version() == _lib.GSR_ABI_VERSION == 5
+    assert b"gfx950" in lib.gsr_build_info() and b"abi5" in lib.gsr_build_info()
+    # ABI 4: one extended launch entry point each way; the per-feature variants of ABI 3 are neither declared nor exported.  ABI 5: nor
+    # are the two calls that took the accumulated alpha as a parameter - an optional image or cotangent is a field of the options
     assert {"gsr_forward_ex", "gsr_backward_ex", "gsr_stage_name"} <= set(names) & set(_lib.EXPORTED_SYMBOLS)
-    for n in ("gsr_forward_scale_rot", "gsr_backward_scale_rot", "gsr_forward_profile", "gsr_backward_profile"):
+    for n in ("gsr_forward_scale_rot", "gsr_backward_scale_rot", "gsr_forward_profile", "gsr_backward_profile",
+              "gsr_forward_alpha", "gsr_backward_alpha"):
         assert n not in names and n not in _lib.EXPORTED_SYMBOLS and not hasattr(lib, n), n
 
 
@@ -86,7 +88,7 @@ def test_oracle_twin_is_rebuilt_by_content_of_its_sources(tmp_path):
     hdr = tmp_path / "gsr.h"
     shutil.copy(_lib.HEADER, hdr)
     assert gsr_oracle._source_stamp(src[:-1] + [str(hdr)]) == gsr_oracle._source_stamp(src)
-    hdr.write_text(hdr.read_text().replace("#define GSR_ABI_VERSION 4", "#define GSR_ABI_VERSION 3"))
+    hdr.write_text(hdr.read_text().replace("#define GSR_ABI_VERSION 5", "#define GSR_ABI_VERSION 4"))
     assert gsr_oracle._source_stamp(src[:-1] + [str(hdr)]) != gsr_oracle._source_stamp(src)
 
 
@@ -94,11 +96,11 @@ def test_struct_layouts_match_header():
     assert ctypes.sizeof(_lib.GsrDims) == 56  # 12 x int32 + int64
     assert rasterizer.VIEW_FLOATS * 4 == 192  # sizeof(GsrView)
     # the options of the _ex calls: the numbers of the static_assert next to forward_impl (csrc/gsr_hip.hip); no implicit padding
-    assert ctypes.sizeof(_lib.GsrForwardOptions) == 24 == sum(ctypes.sizeof(t) for _, t in _lib.GsrForwardOptions._fields_)
-    assert ctypes.sizeof(_lib.GsrBackwardOptions) == 48 == sum(ctypes.sizeof(t) for _, t in _lib.GsrBackwardOptions._fields_)
-    assert [n for n, _ in _lib.GsrForwardOptions._fields_] == ["frames", "num_frames", "scale_rot", "stage_ms"]
+    assert ctypes.sizeof(_lib.GsrForwardOptions) == 32 == sum(ctypes.sizeof(t) for _, t in _lib.GsrForwardOptions._fields_)
+    assert ctypes.sizeof(_lib.GsrBackwardOptions) == 56 == sum(ctypes.sizeof(t) for _, t in _lib.GsrBackwardOptions._fields_)
+    assert [n for n, _ in _lib.GsrForwardOptions._fields_] == ["frames", "num_frames", "scale_rot", "stage_ms", "out_alpha"]
     assert [n for n, _ in _lib.GsrBackwardOptions._fields_] == ["frames", "num_frames", "scale_rot", "dL_dviews", "pose_partials", "stage_ms",
-                                                                "depth_term_only", "reserved_"]
+                                                                "depth_term_only", "reserved_", "dL_dalpha_img"]
     hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "gsr.h")).read(), flags=re.S)
     for struct in (_lib.GsrForwardOptions, _lib.GsrBackwardOptions):  # field for field, in the header's order
         body = re.search(r"typedef struct %s \{(.*?)\}" % struct.__name__, hdr, re.S).group(1)
@@ -137,21 +139,22 @@ def test_workspace_sizes_and_validation():
     # ... and by the extended calls with NULL options, as by the plain ones
     assert lib.gsr_forward_ex(ctypes.byref(bad), *([None] * 12), None, None) == -1
     assert lib.gsr_backward_ex(ctypes.byref(bad), *([None] * 18), None, None) == -1
-    # dims of the previous ABI are refused everywhere: by every helper and every launch
-    old = be._dims(cfg, 2_000_000)
-    assert lib.gsr_workspace_sizes(ctypes.byref(old), ctypes.byref(z), ctypes.byref(z), ctypes.byref(z)) == 0
-    old.abi_version = 3
-    ref, offs = ctypes.byref(old), (ctypes.c_int64 * 8)()
-    assert lib.gsr_workspace_sizes(ref, ctypes.byref(z), ctypes.byref(z), ctypes.byref(z)) == -1
-    assert lib.gsr_workspace_layout(ref, offs) == -1 and lib.gsr_geom_layout(ref, offs) == -1
-    assert lib.gsr_capacity_for(ref, 1000, 10) == -1 and lib.gsr_colour_in_binning(ref) == -1
-    assert lib.gsr_backward_scratch_bytes(ref) == 0 and lib.gsr_pose_partials_bytes(ref) == 0
-    assert lib.gsr_mark_visible(ref, None, None, None, None) == -1
-    assert lib.gsr_forward(ref, *([None] * 13)) == -1 and lib.gsr_backward(ref, *([None] * 19)) == -1
-    assert lib.gsr_forward_ex(ref, *([None] * 12), None, None) == -1 and lib.gsr_backward_ex(ref, *([None] * 18), None, None) == -1
+    # dims of an earlier ABI are refused everywhere: by every helper and every launch
     opts = _lib.GsrForwardOptions(None, 0, 1), _lib.GsrBackwardOptions(None, 0, 1)
-    assert lib.gsr_forward_ex(ref, *([None] * 12), ctypes.byref(opts[0]), None) == -1
-    assert lib.gsr_backward_ex(ref, *([None] * 18), ctypes.byref(opts[1]), None) == -1
+    for version in (3, 4):
+        old = be._dims(cfg, 2_000_000)
+        assert lib.gsr_workspace_sizes(ctypes.byref(old), ctypes.byref(z), ctypes.byref(z), ctypes.byref(z)) == 0
+        old.abi_version = version
+        ref, offs = ctypes.byref(old), (ctypes.c_int64 * 8)()
+        assert lib.gsr_workspace_sizes(ref, ctypes.byref(z), ctypes.byref(z), ctypes.byref(z)) == -1
+        assert lib.gsr_workspace_layout(ref, offs) == -1 and lib.gsr_geom_layout(ref, offs) == -1
+        assert lib.gsr_capacity_for(ref, 1000, 10) == -1 and lib.gsr_colour_in_binning(ref) == -1
+        assert lib.gsr_backward_scratch_bytes(ref) == 0 and lib.gsr_pose_partials_bytes(ref) == 0
+        assert lib.gsr_mark_visible(ref, None, None, None, None) == -1
+        assert lib.gsr_forward(ref, *([None] * 13)) == -1 and lib.gsr_backward(ref, *([None] * 19)) == -1
+        assert lib.gsr_forward_ex(ref, *([None] * 12), None, None) == -1 and lib.gsr_backward_ex(ref, *([None] * 18), None, None) == -1
+        assert lib.gsr_forward_ex(ref, *([None] * 12), ctypes.byref(opts[0]), None) == -1
+        assert lib.gsr_backward_ex(ref, *([None] * 18), ctypes.byref(opts[1]), None) == -1
 
 
 def test_binning_chunk_follows_the_shape_of_the_call():

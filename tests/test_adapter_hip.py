@@ -31,7 +31,7 @@ def test_header_declares_and_library_exports_the_adapter_entry_points():
     for name in ("gsr_adapt", "gsr_adapt_backward", "gsr_adapt_partials_bytes"):
         assert f"{name}(" in header and name in _lib.EXPORTED_SYMBOLS
         getattr(lib, name)
-    assert "#define GSR_ABI_VERSION 4" in header and lib.gsr_abi_version() == 4
+    assert "#define GSR_ABI_VERSION 5" in header and lib.gsr_abi_version() == 5
 
 
 def _abi_args(g=2, p=5, degree=4, stride=82, h=16, w=16, ptr=8):

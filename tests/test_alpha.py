@@ -1,6 +1,7 @@
-"""Accumulated alpha (A = 1 - T_final) without a GPU: the two new entry points of the C ABI (gsr_forward_alpha /
-gsr_backward_alpha) are declared, exported and bound with the argument lists of the _ex calls plus one pointer each; ABI number, the
-pinned structs, the flag mask and every workspace size are what they were; the Python surface has the switch, off by default."""
+"""Accumulated alpha (A = 1 - T_final) without a GPU: the image and its cotangent are the last fields of the launch options structs
+(GsrForwardOptions.out_alpha / GsrBackwardOptions.dL_dalpha_img) and no entry point takes either as a parameter; the _ex calls
+validate as before when the options carry the pointer; the flag mask and every workspace size are what they were; the Python surface
+has the switch, off by default."""
 import ctypes
 import inspect
 import os
@@ -21,51 +22,69 @@ def _params(name):
     return [re.search(r"(\w+)\s*$", a.strip()).group(1) for a in body.split(",")]
 
 
-def test_alpha_entry_points_are_the_ex_calls_plus_one_pointer():
+def _header():
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "gsr.h")).read(), flags=re.S)
+
+
+def _struct_fields(name):
+    """Field names of struct `name` as include/gsr.h declares it, in order."""
+    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), _header(), re.S).group(1)
+    return [re.search(r"(\w+)\s*(\[\w+\])?\s*$", f.strip()).group(1) for f in body.split(";") if f.strip()]
+
+
+def test_alpha_pointers_are_the_last_option_fields_and_no_parameter():
     lib = _lib.load()
-    fwd, bwd = _params("gsr_forward_ex"), _params("gsr_backward_ex")
-    assert _params("gsr_forward_alpha") == fwd[:fwd.index("out_extra") + 1] + ["out_alpha"] + fwd[fwd.index("out_extra") + 1:]
-    assert _params("gsr_backward_alpha") == bwd[:bwd.index("dL_dextra_img") + 1] + ["dL_dalpha_img"] + bwd[bwd.index("dL_dextra_img") + 1:]
-    for name, ex in (("gsr_forward_alpha", lib.gsr_forward_ex), ("gsr_backward_alpha", lib.gsr_backward_ex)):
+    assert _struct_fields("GsrForwardOptions")[-1] == "out_alpha" == _lib.GsrForwardOptions._fields_[-1][0]
+    assert _struct_fields("GsrBackwardOptions")[-1] == "dL_dalpha_img" == _lib.GsrBackwardOptions._fields_[-1][0]
+    functions = re.findall(r"\b(gsr_\w+)\s*\(([^;{}]*?)\)\s*;", _header(), re.S)
+    assert {"gsr_forward", "gsr_backward", "gsr_forward_ex", "gsr_backward_ex"} <= {n for n, _ in functions}
+    for name, params in functions:
+        assert not re.search(r"\b(out_alpha|dL_dalpha_img)\b", params), name
+    for name in ("gsr_forward_ex", "gsr_backward_ex"):  # the one entry point each way that carries the options
         fn = getattr(lib, name)  # exported by the built library
-        assert name in _lib.EXPORTED_SYMBOLS and fn.restype is ctypes.c_int
-        assert len(fn.argtypes) == len(_params(name)) == len(ex.argtypes) + 1
-        assert fn.argtypes[0] is ex.argtypes[0] and fn.argtypes[-2:] == ex.argtypes[-2:]  # dims first; options, stream last
-        assert all(t is ctypes.c_void_p for t in fn.argtypes[1:-2])
+        assert name in _lib.EXPORTED_SYMBOLS and fn.restype is ctypes.c_int and len(fn.argtypes) == len(_params(name))
+        assert _params(name)[-2:] == ["opt", "stream"] and all(t is ctypes.c_void_p for t in fn.argtypes[1:-2])
+    assert lib.gsr_forward_ex.argtypes[-2]._type_ is _lib.GsrForwardOptions and lib.gsr_backward_ex.argtypes[-2]._type_ is _lib.GsrBackwardOptions
 
 
-def test_alpha_entry_points_validate_like_the_ex_calls():
-    """Host-only answers (nothing is launched): bad dims are refused, an empty call is fine."""
+def test_ex_calls_validate_with_an_alpha_pointer_in_their_options():
+    """Host-only answers (nothing is launched, no pointer is followed): bad dims are refused, an empty call is fine."""
     lib = _lib.load()
     be = rasterizer.HipBackend()
     cfg = rasterizer.RasterConfig(1, 1, 1, 16, 8, 8, 0, 0)
-    null = [None] * 13
+    image = (ctypes.c_float * 64)()  # (a non-null address for the alpha fields)
+    fopt = _lib.GsrForwardOptions(None, 0, 0, None, ctypes.addressof(image))
+    bopt = _lib.GsrBackwardOptions(None, 0, 0, None, None, None, 0, 0, ctypes.addressof(image))
+    assert fopt.out_alpha and bopt.dL_dalpha_img
+    fnull, bnull = [None] * 12, [None] * 18
     for flags in (0x100000, 1 << 30, 0x100):  # no new flag bit came with the feature: the mask is what it was
         dims = be._dims(rasterizer.RasterConfig(1, 1, 1, 16, 8, 8, 0, 0, 4, False, flags), 1024)
-        assert lib.gsr_forward_alpha(ctypes.byref(dims), *null, None, None) == -1
-        assert lib.gsr_backward_alpha(ctypes.byref(dims), *null, *[None] * 6, None, None) == -1
+        assert lib.gsr_forward_ex(ctypes.byref(dims), *fnull, ctypes.byref(fopt), None) == -1
+        assert lib.gsr_backward_ex(ctypes.byref(dims), *bnull, ctypes.byref(bopt), None) == -1
         assert lib.gsr_workspace_sizes(ctypes.byref(dims), None, None, None) == -1
     empty = be._dims(rasterizer.RasterConfig(0, 0, 1, 16, 8, 8, 0, 0), 1024)
-    assert lib.gsr_forward_alpha(ctypes.byref(empty), *null, None, None) == 0
-    assert lib.gsr_backward_alpha(ctypes.byref(empty), *null, *[None] * 6, None, None) == 0
+    assert lib.gsr_forward_ex(ctypes.byref(empty), *fnull, ctypes.byref(fopt), None) == 0
+    assert lib.gsr_backward_ex(ctypes.byref(empty), *bnull, ctypes.byref(bopt), None) == 0
     dims = be._dims(cfg, 1024)
-    assert lib.gsr_forward_alpha(ctypes.byref(dims), *null, None, None) == -1  # (views, image and workspaces are required)
+    assert lib.gsr_forward_ex(ctypes.byref(dims), *fnull, ctypes.byref(fopt), None) == -1  # (views, image and workspaces are required)
+    assert lib.gsr_backward_ex(ctypes.byref(dims), *bnull, ctypes.byref(bopt), None) == -1
 
 
-def test_abi_number_structs_and_sizes_are_unchanged():
+def test_the_request_sizes_nothing_and_is_the_last_entry_of_the_call_shape():
     lib = _lib.load()
-    assert lib.gsr_abi_version() == _lib.GSR_ABI_VERSION == 4
-    assert ctypes.sizeof(_lib.GsrDims) == 56 and ctypes.sizeof(_lib.GsrForwardOptions) == 24 and ctypes.sizeof(_lib.GsrBackwardOptions) == 48
-    assert [n for n, _ in _lib.GsrForwardOptions._fields_] == ["frames", "num_frames", "scale_rot", "stage_ms"]
+    assert lib.gsr_abi_version() == _lib.GSR_ABI_VERSION == 5
+    assert ctypes.sizeof(_lib.GsrDims) == 56 and ctypes.sizeof(_lib.GsrForwardOptions) == 32 and ctypes.sizeof(_lib.GsrBackwardOptions) == 56
+    assert [n for n, _ in _lib.GsrForwardOptions._fields_] == ["frames", "num_frames", "scale_rot", "stage_ms", "out_alpha"]
     assert [n for n, _ in _lib.GsrBackwardOptions._fields_] == ["frames", "num_frames", "scale_rot", "dL_dviews", "pose_partials", "stage_ms",
-                                                                "depth_term_only", "reserved_"]
+                                                                "depth_term_only", "reserved_", "dL_dalpha_img"]
     # the request sizes nothing: a call shape with and without it has the same dims, hence the same workspaces
     be = rasterizer.HipBackend()
     plain = rasterizer.RasterConfig(3, 1, 3, 1000, 72, 40, 4, 25, 4, True, 1 << 4)
     wanted = rasterizer.RasterConfig(3, 1, 3, 1000, 72, 40, 4, 25, 4, True, 1 << 4, False, True)
     assert wanted.alpha and not plain.alpha
     assert bytes(be._dims(plain, 1 << 16)) == bytes(be._dims(wanted, 1 << 16))
-    assert rasterizer._cfg_vec(plain) + [1] == rasterizer._cfg_vec(wanted) and len(rasterizer._cfg_vec(plain)) == 12
+    vp, vw = rasterizer._cfg_vec(plain), rasterizer._cfg_vec(wanted)
+    assert len(vp) == len(vw) == 13 and vp[:12] == vw[:12] and (vp[12], vw[12]) == (0, 1)
 
 
 def test_python_surface_has_the_switch_off_by_default():

@@ -1,4 +1,4 @@
-"""Accumulated alpha A = sum_j alpha_j T_j = 1 - T_final on the MI355X (gsr_forward_alpha / gsr_backward_alpha) against the CPU oracle.
+"""Accumulated alpha A = sum_j alpha_j T_j = 1 - T_final on the MI355X (GsrForwardOptions.out_alpha / GsrBackwardOptions.dL_dalpha_img) against the CPU oracle.
 
 The oracle is untouched.  A is what its fp32 instantiation blends for a caller-supplied extra channel of ones; the backward being
 linear in the incoming image gradients over a fixed forward, the reference for (g_color, g_extra, g_A) is the sum of two oracle backwards

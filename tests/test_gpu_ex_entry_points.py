@@ -1,6 +1,7 @@
 """The extended launch entry points (gsr_forward_ex / gsr_backward_ex) through the plan API on the MI355X: stage timing
 (`profile=True`) in the scale / rotation form and together with camera gradients returns the bits of the untimed call, and NULL options
-are the plain gsr_forward.  One small shape: 1 set x 2 views of 16 x 16 pixels, 128 Gaussians, degree 4 (25 coefficients) in
+are the plain gsr_forward; and all four options of a launch - scale / rotation form, stage timing, camera gradients, accumulated alpha
+- meet in one struct each way.  One small shape: 1 set x 2 views of 16 x 16 pixels, 128 Gaussians, degree 4 (25 coefficients) in
 F = 2 frames ("rasterizer" basis), built-in depth channel, a forward that announces its backward - the frame instances of the
 colour pass, the saved Jacobian and both backward kernels."""
 import numpy as np
@@ -86,6 +87,37 @@ def test_profile_together_with_camera_gradients_returns_the_same_bits(case, unpr
     assert torch.equal(d_views[1], d_views[0])
     for k in OUTPUTS + GRADS:
         assert torch.equal(timed[k], plain[k]) and torch.equal(timed[k], unprofiled[k]), k
+
+
+def test_all_four_options_in_one_struct_each_way(case, unprofiled):
+    """Scale / rotation form with frames, stage timing, camera gradients and the accumulated alpha with its cotangent in the same
+    GsrForwardOptions / GsrBackwardOptions: the timed step returns the bits of the untimed one, and the cotangent arrives."""
+    hip = rasterizer.HipBackend()
+    flags = DEPTH | _lib.FLAG_DETERMINISTIC | _lib.FLAG_SH_PLANAR | _lib.FLAG_BACKWARD_FOLLOWS | gpu_util.SH_FRAME_BITS["rasterizer"]
+    plan = hip.make_plan(RasterConfig(VIEWS, 1, VIEWS, N, *HW, 4, 25, 4, True, flags, True, True), DEV, 1 << 16, backward=True)
+    assert plan["alpha_img"].shape == (VIEWS, *HW)
+    c = case
+    g_alpha = torch.rand((VIEWS, *HW), generator=torch.Generator().manual_seed(151)).to(DEV)
+    runs = []
+    for profile in (False, True):
+        d_views = torch.full((VIEWS, rasterizer.VIEW_FLOATS), float("nan"), device=DEV)
+        plan["d_extra"].zero_()  # (not written with the built-in channel)
+        plan["alpha_img"].fill_(float("nan"))
+        fwd_ms = hip.run_forward(plan, c["vb"], c["means"], c["records"], c["opac"], c["sh"], None, profile=profile, frames=c["frames"])
+        bwd_ms = hip.run_backward(plan, c["vb"], c["means"], c["records"], c["opac"], c["sh"], None, c["gc"], c["ge"], profile=profile,
+                                  frames=c["frames"], d_views=d_views, g_alpha_img=g_alpha)
+        torch.cuda.synchronize()
+        assert not hip.read_status(plan)["overflow"]
+        runs.append((fwd_ms, bwd_ms, dict({k: plan[k].clone() for k in OUTPUTS + GRADS + ("alpha_img",)}, d_views=d_views)))
+    (plain_fwd, plain_bwd, plain), (fwd_ms, bwd_ms, timed) = runs
+    assert plain_fwd is None and plain_bwd is None and tuple(fwd_ms) == _lib.FWD_STAGES and tuple(bwd_ms) == _lib.BWD_STAGES
+    assert all(np.isfinite(x) and x >= 0 for ms in (fwd_ms, bwd_ms) for x in ms.values())
+    for k in plain:
+        assert torch.equal(timed[k], plain[k]), k
+    alpha = plain["alpha_img"]
+    assert bool(torch.isfinite(alpha).all()) and float(alpha.min()) >= 0 and float(alpha.max()) < 1 and float(alpha.max()) > 0
+    assert bool(torch.isfinite(plain["d_views"]).all()) and float(plain["d_views"].abs().max()) > 0
+    assert not torch.equal(plain["d_opac"], unprofiled["d_opac"])  # (`unprofiled` has no alpha cotangent: this one came through the struct)
 
 
 def test_null_options_are_the_plain_forward(case):

@@ -1,7 +1,7 @@
 """Measurement aid (GPU box): what the accumulated-alpha image costs on BASELINE configs[3] (B = 1, 131 072 Gaussians, 3 views of
 256 x 256, colour + built-in depth, through the plan API) - forward and training step (forward announced with
-GSR_FLAG_BACKWARD_FOLLOWS + backward) with alpha off (gsr_forward_ex / gsr_backward_ex), with alpha on (gsr_forward_alpha /
-gsr_backward_alpha, dL/dalpha given), and the two-pass alternative alpha replaces: the same call followed by a second forward that
+GSR_FLAG_BACKWARD_FOLLOWS + backward) with alpha off (gsr_forward_ex / gsr_backward_ex), with alpha on (the same calls with
+out_alpha / dL_dalpha_img in their options), and the two-pass alternative alpha replaces: the same call followed by a second forward that
 blends an `extra` array of ones (which cannot share a pass with the depth channel).  The variants are alternated repeat by repeat.
 usage: python tools/alpha_step.py [steps per repeat = 200] [repeats = 5] [out.json]"""
 import json
