@@ -79,8 +79,14 @@ extern "C" {
 #define GSR_FLAG_PREFILTERED 0x1
 #define GSR_FLAG_DEBUG 0x2
 /* Deterministic backward: the per-(view, Gaussian) screen-space gradients are accumulated as 64-bit fixed-point integers
- * (2^-32 resolution, integer atomics commute), so two runs on the same inputs return bit-identical gradients whatever
- * order the tiles finish in.  The scratch buffer is then twice as large (gsr_backward_scratch_bytes). */
+ * (integer atomics commute), so two runs on the same inputs return bit-identical gradients whatever order the tiles finish
+ * in.  The resolution is relative, per view: the sums are kept in units of 2^-e, the power of two that brings the largest finite
+ * |value| of that view's cotangent images (dL_dcolor, dL_dextra_img, dL_dalpha_img) into [1, 2), with a step of 2^-32 of that
+ * unit and a clamp at 2^30 units per contribution - a loss that is a mean over millions of pixels (cotangents of 1e-8) or a
+ * loss-scaled sum (2^20) is served like one of order one, and scaling every cotangent of a view by a power of two scales its
+ * gradients by exactly that power.  A view's pixel whose cotangent is below 2^-32 of the view's largest is below the step.
+ * Non-finite cotangents are not looked at for the unit.  The scratch buffer is then twice as large, plus one 4-byte word per
+ * view (gsr_backward_scratch_bytes). */
 #define GSR_FLAG_DETERMINISTIC 0x80
 /* The caller will run gsr_backward on this forward's workspaces: the forward then also zero-fills the per-(view, Gaussian)
  * screen-space gradient rows (inside `geom`, which is that much larger) from its VALU-bound geometry kernel, and

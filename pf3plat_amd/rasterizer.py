@@ -562,7 +562,9 @@ def rasterize_views(means: Tensor, cov6: Tensor, opacities: Tensor, colors: Tens
     rotations) and use_sh.  A backend without the capability gets the coefficients rotated in torch.
     debug: upstream's `settings.debug` - the library synchronises and checks for errors after every stage and names the
     stage that failed.  deterministic: the backward accumulates per-Gaussian gradients in 64-bit fixed point (bit-identical
-    from run to run); None = follow `torch.are_deterministic_algorithms_enabled()`.
+    from run to run); None = follow `torch.are_deterministic_algorithms_enabled()`.  The fixed point is relative, per view: a
+    step of 2^-32 of the power of two next below the largest |cotangent| of that view's images (colour, extra, alpha), so the
+    gradients of a mean-reduced loss (cotangents of 1e-8) or a loss-scaled one are as exact, relatively, as those of a sum.
     """
     backend = get_backend()
     if sh_frame not in SH_FRAMES:

@@ -70,7 +70,8 @@ def test_source_stamp_covers_every_file_the_library_is_built_from(tmp_path):
     with open(tmp_path / "csrc" / "gsr_torch.cpp", "ab") as f:
         f.write(b"\n")
     assert stamp() == before
-    assert {os.path.basename(s) for s in _lib.hip_sources()} == {"gsr_hip.hip", "gsr.h"}
+    # (preprocess_bwd.inc: the text of k_preprocess_bwd, which gsr_hip.hip compiles twice)
+    assert {os.path.basename(s) for s in _lib.hip_sources()} == {"gsr_hip.hip", "preprocess_bwd.inc", "gsr.h"}
 
 
 def test_oracle_twin_is_rebuilt_by_content_of_its_sources(tmp_path):
@@ -194,11 +195,12 @@ def test_flag_bits_are_validated_and_ablation_switches_are_not_in_the_product_li
     hdr = open(os.path.join(ROOT, "include", "gsr.h")).read()
     product, _, _ = hdr.partition("#ifdef GSR_ABLATE")
     assert "GSR_FLAG_ABLATE" not in product and "GSR_FLAG_DEBUG_TIMING" not in product
-    # scratch sizing of the backward: 12 floats per (view, Gaussian); 12 x 8 bytes in deterministic mode
+    # scratch sizing of the backward: 12 floats per (view, Gaussian); in deterministic mode 12 x 8 bytes and, behind the rows, one
+    # 4-byte word per view (the view's largest cotangent, the unit its fixed-point sums are kept in)
     d = be._dims(rasterizer.RasterConfig(2, 1, 2, 100, 16, 16, 4, 25, 4, False), 1000)
     assert lib.gsr_backward_scratch_bytes(ctypes.byref(d)) == 2 * 100 * 12 * 4
     d = be._dims(rasterizer.RasterConfig(2, 1, 2, 100, 16, 16, 4, 25, 4, False, _lib.FLAG_DETERMINISTIC), 1000)
-    assert lib.gsr_backward_scratch_bytes(ctypes.byref(d)) == 2 * 100 * 12 * 8
+    assert lib.gsr_backward_scratch_bytes(ctypes.byref(d)) == 2 * 100 * 12 * 8 + 2 * 4
     assert lib.gsr_last_failed_stage() == -1
     # a forward that announces its backward keeps the accumulator rows inside geom
     plain, with_rows = ctypes.c_size_t(), ctypes.c_size_t()
