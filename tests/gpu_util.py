@@ -94,13 +94,13 @@ def cov6_in_kernel_order(records, frames=None):
 
 
 def run_oracle(cfg: RasterConfig, viewbuf_cpu, means, cov6, opac, colors, extra=None, g_color=None, g_extra=None,
-               oracle_dtype=np.float32, want_means2d=True, want_views=False, frames=None, sh_frame=None):
+               oracle_dtype=np.float32, want_means2d=True, want_views=False, frames=None, sh_frame=None, threads=8):
     """The oracle side of `run_both`: -> dict(color, extra, radii, handles, stats[, grads]).  Scale / rotation form (cfg.scale_rot): the
     oracle rasterizes `cov6_in_kernel_order(records, frames)` and the records' gradient is pulled back through oracle/adapter.py's
     covariance in fp64.  sh_frame ("rasterizer" | "e3nn"): `colors` are in the coordinates of those frames - they
     are rotated to world space in fp64 (`rasterizer._rotate_in_frames`, the torch path GSR_FLAG_SH_IN_FRAME replaced), rendered, and the
     world harmonics' gradient is pulled back through that rotation with autograd: the gradient comes back in the frames' coordinates."""
-    ob = OracleBackend(dtype=oracle_dtype, threads=8)
+    ob = OracleBackend(dtype=oracle_dtype, threads=threads)  # (threads=1: sums in one fixed order, the same figures on every run)
     cfg = _with_sh_frame(cfg, None)
     local = world = None
     colors_o = colors

@@ -257,3 +257,19 @@ def check_grads(res, cfg, tol=TOL):
             assert val < tol, (k, m)
     _file_counts("grads", m)
     return m
+
+
+def all_checks(cfg, res, lists=True, max_tiles=256, strict=False):
+    """strict (the BASELINE-config tests): no gradient row may be set aside - the 1e-4 bound holds over ALL rows."""
+    for v in range(cfg.num_views):
+        check_preprocess(res, cfg, v)
+        if lists:
+            check_tile_lists(res, cfg, v, max_tiles=max_tiles)
+        check_image_state(res, cfg, v)
+    mi = check_image(res, cfg)
+    if strict:
+        assert mi["color_rel_l2_all"] < TOL, mi
+    if "grads" in res["hip"]:
+        mg = check_grads(res, cfg)
+        if strict:
+            assert_nothing_set_aside(mg)

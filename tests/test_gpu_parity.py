@@ -29,20 +29,7 @@ def _scene_case(seed, n, hw, views=1, use_sh=True, with_extra=True, grads=True, 
     return cfg, gpu_util.run_both(cfg, vb, means, cov6, opac, colors, extra, gc, ge)
 
 
-def _all_checks(cfg, res, lists=True, max_tiles=256, strict=False):
-    """strict (the BASELINE-config tests): no gradient row may be set aside - the 1e-4 bound holds over ALL rows."""
-    for v in range(cfg.num_views):
-        parity_checks.check_preprocess(res, cfg, v)
-        if lists:
-            parity_checks.check_tile_lists(res, cfg, v, max_tiles=max_tiles)
-        parity_checks.check_image_state(res, cfg, v)
-    mi = parity_checks.check_image(res, cfg)
-    if strict:
-        assert mi["color_rel_l2_all"] < parity_checks.TOL, mi
-    if "grads" in res["hip"]:
-        mg = parity_checks.check_grads(res, cfg)
-        if strict:
-            parity_checks.assert_nothing_set_aside(mg)
+_all_checks = parity_checks.all_checks
 
 
 def test_config1_1k_gaussians_64x64():
