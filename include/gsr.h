@@ -104,10 +104,18 @@ extern "C" {
  * stops after a quarter of its list): positions of a list beyond max(512, entries the tile walked) are then undefined.  The
  * backward never reads them.  Images, gradients and the status block are the same either way. */
 #define GSR_FLAG_FULL_LISTS 0x20000
+/* Tan-fov gradient (opt-in; learnable intrinsics): gsr_backward_ex with opt->dL_dviews and depth_term_only == 0 also writes
+ * dL/dtanfovx and dL/dtanfovy into floats [35] and [36] of each view's row - as the operator reads the two fields: through
+ * fx = W / (2 tanfovx), fy = H / (2 tanfovy) of the EWA Jacobian and the 1.3 tanfov limit a clamped t = V p sits on; the projection
+ * matrix stays an independent input, as for the other blocks (gsr_setup_views_backward_ex joins the two halves).  Floats [37, 48)
+ * stay zero.  The partial rows are then 37 floats wide: size pose_partials with gsr_pose_partials_bytes from dims that carry the bit.
+ * Every other entry point, a backward without dL_dviews and one with depth_term_only != 0 accept the bit and ignore it: the same
+ * kernel instances, the same bits out, the same workspace and scratch sizes. */
+#define GSR_FLAG_FOV_GRADIENT 0x200000
 /* Every other bit is rejected (GSR_ERR_INVALID_ARGUMENT). */
 #define GSR_FLAG_VALID_MASK (GSR_FLAG_PREFILTERED | GSR_FLAG_DEBUG | GSR_FLAG_SH_PLANAR | GSR_FLAG_COV_3X3 | 0x70 | \
                              GSR_FLAG_DETERMINISTIC | GSR_FLAG_WINDOWED_BINNING | GSR_FLAG_BACKWARD_FOLLOWS | GSR_FLAG_FULL_LISTS | \
-                             GSR_FLAG_SH_IN_FRAME | GSR_FLAG_SH_FRAME_E3NN)
+                             GSR_FLAG_SH_IN_FRAME | GSR_FLAG_SH_FRAME_E3NN | GSR_FLAG_FOV_GRADIENT)
 #ifdef GSR_ABLATE
 /* Measurement-only build (tools/ablate.py compiles its own copy of the library with -DGSR_ABLATE; the product library does
  * not contain these branches and rejects the bits): switches that make results WRONG on purpose to time a kernel without
@@ -223,10 +231,12 @@ int gsr_backward(const GsrDims* dims, const GsrView* views, const float* means, 
  * dL_dviews != NULL (camera-pose gradients, opt-in - the reference gets none through the operator although
  * PF3plat learns poses): (V, 48) floats laid out like GsrView receive
  * dL/d viewmatrix [0, 16), dL/d projmatrix [16, 32), dL/d campos [32, 35) (zeros behind) - the two matrices as independent
- * inputs, the way the operator takes them; tan-fov, background and scale get none.  Every place the forward reads a camera
+ * inputs, the way the operator takes them; tan-fov gets one only with GSR_FLAG_FOV_GRADIENT (floats [35], [36]), background and
+ * scale get none.  Every place the forward reads a camera
  * is differentiated (EWA covariance through t = V p and J Wr, projection to pixel coordinates, view direction of the
  * harmonics, depth of the built-in extra channel); depth ordering and culling are not, as for the Gaussians.  pose_partials:
- * gsr_pose_partials_bytes(dims) bytes of scratch (four rows per view and 64-Gaussian unit; reduced in a fixed order). */
+ * gsr_pose_partials_bytes(dims) bytes of scratch (four rows per view and 64-Gaussian unit, of 35 floats - 37 with
+ * GSR_FLAG_FOV_GRADIENT in the dims; reduced in a fixed order). */
 #define GSR_FWD_STAGES 5
 #define GSR_BWD_STAGES 2
 typedef struct GsrForwardOptions {
@@ -305,10 +315,21 @@ int gsr_setup_views(int num_views, const float* extrinsics, const float* intrins
 
 /* Backward of gsr_setup_views (scale_invariant as the records say): dL_dviews (V, 48) - the camera-record gradient gsr_backward_ex
  * returns, laid out like GsrView - carried to dL_dextrinsics (V, 4, 4) in closed form (view = (E'^-1)^T, full = view P^T,
- * campos = E'[:3, 3]; fp64 inside), one launch.  Intrinsics, near, far receive nothing.  This is the path by which the one camera
+ * campos = E'[:3, 3]; fp64 inside), one launch.  Intrinsics, near, far receive nothing here (intrinsics: the _ex call below).  This is the path by which the one camera
  * gradient of the reference's training graph - the depth render's extrinsics.inverse(), cuda_splatting.py:239-242 - reaches
  * `extrinsics` without a torch op. */
 int gsr_setup_views_backward(int num_views, const GsrView* views, const float* dL_dviews, float* dL_dextrinsics, void* stream);
+
+/* The same with the intrinsics' share, one launch, one thread per view, fp64 inside.  dL_dextrinsics (V, 4, 4), nullable: exactly
+ * what gsr_setup_views_backward writes.  dL_dintrinsics (V, 3, 3), nullable, fully written: the cotangent of tanfovx is
+ *   dL_dviews[35] + dL/dP[0][0] * (-1 / tanfovx^2),   dL/dP[0][0] = sum_i dL_dviews[16 + 4 i] * viewmatrix[4 i]
+ * (its direct slot - GSR_FLAG_FOV_GRADIENT fills it - plus what the projection block says about P[0][0] = 1 / tanfovx), the y
+ * component likewise with [36], P[1][1] and the indices + 1; both go back through tanf(0.5 acosf(l . r)), the normalised
+ * edge-midpoint rays K^-1 (x, y, 1) of get_fov and K^-1 to `intrinsics` (V, 3, 3), the array gsr_setup_views took, all recomputed from
+ * it in fp64.  Near, far, background and scale still receive nothing.  GSR_ERR_INVALID_ARGUMENT on a negative count or a NULL
+ * views / intrinsics / dL_dviews; nothing is launched for a count of 0. */
+int gsr_setup_views_backward_ex(int num_views, const GsrView* views, const float* intrinsics, const float* dL_dviews,
+                                float* dL_dextrinsics, float* dL_dintrinsics, void* stream);
 
 /* The same for the reference's fake orthographic camera (render_cuda_orthographic, cuda_splatting.py:153-181): per view the
  * extent (width, height) of the orthographic window in world units; the camera is moved back along its own -z by

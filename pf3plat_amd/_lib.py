@@ -28,6 +28,7 @@ FLAG_BACKWARD_FOLLOWS = 0x10000  # forward zero-fills the backward's accumulator
 FLAG_FULL_LISTS = 0x20000  # test aid: every per-tile list depth-ordered to its end (default: the nearest ~512 entries + what the blend walks)
 FLAG_SH_IN_FRAME = 0x40000  # harmonics in the coordinates of their group's frame (scale / rotation form with frames only)
 FLAG_SH_FRAME_E3NN = 0x80000  # ... in the reference's e3nn convention (only together with FLAG_SH_IN_FRAME)
+FLAG_FOV_GRADIENT = 0x200000  # the camera gradient of gsr_backward_ex also fills dL/dtanfovx, dL/dtanfovy (floats 35, 36 of a record's row)
 FLAG_WINDOWED_BINNING = 0x4000  # test aid: the windowed binning path on an image small enough for the fused one
 
 # (-falign-functions=4096: every kernel starts on a page of its own.  Without it the layout of one kernel's hot loop in the instruction
@@ -275,6 +276,8 @@ def load():
     lib.gsr_setup_views.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]
     lib.gsr_setup_views_backward.restype = ctypes.c_int
     lib.gsr_setup_views_backward.argtypes = [ctypes.c_int, vp, vp, vp, vp]
+    lib.gsr_setup_views_backward_ex.restype = ctypes.c_int
+    lib.gsr_setup_views_backward_ex.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, vp]
     lib.gsr_setup_views_orthographic.restype = ctypes.c_int
     lib.gsr_setup_views_orthographic.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_float, vp, vp, vp]
     adapt_head = [ctypes.c_int] * 3 + [vp] * 5 + [ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_float]
@@ -296,7 +299,7 @@ EXPORTED_SYMBOLS = (
     "gsr_capacity_for", "gsr_cov_from_scale_rot", "gsr_cov_from_scale_rot_backward", "gsr_last_failed_stage",
     "gsr_colour_in_binning", "gsr_geom_layout", "gsr_backward_ex", "gsr_pose_partials_bytes", "gsr_backward_scratch_bytes", "gsr_setup_views_orthographic",
     "gsr_image_loss", "gsr_image_loss_partials", "gsr_image_loss_finish", "gsr_pack_view", "gsr_setup_views_backward",
-    "gsr_adapt", "gsr_adapt_backward", "gsr_adapt_partials_bytes",
+    "gsr_adapt", "gsr_adapt_backward", "gsr_adapt_partials_bytes", "gsr_setup_views_backward_ex",
 )
 # The stages of GsrForwardOptions.stage_ms / GsrBackwardOptions.stage_ms as run_forward / run_backward(profile=True) key them (the
 # names a failed debug-mode stage is reported with are the library's: gsr_stage_name).  On images of up to 20 480 tiles (the fused binning path) "preprocess" is the whole binning

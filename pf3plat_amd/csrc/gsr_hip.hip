@@ -3472,11 +3472,15 @@ constexpr int kPoseFloats = 35;  // dL/d viewmatrix (16), projmatrix (16), campo
 // themselves are then not read here at all - 300 B per Gaussian less of the kernel's ~750.
 // kPose: 0 no camera gradient; 1 all of it (35 floats per view); 2 only what the built-in depth channel contributes - the four
 // entries 2, 6, 10, 14 of the view matrix that form z: the ONE camera gradient the reference's own graph carries (its depth render
-// reads extrinsics.inverse() in torch, cuda_splatting.py:239-242; nothing reaches a camera through the rasterizer)
+// reads extrinsics.inverse() in torch, cuda_splatting.py:239-242; nothing reaches a camera through the rasterizer);
+// 3 all of it and the two tan-fov columns (below)
 // kShFrame: GSR_FLAG_SH_IN_FRAME - dL/dsh is evaluated at the direction carried into the Gaussian's frame, and the direction
 // gradient of the recomputing form goes back to world coordinates before the chain into dL/dmeans and dL/dcampos (the saved
 // Jacobian of the kJ form is in world coordinates already: color_eval_lane).  The flag-off instances are the code as it was.
 constexpr int kPoseZFloats = 4;
+// kPose == 3 (GSR_FLAG_FOV_GRADIENT): everything kPose == 1 does, and dL/dtanfovx, dL/dtanfovy behind the 35 - what the EWA Jacobian
+// reads of the two fields (fx, fy and the 1.3 tanfov clamp limit); rows of 37 floats, summed by k_pose_reduce<37>.
+constexpr int kPoseFovFloats = kPoseFloats + 2;
 // The kernel's text is csrc/preprocess_bwd.inc, compiled twice: k_preprocess_bwd, and k_preprocess_bwd_det for GSR_FLAG_DETERMINISTIC.
 #define GSR_PBWD_KERNEL k_preprocess_bwd
 #define GSR_PBWD_UNIT 0
@@ -3490,33 +3494,36 @@ constexpr int kPoseZFloats = 4;
 #undef GSR_PBWD_UNIT
 
 // Sum of camera-gradient rows, two levels, fixed order (deterministic).  Block (v, b) adds rows [b * per, (b + 1) * per) of view
-// v: 245 threads = 7 rows x 35 columns per step, so a step reads 980 consecutive bytes.  Level 1: the rows k_preprocess_bwd
-// wrote -> kPoseBlocks rows per view; level 2 (one block per view): those -> the (V, 48) output record (zeros behind [35]).
+// v: with kCols = 35, 245 threads = 7 rows x 35 columns per step, so a step reads 980 consecutive bytes; with kCols = 37 (the rows
+// with the tan-fov columns) 222 threads = 6 rows x 37.  Level 1: the rows k_preprocess_bwd wrote -> kPoseBlocks rows per view;
+// level 2 (one block per view): those -> the (V, 48) output record (zeros behind [kCols]).
 constexpr int kPoseBlocks = 256;
+template <int kCols>
 __global__ __launch_bounds__(256) void k_pose_reduce(const float* in, int rows, float* out, int out_stride, int out_rows) {
-  __shared__ float part[7][kPoseFloats];
+  constexpr int kRows = 256 / kCols;  // rows a step covers
+  __shared__ float part[kRows][kCols];
   const int v = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   const int per = (rows + (int)gridDim.y - 1) / (int)gridDim.y;
   const int r_begin = b * per, r_end = min(rows, r_begin + per);
-  const int k = tid % kPoseFloats, r0 = tid / kPoseFloats;
-  const float* base = in + (size_t)v * rows * kPoseFloats;
+  const int k = tid % kCols, r0 = tid / kCols;
+  const float* base = in + (size_t)v * rows * kCols;
   float acc = 0.f;
-  if (r0 < 7) {
+  if (r0 < kRows) {
     int r = r_begin + r0;
-    for (; r + 21 < r_end; r += 28) {  // four independent loads in flight, added in a fixed order
-      const float a0 = base[(size_t)r * kPoseFloats + k], a1 = base[(size_t)(r + 7) * kPoseFloats + k];
-      const float a2 = base[(size_t)(r + 14) * kPoseFloats + k], a3 = base[(size_t)(r + 21) * kPoseFloats + k];
+    for (; r + 3 * kRows < r_end; r += 4 * kRows) {  // four independent loads in flight, added in a fixed order
+      const float a0 = base[(size_t)r * kCols + k], a1 = base[(size_t)(r + kRows) * kCols + k];
+      const float a2 = base[(size_t)(r + 2 * kRows) * kCols + k], a3 = base[(size_t)(r + 3 * kRows) * kCols + k];
       acc += a0; acc += a1; acc += a2; acc += a3;
     }
-    for (; r < r_end; r += 7) acc += base[(size_t)r * kPoseFloats + k];
+    for (; r < r_end; r += kRows) acc += base[(size_t)r * kCols + k];
     part[r0][k] = acc;
   }
   __syncthreads();
   float* dst = out + ((size_t)v * out_rows + b) * out_stride;
   if (tid < out_stride) {
     float sum = 0.f;
-    if (tid < kPoseFloats)
-      for (int j = 0; j < 7; ++j) sum += part[j][tid];
+    if (tid < kCols)
+      for (int j = 0; j < kRows; ++j) sum += part[j][tid];
     dst[tid] = sum;
   }
 }
@@ -3677,7 +3684,7 @@ __global__ void k_setup_views_ortho(int V, const float* ext, const float* width,
 // d projmatrix [16, 32), d campos [32, 35)) carried to the (V, 4, 4) camera-to-world extrinsics, one thread per view, in fp64:
 //   view = (E'^-1)^T,  full = view P^T,  campos = E'[:3, 3]   with E' = E, translation times s (the scale-invariant factor)
 //   => dL/dview += dL/dfull P;  dL/dE' = -(E'^-1)^T (dL/d(E'^-1)) (E'^-1)^T;  translation column += dL/dcampos, then times s.
-// Intrinsics, near and far get nothing (the operator treats the fields of view as constants).  What the Python layer used to do
+// Intrinsics, near and far get nothing here (the intrinsics' share: k_setup_views_bwd_ex below).  What the Python layer used to do
 // with a dozen fp64 torch launches per backward (190 us of device time for three cameras) is one ~3 us launch.
 __global__ void k_setup_views_bwd(int V, const GsrView* views, const float* d_views, float* d_ext) {
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
@@ -3731,6 +3738,127 @@ __global__ void k_setup_views_bwd(int V, const GsrView* views, const float* d_vi
       a = -a;
       if (j == 3 && i < 3) a = (a + (double)g[32 + i]) * s;
       o[4 * i + j] = (float)a;
+    }
+}
+
+// The body of k_setup_views_bwd once more, for k_setup_views_bwd_ex: the same expressions in the same order, hence the same bits.  (The
+// kernel above keeps its own text: called through a shared function it compiled to other instructions - commuted operands.)
+__device__ __forceinline__ void setup_views_bwd_ext(const GsrView& c, const float* g, float* o) {
+  const double s = c.scale, nr = (double)c.reserved[0] * s, fr = (double)c.reserved[1] * s;
+  double P[16] = {0};  // the projection matrix of finish_view (row-major)
+  P[0] = 1.0 / c.tanfovx; P[5] = 1.0 / c.tanfovy; P[14] = 1.0;
+  P[10] = fr / (fr - nr); P[11] = -(fr * nr) / (fr - nr);
+  // A = E'^-1 (world -> camera); the record holds A^T:  A[i][j] = viewmatrix[4 j + i]
+  double A[16], dV[16], dA[16];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) A[4 * i + j] = c.viewmatrix[4 * j + i];
+  // dL/dview = dL/dviewmatrix + dL/dprojmatrix P   (full = view P^T, both stored transposed)
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      double a = g[4 * i + j];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) a += (double)g[16 + 4 * i + k] * P[4 * k + j];
+      dV[4 * i + j] = a;
+    }
+  // view = A^T  =>  dL/dA = (dL/dview)^T
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) dA[4 * i + j] = dV[4 * j + i];
+  // A = E'^-1  =>  dL/dE' = -A^T dA A^T
+  double T[16];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      double a = 0.0;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) a += A[4 * k + i] * dA[4 * k + j];  // (A^T dA)[i][j]
+      T[4 * i + j] = a;
+    }
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      double a = 0.0;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) a += T[4 * i + k] * A[4 * j + k];  // (T A^T)[i][j]
+      a = -a;
+      if (j == 3 && i < 3) a = (a + (double)g[32 + i]) * s;
+      o[4 * i + j] = (float)a;
+    }
+}
+
+// gsr_setup_views_backward_ex: the same (d_ext, nullable) and the intrinsics' share (d_intr, nullable) in one launch, one thread per
+// view, fp64.  The two tangents of k_setup_views, tx = tan(acos(l . r) / 2) over the normalised edge-midpoint rays K^-1 (x, y, 1),
+// receive  g[35] + dL/dP[0][0] (-1 / tx^2)  and  g[36] + dL/dP[1][1] (-1 / ty^2):  their own slots (GSR_FLAG_FOV_GRADIENT) and what
+// the projection block sends through P[0][0] = 1 / tx, P[1][1] = 1 / ty (full = view P^T => dL/dP[a][a] = sum_i g[16 + 4 i + a]
+// view[4 i + a]).  Back through tan, acos, the two normalisations and K^-1 (dL/dK = -K^-T dL/dK^-1 K^-T), everything recomputed from
+// the intrinsics in fp64.  Near, far, background and scale get nothing.
+__global__ void k_setup_views_bwd_ex(int V, const GsrView* views, const float* intr, const float* d_views, float* d_ext, float* d_intr) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= V) return;
+  const GsrView& c = views[v];
+  const float* g = d_views + (size_t)v * 48;
+  if (d_ext) setup_views_bwd_ext(c, g, d_ext + (size_t)v * 16);
+  if (!d_intr) return;
+  double K[9], Ki[9];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) K[i] = intr[9 * v + i];
+  {
+    const double c00 = K[4] * K[8] - K[5] * K[7], c01 = K[5] * K[6] - K[3] * K[8], c02 = K[3] * K[7] - K[4] * K[6];
+    const double id = 1.0 / (K[0] * c00 + K[1] * c01 + K[2] * c02);
+    Ki[0] = c00 * id; Ki[1] = (K[2] * K[7] - K[1] * K[8]) * id; Ki[2] = (K[1] * K[5] - K[2] * K[4]) * id;
+    Ki[3] = c01 * id; Ki[4] = (K[0] * K[8] - K[2] * K[6]) * id; Ki[5] = (K[2] * K[3] - K[0] * K[5]) * id;
+    Ki[6] = c02 * id; Ki[7] = (K[1] * K[6] - K[0] * K[7]) * id; Ki[8] = (K[0] * K[4] - K[1] * K[3]) * id;
+  }
+  double dKi[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  // one field of view: the rays through (x0, y0) and (x1, y1), its slot gslot and dL/dP[a][a]
+  auto edge = [&](double x0, double y0, double x1, double y1, double gslot, double dP) {
+    const double p0[3] = {x0, y0, 1.0}, p1[3] = {x1, y1, 1.0};
+    double a0[3], a1[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      a0[i] = Ki[3 * i] * p0[0] + Ki[3 * i + 1] * p0[1] + Ki[3 * i + 2];
+      a1[i] = Ki[3 * i] * p1[0] + Ki[3 * i + 1] * p1[1] + Ki[3 * i + 2];
+    }
+    const double n0 = sqrt(a0[0] * a0[0] + a0[1] * a0[1] + a0[2] * a0[2]), n1 = sqrt(a1[0] * a1[0] + a1[1] * a1[1] + a1[2] * a1[2]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { a0[i] /= n0; a1[i] /= n1; }
+    const double cs = a0[0] * a1[0] + a0[1] * a1[1] + a0[2] * a1[2];
+    const double t = tan(0.5 * acos(cs));
+    const double gt = gslot + dP * (-1.0 / (t * t));
+    const double gc = gt * (-0.5 * (1.0 + t * t) / sqrt(1.0 - cs * cs));  // d tan(acos(c) / 2) / dc
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {  // through the normalisations: d(u / |u|) = (I - a a^T) / |u|
+      const double du0 = gc * (a1[i] - a0[i] * cs) / n0, du1 = gc * (a0[i] - a1[i] * cs) / n1;
+#pragma unroll
+      for (int j = 0; j < 3; ++j) dKi[3 * i + j] += du0 * p0[j] + du1 * p1[j];
+    }
+  };
+  double dP[2] = {0.0, 0.0};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    dP[0] += (double)g[16 + 4 * i] * (double)c.viewmatrix[4 * i];
+    dP[1] += (double)g[16 + 4 * i + 1] * (double)c.viewmatrix[4 * i + 1];
+  }
+  edge(0.0, 0.5, 1.0, 0.5, (double)g[35], dP[0]);
+  edge(0.5, 0.0, 0.5, 1.0, (double)g[36], dP[1]);
+  float* o = d_intr + (size_t)v * 9;
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {  // dL/dK = -Ki^T dKi Ki^T
+      double a = 0.0;
+#pragma unroll
+      for (int p = 0; p < 3; ++p)
+#pragma unroll
+        for (int q = 0; q < 3; ++q) a += Ki[3 * p + i] * dKi[3 * p + q] * Ki[3 * j + q];
+      o[3 * i + j] = (float)-a;
     }
 }
 
@@ -4291,11 +4419,16 @@ static int backward_impl(const GsrDims* dims, const GsrView* views, const float*
   } else if (dL_dviews) {
     if (!pose_partials) return GSR_ERR_INVALID_ARGUMENT;
     p.pose_partials = pose_partials;
-    launch_pbwd(std::integral_constant<int, 1>{});
     const int rows1 = (int)pgrid.x * 4;
-    float* level1 = pose_partials + (size_t)V * rows1 * kPoseFloats;  // behind the rows of the first level
-    hipLaunchKernelGGL(k_pose_reduce, dim3((unsigned)V, kPoseBlocks), dim3(256), 0, st, pose_partials, rows1, level1, kPoseFloats, kPoseBlocks);
-    hipLaunchKernelGGL(k_pose_reduce, dim3((unsigned)V, 1), dim3(256), 0, st, level1, kPoseBlocks, dL_dviews, 48, 1);
+    auto full = [&](auto pose, auto cols) {  // the rows of `cols` floats, then their two-level sum (level 1 behind the rows)
+      constexpr int kCols = decltype(cols)::value;
+      launch_pbwd(pose);
+      float* level1 = pose_partials + (size_t)V * rows1 * kCols;
+      hipLaunchKernelGGL(k_pose_reduce<kCols>, dim3((unsigned)V, kPoseBlocks), dim3(256), 0, st, pose_partials, rows1, level1, kCols, kPoseBlocks);
+      hipLaunchKernelGGL(k_pose_reduce<kCols>, dim3((unsigned)V, 1), dim3(256), 0, st, level1, kPoseBlocks, dL_dviews, 48, 1);
+    };
+    if (d.flags & GSR_FLAG_FOV_GRADIENT) full(std::integral_constant<int, 3>{}, std::integral_constant<int, kPoseFovFloats>{});  // (pose_partials: 37-float rows)
+    else full(std::integral_constant<int, 1>{}, std::integral_constant<int, kPoseFloats>{});
   } else {
     launch_pbwd(std::integral_constant<int, 0>{});
   }
@@ -4307,7 +4440,8 @@ static int backward_impl(const GsrDims* dims, const GsrView* views, const float*
 
 size_t gsr_pose_partials_bytes(const GsrDims* dims) {
   if (!dims_ok(dims)) return 0;
-  return (size_t)dims->num_views * ((size_t)((dims->num_gaussians + 63) / 64) * 4 + kPoseBlocks) * kPoseFloats * sizeof(float);
+  const int cols = (dims->flags & GSR_FLAG_FOV_GRADIENT) ? kPoseFovFloats : kPoseFloats;
+  return (size_t)dims->num_views * ((size_t)((dims->num_gaussians + 63) / 64) * 4 + kPoseBlocks) * cols * sizeof(float);
 }
 
 int gsr_backward_ex(const GsrDims* dims, const GsrView* views, const float* means, const float* cov, const float* opacities,
@@ -4351,6 +4485,17 @@ int gsr_setup_views_backward(int num_views, const GsrView* views, const float* d
   if (!views || !dL_dviews || !dL_dextrinsics) return GSR_ERR_INVALID_ARGUMENT;
   hipLaunchKernelGGL(k_setup_views_bwd, dim3((unsigned)((num_views + 63) / 64)), dim3(64), 0, static_cast<hipStream_t>(stream_),
                      num_views, views, dL_dviews, dL_dextrinsics);
+  GSR_CHECK(hipGetLastError());
+  return GSR_OK;
+}
+
+int gsr_setup_views_backward_ex(int num_views, const GsrView* views, const float* intrinsics, const float* dL_dviews, float* dL_dextrinsics,
+                                float* dL_dintrinsics, void* stream_) {
+  if (num_views < 0) return GSR_ERR_INVALID_ARGUMENT;
+  if (num_views == 0) return GSR_OK;
+  if (!views || !intrinsics || !dL_dviews) return GSR_ERR_INVALID_ARGUMENT;
+  hipLaunchKernelGGL(k_setup_views_bwd_ex, dim3((unsigned)((num_views + 63) / 64)), dim3(64), 0, static_cast<hipStream_t>(stream_),
+                     num_views, views, intrinsics, dL_dviews, dL_dextrinsics, dL_dintrinsics);
   GSR_CHECK(hipGetLastError());
   return GSR_OK;
 }

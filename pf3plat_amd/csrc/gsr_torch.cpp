@@ -54,6 +54,7 @@ struct Abi {
   decltype(&gsr_pack_view) pack_view = nullptr;
   decltype(&gsr_setup_views) setup_views = nullptr;
   decltype(&gsr_setup_views_backward) setup_views_backward = nullptr;
+  decltype(&gsr_setup_views_backward_ex) setup_views_backward_ex = nullptr;
   decltype(&gsr_setup_views_orthographic) setup_views_orthographic = nullptr;
   decltype(&gsr_mark_visible) mark_visible = nullptr;
   decltype(&gsr_cov_from_scale_rot) cov_from_scale_rot = nullptr;
@@ -85,6 +86,7 @@ void init(const std::string& path) {
   resolve(g_abi.pack_view, "gsr_pack_view");
   resolve(g_abi.setup_views, "gsr_setup_views");
   resolve(g_abi.setup_views_backward, "gsr_setup_views_backward");
+  resolve(g_abi.setup_views_backward_ex, "gsr_setup_views_backward_ex");
   resolve(g_abi.setup_views_orthographic, "gsr_setup_views_orthographic");
   resolve(g_abi.mark_visible, "gsr_mark_visible");
   resolve(g_abi.cov_from_scale_rot, "gsr_cov_from_scale_rot");
@@ -457,7 +459,8 @@ class Backend : public std::enable_shared_from_this<Backend> {
       GsrBackwardOptions opt = launch_options<GsrBackwardOptions>(cfg, fr, g_alpha);
       Tensor partials;
       if (want_views) {
-        GsrDims sizing_dims = saved.dims;  // (the helpers take no GSR_FLAG_SH_IN_FRAME bits; they change no size)
+        // (the helpers take no GSR_FLAG_SH_IN_FRAME bits; they change no size.  GSR_FLAG_FOV_GRADIENT stays: it widens the rows)
+        GsrDims sizing_dims = saved.dims;
         sizing_dims.flags &= ~Cfg::kShFrameBits;
         partials = at::empty({(int64_t)std::max<size_t>(16, g_abi.pose_partials_bytes(&sizing_dims))}, f32.dtype(at::kByte));
         opt.dL_dviews = d_views.data_ptr<float>(); opt.pose_partials = reinterpret_cast<float*>(partials.data_ptr()); opt.depth_term_only = want_views == 2;
@@ -720,7 +723,9 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
     ws.token = ctx->saved_data["token"].toInt();
     auto holder = c10::static_intrusive_pointer_cast<BackendHolder>(ctx->saved_data["holder"].toCapsule());
     const bool cam = ctx->needs_input_grad((size_t)ctx->saved_data["viewbuf_edge"].toInt());  // cameras being learned (PF3plat's pose refinement): opt-in, SURVEY 8f-3
-    const int want_views = cam ? (ctx->saved_data["camera_gradient"].toInt() == 2 ? 2 : 1) : 0;
+    // (GSR_FLAG_FOV_GRADIENT in the call's flags - saved.dims carry it into the backward's launch and the partials' size - implies
+    // the full camera gradient: the depth term alone has no tan-fov columns)
+    const int want_views = cam ? ((ctx->saved_data["camera_gradient"].toInt() == 2 && !(cfg.flags & GSR_FLAG_FOV_GRADIENT)) ? 2 : 1) : 0;
     const c10::IValue& fr = ctx->saved_data["frames"];
     std::vector<Tensor> g = holder->be->backward(cfg, ws, viewbuf, means, cov, opac, colors, extra, g_color, g_extra, ctx->saved_data["want_means2d"].toBool(),
                                                  ctx->saved_data["rows_fresh"].toBool(), fr.isTensor() ? fr.toTensor() : Tensor(), want_views,
@@ -756,23 +761,53 @@ Tensor setup_views_backward(const Tensor& viewbuf, const Tensor& d_views) {
   return out;
 }
 
+// ... and with the intrinsics' share: (V, 3, 3) through get_fov's arithmetic (gsr_setup_views_backward_ex, one launch for both).
+// Either result is undefined where it is not wanted.
+std::tuple<Tensor, Tensor> setup_views_backward_ex(const Tensor& viewbuf, const Tensor& intrinsics, const Tensor& d_views, bool want_ext, bool want_intr) {
+  check_device({&viewbuf, &intrinsics, &d_views});
+  const Tensor vb = f32c(viewbuf), intr = f32c(intrinsics), dv = f32c(d_views);
+  TORCH_CHECK(intr.numel() == vb.size(0) * 9, "intrinsics must be (views, 3, 3)");
+  Tensor d_ext, d_intr;
+  if (want_ext) d_ext = at::empty({vb.size(0), 4, 4}, vb.options());
+  if (want_intr) d_intr = at::empty({vb.size(0), 3, 3}, vb.options());
+  c10::hip::HIPGuard guard(vb.device().index());
+  const int rc = g_abi.setup_views_backward_ex((int)vb.size(0), reinterpret_cast<const GsrView*>(vb.data_ptr<float>()), fptr(intr), fptr(dv), fptr_mut(d_ext),
+                                               fptr_mut(d_intr), stream_of(vb.device()));
+  if (rc != 0) throw std::runtime_error("gsr_setup_views_backward_ex failed with code " + std::to_string(rc));
+  return {d_ext, d_intr};
+}
+
 struct SetupViewsFn : public torch::autograd::Function<SetupViewsFn> {
   static Tensor forward(torch::autograd::AutogradContext* ctx, Tensor extrinsics, Tensor intrinsics, Tensor near, Tensor far, Tensor background, bool scale_invariant) {
     Tensor vb = setup_views_raw(extrinsics, intrinsics, near, far, background, scale_invariant);
-    ctx->save_for_backward({vb});
+    ctx->save_for_backward({vb, intrinsics});
     ctx->saved_data["dtype"] = (int64_t)extrinsics.scalar_type();
+    ctx->saved_data["intr_dtype"] = (int64_t)intrinsics.scalar_type();
     return vb;
   }
   static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx, torch::autograd::variable_list grads) {
-    const Tensor out = setup_views_backward(ctx->get_saved_variables()[0], grads[0]);
-    return {out.to((at::ScalarType)ctx->saved_data["dtype"].toInt()), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+    const auto saved = ctx->get_saved_variables();
+    const bool want_ext = ctx->needs_input_grad(0), want_intr = ctx->needs_input_grad(1);
+    Tensor d_ext, d_intr;
+    if (want_intr) {
+      std::tie(d_ext, d_intr) = setup_views_backward_ex(saved[0], saved[1], grads[0], want_ext, true);
+      d_intr = d_intr.to((at::ScalarType)ctx->saved_data["intr_dtype"].toInt()).reshape(saved[1].sizes());
+    } else if (want_ext) {
+      d_ext = setup_views_backward(saved[0], grads[0]);
+    }
+    if (d_ext.defined()) d_ext = d_ext.to((at::ScalarType)ctx->saved_data["dtype"].toInt());
+    return {d_ext, d_intr, Tensor(), Tensor(), Tensor(), Tensor()};
   }
 };
 
+// pose_gradients / intrinsics_gradients: which of the two camera inputs keeps a gradient path (each only if it requires one; the
+// other goes in detached)
 Tensor views_from_cameras(const Tensor& extrinsics, const Tensor& intrinsics, const Tensor& near, const Tensor& far, const Tensor& background, bool scale_invariant,
-                          bool pose_gradients) {
-  if (pose_gradients && at::GradMode::is_enabled() && extrinsics.requires_grad())
-    return SetupViewsFn::apply(extrinsics, intrinsics, near, far, background, scale_invariant);
+                          bool pose_gradients, bool intrinsics_gradients) {
+  const bool grad = at::GradMode::is_enabled();
+  const bool ext = pose_gradients && grad && extrinsics.requires_grad(), intr = intrinsics_gradients && grad && intrinsics.requires_grad();
+  if (ext || intr)
+    return SetupViewsFn::apply(ext ? extrinsics : extrinsics.detach(), intr ? intrinsics : intrinsics.detach(), near, far, background, scale_invariant);
   at::NoGradGuard ng;
   return setup_views_raw(extrinsics, intrinsics, near, far, background, scale_invariant);
 }
@@ -1045,13 +1080,15 @@ pybind11::tuple rasterize_views(PyBackend& pb, const Tensor& means_in, const Ten
                                 int64_t h, int64_t w, int64_t sh_degree, bool use_sh, int64_t views_per_set, const c10::optional<Tensor>& extra_in,
                                 const c10::optional<Tensor>& means2d, int64_t max_sh_eval, bool sh_planar, bool cov_3x3, int64_t extra_mode, bool debug,
                                 bool prefiltered, int64_t deterministic, bool scale_rot, const c10::optional<Tensor>& frames_in, int64_t camera_gradient,
-                                int64_t sh_frame, bool return_alpha) {
+                                int64_t sh_frame, bool return_alpha, bool intrinsics_gradients) {
   RasterOut result;
   {
   pybind11::gil_scoped_release nogil;
   Prepared p = prepare_call(means_in, cov_in, opac_in, colors_in, viewbuf_in, h, w, sh_degree, use_sh, views_per_set, extra_in, means2d, max_sh_eval, sh_planar,
                                   cov_3x3, extra_mode, debug, prefiltered, deterministic, scale_rot, frames_in, camera_gradient, sh_frame);
   p.cfgv[12] = return_alpha;  // (Cfg::alpha)
+  // the tan-fov columns of the camera gradient (GSR_FLAG_FOV_GRADIENT): only where a backward will ask for the camera gradient at all
+  if (intrinsics_gradients && (p.cfgv[10] & GSR_FLAG_BACKWARD_FOLLOWS) && viewbuf_in.requires_grad()) p.cfgv[10] |= GSR_FLAG_FOV_GRADIENT;
   result = rasterize_impl(pb, p.means, p.cov, p.opac, p.colors, p.extra, means2d, p.viewbuf, p.cfgv, p.frames, camera_gradient);
   }
   return raster_tuple(result);
@@ -1203,6 +1240,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("views_from_cameras", &views_from_cameras);
   m.def("setup_views", &setup_views_raw);
   m.def("setup_views_backward", &setup_views_backward);
+  m.def("setup_views_backward_ex", [](const Tensor& viewbuf, const Tensor& intrinsics, const Tensor& d_views, bool want_ext, bool want_intr) {
+    const auto r = setup_views_backward_ex(viewbuf, intrinsics, d_views, want_ext, want_intr);
+    return pybind11::make_tuple(or_none(std::get<0>(r)), or_none(std::get<1>(r)));
+  });
   m.def("setup_views_orthographic", &setup_views_orthographic);
   m.def("mark_visible", [](const std::vector<int64_t>& cfgv, const Tensor& viewbuf, const Tensor& means) { return mark_visible(cfg_from(cfgv), viewbuf, means); });
   m.def("adapt", &adapt, "Gaussian adapter, one launch each way: (means (G, P, 3), scale + quaternion records (G, P, 7), masked harmonics (G, P, 3, M))");

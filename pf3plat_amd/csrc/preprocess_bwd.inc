@@ -5,6 +5,8 @@
 // (a shared __device__ body was tried first: inlined into the kernel it did not compile to the instructions of the kernel it came from)
 template <int kPose, bool kJ, bool kShFrame = false>
 __global__ __launch_bounds__(64) void GSR_PBWD_KERNEL(const Params p) {
+  constexpr bool kCam = kPose == 1 || kPose == 3;                 // the whole camera gradient (kPose == 3: with the two tan-fov columns)
+  constexpr int kRow = kPose == 3 ? kPoseFovFloats : kPoseFloats;  // floats of a partial row
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int lane = threadIdx.x, set = blockIdx.y;
   const int N = p.d.num_gaussians, Vs = p.d.views_per_set;
@@ -124,11 +126,11 @@ __global__ __launch_bounds__(64) void GSR_PBWD_KERNEL(const Params p) {
     // Camera gradients (SURVEY 8f-3, opt-in): what this (view, Gaussian) contributes to dL/d viewmatrix [0..16), projmatrix
     // [16..32) and campos [32..35) - every place the forward reads them: t = V p and M = J Wr in the EWA covariance, the
     // projection p_hom = F p, the view direction of the harmonics, the depth of the built-in extra channel.  Summed over
-    // the wave below, one partial row per (view, workgroup); k_pose_reduce adds the rows up.
-    float pose[kPose == 1 ? kPoseFloats : kPoseZFloats];
+    // the wave below, one partial row per (view, workgroup); k_pose_reduce adds the rows up.  kPose == 3: tanfovx, tanfovy too [35, 37).
+    float pose[kCam ? kRow : kPoseZFloats];
     if (kPose) {
 #pragma unroll
-      for (int k = 0; k < (kPose == 1 ? kPoseFloats : kPoseZFloats); ++k) pose[k] = 0.f;
+      for (int k = 0; k < (kCam ? kRow : kPoseZFloats); ++k) pose[k] = 0.f;
     }
     if (vis) {
     seen = true;
@@ -181,7 +183,7 @@ __global__ __launch_bounds__(64) void GSR_PBWD_KERNEL(const Params p) {
     float dm[3];
 #pragma unroll
     for (int j = 0; j < 3; ++j) dm[j] = vw[4 * j + 0] * dtx + vw[4 * j + 1] * dty + vw[4 * j + 2] * dtz;
-    if (kPose == 1) {
+    if (kCam) {
       const float mj[4] = {mx, my, mz, 1.f}, dt[3] = {dtx, dty, dtz};
 #pragma unroll
       for (int j = 0; j < 4; ++j)
@@ -195,6 +197,14 @@ __global__ __launch_bounds__(64) void GSR_PBWD_KERNEL(const Params p) {
         pose[4 * j + 2] += dM[j] * J02 + dM[3 + j] * J12;
       }
     }
+    if (kPose == 3) {  // tan-fov (GSR_FLAG_FOV_GRADIENT): fx = W / (2 tanfovx) in J00 and J02, and the limit 1.3 tanfovx a clamped t0 sits on
+      const float gfx = dJ00 * tz - dJ02 * c2.t0 * tz2, gfy = dJ11 * tz - dJ12 * c2.t1 * tz2;  // dL/dfx, dL/dfy at the clamped t
+      float gx = gfx * (-c2.fx / cam.tanfovx), gy = gfy * (-c2.fy / cam.tanfovy);
+      // clamped: t0 = +-1.3 tanfovx t2, the sign that of t0 / t2;  J02 = -fx t0 / t2^2
+      if (c2.xcl) gx += (-c2.fx * tz2 * dJ02) * ((c2.t0 * tz < 0.f ? -1.3f : 1.3f) * c2.t2);
+      if (c2.ycl) gy += (-c2.fy * tz2 * dJ12) * ((c2.t1 * tz < 0.f ? -1.3f : 1.3f) * c2.t2);
+      pose[kPoseFloats] += gx; pose[kPoseFloats + 1] += gy;
+    }
     // --- projection
     const float* pr = cam.projmatrix;
     const float mh3 = pr[3] * mx + pr[7] * my + pr[11] * mz + pr[15];
@@ -204,7 +214,7 @@ __global__ __launch_bounds__(64) void GSR_PBWD_KERNEL(const Params p) {
     dm[0] += (pr[0] * m_w - pr[3] * mul1) * sg[0] + (pr[1] * m_w - pr[3] * mul2) * sg[1];
     dm[1] += (pr[4] * m_w - pr[7] * mul1) * sg[0] + (pr[5] * m_w - pr[7] * mul2) * sg[1];
     dm[2] += (pr[8] * m_w - pr[11] * mul1) * sg[0] + (pr[9] * m_w - pr[11] * mul2) * sg[1];
-    if (kPose == 1) {  // p_hom_k = sum_j F[4j + k] m_j;  ndc = p_hom.xy / (p_hom.w + eps)
+    if (kCam) {  // p_hom_k = sum_j F[4j + k] m_j;  ndc = p_hom.xy / (p_hom.w + eps)
       const float mj[4] = {mx, my, mz, 1.f};
       const float gk[4] = {sg[0] * m_w, sg[1] * m_w, 0.f, -(sg[0] * mul1 + sg[1] * mul2)};
 #pragma unroll
@@ -258,7 +268,7 @@ __global__ __launch_bounds__(64) void GSR_PBWD_KERNEL(const Params p) {
       const float gdir1 = (-ox * oy * ddx + (sum2 - oy * oy) * ddy - oz * oy * ddz) * invsum32;
       const float gdir2 = (-ox * oz * ddx - oy * oz * ddy + (sum2 - oz * oz) * ddz) * invsum32;
       dm[0] += gdir0; dm[1] += gdir1; dm[2] += gdir2;
-      if (kPose == 1) { pose[32] -= gdir0; pose[33] -= gdir1; pose[34] -= gdir2; }  // direction = mean - campos
+      if (kCam) { pose[32] -= gdir0; pose[33] -= gdir1; pose[34] -= gdir2; }  // direction = mean - campos
     } else {
       dcol[0] += sg[6]; dcol[1] += sg[7]; dcol[2] += sg[8];
     }
@@ -271,16 +281,16 @@ __global__ __launch_bounds__(64) void GSR_PBWD_KERNEL(const Params p) {
       (void)extra_from_depth(emode, z, cam.reserved[0], cam.reserved[1], dfdz);
       const float gz = sg[9] * dfdz;
       dmean[0] += gz * vw[2]; dmean[1] += gz * vw[6]; dmean[2] += gz * vw[10];
-      if (kPose == 1) { const float gs = gz / cam.scale; pose[2] += gs * mx; pose[6] += gs * my; pose[10] += gs * mz; pose[14] += gs; }
+      if (kCam) { const float gs = gz / cam.scale; pose[2] += gs * mx; pose[6] += gs * my; pose[10] += gs * mz; pose[14] += gs; }
       if (kPose == 2) { const float gs = gz / cam.scale; pose[0] += gs * mx; pose[1] += gs * my; pose[2] += gs * mz; pose[3] += gs; }
     }
 #pragma unroll
     for (int k = 0; k < 6; ++k) dcov[k] += dcv[k] * cam.scale2;
     }  // vis
-    if (kPose == 1) {  // sums over the four 16-lane DPP rows (4 DPP adds per value; a full wave sum costs 6 LDS permutes): 4 partial rows
-      float* row = p.pose_partials + (((size_t)v * gridDim.x + blockIdx.x) * 4 + (lane >> 4)) * kPoseFloats;
+    if (kCam) {  // sums over the four 16-lane DPP rows (4 DPP adds per value; a full wave sum costs 6 LDS permutes): 4 partial rows
+      float* row = p.pose_partials + (((size_t)v * gridDim.x + blockIdx.x) * 4 + (lane >> 4)) * kRow;
 #pragma unroll
-      for (int k = 0; k < kPoseFloats; ++k) {
+      for (int k = 0; k < kRow; ++k) {
         const float s = row_allreduce(pose[k]);
         if ((lane & 15) == 0) row[k] = s;
       }

@@ -73,13 +73,14 @@ class DecoderSplattingCUDA(Decoder):
         depth_mode: Optional[DepthRenderingMode] = None,
         pose_gradients: bool = False,  # extension: let the render's gradient reach `extrinsics`
         alpha: bool = False,  # extension: also return the accumulated opacity A = 1 - T_final (DecoderOutput.alpha), same pass
+        intrinsics_gradients: bool = False,  # extension: let the render's gradient reach `intrinsics` (when they require grad)
     ) -> DecoderOutput:
         color, depth, *acc = render_views(
             extrinsics, intrinsics, near, far, image_shape,
             self.background_color.to(extrinsics.device),
             gaussians.means, gaussians.covariances, gaussians.harmonics, gaussians.opacities,
             depth_mode=depth_mode, gaussian_scales=gaussians.scales, gaussian_rotations=gaussians.rotations, frames=gaussians.frames,
-            pose_gradients=pose_gradients, sh_frame=gaussians.sh_frame, alpha=alpha,
+            pose_gradients=pose_gradients, sh_frame=gaussians.sh_frame, alpha=alpha, intrinsics_gradients=intrinsics_gradients,
         )
         return DecoderOutput(color, depth, *acc)
 

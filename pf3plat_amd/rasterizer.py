@@ -221,7 +221,8 @@ class HipBackend:
     @staticmethod
     def _sizing_dims(dims: _lib.GsrDims) -> _lib.GsrDims:
         """A copy of launch dims without the GSR_FLAG_SH_IN_FRAME bits: what the sizing and layout helpers take (the bits size
-        nothing, and the helpers refuse them; a plan's dims and a forward's saved dims carry them)."""
+        nothing, and the helpers refuse them; a plan's dims and a forward's saved dims carry them).  GSR_FLAG_FOV_GRADIENT stays:
+        gsr_pose_partials_bytes sizes the wider rows from it."""
         d = _lib.GsrDims.from_buffer_copy(dims)
         d.flags &= ~(_lib.FLAG_SH_IN_FRAME | _lib.FLAG_SH_FRAME_E3NN)
         return d
@@ -338,7 +339,8 @@ class HipBackend:
         accumulated alpha, or None).  profile=True returns per-stage ms
         (synchronises), in the scale / rotation form and together with d_views too.
         d_views: a (V, 48) fp32 tensor that receives the camera gradients; depth_term_only: only what the built-in
-        depth channel sends to the camera (the z row of the view matrix), the gradient of the reference's graph."""
+        depth channel sends to the camera (the z row of the view matrix), the gradient of the reference's graph.  A plan whose
+        cfg.flags carry FLAG_FOV_GRADIENT also gets dL/dtanfovx, dL/dtanfovy in floats 35, 36 of the full camera gradient."""
         cfg = plan["cfg"]
         stream = _stream_ptr(plan["device"])
         fr, nf = self._ext.frames_arg(_cfg_vec(cfg), frames) if cfg.scale_rot else (None, 0)
@@ -346,10 +348,9 @@ class HipBackend:
         partials = None
         if d_views is not None:
             partials = plan.get("pose_partials")
-            if partials is None:
-                partials = plan["pose_partials"] = torch.empty(
-                    max(16, int(self.lib.gsr_pose_partials_bytes(ctypes.byref(self._sizing_dims(plan["dims"]))))), dtype=torch.uint8,
-                    device=plan["device"])
+            need = max(16, int(self.lib.gsr_pose_partials_bytes(ctypes.byref(self._sizing_dims(plan["dims"])))))
+            if partials is None or partials.numel() < need:  # (a plan whose dims gained FLAG_FOV_GRADIENT since: 37-float rows)
+                partials = plan["pose_partials"] = torch.empty(need, dtype=torch.uint8, device=plan["device"])
         opt = None  # (nothing asked for: NULL options, the plain call)
         if cfg.scale_rot or profile or d_views is not None or g_alpha_img is not None:
             opt = ctypes.byref(_lib.GsrBackwardOptions(_ptr(fr), nf, int(cfg.scale_rot), _ptr(d_views), _ptr(partials), ms,
@@ -430,6 +431,12 @@ class HipBackend:
     def setup_views_backward(self, viewbuf: Tensor, d_views: Tensor) -> Tensor:
         """(V, 48) camera records + their gradient -> dL/d extrinsics (V, 4, 4), one launch (gsr_setup_views_backward)."""
         return self._ext.setup_views_backward(viewbuf, d_views)
+
+    def setup_views_backward_ex(self, viewbuf: Tensor, intrinsics: Tensor, d_views: Tensor, want_extrinsics: bool = True,
+                                want_intrinsics: bool = True):
+        """(V, 48) camera records, the (V, 3, 3) intrinsics they were set up from and the records' gradient -> (dL/d extrinsics
+        (V, 4, 4) | None, dL/d intrinsics (V, 3, 3) | None), one launch (gsr_setup_views_backward_ex)."""
+        return self._ext.setup_views_backward_ex(viewbuf, intrinsics, d_views, bool(want_extrinsics), bool(want_intrinsics))
 
     def setup_views_orthographic(self, extrinsics, width, height, near, far, background, fov_degrees: float):
         """Cameras of the reference's fake orthographic render (cuda_splatting.py:153-181) in one launch
@@ -536,7 +543,8 @@ def rasterize_views(means: Tensor, cov6: Tensor, opacities: Tensor, colors: Tens
                     means2d: Optional[Tensor] = None, max_sh_eval: int = 4, sh_planar: bool = False, cov_3x3: bool = False,
                     extra_mode: Optional[str] = None, debug: bool = False, prefiltered: bool = False,
                     deterministic: Optional[bool] = None, scale_rot: bool = False, frames: Optional[Tensor] = None,
-                    camera_gradient: str = "full", sh_frame: Optional[str] = None, return_alpha: bool = False):
+                    camera_gradient: str = "full", sh_frame: Optional[str] = None, return_alpha: bool = False,
+                    intrinsics_gradients: bool = False):
     """Render V = num_sets * views_per_set views in one launch chain.
 
     means (S,N,3); cov6 (S,N,6) or, with cov_3x3, the full symmetric (S,N,3,3); opacities (S,N); colors (S,N,M,3) or, with
@@ -555,6 +563,9 @@ def rasterize_views(means: Tensor, cov6: Tensor, opacities: Tensor, colors: Tens
     camera_gradient (only matters when `viewbuf` requires grad, i.e. comes from `views_from_cameras(pose_gradients=True)`): "full" -
     every place the forward reads a camera (an extension); "depth" - only the built-in depth channel's term, which
     is what the reference's own graph sends to `extrinsics` (cuda_splatting.py:239-242).
+    intrinsics_gradients (opt-in, with a `viewbuf` from `views_from_cameras(intrinsics_gradients=True)`): the camera gradient also
+    carries dL/dtanfovx, dL/dtanfovy (GSR_FLAG_FOV_GRADIENT in the call's flags), which the set-up's backward takes to `intrinsics`;
+    it implies camera_gradient="full".
     sh_frame: "rasterizer" or "e3nn" - the harmonics of each group are in the coordinates of its frame (what the encoder's adapter
     produces before its SH rotation, reference gaussian_adapter.py:90-92); the image and every gradient are those of
     `sh_rotation.rotate_sh(harmonics, frame, basis=sh_frame)` rendered as usual, but the kernels evaluate the unrotated coefficients
@@ -579,9 +590,11 @@ def rasterize_views(means: Tensor, cov6: Tensor, opacities: Tensor, colors: Tens
             backend._c, means, cov6, opacities, colors, viewbuf, int(image_shape[0]), int(image_shape[1]), int(sh_degree), bool(use_sh),
             int(views_per_set), extra, means2d, int(max_sh_eval), bool(sh_planar), bool(cov_3x3), EXTRA_MODES[extra_mode] if extra_mode is not None else 0,
             bool(debug), bool(prefiltered), -1 if deterministic is None else int(bool(deterministic)), bool(scale_rot), frames,
-            2 if camera_gradient == "depth" else 1, sh_code, bool(return_alpha))
+            2 if camera_gradient == "depth" else 1, sh_code, bool(return_alpha), bool(intrinsics_gradients))
     if return_alpha:
         raise NotImplementedError("return_alpha needs the HIP backend")
+    if intrinsics_gradients:
+        raise NotImplementedError("intrinsics_gradients needs the HIP backend")
     # any other backend object (tests slide the CPU oracle under the host wrappers): the SAME statement of the call shape - the
     # compiled `prepare_call` (csrc/gsr_torch.cpp: checks, normalisation, flags; it touches no device) - then that backend's forward
     if camera_gradient not in ("full", "depth"):
@@ -609,7 +622,7 @@ class _SetupViews(torch.autograd.Function):
     is the library's one-launch set-up (gsr_setup_views); the backward carries the (V, 48) record gradient that
     `rasterize_views` returns through  view = inv(c2w')^T,  full = view P^T,  campos = c2w'[:3, 3]  (c2w' = c2w with its
     translation times 1 / near when scale_invariant) in closed form - a handful of 4x4 products per view.  Intrinsics, near
-    and far get no gradient (the operator itself treats the fields of view as constants)."""
+    and far get no gradient on this path (backends other than the HIP one; the compiled node also serves the intrinsics)."""
 
     @staticmethod
     def forward(ctx, extrinsics, intrinsics, near, far, background, scale_invariant: bool):
@@ -626,13 +639,19 @@ class _SetupViews(torch.autograd.Function):
 
 
 def views_from_cameras(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tensor, background: Tensor,
-                       scale_invariant: bool = True, pose_gradients: bool = False) -> Tensor:
+                       scale_invariant: bool = True, pose_gradients: bool = False, intrinsics_gradients: bool = False) -> Tensor:
     """(V,4,4) camera-to-world, (V,3,3) normalised intrinsics, (V,), (V,), (3,) | (V,3) -> (V,48) camera records in one launch
     (the arithmetic of cuda_splatting.py:64-71, :80-87).  pose_gradients: keep a gradient path from the render back to
-    `extrinsics` (the reference has none through its rasterizer: opt-in)."""
+    `extrinsics` (the reference has none through its rasterizer: opt-in).  intrinsics_gradients: likewise back to `intrinsics`
+    (learnable focal length / principal point), through get_fov's arithmetic: the projection block of the camera gradient and - when
+    the render is called with intrinsics_gradients=True too - its tan-fov columns.  Each input gets a gradient only if it
+    requires one; near and far get none."""
     backend = get_backend()
-    if isinstance(backend, HipBackend):  # (compiled: gsr_setup_views, and gsr_setup_views_backward as the node's backward)
-        return backend._ext.views_from_cameras(extrinsics, intrinsics, near, far, background, bool(scale_invariant), bool(pose_gradients))
+    if isinstance(backend, HipBackend):  # (compiled: gsr_setup_views, and gsr_setup_views_backward[_ex] as the node's backward)
+        return backend._ext.views_from_cameras(extrinsics, intrinsics, near, far, background, bool(scale_invariant), bool(pose_gradients),
+                                               bool(intrinsics_gradients))
+    if intrinsics_gradients:
+        raise NotImplementedError("intrinsics_gradients needs the HIP backend")
     if pose_gradients and torch.is_grad_enabled() and extrinsics.requires_grad:
         return _SetupViews.apply(extrinsics, intrinsics, near, far, background, bool(scale_invariant))
     with torch.no_grad():

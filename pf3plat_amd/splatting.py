@@ -24,12 +24,13 @@ from .rasterizer import get_backend, rasterize_views, views_from_cameras
 from .types import DepthRenderingMode
 
 
-def _viewbuf(extrinsics, intrinsics, near, far, background_color, scale_invariant: bool, pose_gradients: bool = False) -> Tensor:
+def _viewbuf(extrinsics, intrinsics, near, far, background_color, scale_invariant: bool, pose_gradients: bool = False,
+             intrinsics_gradients: bool = False) -> Tensor:
     """Camera records for `rasterize_views`: the arithmetic of the reference wrapper at cuda_splatting.py:64-71 / :80-87
     (1 / near rescale, get_fov, get_projection_matrix, extrinsics.inverse(), view @ proj) in ONE launch of the raster
     library (`gsr_setup_views`), straight into the records the kernels read.  Cameras carry no gradient (settings object)
-    unless pose_gradients asks for one."""
-    return views_from_cameras(extrinsics, intrinsics, near, far, background_color, scale_invariant, pose_gradients)
+    unless pose_gradients (to `extrinsics`) or intrinsics_gradients (to `intrinsics`) asks for one."""
+    return views_from_cameras(extrinsics, intrinsics, near, far, background_color, scale_invariant, pose_gradients, intrinsics_gradients)
 
 
 def depth_fake_color(extrinsics: Tensor, near: Tensor, far: Tensor, gaussian_means: Tensor, mode: DepthRenderingMode) -> Tensor:
@@ -93,9 +94,10 @@ def render_cuda(
     gaussian_opacities: Tensor,  # (batch, gaussian)
     scale_invariant: bool = True,
     use_sh: bool = True,
+    intrinsics_gradients: bool = False,  # opt-in: the render's gradient reaches `intrinsics` (the reference's does not)
 ) -> Tensor:  # (batch, 3, height, width)
     assert use_sh or gaussian_sh_coefficients.shape[-1] == 1
-    viewbuf = _viewbuf(extrinsics, intrinsics, near, far, background_color, scale_invariant)
+    viewbuf = _viewbuf(extrinsics, intrinsics, near, far, background_color, scale_invariant, False, intrinsics_gradients)
     _, _, _, n = gaussian_sh_coefficients.shape
     degree = isqrt(n) - 1
     # harmonics (b, g, 3, d_sh) and covariances (b, g, 3, 3) go to the operator as they are (no re-layout copies;
@@ -103,7 +105,8 @@ def render_cuda(
     colors = gaussian_sh_coefficients if use_sh else gaussian_sh_coefficients[:, :, :, 0]
     color, _, _ = rasterize_views(
         gaussian_means, gaussian_covariances, gaussian_opacities, colors, viewbuf,
-        image_shape=image_shape, sh_degree=degree, use_sh=use_sh, views_per_set=1, sh_planar=True, cov_3x3=True)
+        image_shape=image_shape, sh_degree=degree, use_sh=use_sh, views_per_set=1, sh_planar=True, cov_3x3=True,
+        intrinsics_gradients=intrinsics_gradients)
     return color
 
 
@@ -208,12 +211,16 @@ def render_views(
     pose_gradients: bool = False,  # opt-in: the render's gradient reaches `extrinsics` (the reference's does not)
     sh_frame: Optional[str] = None,  # "e3nn" | "rasterizer": the harmonics are in the coordinates of `frames` (rasterize_views)
     alpha: bool = False,  # also return the accumulated opacity A = 1 - T_final of every pixel (rasterize_views(return_alpha=True))
+    intrinsics_gradients: bool = False,  # opt-in: the render's gradient reaches `intrinsics` (focal lengths, principal point)
 ):
     """Fused decoder path: all views of all scenes in one launch chain, Gaussians read once per scene
     (no V-fold `repeat`, reference decoder_splatting_cuda.py:52-56), depth as a 4th blended channel.
     Returns (color (scene, view, 3, h, w), depth (scene, view, h, w) | None) and, with alpha=True, a third element: the accumulated
     opacity (scene, view, h, w), differentiable like the other two.  The depth the reference blends is un-normalised (sum z alpha T);
-    the expected depth of a pixel is depth / alpha, from this one pass - how to clamp a small alpha is the caller's choice."""
+    the expected depth of a pixel is depth / alpha, from this one pass - how to clamp a small alpha is the caller's choice.
+    intrinsics_gradients: when `intrinsics` requires grad it receives the render's gradient - the full camera gradient of the records
+    with its tan-fov columns (GSR_FLAG_FOV_GRADIENT), carried through the set-up's arithmetic.  `extrinsics` gets a gradient from such a
+    call only with pose_gradients (the depth term alone, which a call without either request sends it, is not formed next to it)."""
     s, v = extrinsics.shape[:2]
     ext = extrinsics.reshape(s * v, 4, 4)
     intr = intrinsics.reshape(s * v, 3, 3)
@@ -224,9 +231,10 @@ def render_views(
     # pose gradient, the reference's own graph still sends ONE gradient to it - through the depth render's extrinsics.inverse()
     # (cuda_splatting.py:239-242; training: model_wrapper.py:148-156 with config/main.yaml:50) - and the backward returns exactly
     # that term (GsrBackwardOptions.depth_term_only), carried to `extrinsics` by the closed-form backward of the camera set-up.
-    depth_cam = depth_mode is not None and not pose_gradients and _camera_wants_depth_gradient(extrinsics)
-    viewbuf = _viewbuf(ext, intr, nr, fr, background_color.reshape(3), scale_invariant, pose_gradients or depth_cam)
-    channel = dict(extra_mode=depth_mode, camera_gradient="depth" if depth_cam else "full", return_alpha=alpha)
+    fov = intrinsics_gradients and torch.is_grad_enabled() and intrinsics.requires_grad
+    depth_cam = depth_mode is not None and not pose_gradients and not fov and _camera_wants_depth_gradient(extrinsics)
+    viewbuf = _viewbuf(ext, intr, nr, fr, background_color.reshape(3), scale_invariant, pose_gradients or depth_cam, fov)
+    channel = dict(extra_mode=depth_mode, camera_gradient="depth" if depth_cam else "full", return_alpha=alpha, intrinsics_gradients=fov)
     if gaussian_covariances is None:  # scale + quaternion records, as the encoder's adapter emits them
         records = _scale_rot_records(gaussian_scales, gaussian_rotations)
         color, depth, _, *acc = rasterize_views(
