@@ -390,10 +390,22 @@ int gsr_image_loss_finish(int num_images, int height, int width, const float* pa
  * and dL_dextrinsics (G, 4, 4): rows 0-2 x columns 0-2 the sum over the group of dmean (x) (depth ray), column 3 the sum of
  * dmean, bottom row zero (PF3plat's extrinsics are learned poses: this is how the render loss reaches them through the means).
  * That sum is formed in a fixed order - one row per workgroup in `partials` (gsr_adapt_partials_bytes(G, P) bytes of scratch:
- * host arithmetic), then one reduce launch - so the same bits come out on every run.  Intrinsics get no gradient; a zero
- * quaternion takes the norm's gradient as 0, as torch does.  Both calls: GSR_ERR_INVALID_ARGUMENT on negative sizes, a degree
- * outside 0..4, a stride below 7 + 3 M or a NULL required pointer; nothing is launched when G or P is 0. */
+ * host arithmetic), then one reduce launch - so the same bits come out on every run.  A zero quaternion takes the norm's
+ * gradient as 0, as torch does.
+ * gsr_adapt_backward_ex is gsr_adapt_backward with one more output, dL_dintrinsics (G, 3, 3), nullable.  NULL: the same kernels,
+ * launches, output bits and `partials` size as gsr_adapt_backward (which is this call with NULL).  Otherwise `partials` holds
+ * gsr_adapt_partials_bytes_ex(G, P, 1) bytes (rows of 22 floats instead of 12; with_intrinsics = 0 gives gsr_adapt_partials_bytes),
+ * the per-workgroup rows also carry Ginv = sum over the group of d_p (x) (u, v, 1) - d_p the cotangent of p = K^-1 (u, v, 1),
+ * taken as orthogonal to the ray where the norm was not clamped - and g_mult = sum of depth x sum_r dL_dscale[r] (scale_min +
+ * (scale_max - scale_min) sigmoid(r)), the cotangent of the multiplier, and the reduce launch (still the only one) writes, in fp64,
+ *   dL/dK          = -K^-T Ginv K^-T                                  (all nine entries)
+ *   dL/dK[:2, :2] += -0.1 g_mult (K2^-T 1) (K2^-1 q)^T,   K2 = K[:2, :2], q = (1 / width, 1 / height), 1 = (1, 1)
+ * the second line being the backward of the multiplier 0.1 1^T K2^-1 q.  dL_dintrinsics is fully written; a group whose cotangents
+ * are all NULL or zero gets zeros.
+ * All calls: GSR_ERR_INVALID_ARGUMENT on negative sizes, a degree outside 0..4, a stride below 7 + 3 M or a NULL required pointer;
+ * nothing is launched when G or P is 0. */
 size_t gsr_adapt_partials_bytes(int num_groups, int gaussians_per_group);
+size_t gsr_adapt_partials_bytes_ex(int num_groups, int gaussians_per_group, int with_intrinsics);
 int gsr_adapt(int num_groups, int gaussians_per_group, int sh_degree, const float* extrinsics, const float* intrinsics,
               const float* coordinates, const float* depths, const float* raw, int64_t raw_row_stride, float scale_min,
               float scale_max, int height, int width, float eps, float* means, float* scale_rot, float* harmonics, void* stream);
@@ -402,6 +414,11 @@ int gsr_adapt_backward(int num_groups, int gaussians_per_group, int sh_degree, c
                        float scale_max, int height, int width, float eps, const float* dL_dmeans, const float* dL_dscale_rot,
                        const float* dL_dharmonics, float* dL_draw, float* dL_ddepths, float* dL_dcoordinates, float* dL_dextrinsics,
                        float* partials, void* stream);
+int gsr_adapt_backward_ex(int num_groups, int gaussians_per_group, int sh_degree, const float* extrinsics, const float* intrinsics,
+                          const float* coordinates, const float* depths, const float* raw, int64_t raw_row_stride, float scale_min,
+                          float scale_max, int height, int width, float eps, const float* dL_dmeans, const float* dL_dscale_rot,
+                          const float* dL_dharmonics, float* dL_draw, float* dL_ddepths, float* dL_dcoordinates, float* dL_dextrinsics,
+                          float* dL_dintrinsics, float* partials, void* stream);
 
 /* Measurement aid: 1 when gsr_forward runs the colour pass inside the binning launch for these dims (two launches: binning +
  * colour, per-tile sort + blend), 0 when the colour pass is a launch of its own (images of more than 4608 8x8 tiles, more than

@@ -287,6 +287,10 @@ def load():
     lib.gsr_adapt.argtypes = adapt_head + [vp] * 4
     lib.gsr_adapt_backward.restype = ctypes.c_int
     lib.gsr_adapt_backward.argtypes = adapt_head + [vp] * 9
+    lib.gsr_adapt_partials_bytes_ex.restype = ctypes.c_size_t
+    lib.gsr_adapt_partials_bytes_ex.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    lib.gsr_adapt_backward_ex.restype = ctypes.c_int
+    lib.gsr_adapt_backward_ex.argtypes = adapt_head + [vp] * 10
     if lib.gsr_abi_version() != GSR_ABI_VERSION:
         raise RuntimeError(f"libgsr_hip.so ABI {lib.gsr_abi_version()} != expected {GSR_ABI_VERSION}; rebuild")
     _lib = lib
@@ -299,7 +303,7 @@ EXPORTED_SYMBOLS = (
     "gsr_capacity_for", "gsr_cov_from_scale_rot", "gsr_cov_from_scale_rot_backward", "gsr_last_failed_stage",
     "gsr_colour_in_binning", "gsr_geom_layout", "gsr_backward_ex", "gsr_pose_partials_bytes", "gsr_backward_scratch_bytes", "gsr_setup_views_orthographic",
     "gsr_image_loss", "gsr_image_loss_partials", "gsr_image_loss_finish", "gsr_pack_view", "gsr_setup_views_backward",
-    "gsr_adapt", "gsr_adapt_backward", "gsr_adapt_partials_bytes", "gsr_setup_views_backward_ex",
+    "gsr_adapt", "gsr_adapt_backward", "gsr_adapt_partials_bytes", "gsr_adapt_backward_ex", "gsr_adapt_partials_bytes_ex", "gsr_setup_views_backward_ex",
 )
 # The stages of GsrForwardOptions.stage_ms / GsrBackwardOptions.stage_ms as run_forward / run_backward(profile=True) key them (the
 # names a failed debug-mode stage is reported with are the library's: gsr_stage_name).  On images of up to 20 480 tiles (the fused binning path) "preprocess" is the whole binning

@@ -16,12 +16,13 @@ carried into that frame (GSR_FLAG_SH_IN_FRAME) - the same image and gradients wi
 matrices torch's broadcasting builds.  `AdaptedGaussians.world_harmonics` still yields the rotated coefficients.
 
 With `fused=True` the adapter's own arithmetic - K^-1, the ray, the mean, sigmoid and footprint of the scales, the quaternion
-normalisation, the masked copy of the harmonics - is ONE HIP launch in each direction (`gsr_adapt` / `gsr_adapt_backward`, an
+normalisation, the masked copy of the harmonics - is ONE HIP launch in each direction (`gsr_adapt` / `gsr_adapt_backward_ex`, an
 autograd node of the compiled binding) instead of torch ops: `raw_gaussians` is read where it lies (the encoder's
 `gaussians[..., 2:]` slice included), scales and rotations come back as the two slices of one (..., 7) record tensor - the form
 the raster kernels take, which the decoder then passes on without a `cat` - and gradients reach raw_gaussians, depths,
-coordinates and extrinsics.  It applies to calls whose per-Gaussian arguments all cover the full (b, v, *rest) shape, in float32,
-with intrinsics that do not require grad; any other call runs the torch ops below unchanged (`last_path` says which ran).  It is
+coordinates, extrinsics and - when they require grad, as for any other input - intrinsics (through K^-1 of the ray and through
+the footprint K[:2, :2]^-1 sets; the backward stays two launches).  It applies to calls whose per-Gaussian arguments all cover
+the full (b, v, *rest) shape, in float32; any other call runs the torch ops below unchanged (`last_path` says which ran).  It is
 independent of `fuse_sh_rotation`; PF3plat's training configuration is both.
 """
 from __future__ import annotations
@@ -129,16 +130,15 @@ class GaussianAdapter(nn.Module):
 
     def _hip_applies(self, extrinsics: Tensor, intrinsics: Tensor, coordinates: Tensor, depths: Tensor, raw_gaussians: Tensor, full: tuple) -> bool:
         """The compiled path covers calls whose per-Gaussian arguments all have the full (b, v, *rest) shape (every shipped config:
-        one surface, one Gaussian per pixel) and one camera per view, in float32, with no gradient wanted for the intrinsics."""
+        one surface, one Gaussian per pixel) and one camera per view, in float32.  Whether the intrinsics require grad does not matter:
+        their gradient comes out of the same backward launches."""
         if not self.fused or self.cfg.sh_degree > 4:
             return False
         if tuple(depths.shape) != full or tuple(coordinates.shape) != (*full, 2) or tuple(raw_gaussians.shape) != (*full, self.d_in):
             return False
         if tuple(intrinsics.shape[:2]) != full[:2] or any(d != 1 for d in intrinsics.shape[2:-2]) or tuple(intrinsics.shape[-2:]) != (3, 3):
             return False
-        if any(t.dtype != torch.float32 for t in (extrinsics, intrinsics, coordinates, depths, raw_gaussians)):
-            return False
-        return not (torch.is_grad_enabled() and intrinsics.requires_grad)
+        return all(t.dtype == torch.float32 for t in (extrinsics, intrinsics, coordinates, depths, raw_gaussians))
 
     def get_scale_multiplier(self, intrinsics: Tensor, pixel_size: Tensor, multiplier: float = 0.1) -> Tensor:
         """How large one pixel is at unit depth, summed over x and y: (K[:2, :2]^-1 pixel_size) . (1, 1), times `multiplier`."""

@@ -4820,11 +4820,15 @@ int gsr_image_loss_finish(int num_images, int height, int width, const float* pa
 // stores, the band mask chosen by column.  The backward recomputes everything from the forward's inputs (nothing is saved),
 // assembles the block's dL/draw rows in LDS and writes them with streaming 16-byte stores; the camera-to-world gradient is one
 // wave-reduced row of 12 floats per workgroup, added up in a fixed order by k_adapt_pose_reduce: the same bits on every run.
+// When the intrinsics want a gradient (gsr_adapt_backward_ex with dL_dintrinsics) a second instance of the backward appends ten
+// sums to that row - the cotangents of K^-1 (9) and of the scale multiplier (1) - and k_adapt_camera_reduce, launched in place of
+// k_adapt_pose_reduce, carries them back to K in fp64 (formulas: include/gsr.h).  Still two launches.
 // ------------------------------------------------------------------------------------------------
 namespace gsr {
 constexpr int kAdaptBlock = 64;       // Gaussians per workgroup
 constexpr int kAdaptThreads = 256;
 constexpr int kAdaptPoseFloats = 12;  // sum of dmean (x) (depth ray) (9), sum of dmean (3)
+constexpr int kAdaptIntrFloats = 10;  // behind them when intrinsics want a gradient: sum of d_p (x) (u, v, 1) (9), cotangent of AdaptGroup::mult (1)
 constexpr int kAdaptSlack = 8;        // a row stride of up to this many floats over the row width is streamed gaps included
 
 struct AdaptArgs {
@@ -4953,9 +4957,11 @@ __global__ __launch_bounds__(kAdaptThreads) void k_adapt_fwd(const AdaptArgs a) 
   }
 }
 
-template <int D>
+// KG: the intrinsics want a gradient - the partial row is kAdaptPoseFloats + kAdaptIntrFloats wide; everything else is the same code
+template <int D, bool KG>
 __global__ __launch_bounds__(kAdaptThreads) void k_adapt_bwd(const AdaptArgs a) {
   constexpr int M = (D + 1) * (D + 1), C = 3 * M, ROWF = 7 + C;
+  constexpr int PARTF = kAdaptPoseFloats + (KG ? kAdaptIntrFloats : 0);
   __shared__ __attribute__((aligned(16))) float rows[kAdaptBlock * ROWF];  // the block's dL/draw rows
   const int nb = (a.P + kAdaptBlock - 1) / kAdaptBlock;
   const int g = (int)blockIdx.x / nb, blk = (int)blockIdx.x - g * nb, r0 = blk * kAdaptBlock;
@@ -4983,6 +4989,9 @@ __global__ __launch_bounds__(kAdaptThreads) void k_adapt_bwd(const AdaptArgs a) 
     float pose[kAdaptPoseFloats];
 #pragma unroll
     for (int k = 0; k < kAdaptPoseFloats; ++k) pose[k] = 0.f;
+    float kg[kAdaptIntrFloats];  // (dead code without KG)
+#pragma unroll
+    for (int k = 0; k < kAdaptIntrFloats; ++k) kg[k] = 0.f;
     if (tid < cnt) {
       const AdaptGroup grp = adapt_group(a.ext + (size_t)g * 16, a.intr + (size_t)g * 9, a.height, a.width);
       const size_t gi = first + tid;
@@ -5022,6 +5031,15 @@ __global__ __launch_bounds__(kAdaptThreads) void k_adapt_bwd(const AdaptArgs a) 
         const float d_p = (d_ray[r] - pt.ray[r] * along) / pt.denom;
         d_u += d_p * grp.kinv[3 * r];
         d_v += d_p * grp.kinv[3 * r + 1];
+        if constexpr (KG) {
+          kg[3 * r] = d_p * u; kg[3 * r + 1] = d_p * v; kg[3 * r + 2] = d_p;
+        }
+      }
+      if constexpr (KG) {
+        float d_fp = 0.f;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) d_fp += gs[r] * (a.lo + range * pt.sig[r]);
+        kg[9] = dep * d_fp;
       }
       a.d_coords[2 * gi] = d_u;
       a.d_coords[2 * gi + 1] = d_v;
@@ -5039,7 +5057,17 @@ __global__ __launch_bounds__(kAdaptThreads) void k_adapt_bwd(const AdaptArgs a) 
         float mine = 0.f;
 #pragma unroll
         for (int k = 0; k < kAdaptPoseFloats; ++k) mine = tid == k ? pose[k] : mine;
-        a.partials[((size_t)g * nb + blk) * kAdaptPoseFloats + tid] = mine;
+        a.partials[((size_t)g * nb + blk) * PARTF + tid] = mine;
+      }
+      if constexpr (KG) {
+#pragma unroll
+        for (int k = 0; k < kAdaptIntrFloats; ++k) kg[k] = wave_sum(kg[k]);
+        if (tid >= kAdaptPoseFloats && tid < PARTF) {
+          float mine = 0.f;
+#pragma unroll
+          for (int k = 0; k < kAdaptIntrFloats; ++k) mine = tid == kAdaptPoseFloats + k ? kg[k] : mine;
+          a.partials[((size_t)g * nb + blk) * PARTF + tid] = mine;
+        }
       }
     }
   }
@@ -5084,6 +5112,72 @@ __global__ __launch_bounds__(256) void k_adapt_pose_reduce(const float* __restri
   }
 }
 
+// The same sum over rows of kAdaptPoseFloats + kAdaptIntrFloats floats (k_adapt_bwd<D, true>): dL/dextrinsics from the first 12
+// columns in exactly k_adapt_pose_reduce's order (the same bits), and dL/dintrinsics (G, 3, 3) from the other ten, added up in
+// fp64 in the same fixed order and carried through K^-1 and the scale multiplier of adapt_group in fp64:
+//   dL/dK = -K^-T Ginv K^-T,   dL/dK[:2, :2] += -0.1 g_mult (K2^-T 1) (K2^-1 q)^T,   K2 = K[:2, :2], q = (1 / w, 1 / h)
+__global__ __launch_bounds__(256) void k_adapt_camera_reduce(const float* __restrict__ partials, int nb, const float* __restrict__ intr, int h, int w,
+                                                             float* __restrict__ d_ext, float* __restrict__ d_intr) {
+  constexpr int PARTF = kAdaptPoseFloats + kAdaptIntrFloats;
+  __shared__ float part[21][kAdaptPoseFloats];
+  __shared__ double parti[21][kAdaptIntrFloats];
+  __shared__ double tot[kAdaptIntrFloats];
+  const int g = blockIdx.x, tid = threadIdx.x, k = tid % kAdaptPoseFloats, r = tid / kAdaptPoseFloats;
+  const float* base = partials + (size_t)g * nb * PARTF;
+  if (r < 21) {
+    float acc = 0.f;
+    for (int i = r; i < nb; i += 21) acc += base[(size_t)i * PARTF + k];
+    part[r][k] = acc;
+    if (k < kAdaptIntrFloats) {
+      double wide = 0.0;
+      for (int i = r; i < nb; i += 21) wide += (double)base[(size_t)i * PARTF + kAdaptPoseFloats + k];
+      parti[r][k] = wide;
+    }
+  }
+  __syncthreads();
+  if (tid < 16) {
+    const int row = tid >> 2, col = tid & 3;
+    float sum = 0.f;
+    if (row < 3) {
+      const int idx = col < 3 ? 3 * row + col : 9 + row;
+      for (int j = 0; j < 21; ++j) sum += part[j][idx];
+    }
+    d_ext[(size_t)g * 16 + tid] = sum;
+  } else if (tid >= 64 && tid < 64 + kAdaptIntrFloats) {
+    double sum = 0.0;
+    for (int j = 0; j < 21; ++j) sum += parti[j][tid - 64];
+    tot[tid - 64] = sum;
+  }
+  __syncthreads();
+  if (tid < 9) {
+    const float* kk = intr + (size_t)g * 9;
+    const double a = kk[0], b = kk[1], c = kk[2], d = kk[3], ee = kk[4], f = kk[5], gg = kk[6], hh = kk[7], i = kk[8];
+    double inv[9] = {ee * i - f * hh, c * hh - b * i, b * f - c * ee, f * gg - d * i, a * i - c * gg, c * d - a * f,
+                     d * hh - ee * gg, b * gg - a * hh, a * ee - b * d};
+    const double det2 = inv[8], rdet = 1.0 / (a * inv[0] + b * inv[3] + c * inv[6]);
+#pragma unroll
+    for (int j = 0; j < 9; ++j) inv[j] *= rdet;
+    const int row = tid / 3, col = tid - 3 * row;
+    // -(K^-T Ginv K^-T)[row][col] = -sum_rc K^-1[r][row] Ginv[r][c] K^-1[col][c]
+    double sum = 0.0;
+#pragma unroll
+    for (int rr = 0; rr < 3; ++rr) {
+      double t = 0.0;
+#pragma unroll
+      for (int cc = 0; cc < 3; ++cc) t += tot[3 * rr + cc] * inv[3 * col + cc];
+      sum += inv[3 * rr + row] * t;
+    }
+    sum = -sum;
+    if (row < 2 && col < 2) {
+      const double px = (double)(1.0f / (float)w), py = (double)(1.0f / (float)h);
+      const double ones[2] = {(ee - d) / det2, (a - b) / det2};               // K2^-T (1, 1)
+      const double q[2] = {(ee * px - b * py) / det2, (a * py - d * px) / det2};  // K2^-1 (1 / w, 1 / h)
+      sum -= 0.1 * tot[9] * ones[row] * q[col];
+    }
+    d_intr[(size_t)g * 9 + tid] = (float)sum;
+  }
+}
+
 static bool adapt_sizes_ok(int G, int P, int sh_degree, int64_t stride, int height, int width) {
   if (G < 0 || P < 0 || sh_degree < 0 || sh_degree > 4 || height <= 0 || width <= 0) return false;
   const int rowf = 7 + 3 * (sh_degree + 1) * (sh_degree + 1);
@@ -5114,17 +5208,25 @@ struct AdaptFwdLaunch {
 template <int D>
 struct AdaptBwdLaunch {
   static void go(const AdaptArgs& a, hipStream_t st) {
-    hipLaunchKernelGGL(k_adapt_bwd<D>, dim3(adapt_grid(a)), dim3(kAdaptThreads), 0, st, a);
+    hipLaunchKernelGGL((k_adapt_bwd<D, false>), dim3(adapt_grid(a)), dim3(kAdaptThreads), 0, st, a);
+  }
+};
+template <int D>
+struct AdaptBwdIntrLaunch {
+  static void go(const AdaptArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL((k_adapt_bwd<D, true>), dim3(adapt_grid(a)), dim3(kAdaptThreads), 0, st, a);
   }
 };
 }  // namespace gsr
 
 extern "C" {
 
-size_t gsr_adapt_partials_bytes(int num_groups, int gaussians_per_group) {
+size_t gsr_adapt_partials_bytes_ex(int num_groups, int gaussians_per_group, int with_intrinsics) {
   if (num_groups <= 0 || gaussians_per_group <= 0) return 0;
-  return (size_t)num_groups * (size_t)((gaussians_per_group + gsr::kAdaptBlock - 1) / gsr::kAdaptBlock) * gsr::kAdaptPoseFloats * sizeof(float);
+  const int rowf = gsr::kAdaptPoseFloats + (with_intrinsics ? gsr::kAdaptIntrFloats : 0);
+  return (size_t)num_groups * (size_t)((gaussians_per_group + gsr::kAdaptBlock - 1) / gsr::kAdaptBlock) * rowf * sizeof(float);
 }
+size_t gsr_adapt_partials_bytes(int num_groups, int gaussians_per_group) { return gsr_adapt_partials_bytes_ex(num_groups, gaussians_per_group, 0); }
 
 int gsr_adapt(int num_groups, int gaussians_per_group, int sh_degree, const float* extrinsics, const float* intrinsics,
               const float* coordinates, const float* depths, const float* raw, int64_t raw_row_stride, float scale_min,
@@ -5150,6 +5252,16 @@ int gsr_adapt_backward(int num_groups, int gaussians_per_group, int sh_degree, c
                        float scale_max, int height, int width, float eps, const float* dL_dmeans, const float* dL_dscale_rot,
                        const float* dL_dharmonics, float* dL_draw, float* dL_ddepths, float* dL_dcoordinates, float* dL_dextrinsics,
                        float* partials, void* stream_) {
+  return gsr_adapt_backward_ex(num_groups, gaussians_per_group, sh_degree, extrinsics, intrinsics, coordinates, depths, raw, raw_row_stride, scale_min,
+                               scale_max, height, width, eps, dL_dmeans, dL_dscale_rot, dL_dharmonics, dL_draw, dL_ddepths, dL_dcoordinates,
+                               dL_dextrinsics, nullptr, partials, stream_);
+}
+
+int gsr_adapt_backward_ex(int num_groups, int gaussians_per_group, int sh_degree, const float* extrinsics, const float* intrinsics,
+                          const float* coordinates, const float* depths, const float* raw, int64_t raw_row_stride, float scale_min,
+                          float scale_max, int height, int width, float eps, const float* dL_dmeans, const float* dL_dscale_rot,
+                          const float* dL_dharmonics, float* dL_draw, float* dL_ddepths, float* dL_dcoordinates, float* dL_dextrinsics,
+                          float* dL_dintrinsics, float* partials, void* stream_) {
   using namespace gsr;
   if (!adapt_sizes_ok(num_groups, gaussians_per_group, sh_degree, raw_row_stride, height, width)) return GSR_ERR_INVALID_ARGUMENT;
   if (num_groups == 0 || gaussians_per_group == 0) return GSR_OK;
@@ -5162,10 +5274,17 @@ int gsr_adapt_backward(int num_groups, int gaussians_per_group, int sh_degree, c
   a.ext = extrinsics; a.intr = intrinsics; a.coords = coordinates; a.depths = depths; a.raw = raw;
   a.d_means = dL_dmeans; a.d_sr = dL_dscale_rot; a.d_harm = dL_dharmonics;
   a.d_raw = dL_draw; a.d_depths = dL_ddepths; a.d_coords = dL_dcoordinates; a.partials = partials;
-  adapt_dispatch<AdaptBwdLaunch>(sh_degree, a, st);
-  GSR_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_adapt_pose_reduce, dim3((unsigned)num_groups), dim3(256), 0, st, partials,
-                     (gaussians_per_group + kAdaptBlock - 1) / kAdaptBlock, dL_dextrinsics);
+  const int nb = (gaussians_per_group + kAdaptBlock - 1) / kAdaptBlock;
+  if (dL_dintrinsics) {
+    adapt_dispatch<AdaptBwdIntrLaunch>(sh_degree, a, st);
+    GSR_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(k_adapt_camera_reduce, dim3((unsigned)num_groups), dim3(256), 0, st, partials, nb, intrinsics, height, width, dL_dextrinsics,
+                       dL_dintrinsics);
+  } else {
+    adapt_dispatch<AdaptBwdLaunch>(sh_degree, a, st);
+    GSR_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(k_adapt_pose_reduce, dim3((unsigned)num_groups), dim3(256), 0, st, partials, nb, dL_dextrinsics);
+  }
   GSR_CHECK(hipGetLastError());
   return GSR_OK;
 }

@@ -60,8 +60,8 @@ struct Abi {
   decltype(&gsr_cov_from_scale_rot) cov_from_scale_rot = nullptr;
   decltype(&gsr_cov_from_scale_rot_backward) cov_from_scale_rot_backward = nullptr;
   decltype(&gsr_adapt) adapt = nullptr;
-  decltype(&gsr_adapt_backward) adapt_backward = nullptr;
-  decltype(&gsr_adapt_partials_bytes) adapt_partials_bytes = nullptr;
+  decltype(&gsr_adapt_backward_ex) adapt_backward_ex = nullptr;
+  decltype(&gsr_adapt_partials_bytes_ex) adapt_partials_bytes_ex = nullptr;
 } g_abi;
 
 template <class F>
@@ -92,8 +92,8 @@ void init(const std::string& path) {
   resolve(g_abi.cov_from_scale_rot, "gsr_cov_from_scale_rot");
   resolve(g_abi.cov_from_scale_rot_backward, "gsr_cov_from_scale_rot_backward");
   resolve(g_abi.adapt, "gsr_adapt");
-  resolve(g_abi.adapt_backward, "gsr_adapt_backward");
-  resolve(g_abi.adapt_partials_bytes, "gsr_adapt_partials_bytes");
+  resolve(g_abi.adapt_backward_ex, "gsr_adapt_backward_ex");
+  resolve(g_abi.adapt_partials_bytes_ex, "gsr_adapt_partials_bytes_ex");
   TORCH_CHECK(g_abi.abi_version() == GSR_ABI_VERSION, "pf3plat_amd: raster library ABI ", g_abi.abi_version(), " != ", GSR_ABI_VERSION, "; rebuild");
 }
 
@@ -887,7 +887,7 @@ Tensor pack_view(const Tensor& viewmatrix, const Tensor& projmatrix, const Tenso
   return out;
 }
 
-// ---- the Gaussian adapter (gsr_adapt / gsr_adapt_backward): one autograd node around the two calls ---------------------------------
+// ---- the Gaussian adapter (gsr_adapt / gsr_adapt_backward_ex): one autograd node around the two calls ------------------------------
 // raw (..., 7 + 3 M) is read where it is: its rows must lie a constant number of floats apart (the encoder's `gaussians[..., 2:]`
 // slice of an 84-wide tensor does: stride 84); only a tensor whose leading dims do not collapse to one row stride is copied.
 bool rows_evenly_spaced(const Tensor& t, int64_t* row_stride) {
@@ -950,13 +950,16 @@ struct AdaptFn : public torch::autograd::Function<AdaptFn> {
     Tensor d_raw = at::empty({g, p, 7 + 3 * m}, ext.options()), d_dep = at::empty({g, p}, ext.options()), d_coords = at::empty({g, p, 2}, ext.options());
     Tensor d_ext = g * p > 0 ? at::empty({g, 4, 4}, ext.options()) : at::zeros({g, 4, 4}, ext.options());
     c10::hip::HIPGuard guard(ext.device().index());
-    Tensor partials = at::empty({(int64_t)g_abi.adapt_partials_bytes((int)g, (int)p)}, ext.options().dtype(at::kByte));
-    const int rc = g_abi.adapt_backward((int)g, (int)p, (int)degree, fptr(ext), fptr(intr), fptr(coords), fptr(dep), fptr(raw), stride, (float)scal[0], (float)scal[1],
+    // intrinsics being learned: their gradient comes out of the same two launches (wider partial rows); otherwise NULL, which is gsr_adapt_backward
+    const bool want_intr = ctx->needs_input_grad(1);
+    Tensor d_intr = !want_intr ? Tensor() : g * p > 0 ? at::empty({g, 3, 3}, ext.options()) : at::zeros({g, 3, 3}, ext.options());
+    Tensor partials = at::empty({(int64_t)g_abi.adapt_partials_bytes_ex((int)g, (int)p, want_intr ? 1 : 0)}, ext.options().dtype(at::kByte));
+    const int rc = g_abi.adapt_backward_ex((int)g, (int)p, (int)degree, fptr(ext), fptr(intr), fptr(coords), fptr(dep), fptr(raw), stride, (float)scal[0], (float)scal[1],
                                         (int)shape[4], (int)shape[5], (float)scal[2], fptr(d_means), fptr(d_rec), fptr(d_harm), d_raw.data_ptr<float>(),
-                                        d_dep.data_ptr<float>(), d_coords.data_ptr<float>(), d_ext.data_ptr<float>(),
+                                        d_dep.data_ptr<float>(), d_coords.data_ptr<float>(), d_ext.data_ptr<float>(), fptr_mut(d_intr),
                                         reinterpret_cast<float*>(partials.data_ptr<uint8_t>()), stream_of(ext.device()));
-    if (rc != 0) throw std::runtime_error("gsr_adapt_backward failed with code " + std::to_string(rc));
-    return {d_ext, Tensor(), d_coords.reshape(ctx->saved_data["coord_sizes"].toIntVector()), d_dep, d_raw.reshape(ctx->saved_data["raw_sizes"].toIntVector()),
+    if (rc != 0) throw std::runtime_error("gsr_adapt_backward_ex failed with code " + std::to_string(rc));
+    return {d_ext, d_intr, d_coords.reshape(ctx->saved_data["coord_sizes"].toIntVector()), d_dep, d_raw.reshape(ctx->saved_data["raw_sizes"].toIntVector()),
             Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
   }
 };
