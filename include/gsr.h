@@ -372,6 +372,32 @@ int gsr_image_loss(int num_images, int height, int width, const float* predictio
 int gsr_image_loss_finish(int num_images, int height, int width, const float* partials, float mse_weight, float ssim_weight,
                           float* sums, float* totals, void* stream);
 
+/* Evaluation metrics of the raster path (reference src/evaluation/metrics.py: compute_psnr :11-19, compute_ssim :36-52), forward
+ * only, for `num_images` pairs (num_images, 3, H, W), H and W at least 11.  The SSIM here is the METRIC, what
+ *   skimage.metrics.structural_similarity(ground_truth, prediction, win_size=11, gaussian_weights=True, channel_axis=0, data_range=1.0)
+ * returns for one image, and differs from the SSIM of gsr_image_loss (the training loss's) in four places.  Per image and channel,
+ * x the ground truth and y the prediction:
+ *   window    w[k] = exp(-k^2 / (2 * 1.5^2)), k = -5..5, normalised to sum 1, applied along both axes (the loss's eleven numbers);
+ *   boundary  the image is extended by reflection about its edge, d c b a | a b c d | d c b a: index -1 - j reads j and H + j reads
+ *             H - 1 - j (scipy.ndimage mode="reflect", numpy pad "symmetric").  The loss pads with zeros.
+ *   moments   ux, uy, uxx, uyy, uxy = the filtered x, y, x^2, y^2, x y;
+ *   variances the SAMPLE ones: vx = cn (uxx - ux^2), vy = cn (uyy - uy^2), vxy = cn (uxy - ux uy), cn = 121 / 120.  The loss uses cn = 1.
+ *   map       S = (2 ux uy + C1)(2 vxy + C2) / ((ux^2 + uy^2 + C1)(vx + vy + C2)), C1 = 1e-4, C2 = 9e-4, on every pixel;
+ *   mean      a channel's value is the mean of S over 5 <= row < H - 5, 5 <= col < W - 5 (the loss: over every pixel), an image's
+ *             value the mean of its three channels' (the loss: one mean over the batch).  The inputs are not clipped.
+ * gsr_image_metrics is one launch: it writes S to ssim_map (num_images, 3, H, W) unless that is NULL, and one slot of 4 floats per
+ * workgroup into `partials` (gsr_image_metrics_partials(...) slots; layout and order of gsr_image_loss's): sum of squared errors,
+ * sum of squared errors of the inputs clipped to [0, 1], sum of S over the workgroup's interior pixels, 0.
+ * gsr_image_metrics_partials is 0 for whatever the launch refuses (a side below 11, num_images <= 0 or 3 num_images > 65535).
+ * The slots are added up by this call's OWN finish, gsr_image_metrics_finish (one workgroup, fixed order, no atomics: the same bits
+ * every time, an image's row independent of the rest of the batch): metrics (4, num_images) floats = per image the SSIM, the PSNR
+ * -10 log10(clipped squared error / (3 H W)), the interior sum of S and the clipped squared-error sum.  (gsr_image_loss_finish reads
+ * the same slots and would return the three raw sums; its totals divide by every pixel and mean nothing here.) */
+size_t gsr_image_metrics_partials(int num_images, int height, int width);
+int gsr_image_metrics(int num_images, int height, int width, const float* ground_truth, const float* prediction,
+                      float* ssim_map /* NULL = none */, float* partials, void* stream);
+int gsr_image_metrics_finish(int num_images, int height, int width, const float* partials, float* metrics, void* stream);
+
 /* The encoder-side Gaussian adapter, the step right in front of the raster path (reference
  * src/model/encoder/common/gaussian_adapter.py:60-87 with get_world_rays), one launch: G groups (scene x source view) of P
  * pixel-aligned Gaussians each, M = (sh_degree + 1)^2 for sh_degree 0..4.

@@ -268,6 +268,12 @@ def load():
     lib.gsr_image_loss.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_float, ctypes.c_float, vp, vp, vp]
     lib.gsr_image_loss_finish.restype = ctypes.c_int
     lib.gsr_image_loss_finish.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_float, ctypes.c_float, vp, vp, vp]
+    lib.gsr_image_metrics_partials.restype = ctypes.c_size_t
+    lib.gsr_image_metrics_partials.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    lib.gsr_image_metrics.restype = ctypes.c_int
+    lib.gsr_image_metrics.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp]
+    lib.gsr_image_metrics_finish.restype = ctypes.c_int
+    lib.gsr_image_metrics_finish.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp]
     lib.gsr_pack_view.restype = ctypes.c_int
     lib.gsr_pack_view.argtypes = [vp, vp, vp, ctypes.c_int, vp, ctypes.c_float, ctypes.c_float, vp, vp, ctypes.c_float, vp, vp]
     lib.gsr_mark_visible.restype = ctypes.c_int
@@ -304,6 +310,7 @@ EXPORTED_SYMBOLS = (
     "gsr_colour_in_binning", "gsr_geom_layout", "gsr_backward_ex", "gsr_pose_partials_bytes", "gsr_backward_scratch_bytes", "gsr_setup_views_orthographic",
     "gsr_image_loss", "gsr_image_loss_partials", "gsr_image_loss_finish", "gsr_pack_view", "gsr_setup_views_backward",
     "gsr_adapt", "gsr_adapt_backward", "gsr_adapt_partials_bytes", "gsr_adapt_backward_ex", "gsr_adapt_partials_bytes_ex", "gsr_setup_views_backward_ex",
+    "gsr_image_metrics", "gsr_image_metrics_partials", "gsr_image_metrics_finish",
 )
 # The stages of GsrForwardOptions.stage_ms / GsrBackwardOptions.stage_ms as run_forward / run_backward(profile=True) key them (the
 # names a failed debug-mode stage is reported with are the library's: gsr_stage_name).  On images of up to 20 480 tiles (the fused binning path) "preprocess" is the whole binning

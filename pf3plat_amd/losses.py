@@ -2,7 +2,9 @@
 (src/loss/loss_mse.py:23-36), `LossMultiSSIM` / `ssim` (src/loss/loss_multissim.py:24-83) and `compute_psnr`
 (src/evaluation/metrics.py:11-19), all evaluated by ONE launch of the raster library (`gsr_image_loss`) that also writes
 dL/dprediction in the layout the rasterizer's backward reads - the loss's backward is then a no-op (the gradient already
-exists) instead of five depthwise convolutions and their transposes.  No CPU fallback: tensors must be on a ROCm device.
+exists) instead of five depthwise convolutions and their transposes.  The evaluation's metrics - `compute_psnr` and `compute_ssim`
+(src/evaluation/metrics.py:36-52: scikit-image's structural_similarity, another SSIM than the loss's) - come from a launch pair of
+their own (`gsr_image_metrics`, forward only).  No CPU fallback: tensors must be on a ROCm device.
 """
 from __future__ import annotations
 
@@ -82,6 +84,62 @@ def compute_psnr(ground_truth: Tensor, predicted: Tensor) -> Tensor:
     """(batch, 3, h, w) x 2 -> (batch,): -10 log10 of the mean squared error of the inputs clipped to [0, 1]."""
     sums, _totals, _, per_image = _launch(predicted, ground_truth, 0.0, 0.0, False)
     return -10 * (sums[:, 1] / per_image).log10()
+
+
+def _launch_metrics(ground_truth: Tensor, predicted: Tensor, want_map: bool):
+    """-> (metrics (4, n): per image SSIM, PSNR, interior sum of the SSIM map, clipped squared error; the map (n, 3, h, w) or None).
+    Two launches (gsr_image_metrics, gsr_image_metrics_finish), no torch op.  The shapes are checked first, before the device and
+    before the library is loaded."""
+    if ground_truth.shape != predicted.shape or ground_truth.dim() != 4 or ground_truth.shape[1] != 3:
+        raise ValueError(f"expected two (n, 3, h, w) images, got {tuple(ground_truth.shape)} and {tuple(predicted.shape)}")
+    n, _, h, w = ground_truth.shape
+    if h < 11 or w < 11:
+        raise ValueError(f"win_size exceeds image extent: the 11 x 11 window of compute_ssim needs h, w >= 11, got {h} x {w}")
+    if not (ground_truth.is_cuda and predicted.is_cuda):
+        raise RuntimeError("pf3plat_amd losses: tensors must be on a ROCm device (there is no CPU fallback path)")
+    lib = _lib.load()
+    f32 = torch.float32
+    gt = ground_truth.detach()
+    pred = predicted.detach()
+    if gt.dtype != f32 or not gt.is_contiguous():
+        gt = gt.to(f32).contiguous()
+    if pred.dtype != f32 or not pred.is_contiguous():
+        pred = pred.to(f32).contiguous()
+    dev = gt.device
+    out = torch.empty((4, n), dtype=f32, device=dev)
+    smap = torch.empty((n, 3, h, w), dtype=f32, device=dev) if want_map else None
+    if n == 0:
+        return out, smap
+    slots = int(lib.gsr_image_metrics_partials(n, h, w))
+    if slots == 0:
+        raise RuntimeError(f"gsr_image_metrics takes at most 21845 images in one call, got {n}")
+    partials = torch.empty((slots, 4), dtype=f32, device=dev)
+    stream = _stream_ptr(dev)
+    with _on_device(dev):
+        rc = lib.gsr_image_metrics(n, h, w, gt.data_ptr(), pred.data_ptr(), None if smap is None else smap.data_ptr(),
+                                   partials.data_ptr(), stream)
+        if rc == 0:
+            rc = lib.gsr_image_metrics_finish(n, h, w, partials.data_ptr(), out.data_ptr(), stream)
+    if rc != 0:
+        raise RuntimeError(f"gsr_image_metrics failed with code {rc}")
+    return out, smap
+
+
+@torch.no_grad()
+def compute_image_metrics(ground_truth: Tensor, predicted: Tensor, ssim_map: bool = False):
+    """(batch, 3, h, w) x 2 -> (psnr (batch,), ssim (batch,)[, map (batch, 3, h, w)]): the reference's compute_psnr and compute_ssim
+    (src/evaluation/metrics.py:11-19, 36-52) from one launch pair, without a host synchronisation; `ssim_map`: also the SSIM map
+    on every pixel (scikit-image's `full=True`), border included.  h, w >= 11."""
+    out, smap = _launch_metrics(ground_truth, predicted, ssim_map)
+    return (out[1], out[0], smap) if ssim_map else (out[1], out[0])
+
+
+@torch.no_grad()
+def compute_ssim(ground_truth: Tensor, predicted: Tensor) -> Tensor:
+    """(batch, 3, h, w) x 2 -> (batch,): per image skimage.metrics.structural_similarity(gt, hat, win_size=11, gaussian_weights=True,
+    channel_axis=0, data_range=1.0) - reflected borders, sample covariance, mean over the interior without its 5-pixel border, mean
+    of the three channels (include/gsr.h states the definition).  NOT `ssim` above, which is the training loss's."""
+    return _launch_metrics(ground_truth, predicted, False)[0][0]
 
 
 @dataclass
