@@ -446,6 +446,51 @@ int gsr_adapt_backward_ex(int num_groups, int gaussians_per_group, int sh_degree
                           const float* dL_dharmonics, float* dL_draw, float* dL_ddepths, float* dL_dcoordinates, float* dL_dextrinsics,
                           float* dL_dintrinsics, float* partials, void* stream);
 
+/* The pose loss of the training step (reference src/loss/loss_pose.py:28-129, `Losspose`), one launch chain each way.
+ * Inputs, all f32 unless said otherwise, b scenes of v >= 2 views of H x W pixels:
+ *   xyz (b, v, 3, H, W) per-pixel points; depth (b, v, H, W); poses (b, v, 4, 4) - of a pose only the top three rows are read and
+ *   only they receive a gradient (the bottom row is taken as (0, 0, 0, 1)); intrinsics (b, v, 3, 3), normalised, no gradient;
+ *   one match list per pair p = (i, j), i < j - pairs in the order [(a, c) for a in range(v) for c in range(a + 1, v)], num_pairs =
+ *   v (v - 1) / 2 - and per scene s, list l = p b + s (pair-major): entries offsets[l] .. offsets[l + 1] of ids_i, ids_j (int64, flat
+ *   pixel indices y W + x) and weights (the matcher's scores); conf (num_pairs b) one confidence per list.  Scores and confidences get
+ *   no gradient.  A list may be empty; its length is not bounded.  IDS ARE NOT CHECKED: an id outside [0, H W) is the caller's error
+ *   and reads or adds out of bounds.
+ * Per list: Rt = poses[s, j] when i == 0 (the reference's shortcut: poses[s, 0] is never read, whatever it holds), otherwise
+ *   Rt = poses[s, j] poses[s, i]^-1, the affine inverse with a general 3 x 3 inverse, formed in fp64 once per list; R, t its parts.
+ *   3D term  L3 = conf sum_m w_m |R x_i[id_i_m] + t - x_j[id_j_m]| / max(sum_m |w_m|, 1e-12)
+ *   2D term  c(id) = ((id % W + 0.5) / W, (id / W + 0.5) / H) in fp32;  P = depth_i[id_i] K_i^-1 (c(id_i), 1);
+ *            Q = (R P + t) / (1 + 1e-6);  q = (K_j Q)_xy / ((K_j Q)_z + 1e-6);  r = |q - c(id_j)|;
+ *            L2 = sum_m huber(r_m, delta = 0.01) / 0.01   (a sum, unweighted)
+ *   loss = weight_3d mean_l L3 + weight_2d mean_l L2; an empty list adds 0 and counts in the means' denominators; the gradient of a
+ *   norm at an exactly zero residual is 0.
+ * Work is cut into units of 256 consecutive matches of one list; gsr_pose_loss_units (host arithmetic) counts them from the
+ * num_lists + 1 offsets - -1 for a NULL pointer, a negative count or start, or offsets that decrease.  `offsets` is that HOST array
+ * (it is validated and sizes the launch), `offsets_device` the same numbers in device memory (the kernels read them).
+ * gsr_pose_loss: one launch over the units - `partials`: units x 4 floats - and a one-workgroup finish that adds the rows of each
+ *   list and then the lists in fp64 in a fixed order: out[0..3] = loss, mean L3, mean L2, 0; lists (num_lists, 4) = per list L3, L2,
+ *   the factor weight_3d conf / (max(sum |w|, 1e-12) num_lists) the backward takes, sum |w|.  The same bits on every run, and a
+ *   list's row does not depend on the other lists.
+ * gsr_pose_loss_backward: takes the same inputs again (everything is recomputed), `lists` as the forward wrote it and the upstream
+ *   cotangent dL_dloss as ONE FLOAT IN DEVICE MEMORY (no host read).  It zero-fills dL_dxyz (b, v, 3, H, W) and dL_ddepth (b, v, H, W)
+ *   and adds into them with float atomics - order-independent, hence the same bits on every run, wherever a pixel receives at most
+ *   two contributions (with three views nearly everywhere; a pixel can occur in several lists, and twice in one when two keypoints
+ *   truncate to it); elsewhere the last bits may differ between runs.  dL/dRt leaves as one row of 12 floats per unit (`partials`:
+ *   units x 12 floats) that a reduce launch adds per list in fp64 in a fixed order, carries to poses[s, j] and, for i > 0, through
+ *   the inverse to poses[s, i], and sums per view over its pairs in their order: dL_dposes (b, v, 4, 4), bottom rows zero, the
+ *   same bits on every run.
+ * Both: GSR_ERR_INVALID_ARGUMENT, nothing launched, on a NULL required pointer, negative or decreasing offsets, num_views < 2,
+ * num_pairs != v (v - 1) / 2, a non-positive extent or H W > 2^31 - 1.  num_scenes == 0: the forward writes zeros to `out`. */
+int64_t gsr_pose_loss_units(int num_lists, const int32_t* offsets);
+int gsr_pose_loss(int num_scenes, int num_views, int height, int width, int num_pairs, const float* xyz, const float* depth,
+                  const float* poses, const float* intrinsics, const int64_t* ids_i, const int64_t* ids_j, const float* weights,
+                  const float* conf, const int32_t* offsets, const int32_t* offsets_device, float weight_2d, float weight_3d,
+                  float* partials, float* lists, float* out, void* stream);
+int gsr_pose_loss_backward(int num_scenes, int num_views, int height, int width, int num_pairs, const float* xyz, const float* depth,
+                           const float* poses, const float* intrinsics, const int64_t* ids_i, const int64_t* ids_j,
+                           const float* weights, const float* conf, const int32_t* offsets, const int32_t* offsets_device,
+                           float weight_2d, float weight_3d, const float* lists, const float* dL_dloss, float* dL_dxyz,
+                           float* dL_ddepth, float* dL_dposes, float* partials, void* stream);
+
 /* Measurement aid: 1 when gsr_forward runs the colour pass inside the binning launch for these dims (two launches: binning +
  * colour, per-tile sort + blend), 0 when the colour pass is a launch of its own (images of more than 4608 8x8 tiles, more than
  * four views per set, the windowed binning path), negative on bad dims. */

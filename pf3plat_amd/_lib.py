@@ -297,6 +297,14 @@ def load():
     lib.gsr_adapt_partials_bytes_ex.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
     lib.gsr_adapt_backward_ex.restype = ctypes.c_int
     lib.gsr_adapt_backward_ex.argtypes = adapt_head + [vp] * 10
+    i32p = ctypes.POINTER(ctypes.c_int32)
+    pose_head = [ctypes.c_int] * 5 + [vp] * 8 + [i32p, vp, ctypes.c_float, ctypes.c_float]  # sizes, arrays, host + device offsets, weights
+    lib.gsr_pose_loss_units.restype = ctypes.c_int64
+    lib.gsr_pose_loss_units.argtypes = [ctypes.c_int, i32p]
+    lib.gsr_pose_loss.restype = ctypes.c_int
+    lib.gsr_pose_loss.argtypes = pose_head + [vp] * 4
+    lib.gsr_pose_loss_backward.restype = ctypes.c_int
+    lib.gsr_pose_loss_backward.argtypes = pose_head + [vp] * 7
     if lib.gsr_abi_version() != GSR_ABI_VERSION:
         raise RuntimeError(f"libgsr_hip.so ABI {lib.gsr_abi_version()} != expected {GSR_ABI_VERSION}; rebuild")
     _lib = lib
@@ -311,6 +319,7 @@ EXPORTED_SYMBOLS = (
     "gsr_image_loss", "gsr_image_loss_partials", "gsr_image_loss_finish", "gsr_pack_view", "gsr_setup_views_backward",
     "gsr_adapt", "gsr_adapt_backward", "gsr_adapt_partials_bytes", "gsr_adapt_backward_ex", "gsr_adapt_partials_bytes_ex", "gsr_setup_views_backward_ex",
     "gsr_image_metrics", "gsr_image_metrics_partials", "gsr_image_metrics_finish",
+    "gsr_pose_loss", "gsr_pose_loss_backward", "gsr_pose_loss_units",
 )
 # The stages of GsrForwardOptions.stage_ms / GsrBackwardOptions.stage_ms as run_forward / run_backward(profile=True) key them (the
 # names a failed debug-mode stage is reported with are the library's: gsr_stage_name).  On images of up to 20 480 tiles (the fused binning path) "preprocess" is the whole binning

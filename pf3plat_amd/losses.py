@@ -4,10 +4,13 @@
 dL/dprediction in the layout the rasterizer's backward reads - the loss's backward is then a no-op (the gradient already
 exists) instead of five depthwise convolutions and their transposes.  The evaluation's metrics - `compute_psnr` and `compute_ssim`
 (src/evaluation/metrics.py:36-52: scikit-image's structural_similarity, another SSIM than the loss's) - come from a launch pair of
-their own (`gsr_image_metrics`, forward only).  No CPU fallback: tensors must be on a ROCm device.
+their own (`gsr_image_metrics`, forward only).  The fourth loss of the training step, `Losspose` (src/loss/loss_pose.py:28-129), is
+`pose_loss` / `Losspose` at the end of this file: one launch chain in each direction (`gsr_pose_loss`, `gsr_pose_loss_backward`)
+instead of a Python loop over the (scene, pair) lists.  No CPU fallback: tensors must be on a ROCm device.
 """
 from __future__ import annotations
 
+import ctypes
 from dataclasses import dataclass
 from typing import Optional
 
@@ -191,3 +194,170 @@ class LossPhotometric(torch.nn.Module):
 
     def forward(self, prediction, batch, *unused) -> Tensor:
         return photometric_loss(*_inner_views(prediction.color, batch), self.mse_weight, self.ssim_weight)[0]
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# The pose loss (reference src/loss/loss_pose.py; the definition is stated in include/gsr.h)
+# ------------------------------------------------------------------------------------------------------------------------
+@dataclass
+class PackedCorrespondences:
+    """The match lists of one batch as the kernels read them: list l = pair x num_scenes + scene (pair-major, pairs in the order
+    [(a, c) for a in range(v) for c in range(a + 1, v)]) holds entries offsets[l] .. offsets[l + 1] of the three arrays."""
+    ids_i: Tensor           # (M,) int64 flat pixel indices y * w + x in the pair's first view
+    ids_j: Tensor           # (M,) int64, in its second view
+    weights: Tensor         # (M,) float32 scores
+    conf: Tensor            # (num_pairs * num_scenes,) float32, one confidence per list
+    offsets: tuple          # num_lists + 1 Python ints (from the shapes: nothing is read off the device)
+    offsets_device: Tensor  # the same as int32 on the arrays' device
+    num_scenes: int
+    num_pairs: int
+
+
+def pack_correspondences(corr, conf) -> PackedCorrespondences:
+    """The reference's `corr[0]` - {(i, j): [(id_i, id_j, score) per scene]} - and `corr[2]` - {(i, j): one confidence per scene} -
+    as four arrays: one `torch.cat` each, in the order the reference indexes them, the offsets from the shapes (no synchronisation:
+    on a device the offsets go up from pinned memory without waiting).  Neither scores nor confidences carry a gradient.  Ids outside
+    [0, h * w) are the caller's error: nobody checks them per match, here or in the kernels."""
+    pairs = sorted(corr.keys())
+    if not pairs:
+        raise ValueError("pack_correspondences: no pairs")
+    num_views = max(j for _, j in pairs) + 1
+    if pairs != [(a, c) for a in range(num_views) for c in range(a + 1, num_views)]:
+        raise ValueError(f"pack_correspondences: expected every pair (i, j), i < j, of {num_views} views, got {pairs}")
+    num_scenes = len(corr[pairs[0]])
+    if any(len(corr[p]) != num_scenes or len(conf[p]) != num_scenes for p in pairs):
+        raise ValueError("pack_correspondences: every pair needs one list and one confidence per scene")
+    lists = [corr[p][s] for p in pairs for s in range(num_scenes)]
+    offsets = [0]
+    for ids_i, ids_j, score in lists:
+        if not (ids_i.dim() == ids_j.dim() == score.dim() == 1 and ids_i.shape == ids_j.shape == score.shape):
+            raise ValueError(f"pack_correspondences: a list is three equal 1-D tensors, got {tuple(ids_i.shape)}, {tuple(ids_j.shape)}, {tuple(score.shape)}")
+        offsets.append(offsets[-1] + ids_i.shape[0])
+    if offsets[-1] > 0x7fffffff:
+        raise ValueError("pack_correspondences: more than 2^31 - 1 matches in one call")
+    ids_i = torch.cat([t[0] for t in lists]).detach().to(torch.int64)
+    ids_j = torch.cat([t[1] for t in lists]).detach().to(torch.int64)
+    weights = torch.cat([t[2] for t in lists]).detach().to(torch.float32)
+    dev = weights.device
+    cf = torch.cat([(conf[p] if isinstance(conf[p], Tensor) else torch.stack([torch.as_tensor(c, device=dev) for c in conf[p]])).reshape(-1) for p in pairs])
+    cf = cf.detach().to(device=dev, dtype=torch.float32)
+    off = torch.tensor(offsets, dtype=torch.int32)
+    off = off.pin_memory().to(dev, non_blocking=True) if dev.type == "cuda" else off
+    return PackedCorrespondences(ids_i, ids_j, weights, cf, tuple(offsets), off, num_scenes, len(pairs))
+
+
+def _f32(t: Tensor) -> Tensor:
+    t = t.detach()
+    return t if t.dtype == torch.float32 and t.is_contiguous() else t.to(torch.float32).contiguous()
+
+
+def _pose_loss_args(xyz, depth, poses, intrinsics, packed):
+    """The shape checks (before the device is looked at and before the library is loaded), then the device check."""
+    if xyz.dim() != 5 or xyz.shape[2] != 3:
+        raise ValueError(f"pose_loss: expected xyz (b, v, 3, h, w), got {tuple(xyz.shape)}")
+    b, v, _, h, w = xyz.shape
+    if v < 2:
+        raise ValueError(f"pose_loss: needs at least two views, got {v}")
+    if tuple(depth.shape) not in ((b * v, 1, h, w), (b, v, h, w)):
+        raise ValueError(f"pose_loss: expected depth ((b v), 1, h, w) or (b, v, h, w) = ({b * v}, 1, {h}, {w}), got {tuple(depth.shape)}")
+    if tuple(poses.shape) != (b, v, 4, 4):
+        raise ValueError(f"pose_loss: expected poses (b, v, 4, 4) = ({b}, {v}, 4, 4), got {tuple(poses.shape)}")
+    if tuple(intrinsics.shape) != (b, v, 3, 3):
+        raise ValueError(f"pose_loss: expected intrinsics (b, v, 3, 3) = ({b}, {v}, 3, 3), got {tuple(intrinsics.shape)}")
+    if packed.num_scenes != b or packed.num_pairs != v * (v - 1) // 2 or len(packed.offsets) != b * packed.num_pairs + 1:
+        raise ValueError(f"pose_loss: the correspondences are packed for {packed.num_scenes} scenes and {packed.num_pairs} pairs, "
+                         f"the points are of {b} scenes and {v} views ({v * (v - 1) // 2} pairs)")
+    tensors = (xyz, depth, poses, intrinsics, packed.ids_i, packed.ids_j, packed.weights, packed.conf, packed.offsets_device)
+    if not all(t.is_cuda for t in tensors):
+        raise RuntimeError("pf3plat_amd losses: tensors must be on a ROCm device (there is no CPU fallback path)")
+    if any(t.device != xyz.device for t in tensors):
+        raise RuntimeError("pose_loss: every tensor must be on the same device")
+    return b, v, h, w
+
+
+def _pose_call(fn, b, v, h, w, packed, arrays, weight_2d, weight_3d, tail, dev):
+    n = len(packed.offsets)
+    host = (ctypes.c_int32 * n)(*packed.offsets)
+    with _on_device(dev):
+        rc = fn(b, v, h, w, packed.num_pairs, *(t.data_ptr() for t in arrays), packed.ids_i.data_ptr(), packed.ids_j.data_ptr(),
+                packed.weights.data_ptr(), packed.conf.data_ptr(), host, packed.offsets_device.data_ptr(), weight_2d, weight_3d,
+                *(t.data_ptr() for t in tail), _stream_ptr(dev))
+    return rc
+
+
+def _pose_units(lib, packed) -> int:
+    n = len(packed.offsets)
+    units = int(lib.gsr_pose_loss_units(n - 1, (ctypes.c_int32 * n)(*packed.offsets)))
+    if units < 0:
+        raise RuntimeError("gsr_pose_loss_units refused the offsets")
+    return units
+
+
+class _PoseLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xyz, depth, poses, intrinsics, packed, weight_2d, weight_3d):
+        b, v, h, w = _pose_loss_args(xyz, depth, poses, intrinsics, packed)
+        lib = _lib.load()
+        dev, f32 = xyz.device, torch.float32
+        arrays = (_f32(xyz), _f32(depth), _f32(poses), _f32(intrinsics))
+        units = _pose_units(lib, packed)
+        partials = torch.empty((max(units, 1), 4), dtype=f32, device=dev)
+        lists = torch.empty((max(b * packed.num_pairs, 1), 4), dtype=f32, device=dev)
+        out = torch.empty(4, dtype=f32, device=dev)
+        rc = _pose_call(lib.gsr_pose_loss, b, v, h, w, packed, arrays, weight_2d, weight_3d, (partials, lists, out), dev)
+        if rc != 0:
+            raise RuntimeError(f"gsr_pose_loss failed with code {rc}")
+        ctx.save_for_backward(xyz, depth, poses, intrinsics, lists)
+        ctx.call = (b, v, h, w, packed, weight_2d, weight_3d, units)
+        loss, loss_3d, loss_2d = out[0], out[1], out[2]
+        ctx.mark_non_differentiable(loss_3d, loss_2d)
+        return loss, loss_3d, loss_2d
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_3d, _g_2d):
+        xyz, depth, poses, intrinsics, lists = ctx.saved_tensors
+        b, v, h, w, packed, weight_2d, weight_3d, units = ctx.call
+        lib = _lib.load()
+        dev, f32 = xyz.device, torch.float32
+        arrays = (_f32(xyz), _f32(depth), _f32(poses), _f32(intrinsics))
+        d_xyz = torch.empty((b, v, 3, h, w), dtype=f32, device=dev)  # (zero-filled by the call)
+        d_depth = torch.empty((b, v, h, w), dtype=f32, device=dev)
+        d_poses = torch.empty((b, v, 4, 4), dtype=f32, device=dev)
+        partials = torch.empty((max(units, 1), 12), dtype=f32, device=dev)
+        up = _f32(g_loss).reshape(1)
+        rc = _pose_call(lib.gsr_pose_loss_backward, b, v, h, w, packed, arrays, weight_2d, weight_3d,
+                        (lists, up, d_xyz, d_depth, d_poses, partials), dev)
+        if rc != 0:
+            raise RuntimeError(f"gsr_pose_loss_backward failed with code {rc}")
+        need = ctx.needs_input_grad
+        return (d_xyz.to(xyz.dtype) if need[0] else None, d_depth.reshape(depth.shape).to(depth.dtype) if need[1] else None,
+                d_poses.to(poses.dtype) if need[2] else None, None, None, None, None)
+
+
+def pose_loss(xyz: Tensor, depth: Tensor, poses: Tensor, intrinsics: Tensor, packed: PackedCorrespondences, weight_2d: float, weight_3d: float):
+    """xyz (b, v, 3, h, w), depth ((b v), 1, h, w) or (b, v, h, w), poses (b, v, 4, 4) (the top three rows are read), normalised
+    intrinsics (b, v, 3, 3), the packed match lists -> (loss, mean 3D term, mean 2D term), loss = weight_3d x mean 3D + weight_2d x
+    mean 2D as include/gsr.h defines them; differentiable in xyz, depth and poses (the two means are for logging).  Two launches
+    forward, a zero-fill and two launches backward, no host synchronisation either way.  Inputs that are not float32 or not
+    contiguous are converted.  Ids outside [0, h * w) are the caller's error and are NOT checked per match."""
+    return _PoseLoss.apply(xyz, depth, poses, intrinsics, packed, float(weight_2d), float(weight_3d))
+
+
+@dataclass
+class LossposeCfg:
+    weight_2d: float
+    weight_3d: float
+
+
+class Losspose(torch.nn.Module):
+    """`forward(prediction, batch, gaussians, global_step, c2w, depth, corr, xyz_h)` as the reference's Losspose: it reads
+    batch["target"]["intrinsics"], the learned poses c2w[1], the refined depth depth[0], the matches corr[0] with their confidences
+    corr[2] and the refined points xyz_h, and ignores c2w[0] (the reference computes a second pair of terms from it and drops them)."""
+
+    def __init__(self, cfg: LossposeCfg):
+        super().__init__()
+        self.cfg = cfg
+
+    def forward(self, prediction, batch, gaussians, global_step, c2w, depth, corr, xyz_h) -> Tensor:
+        packed = pack_correspondences(corr[0], corr[2])
+        return pose_loss(xyz_h, depth[0], c2w[1], batch["target"]["intrinsics"], packed, self.cfg.weight_2d, self.cfg.weight_3d)[0]
