@@ -5519,7 +5519,8 @@ struct PoseLossArgs {
 
 struct PoseList {
   int list, s, i, j, begin, end;
-  float R[9], t[3], Ki[9], Kj[9];  // Rt of the list (i -> j), K_i^-1, K_j
+  float R[9], t[3], Kj[9];      // Rt of the list (i -> j), K_j
+  double Rd[9], td[3], Kid[9];  // Rt before its rounding to float and K_i^-1: the reprojection chain (pose_match) runs in fp64
 };
 
 __device__ __forceinline__ int pose_units_of(int m0, int m1) { return (m1 - m0 + kPoseUnit - 1) / kPoseUnit; }
@@ -5574,6 +5575,10 @@ __device__ __forceinline__ void pose_list_of_unit(const PoseLossArgs& a, int uni
   if (c.i == 0) {  // the reference's shortcut: poses[s, 0] is taken as the identity, whatever it holds
 #pragma unroll
     for (int k = 0; k < 3; ++k) { c.R[3 * k] = Pj[4 * k]; c.R[3 * k + 1] = Pj[4 * k + 1]; c.R[3 * k + 2] = Pj[4 * k + 2]; c.t[k] = Pj[4 * k + 3]; }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) c.Rd[k] = (double)c.R[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) c.td[k] = (double)c.t[k];
   } else {
     double A[12];
     pose_affine_inverse(a.poses + ((size_t)c.s * a.V + c.i) * 16, A);
@@ -5581,18 +5586,17 @@ __device__ __forceinline__ void pose_list_of_unit(const PoseLossArgs& a, int uni
     for (int k = 0; k < 3; ++k) {
       const double x = Pj[4 * k], y = Pj[4 * k + 1], z = Pj[4 * k + 2];
 #pragma unroll
-      for (int q = 0; q < 3; ++q) c.R[3 * k + q] = (float)(x * A[q] + y * A[4 + q] + z * A[8 + q]);
-      c.t[k] = (float)(x * A[3] + y * A[7] + z * A[11] + (double)Pj[4 * k + 3]);
+      for (int q = 0; q < 3; ++q) { c.Rd[3 * k + q] = x * A[q] + y * A[4 + q] + z * A[8 + q]; c.R[3 * k + q] = (float)c.Rd[3 * k + q]; }
+      c.td[k] = x * A[3] + y * A[7] + z * A[11] + (double)Pj[4 * k + 3];
+      c.t[k] = (float)c.td[k];
     }
   }
   const float* Ki = a.intr + ((size_t)c.s * a.V + c.i) * 9;
   const float* Kj = a.intr + ((size_t)c.s * a.V + c.j) * 9;
-  double k64[9], kinv[9];
+  double k64[9];
 #pragma unroll
   for (int k = 0; k < 9; ++k) { k64[k] = (double)Ki[k]; c.Kj[k] = Kj[k]; }
-  pose_inv3(k64, kinv);
-#pragma unroll
-  for (int k = 0; k < 9; ++k) c.Ki[k] = (float)kinv[k];
+  pose_inv3(k64, c.Kid);
 }
 
 struct PoseMatch {
@@ -5617,18 +5621,24 @@ __device__ __forceinline__ void pose_match(const PoseLossArgs& a, const PoseList
   const float fw = (float)a.W, fh = (float)a.H;
   const float cx = ((float)(ia - ya * W) + 0.5f) / fw, cy = ((float)ya + 0.5f) / fh;
   const float bx = ((float)(ib - yb * W) + 0.5f) / fw, by = ((float)yb + 0.5f) / fh;
-  float Q[3];
+  // The reprojection in fp64, from the float32 pixel centres to the residual: where the poses are near the identity q and c(id_j)
+  // agree to 1e-3 and float32 would keep four digits of their difference (and of the 2D term and its gradient, list after list:
+  // much of that rounding sits in Rt and K_i^-1, common to a list's matches).  What the backward reads comes out as floats.
+  const double eps = 1e-6;
+  double ray[3], P[3], Q[3], u[3];
 #pragma unroll
-  for (int k = 0; k < 3; ++k) { m.ray[k] = c.Ki[3 * k] * cx + c.Ki[3 * k + 1] * cy + c.Ki[3 * k + 2]; m.P[k] = m.ray[k] * d; }
+  for (int k = 0; k < 3; ++k) { ray[k] = c.Kid[3 * k] * (double)cx + c.Kid[3 * k + 1] * (double)cy + c.Kid[3 * k + 2]; P[k] = ray[k] * (double)d; }
 #pragma unroll
-  for (int k = 0; k < 3; ++k) Q[k] = (c.R[3 * k] * m.P[0] + c.R[3 * k + 1] * m.P[1] + c.R[3 * k + 2] * m.P[2] + c.t[k]) / (1.f + kPoseHomEps);
-  float u[3];
+  for (int k = 0; k < 3; ++k) Q[k] = (c.Rd[3 * k] * P[0] + c.Rd[3 * k + 1] * P[1] + c.Rd[3 * k + 2] * P[2] + c.td[k]) / (1.0 + eps);
 #pragma unroll
-  for (int k = 0; k < 3; ++k) u[k] = c.Kj[3 * k] * Q[0] + c.Kj[3 * k + 1] * Q[1] + c.Kj[3 * k + 2] * Q[2];
-  m.uz = u[2] + kPoseHomEps;
-  m.q[0] = u[0] / m.uz; m.q[1] = u[1] / m.uz;
-  m.e[0] = m.q[0] - bx; m.e[1] = m.q[1] - by;
-  m.r2 = sqrtf(m.e[0] * m.e[0] + m.e[1] * m.e[1]);
+  for (int k = 0; k < 3; ++k) u[k] = (double)c.Kj[3 * k] * Q[0] + (double)c.Kj[3 * k + 1] * Q[1] + (double)c.Kj[3 * k + 2] * Q[2];
+  const double uz = u[2] + eps, q0 = u[0] / uz, q1 = u[1] / uz, e0 = q0 - (double)bx, e1 = q1 - (double)by;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { m.ray[k] = (float)ray[k]; m.P[k] = (float)P[k]; }
+  m.uz = (float)uz;
+  m.q[0] = (float)q0; m.q[1] = (float)q1;
+  m.e[0] = (float)e0; m.e[1] = (float)e1;
+  m.r2 = (float)sqrt(e0 * e0 + e1 * e1);
 }
 
 template <int kUnit>

@@ -77,8 +77,10 @@ def residuals(scene_or_tensors, dtype=torch.float64):
     return torch.cat(r3), torch.cat(r2), torch.cat(lid)
 
 
-def pose_loss(xyz, depth, poses, intrinsics, corr, conf, weight_2d, weight_3d, dtype=torch.float64):
-    """-> (loss, mean L3, mean L2); differentiable in xyz, depth and (the top three rows of) poses."""
+def pose_loss(xyz, depth, poses, intrinsics, corr, conf, weight_2d, weight_3d, dtype=torch.float64, per_list=False):
+    """-> (loss, mean L3, mean L2); differentiable in xyz, depth and (the top three rows of) poses.  per_list: a fourth entry,
+    (l3, l2, sum |score|) of every list in the kernels' list order (pair-major, then scene) - l3 with its confidence and its
+    normalisation, the sum of the scores as it is (not clamped)."""
     b, v = xyz.shape[:2]
     lists = b * len(pairs_of(v))
     r3, r2, lid = residuals((xyz, depth, poses, intrinsics, corr), dtype)
@@ -86,11 +88,12 @@ def pose_loss(xyz, depth, poses, intrinsics, corr, conf, weight_2d, weight_3d, d
     wgt = torch.cat([corr[p][s][2] for p, s in order]).to(dtype)
     cf = torch.stack([torch.as_tensor(conf[p][s]) for p, s in order]).to(dtype).reshape(lists)
     zero = torch.zeros(lists, dtype=dtype)
-    norm = zero.index_add(0, lid, wgt.abs()).clamp_min(1e-12)
-    l3 = cf * zero.index_add(0, lid, wgt * r3) / norm
+    sw = zero.index_add(0, lid, wgt.abs())
+    l3 = cf * zero.index_add(0, lid, wgt * r3) / sw.clamp_min(1e-12)
     l2 = zero.index_add(0, lid, _huber(r2))
     m3, m2 = l3.mean(), l2.mean()
-    return weight_3d * m3 + weight_2d * m2, m3, m2
+    loss = weight_3d * m3 + weight_2d * m2
+    return (loss, m3, m2, (l3, l2, sw)) if per_list else (loss, m3, m2)
 
 
 def pose_loss_loop(xyz, depth, poses, intrinsics, corr, conf, weight_2d, weight_3d):
@@ -133,13 +136,16 @@ def _rotation(g, angle):
     return torch.eye(3, dtype=torch.float64) + torch.sin(a) * k + (1 - torch.cos(a)) * (k @ k)
 
 
-def build_scene(seed, b, v, h, w, lengths, kinds, zero_weight_lists=(), repeat_lists=(), exact=False) -> Scene:
+def build_scene(seed, b, v, h, w, lengths, kinds, zero_weight_lists=(), repeat_lists=(), exact=False, signed_lists=(), corner_lists=()) -> Scene:
     """Seeded inputs.  lengths: one per list, pair-major then scene.  kinds: one per scene -
       "near":   every pose within 1e-3 of the identity, one K for the scene's views, id_j = id_i and x_j = x_i + 1e-2 noise: the
                 reprojection lands within ~1e-3 of the pixel it left, the QUADRATIC side of the Huber threshold 0.01;
       "random": general poses (view 0 included: the i == 0 shortcut must not read it), a K per view, unrelated random ids: the
                 reprojection misses by a good part of the image, the LINEAR side.
-    zero_weight_lists: lists whose scores are all 0.  repeat_lists: lists whose every entry names one pixel pair.  exact: poses
+    zero_weight_lists: lists whose scores are all 0.  repeat_lists: lists whose every entry names one pixel pair.  signed_lists:
+    lists whose scores carry a random sign each, |score| in [0.05, 1] as everywhere (the L1 norm is of |score|).  corner_lists: lists
+    whose first two matches name pixel 0 and pixel h * w - 1 in the first view - and the same two in the second view of a "near" scene,
+    crossed (h * w - 1, then 0) in that of a "random" one.  Neither option draws a number in a list it does not name.  exact: poses
     that are translations by multiples of 1 / 8, one K, and ONE point (multiples of 1 / 8 too) on every pixel of a scene, moved by
     each view's translation - the 3D residual of any two ids is exactly 0 in either precision (the norm's gradient there is taken
     as 0), while the ids, and with them the 2D term and the depth's gradient, stay those of the scene's kind."""
@@ -177,10 +183,16 @@ def build_scene(seed, b, v, h, w, lengths, kinds, zero_weight_lists=(), repeat_l
         for s in range(b):
             n = lengths[at]
             a = torch.randint(0, h * w, (n,), generator=g)
+            if at in corner_lists:
+                a[0], a[1] = 0, h * w - 1
             c = a.clone() if kinds[s] == "near" else torch.randint(0, h * w, (n,), generator=g)
             if at in repeat_lists:
                 a, c = a[:1].repeat(n), c[:1].repeat(n)
+            if at in corner_lists and kinds[s] != "near":
+                c[0], c[1] = h * w - 1, 0
             score = torch.zeros(n) if at in zero_weight_lists else (0.05 + 0.95 * rand(n)).to(torch.float32)
+            if at in signed_lists:
+                score = score * (2 * torch.randint(0, 2, (n,), generator=g) - 1).to(torch.float32)
             corr[p].append((a, c, score))
             at += 1
     assert at == len(lengths) == b * len(pairs_of(v))

@@ -2,7 +2,20 @@
 restatement tests/pose_loss_ref.py.  CPU: the float64 restatement against numbers recorded from the reference's own Losspose
 (tests/golden/pose_loss_fixtures.npz), the host side of the three C entry points, the Python argument checks, and the conditions the
 GPU cases rely on (both sides of the Huber threshold populated; every bar under the project's 1e-4).  GPU: value and the three
-gradients of every case against the float64 restatement, the bar tied to what the SAME restatement loses in float32."""
+gradients of every case against the float64 restatement, the bar tied to what the SAME restatement loses in float32; the rows of
+`lists` and the two logged means of the larger cases against float64, list by list, through the C entry point.
+
+The first eight cases end every reduction loop of the four kernels in one trip.  The others are there for the further trips:
+  l16      16 lists: k_pose_loss_finish's loop over blocks of 16 lists runs once, full to its last wave;
+  l17      17 lists: a second block that holds one list, which finds its rows behind `first += total` of block 0; list 15, the last
+           wave of block 0, is empty;
+  train42  42 lists of about 1000 matches (the training batch's count, 14 scenes x 3 pairs): three blocks, `first` carried twice,
+           `before` inside a block over lists of 3 to 6 units, lengths 0 / 1024 / 1023 / 1025 on the two block edges;
+  b7v5     70 lists, five views: the final sum over lists (l = lane, lane + 64) takes a second trip for lists 64 .. 69, as does
+           k_pose_loss_pose_reduce's count of the units in front of list l for l >= 65; pose_pair_of for ten pairs, i up to 3;
+  long     lists of 16 641 and 16 384 matches: 66 units (lane k of the finish adds rows k and k + 64) beside exactly 64 (one trip);
+  signed   scores of both signs: the L1 norm is of |score|;
+  wide     200 x 328 pixels: ids above 2^16, the first and the last pixel, / and % by a width that is no power of two."""
 import ctypes
 import functools
 import os
@@ -24,7 +37,8 @@ K_OWN = 4.0  # tests/test_losses.py: another order of the same float32 operation
 FLOOR = {"value": 2.3e-6, "xyz": 3.9e-6, "depth": 2.5e-6, "poses": 2.1e-5}
 CAP = 1e-4  # the project's bar: no case's may be wider - an input that needs more is badly chosen
 EDGE_LENGTHS = (0, 1, 7, 63, 64, 65, 255, 256, 257, 700, 130, 0)  # wave and unit edges, several units in a list
-# name -> build_scene arguments (seed, b, v, h, w, lengths, kinds, ...)
+MIXED = ("random", "random", "near")  # kinds by scene, s % 3
+# name -> build_scene arguments (seed, b, v, lengths, kinds, ...; h, w where they are not H, W)
 CASES = {
     # scene 1 "random": poses[1, 0] is a general matrix, which the i == 0 shortcut must not read
     "b2v3": dict(seed=1, b=2, v=3, lengths=(65, 0, 256, 7, 130, 63), kinds=("near", "random")),
@@ -35,14 +49,31 @@ CASES = {
     "one_pixel": dict(seed=6, b=1, v=3, lengths=(300, 5, 70), kinds=("random",), repeat_lists=(0, 2)),
     "zero_residual": dict(seed=7, b=1, v=2, lengths=(100,), kinds=("random",), exact=True),  # 3D residuals exactly 0
     "fixture": dict(seed=77, b=2, v=3, lengths=(0, 1, 7, 64, 65, 130), kinds=("near", "random")),  # make_pose_loss_fixtures.py's
+    # the loops past their first trip (the header says which).  Seeds: among ~20 000 unrelated id pairs a few reproject within 0.01 of
+    # their partner by chance; each seed is the first from the case's own number (16, 17, 42, 75, 8, 9, 10) that leaves every match at
+    # least 1e-4 on its scene's side of the Huber threshold in float64.  l16, l17: 15 and 16 units
+    "l16": dict(seed=17, b=16, v=2, lengths=(0, 1, 255, 256, 257, 65, 0, 1, 255, 256, 257, 65, 0, 1, 255, 256), kinds=(MIXED * 6)[:16]),
+    "l17": dict(seed=18, b=17, v=2, lengths=(0, 1, 255, 256, 257, 65, 0, 1, 255, 256, 257, 65, 0, 1, 255, 0, 300), kinds=(MIXED * 6)[:17]),
+    # 184 units; lists 15 | 16 and 31 | 32 lie on the block edges
+    "train42": dict(seed=65, b=14, v=3, h=32, w=48, kinds=("random", "near") * 7,
+                    lengths=(1056, 1199, 940, 1036, 870, 827, 1210, 1010, 1378, 755, 1135, 748, 1166, 1059, 789, 0,
+                             1024, 1243, 1278, 838, 775, 797, 610, 749, 1337, 1288, 1178, 1194, 1141, 1375, 756, 1023,
+                             1025, 841, 986, 1075, 647, 1316, 1060, 765, 827, 1300)),
+    # 74 units; the cycle 0, 1, 7, 63, 64, 65, 255, 256, 257 up to list 63, then lists 64 .. 69 of 2, 1, 3, 1, 3 and 1 units
+    "b7v5": dict(seed=75, b=7, v=5, kinds=("random", "random", "near", "random", "random", "near", "random"),
+                 lengths=(0, 1, 7, 63, 64, 65, 255, 256, 257) * 7 + (0, 257, 65, 700, 7, 513, 256)),
+    "long": dict(seed=16, b=2, v=2, h=96, w=176, lengths=(16641, 16384), kinds=("random", "near")),  # 66 and 64 units
+    "signed": dict(seed=10, b=1, v=3, lengths=(70, 257, 9), kinds=("random",), signed_lists=(0, 1, 2)),
+    "wide": dict(seed=10, b=1, v=2, h=200, w=328, lengths=(600,), kinds=("random",), corner_lists=(0,)),
 }
+LIST_CASES = ("l17", "train42", "b7v5", "long")  # the cases whose rows of `lists` are compared one by one
 QUANTITIES = ("value", "xyz", "depth", "poses")
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pose_loss_fixtures.npz")
 
 
 @functools.lru_cache(maxsize=None)
 def scene(name):
-    return ref.build_scene(h=H, w=W, **CASES[name])
+    return ref.build_scene(**{"h": H, "w": W, **CASES[name]})
 
 
 @functools.lru_cache(maxsize=None)
@@ -72,6 +103,30 @@ def own_error(name):
 
 def bars(name):
     return {q: max(FLOOR[q], K_OWN * e) for q, e in own_error(name).items()}
+
+
+@functools.lru_cache(maxsize=None)
+def restated_lists(name, dtype):
+    """-> (rows, m3, m2): the rows of `lists` as include/gsr.h defines them - (conf x L3 term, L2 term, w3d x conf / (max(sum |w|,
+    1e-12) x L), sum |w|), list order pair-major then scene - from the restatement's per-list terms and the inputs, and the two
+    logged means; everything computed in `dtype`, returned as float64 numpy."""
+    sc = scene(name)
+    with torch.no_grad():
+        _, m3, m2, (l3, l2, sw) = ref.pose_loss(sc.xyz, sc.depth, sc.poses, sc.intrinsics, sc.corr, sc.conf, WEIGHT_2D, WEIGHT_3D, dtype, per_list=True)
+    b, v = sc.xyz.shape[:2]
+    cf = torch.stack([sc.conf[p][s] for p in ref.pairs_of(v) for s in range(b)]).to(dtype)
+    factor = torch.tensor(WEIGHT_3D, dtype=dtype) * cf / (sw.clamp_min(1e-12) * len(cf))
+    rows = torch.stack([l3, l2, factor, sw], -1)
+    assert rows.dtype == dtype and rows.shape == (len(CASES[name]["lengths"]), 4)
+    return rows.double().numpy(), float(m3), float(m2)
+
+
+def per_entry(got, want):
+    """|got - want| / |want| entry by entry; where the reference is exactly zero: 0 for an exact zero, inf for anything else."""
+    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
+    assert got.shape == want.shape and np.all(np.isfinite(got))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(want != 0, np.abs(got - want) / np.abs(want), np.where(got == 0, 0.0, np.inf))
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -116,6 +171,14 @@ def test_cases_populate_both_sides_of_the_huber_threshold_and_bars_stay_under_th
               + "  ".join(f"{q} {own[q]:.1e}" for q in QUANTITIES))
         assert all(b <= CAP for b in bar.values()), (name, bar)
     assert sorted(set(CASES["v4"]["lengths"])) == [0, 1, 7, 63, 64, 65, 130, 255, 256, 257, 700]
+    sc = scene("signed")  # both signs in every list, and an L1 norm that is nowhere near the clamp at 1e-12
+    for p in ref.pairs_of(3):
+        score = sc.corr[p][0][2]
+        assert bool((score < 0).any()) and bool((score > 0).any()) and float(score.abs().min()) >= 0.05 and float(score.abs().sum()) > 1, p
+        assert abs(float(score.sum())) < 0.75 * float(score.abs().sum()), p  # a sum without the absolute value is another number
+    sc = scene("wide")
+    a, c, _ = sc.corr[(0, 1)][0]
+    assert (sc.xyz.shape[-2:], a[:2].tolist(), c[:2].tolist()) == ((200, 328), [0, 200 * 328 - 1], [200 * 328 - 1, 0]) and 200 * 328 > 1 << 16
 
 
 def test_pose_loss_symbols_unit_count_and_argument_errors():
@@ -135,6 +198,13 @@ def test_pose_loss_symbols_unit_count_and_argument_errors():
     assert units(0) == 0 and units(0, 0, 0) == 0 and units(0, 1) == 1 and units(0, 256) == 1 and units(0, 257) == 2
     assert units(*np.cumsum((0,) + EDGE_LENGTHS).tolist()) == 0 + 1 + 1 + 1 + 1 + 1 + 1 + 1 + 2 + 3 + 1 + 0 == 13
     assert units(5, 5, 261, 1000) == 0 + 1 + 3  # a start other than 0 is allowed
+    of_case = lambda name: units(*np.cumsum((0,) + CASES[name]["lengths"]).tolist())
+    assert (of_case("l16"), of_case("l17"), of_case("train42"), of_case("b7v5"), of_case("long")) == (15, 16, 184, 74, 66 + 64)
+    assert [len(CASES[n]["lengths"]) for n in ("l16", "l17", "train42", "b7v5", "long")] == [16, 17, 42, 70, 2]
+    assert units(0, *np.cumsum(CASES["b7v5"]["lengths"][:64]).tolist()) == 63 and units(0, *np.cumsum(CASES["b7v5"]["lengths"][64:]).tolist()) == 11
+    assert CASES["l17"]["lengths"][15:] == (0, 300) and all(n > 0 for n in CASES["b7v5"]["lengths"][64:])
+    t42 = CASES["train42"]["lengths"]
+    assert (t42[15], t42[16], t42[31], t42[32]) == (0, 1024, 1023, 1025) and t42[41] > 4 * 256 and 950 < sum(t42) / 42 < 1050
     assert units(0, 3, 2) == -1 and units(-1, 3) == -1 and lib.gsr_pose_loss_units(1, None) == -1 and lib.gsr_pose_loss_units(-1, arr(0)) == -1
     invalid = -1  # GSR_ERR_INVALID_ARGUMENT of include/gsr.h
     p = ctypes.c_void_p(4096)  # a non-null address that is never read: every call below returns before its launch
@@ -258,10 +328,103 @@ def test_hip_pose_loss_against_float64_restatement(name):
         assert all(not bool(got[q].any()) for q in QUANTITIES)
 
 
+def run_c_forward(name):
+    """gsr_pose_loss itself on a case's inputs (ctypes, as tools/pose_loss_prof.py calls it: `lists` is no output of the torch
+    function) -> (lists (L, 4), out (4,)) as float64 numpy.  All three outputs start as NaN: what the kernels leave out shows."""
+    from pf3plat_amd import _lib, losses
+    from pf3plat_amd.rasterizer import _stream_ptr
+
+    lib, dev = _lib.load(), torch.device(DEV)
+    sc = scene(name)
+    b, v, _, h, w = sc.xyz.shape
+    xyz, depth, poses, intr = (t.to(dev).contiguous() for t in (sc.xyz, sc.depth, sc.poses, sc.intrinsics))
+    corr = {p: [tuple(t.to(dev) for t in entry) for entry in lists] for p, lists in sc.corr.items()}
+    packed = losses.pack_correspondences(corr, {p: c.to(dev) for p, c in sc.conf.items()})
+    num_lists = len(packed.offsets) - 1
+    host = (ctypes.c_int32 * len(packed.offsets))(*packed.offsets)
+    units = int(lib.gsr_pose_loss_units(num_lists, host))
+    assert num_lists == len(CASES[name]["lengths"]) and units >= 0 and packed.offsets[-1] == sum(CASES[name]["lengths"])
+    nan = dict(dtype=torch.float32, device=dev)
+    partials, lists, out = torch.full((max(units, 1), 4), float("nan"), **nan), torch.full((num_lists, 4), float("nan"), **nan), torch.full((4,), float("nan"), **nan)
+    status = lib.gsr_pose_loss(b, v, h, w, v * (v - 1) // 2, xyz.data_ptr(), depth.data_ptr(), poses.data_ptr(), intr.data_ptr(), packed.ids_i.data_ptr(),
+                               packed.ids_j.data_ptr(), packed.weights.data_ptr(), packed.conf.data_ptr(), host, packed.offsets_device.data_ptr(),
+                               WEIGHT_2D, WEIGHT_3D, partials.data_ptr(), lists.data_ptr(), out.data_ptr(), _stream_ptr(dev))
+    assert status == 0
+    return lists.double().cpu().numpy(), out.double().cpu().numpy()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", LIST_CASES)
+def test_hip_pose_loss_rows_of_lists_and_the_two_means_against_float64(name):
+    """Every row of `lists` - (conf x L3 term, L2 term, w3d x conf / (max(sum |w|, 1e-12) x L), sum |w|) - against the float64
+    restatement's per-list terms and the inputs, entry by entry and relative; an entry that is exactly 0 in float64 (an empty list's
+    sums) has to be exactly 0.  A list's bar is the value rule applied to that list: max(FLOOR["value"], 4 x the largest relative
+    distance of the float32 restatement's row of the same list), never above 1e-4.  The value alone cannot see a unit that went to
+    the wrong list - the total of the 2D term does not change - and sees a wrong 3D row only through that list's normalisation.
+    out[1] and out[2] against the float64 means at the case's value bar.
+    The 2D entry is what this test changed in the kernels.  In a "near" scene every 2D residual is the difference of two
+    coordinates near 0.5 that agree to 1e-3; with the reprojection in float32 the kernel kept four digits of it, as the float32
+    restatement does (its rows are up to 4.0e-5 from float64 in this entry), and three rows - train42 lists 33 and 37, b7v5 list 37,
+    all of pairs with i > 0 - lay 4.3e-5, 2.3e-5 and 4.5e-5 from float64 against bars of 1.4e-5, 4.3e-6 and 2.1e-5: one list's own
+    float32 distance is one draw from a range, the kernel's another.  pose_match now carries the reprojection from the pixel centre
+    to the residual in fp64 (Rt and K_i^-1 unrounded), and the worst row of the four cases is 7.4e-6 from float64 (docs/PARITY.md 13.1)."""
+    got, out = run_c_forward(name)
+    (want, m3, m2), (own_rows, _, _) = restated_lists(name, torch.float64), restated_lists(name, torch.float32)
+    lengths = CASES[name]["lengths"]
+    units = [(n + 255) // 256 for n in lengths]
+    assert got.shape == want.shape == (len(lengths), 4)
+    each = per_entry(got, want)
+    err, own = each.max(axis=1), per_entry(own_rows, want).max(axis=1)
+    assert np.all(np.isfinite(own)), name
+    bar = np.minimum(np.maximum(FLOOR["value"], K_OWN * own), CAP)
+    worst = int(np.argmax(err / bar))
+    entry = ("conf x L3", "L2", "3D factor", "sum |w|")[int(np.argmax(each[worst]))]
+    where = f"list {worst} (block {worst // 16}, {lengths[worst]} matches in {units[worst]} units, {sum(units[:worst])} units in front of it), entry {entry}"
+    print(f"[pose] {name:13s} lists   hip vs float64, worst in bars: {err[worst]:.3e} of {bar[worst]:.3e} at {where}; largest distance {err.max():.3e} "
+          f"(list {int(np.argmax(err))}); float32 restatement vs float64, largest: {own.max():.3e} (list {int(np.argmax(own))})")
+    value_bar = bars(name)["value"]
+    means = {"mean L3": distance(out[1], m3), "mean L2": distance(out[2], m2)}
+    print(f"[pose] {name:13s} means   hip vs float64: " + "  ".join(f"{k} {e:.3e}" for k, e in means.items()) + f"   bar: {value_bar:.3e}")
+    over = np.nonzero(~(err <= bar))[0]
+    problems = []
+    if len(over):
+        problems.append(f"{len(over)} of {len(lengths)} rows of lists off; worst: {where}, row {got[worst].tolist()} against {want[worst].tolist()}, "
+                        f"{err[worst]:.3e} > {bar[worst]:.3e}; all (list, block, units, distance, bar): "
+                        + str([(int(l), int(l) // 16, units[l], float(f"{err[l]:.3e}"), float(f"{bar[l]:.3e}")) for l in over]))
+    if not (value_bar <= CAP and all(e <= value_bar for e in means.values())):
+        problems.append(f"means off: {means}, bar {value_bar:.3e}")
+    assert not problems, f"{name}: " + "; ".join(problems)
+    assert out[3] == 0.0
+
+
+@pytest.mark.gpu
+def test_hip_pose_loss_first_and_last_pixel_of_a_wide_image():
+    """200 x 328: ids above 2^16 and a width that is no power of two.  The gradients reach pixel 0 and pixel h * w - 1 of the first
+    view (the case's first two matches name them) and are exactly zero at every pixel that no match names (dL/ddepth: of the pair's
+    second view at every pixel - only the first view's depth is read)."""
+    sc = scene("wide")
+    h, w = sc.xyz.shape[-2:]
+    a, c, _ = sc.corr[(0, 1)][0]
+    _, got = run_hip("wide")
+    d_xyz, d_depth = got["xyz"].reshape(2, 3, h * w).cpu(), got["depth"].reshape(2, h * w).cpu()
+    for pixel in (0, h * w - 1):
+        assert bool((d_xyz[0, :, pixel] != 0).all()) and bool((d_xyz[1, :, pixel] != 0).all()) and float(d_depth[0, pixel]) != 0, pixel
+    named = torch.zeros(2, h * w, dtype=torch.bool)
+    named[0, a], named[1, c] = True, True
+    assert int(named[0].sum()) > 500 and not bool(d_xyz.permute(0, 2, 1)[~named].any())
+    assert not bool(d_depth[0][~named[0]].any()) and not bool(d_depth[1].any())
+    assert bool((d_xyz.permute(0, 2, 1)[named] != 0).any(-1).all()) and bool((d_depth[0][named[0]] != 0).all())
+
+
 @pytest.mark.gpu
 def test_hip_pose_loss_repeats_bit_for_bit():
-    """The loss and dL/dposes of a repeated call are the same bits (fixed-order reductions); so are the gradients of a case in which
-    no pixel receives more than two contributions."""
+    """The loss and dL/dposes of a repeated call are the same bits (fixed-order reductions), at every list count and list length
+    (three blocks of lists, more than 64 lists, more than 64 units in a list); so are the gradients of a case in which no pixel
+    receives more than two contributions."""
+    for name in ("train42", "b7v5", "long"):
+        (a, _, _), ga = run_hip(name)
+        (b, _, _), gb = run_hip(name)
+        assert torch.equal(a, b) and torch.equal(ga["poses"], gb["poses"]), name
     for name in ("v4", "v2"):
         (a, _, _), ga = run_hip(name)
         (b, _, _), gb = run_hip(name)
