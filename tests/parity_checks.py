@@ -92,12 +92,13 @@ FLAG_FULL_LISTS = 0x20000  # GSR_FLAG_FULL_LISTS (include/gsr.h)
 PREFIX = 512  # list positions the tile launch of the usual case orders before it blends (kPrefix, gsr_hip.hip)
 
 
-def check_tile_lists(res, cfg, v=0, max_tiles=None, rng=None):
+def check_tile_lists(res, cfg, v=0, max_tiles=None, rng=None, tiles=None):
     """Each 8x8 tile's list is sorted by (depth, id), is a subset of the reference's 16x16-tile list for the parent
     tile, and contains every splat of that list that can contribute in the tile (so dropping the rest changes nothing).
     Without GSR_FLAG_FULL_LISTS only the nearest part of a list is ordered - max(512, entries the tile walked) positions are
     guaranteed (include/gsr.h) - and that part is what is checked: sorted, a subset, and complete up to its last key (no
-    contributing splat of the parent list that is nearer than the prefix's last entry may be absent from it)."""
+    contributing splat of the parent list that is nearer than the prefix's last entry may be absent from it).
+    Which tiles: all T, a random sample of `max_tiles`, or exactly the indices in `tiles`."""
     ws = res["hip"]["ws"]
     o, _ = res["oracle"]["handles"][v]
     geo = o.geometry()
@@ -107,9 +108,12 @@ def check_tile_lists(res, cfg, v=0, max_tiles=None, rng=None):
     sgx, T = ws["sgx"], ws["T"]
     full = bool(cfg.flags & FLAG_FULL_LISTS)
     depth_bits = geo["depth"].astype(np.float32).view(np.uint32).astype(np.int64)
-    tiles = np.arange(T)
-    if max_tiles is not None and T > max_tiles:
+    if tiles is not None:
+        tiles = np.asarray(tiles, dtype=np.int64)
+    elif max_tiles is not None and T > max_tiles:
         tiles = (rng or np.random.default_rng(0)).choice(T, max_tiles, replace=False)
+    else:
+        tiles = np.arange(T)
     m = dict(unsorted=0, not_subset=0, missing=0, pairs=0, pairs16=int(len(binn["point_list"])), checked_tiles=len(tiles),
              extra_kept=0, prefix_only_tiles=0)
     for t in tiles:
@@ -136,6 +140,59 @@ def check_tile_lists(res, cfg, v=0, max_tiles=None, rng=None):
         m["extra_kept"] += len(ids) - len(need)
     assert m["unsorted"] == 0 and m["not_subset"] == 0 and m["missing"] == 0, m
     return m
+
+
+def _all_lists(ws, V, T):
+    """Every (view, tile) list of a decoded workspace laid end to end in (v, t) order: -> (lens int64 (V * T,), ids)."""
+    r = ws["ranges"].reshape(V * T, 2).astype(np.int64)
+    lens = r[:, 1] - r[:, 0]
+    assert (lens >= 0).all() and (r[:, 0] >= 0).all() and (r[:, 1] <= len(ws["point_list"])).all(), "a range outside the index list"
+    first = np.cumsum(lens) - lens  # position of each list in the concatenation
+    idx = np.repeat(r[:, 0] - first, lens) + np.arange(int(lens.sum()), dtype=np.int64)
+    return lens, ws["point_list"][idx]
+
+
+def ranges_are_the_scan(ws, V, T):
+    """The windowed chain's list ranges are, by definition (k_tile_scan, or the scan inside k_emit), the exclusive prefix sum of the
+    list lengths over ALL (view, tile) in that order, the last end is the pair total, the longest list is max_list, and nothing
+    overflowed.  Exact: plain int64 numpy over every one of the V * T ranges."""
+    r = ws["ranges"].reshape(V * T, 2).astype(np.int64)
+    lens = r[:, 1] - r[:, 0]
+    assert ws["overflow"] == 0, ws["overflow"]
+    assert (lens >= 0).all(), ("negative list length", int((lens < 0).sum()))
+    start = np.cumsum(lens) - lens
+    bad = np.flatnonzero(r[:, 0] != start)
+    assert bad.size == 0, ("range starts differ from the exclusive scan of the lengths", bad.size, "first (v, t)", divmod(int(bad[0]), T),
+                           "is", int(r[bad[0], 0]), "scan", int(start[bad[0]]))
+    assert int(r[-1, 1]) == ws["num_pairs"], (int(r[-1, 1]), ws["num_pairs"])
+    assert int(lens.max()) == ws["max_list"], (int(lens.max()), ws["max_list"])
+    return dict(lists=int(V * T), pairs=int(lens.sum()), max_list=int(lens.max()), empty_lists=int((lens == 0).sum()))
+
+
+def same_lists_as_fused(ws_windowed, ws_fused, V, T, full=True):
+    """Every (view, tile) list of the windowed chain against the fused binning's for the same call, over ALL V * T lists: equal
+    lengths, equal pair total and max_list, and equal ids position by position (`full`: both calls carried GSR_FLAG_FULL_LISTS, so
+    whole lists are ordered).  Without the flag only the part check_tile_lists calls ordered - max(512, entries walked) positions -
+    is compared position by position and the rest of each list as a sorted id array."""
+    assert ws_windowed["num_pairs"] == ws_fused["num_pairs"] and ws_windowed["max_list"] == ws_fused["max_list"], \
+        (ws_windowed["num_pairs"], ws_fused["num_pairs"], ws_windowed["max_list"], ws_fused["max_list"])
+    lw, iw = _all_lists(ws_windowed, V, T)
+    lf, if_ = _all_lists(ws_fused, V, T)
+    bad = np.flatnonzero(lw != lf)
+    assert bad.size == 0, ("list lengths differ", bad.size, "first (v, t)", divmod(int(bad[0]), T), int(lw[bad[0]]), int(lf[bad[0]]))
+    if not full:  # beyond the ordered prefix: as sets - sort both tails by (list, id); the prefix keeps its positions
+        keep = np.minimum(lw, np.maximum(np.minimum(ws_windowed["walked"].reshape(-1), ws_fused["walked"].reshape(-1)).astype(np.int64), PREFIX))
+        lst = np.repeat(np.arange(V * T, dtype=np.int64), lw)
+        pos = np.arange(len(iw), dtype=np.int64) - np.repeat(np.cumsum(lw) - lw, lw)
+        tail = pos >= np.repeat(keep, lw)
+        for ids in (iw, if_):
+            k = np.lexsort((ids[tail], lst[tail]))
+            ids[tail] = ids[tail][k]
+    diff = np.flatnonzero(iw != if_)
+    if diff.size:
+        which = np.searchsorted(np.cumsum(lw), diff[0], side="right")
+        raise AssertionError(("list entries differ", int(diff.size), "of", int(len(iw)), "first in (v, t)", divmod(int(which), T)))
+    return dict(lists=int(V * T), pairs=int(len(iw)))
 
 
 def check_image(res, cfg, tol=TOL):
