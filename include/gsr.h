@@ -491,6 +491,47 @@ int gsr_pose_loss_backward(int num_scenes, int num_views, int height, int width,
                            float weight_2d, float weight_3d, const float* lists, const float* dL_dloss, float* dL_dxyz,
                            float* dL_ddepth, float* dL_dposes, float* partials, void* stream);
 
+/* The plane-sweep cost volume of the encoder (reference src/model/encoder/costvolume/depth_predictor_multiview.py:28-141 and
+ * 321-343: prepare_feat_proj_data_lists, warp_with_pose_depth_candidates and the correlation), one launch chain each way.
+ * Inputs, all f32: features (b, v, c, h, w); intrinsics (b, v, 3, 3), normalised; extrinsics (b, v, 4, 4), camera-to-world - the top
+ * three rows are read, the bottom row is taken as (0, 0, 0, 1); near, far (b, v); D = num_depth_candidates.
+ * Output: cost (v b, D, h, w), VIEW-MAJOR: row i b + s is view i of scene s (the reference's `(v b)` order).
+ * For row (i, s), pixel (x, y) with integer x in 0..w-1, y in 0..h-1 (no half-pixel offset) and candidate d:
+ *   K       = intrinsics[s, i] with row 0 x w and row 1 x h; view i's K both unprojects and reprojects into the other view (a
+ *             property of the reference, kept);
+ *   depth_d = 1 / (1 / far[s, i] + lin_d (1 / near[s, i] - 1 / far[s, i])), lin = linspace(0, 1, D) formed in float32 (D = 1: lin = [0]);
+ *   for k = 1 .. v-1 the other view is j = (i + k) mod v and P = extrinsics[s, j]^-1 extrinsics[s, i] (for v = 2, i = 1 the reference
+ *             forms the inverse of row 0's matrix: the same matrix), R_P, t_P its parts;
+ *   q       = K (R_P K^-1 (x, y, 1)^T depth_d + t_P);  px = q_x / max(q_z, 1e-3), py = q_y / max(q_z, 1e-3);
+ *   warp_k[c] = the bilinear sample of features[s, j, c] at (px, py) in pixel-index units (grid_sample with align_corners = True,
+ *             the reference's 2 px / (w - 1) - 1 undone), zero padding: a tap outside [0, w-1] x [0, h-1] contributes 0;
+ *   cost[i b + s, d, y, x] = 1 / (v - 1) sum_k sum_c features[s, i, c, y, x] warp_k[c] / sqrt(c).
+ * Set-up (P, K R_P K^-1, K t_P, the candidates) is formed in fp64 once per (row, other view); a sample is q = depth a + K t in
+ * fp32.  Whether a tap is inside is decided on floats before anything is converted to an integer: no px, py - huge, infinite or
+ * NaN (points behind the camera, q_z clamped) - leads to a read or an add outside the arrays.
+ * Gradients go to `features` only (the reference builds its grid under no_grad and detaches the candidates): each features row
+ * receives one gradient as the reference feature of its own row and one as the sampled feature of every row that samples it.
+ * Nothing proportional to c D h w exists in either direction.  `scratch`: gsr_cost_volume_scratch_bytes(b, v, c, h, w, backward)
+ * bytes (host arithmetic; 0 for sizes the calls refuse) - forward one channels-last copy of the features, (b, v, h, w, c rounded up
+ * to 4) floats; backward that copy again (everything is recomputed from the inputs: nothing is saved) and a gradient of the same
+ * shape, which the call zero-fills.
+ * gsr_cost_volume: a transpose launch and one launch over the volume; the same bits on every run.
+ * gsr_cost_volume_backward: takes the forward's inputs and dL_dcost (v b, D, h, w); a zero-fill, the transpose, one launch over the
+ *   volume and a transpose back; dL_dfeatures (b, v, c, h, w) is fully written.  The sampled-feature gradient is a scatter with
+ *   float atomics (the taps of consecutive candidates on the same source pixels are summed on chip first), and a pixel receives
+ *   adds from many rows' pixels in the order they arrive: dL_dfeatures is NOT bit-reproducible - its last bits can differ from run
+ *   to run wherever a source pixel is sampled from more than one pixel or walk segment (nearly everywhere).
+ * All three: GSR_ERR_INVALID_ARGUMENT (0 bytes), nothing launched, on a NULL pointer, b < 0, v < 2, c < 1, h < 2 or w < 2 (the
+ * reference's normalisation divides by w - 1), D < 1, or more than 2^31 - 1 elements in the features, the padded copy or the
+ * volume.  b == 0: nothing is launched. */
+size_t gsr_cost_volume_scratch_bytes(int num_scenes, int num_views, int channels, int height, int width, int backward);
+int gsr_cost_volume(int num_scenes, int num_views, int channels, int height, int width, int num_depth_candidates, const float* features,
+                    const float* intrinsics, const float* extrinsics, const float* near, const float* far, float* cost, void* scratch,
+                    void* stream);
+int gsr_cost_volume_backward(int num_scenes, int num_views, int channels, int height, int width, int num_depth_candidates,
+                             const float* features, const float* intrinsics, const float* extrinsics, const float* near,
+                             const float* far, const float* dL_dcost, float* dL_dfeatures, void* scratch, void* stream);
+
 /* Measurement aid: 1 when gsr_forward runs the colour pass inside the binning launch for these dims (two launches: binning +
  * colour, per-tile sort + blend), 0 when the colour pass is a launch of its own (images of more than 4608 8x8 tiles, more than
  * four views per set, the windowed binning path), negative on bad dims. */

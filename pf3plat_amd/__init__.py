@@ -24,3 +24,5 @@ __version__ = "0.1.0"
 from .ply_export import export_ply, gaussians_from_ply, read_ply  # noqa: F401,E402
 from .sh_rotation import rotate_sh  # noqa: F401,E402
 from . import losses  # noqa: F401,E402
+from . import cost_volume  # noqa: F401,E402
+from .cost_volume import depth_candidates, plane_sweep_cost_volume  # noqa: F401,E402

@@ -305,6 +305,12 @@ def load():
     lib.gsr_pose_loss.argtypes = pose_head + [vp] * 4
     lib.gsr_pose_loss_backward.restype = ctypes.c_int
     lib.gsr_pose_loss_backward.argtypes = pose_head + [vp] * 7
+    lib.gsr_cost_volume_scratch_bytes.restype = ctypes.c_size_t
+    lib.gsr_cost_volume_scratch_bytes.argtypes = [ctypes.c_int] * 6
+    lib.gsr_cost_volume.restype = ctypes.c_int
+    lib.gsr_cost_volume.argtypes = [ctypes.c_int] * 6 + [vp] * 8  # sizes; features, intrinsics, extrinsics, near, far, cost, scratch, stream
+    lib.gsr_cost_volume_backward.restype = ctypes.c_int
+    lib.gsr_cost_volume_backward.argtypes = [ctypes.c_int] * 6 + [vp] * 9  # ...; far, dL_dcost, dL_dfeatures, scratch, stream
     if lib.gsr_abi_version() != GSR_ABI_VERSION:
         raise RuntimeError(f"libgsr_hip.so ABI {lib.gsr_abi_version()} != expected {GSR_ABI_VERSION}; rebuild")
     _lib = lib
@@ -320,6 +326,7 @@ EXPORTED_SYMBOLS = (
     "gsr_adapt", "gsr_adapt_backward", "gsr_adapt_partials_bytes", "gsr_adapt_backward_ex", "gsr_adapt_partials_bytes_ex", "gsr_setup_views_backward_ex",
     "gsr_image_metrics", "gsr_image_metrics_partials", "gsr_image_metrics_finish",
     "gsr_pose_loss", "gsr_pose_loss_backward", "gsr_pose_loss_units",
+    "gsr_cost_volume", "gsr_cost_volume_backward", "gsr_cost_volume_scratch_bytes",
 )
 # The stages of GsrForwardOptions.stage_ms / GsrBackwardOptions.stage_ms as run_forward / run_backward(profile=True) key them (the
 # names a failed debug-mode stage is reported with are the library's: gsr_stage_name).  On images of up to 20 480 tiles (the fused binning path) "preprocess" is the whole binning
