@@ -538,8 +538,10 @@ int gsr_cost_volume_backward(int num_scenes, int num_views, int channels, int he
 int gsr_colour_in_binning(const GsrDims* dims);
 
 /* Debug aid for tests: byte offsets of the sub-buffers inside `bin` (status, counts, tile_total, ranges, keys,
- * point_list) and `img` (final_T, n_contrib). */
-int gsr_workspace_layout(const GsrDims* dims, int64_t* offsets8);
+ * point_list) and `img` (final_T, n_contrib), then - NINE entries - `bin`'s tile_order: one uint32 per (view, tile), the tile every
+ * workgroup of the tile launch took where the forward deals its tiles by the previous call's walked counts (one view of 257 ... 1024
+ * tiles on the fused binning path whose binning launch leaves eight compute units idle; unused by every other call). */
+int gsr_workspace_layout(const GsrDims* dims, int64_t* offsets9);
 /* The same for `geom`: [0] bytes per projected record (32: x, y, conic a b c, opacity, extra channel, radius bits),
  * [1] offset of the 16-byte footprint words of the windowed binning chain (-1 on the fused path: they never leave registers),
  * [2] offset of the (r, g, b, clamp bits) array, [3] offset of the backward's accumulator rows (-1 without

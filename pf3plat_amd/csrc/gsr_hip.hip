@@ -100,7 +100,7 @@ __host__ __device__ inline Grid make_grid(int W, int H) {
 struct Layout {
   size_t geom_bytes, bin_bytes, img_bytes;
   size_t o_aux, o_rgbc, o_rows, o_shj;  // o_aux: 0 = none (fused binning path)  // in geom (only with GSR_FLAG_BACKWARD_FOLLOWS: o_rows screen-space gradient rows, o_shj d rgb / d direction)
-  size_t o_status, o_counts, o_total, o_ranges, o_keys, o_list, o_blk, o_blktot;  // in bin
+  size_t o_status, o_counts, o_total, o_ranges, o_keys, o_list, o_blk, o_blktot, o_order;  // in bin
   size_t key_slots;  // keys: one fixed slot of kStagePairs keys per binning workgroup, then ...
   size_t key_pages;  // ... a pool of pages of kPage keys (regions / scratch too long for a slot)
   size_t stride;     // fused binning: entries of the index list owned by every (view, tile)
@@ -205,6 +205,7 @@ static Layout make_layout(const GsrDims& d) {
   L.o_list = o; o = align_up(o + cap * 4, 256);
   L.o_blk = o; o = align_up(o + blocks * 4, 256);
   L.o_blktot = o; o = align_up(o + blocks * 4, 256);
+  L.o_order = o; o = align_up(o + VT * 4, 256);  // tile_order (device side: tile_order_of - directly behind blk_total)
   L.stride = VT > 0 ? cap / (2 * VT) : 0;  // half of the index list in per-tile slots, the rest a shared tail (longer lists)
   L.bin_bytes = o;
   const size_t px = V * (size_t)d.height * d.width;
@@ -344,6 +345,84 @@ __device__ __forceinline__ int xcd_remap(int b, int n) {
   const int xcd = b & 7, k = b >> 3;
   const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
   return base + k;
+}
+
+// ---- The deal of an XCD's tiles to its 32 CUs by load: heaviest first, every other round of 32 mirrored (k_blend_bwd has the
+// measurements).  Shared by k_blend_bwd, which finds its tile from the forward's walked counts, and by the single view's forward
+// tile launch, which takes its tile from a table (tile_order) the binning launch builds from what the PREVIOUS forward walked.
+constexpr int kBalanceMax = 256;  // tiles per XCD up to which the deal is computed (more: image order; later rounds balance themselves)
+// keys (load + 1) << 8 | (255 - index): distinct, heavier first, equal loads in index order.  CORRECTNESS rests on the low 8 bits
+// alone - they are distinct, so the deal is a bijection of the XCD's tiles whatever the counts hold (walked counts after a normal
+// forward; binning totals or anything else after an overflowed one, or in a fresh workspace) - the load only decides the ORDER; it
+// is clamped so that the shift cannot drop its high bits (the order stays monotonic)
+__device__ __forceinline__ uint32_t deal_key(uint32_t load, int index) {
+  return ((min(load, 0xfffffeu) + 1u) << 8) | (uint32_t)(255 - index);
+}
+// position in heaviest-first order that the XCD's k-th workgroup takes; its own inverse (the k of the workgroup that takes position k)
+__device__ __forceinline__ int deal_position(int k, int cnt) {
+  const int round = k >> 5, in = k & 31, len = cnt - (round << 5) < 32 ? cnt - (round << 5) : 32;
+  return (round << 5) + ((round & 1) ? len - 1 - in : in);
+}
+// The forward's deal: one view whose tile workgroups are all resident at once (four per CU) - what a CU is busy for is then the sum
+// of its up to four tiles, and nothing rebalances it.  Every other call keeps xcd_remap's image order: several views, more tiles
+// than one round, no more tiles than CUs (nothing to balance) - or a binning launch without kDealBlocks idle CUs for the table's
+// builders (below): they would be a second round of that launch (one 131 072-Gaussian view, 256 binning workgroups: binning
+// 16.7 -> 19.7 us for a tile launch 2.3 us shorter).
+constexpr int kDealBlocks = 8;  // one builder workgroup per XCD
+__host__ __device__ __forceinline__ bool fwd_deal_active(const Params& p) {
+  return p.d.num_views == 1 && p.g.T > kCUs && p.g.T <= 4 * kCUs && p.rows + kDealBlocks <= kCUs;
+}
+// tile_order: one word per (view, tile), behind blk_total in `bin` (make_layout: o_order)
+__device__ __forceinline__ uint32_t* tile_order_of(const Params& p) {
+  return p.blk_total + ((((size_t)p.d.num_views * p.rows * 4 + 255) & ~(size_t)255) >> 2);
+}
+// K1's side: wave c (0 ... 3) of a workgroup ranks keys 64 c ... 64 c + 63 of XCD `xcd` among the XCD's <= kBalanceMax keys - the
+// keys pass as lane broadcasts, no LDS, no barrier - and stores tile_order[block] = tile for the workgroups that take them.
+__device__ __forceinline__ void build_tile_order_wave(const Params& p, const int xcd, const int c, const int lane) {
+  const int T = p.g.T, cnt = (T >> 3) + (xcd < (T & 7) ? 1 : 0), base = xcd_remap(xcd, T);  // this XCD's tiles: [base, base + cnt)
+  if (cnt > kBalanceMax || 64 * c >= cnt) return;
+  const uint32_t* tot = p.tile_total + base;
+  uint32_t key[4], mine = 0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int i = lane + 64 * q;
+    key[q] = i < cnt ? deal_key(tot[i], i) : 0u;  // (0: below every key)
+    mine = q == c ? key[q] : mine;
+  }
+  int rank = 0;  // keys above mine = my position in heaviest-first order
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    if (64 * q >= cnt) break;
+#pragma unroll 8
+    for (int j = 0; j < 64; ++j) rank += (uint32_t)__builtin_amdgcn_readlane((int)key[q], j) > mine ? 1 : 0;
+  }
+  const int i = lane + 64 * c;
+  if (i < cnt) tile_order_of(p)[(deal_position(rank, cnt) << 3) | xcd] = (uint32_t)(base + i);
+}
+// Who builds it: kDealBlocks workgroups of the fused binning launch BEHIND its `rows` binning workgroups, one per XCD's table (the
+// tile launch runs after that kernel, the previous call's tile launch - which left the counts - before it).  They are workgroups of
+// their own because the launch has compute units to spare for them - 247 binning workgroups on 256 CUs in the 300 k view - and
+// none of its own waves has: built by the binning waves of rows 0 ... 7 in their tail, under the harmonics stream, the same table
+// made the launch 1.0 us longer (23.9 -> 24.9 us; a trip to memory and ~400 VALU instructions per wave on SIMDs the colour waves fill).
+// A single view that takes the binning launch WITHOUT colour waves (a device that does not grant it the LDS) gets the table from
+// a launch of its own, k_tile_order, in front: those instances stay the code they were (the two-per-CU one spills with it).
+__device__ __forceinline__ void build_tile_order(const Params& p, const int xcd, const int w, const int lane) {
+  if (w < 4) build_tile_order_wave(p, xcd, w, lane);
+}
+__global__ __launch_bounds__(256) void k_tile_order(const Params p) {
+  build_tile_order(p, (int)blockIdx.x, (int)(threadIdx.x >> 6), (int)(threadIdx.x & 63));
+}
+// K2's side: the (view, tile) of workgroup `bid` of a gathering tile launch, in two steps so that a kernel can ask for the word at
+// its start and look at it where it first needs the tile.  The dealt tile is read from the table - never from tile_total itself,
+// which tiles of the same launch overwrite - and is clamped: whatever the word holds, the tile exists.  A VECTOR load (the
+// relaxed atomic keeps it one): the scalar loads of a wave return in any order, so the next wait for one of them - the status
+// word thread 0 asks for - would wait for this word too, one round trip behind the other.
+__device__ __forceinline__ uint32_t fwd_tile_word(const Params& p, const uint32_t bid) {
+  if (!fwd_deal_active(p)) return (uint32_t)xcd_remap((int)bid, (int)p.sort_blocks);
+  return __hip_atomic_load(tile_order_of(p) + bid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ int fwd_tile_of(const Params& p, const uint32_t word) {
+  return (int)min((uint32_t)__builtin_amdgcn_readfirstlane((int)word), p.sort_blocks - 1u);
 }
 
 // Real-SH polynomial basis and its x/y/z partials, visited in coefficient order with compile-time k.
@@ -1274,8 +1353,14 @@ __global__ __launch_bounds__(kBinThreads, (!kColor && kMaxT == kBinTwoMaxT) ? 8 
   __shared__ uint32_t nbig, wtot[kBinThreads / 64], sBase, next_unit, bin_bar;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, row = blockIdx.x, v = blockIdx.y;
   const int T = p.g.T, N = p.d.num_gaussians;
+  if constexpr (kColor) {
+    if (row >= p.rows) {  // (workgroup-uniform) one of the kDealBlocks workgroups behind the rows: the tile launch's deal, nothing else
+      build_tile_order(p, row - p.rows, w, lane);
+      return;
+    }
+  }
   const bool dbg = GSR_ABL(p.d.flags, GSR_FLAG_DEBUG_TIMING);
-  unsigned long long* stamp = dbg_stamps(p, (size_t)(blockIdx.y * gridDim.x + blockIdx.x));
+  unsigned long long* stamp = dbg_stamps(p, (size_t)(blockIdx.y * p.rows + blockIdx.x));
   GSR_STAMP(0);
   for (int k = tid; k < T; k += kBinThreads) hist[k] = 0;
   if (tid == 0) {
@@ -1951,9 +2036,10 @@ struct SortLds {
 
 // The sort of one tile's list: returns the tile's range of the index list (empty when the tile has no entry or the list did
 // not fit: then status->overflow is set).  All `return`s are workgroup-uniform.  The caller provides `smem`
-// (SortLds<kLds>::kWords 8-byte words, 16-byte aligned), red[8] and sInfo[4] in LDS.
+// (SortLds<kLds>::kWords 8-byte words, 16-byte aligned), red[8] and sInfo[4] in LDS, and (kGather) `tg`, the (view, tile) this
+// workgroup takes: the caller decides it once - xcd_remap's image order or the deal - for the sort and the blend alike.
 template <bool kGather, int kLds>
-__device__ __forceinline__ uint2 sort_tile(const Params& p, const uint32_t bid, unsigned long long* smem, uint32_t* red,
+__device__ __forceinline__ uint2 sort_tile(const Params& p, const uint32_t bid, const int tg, unsigned long long* smem, uint32_t* red,
                                            uint32_t* sInfo) {
   // kLds keys sort in LDS over SortLds<kLds>::kBuckets depth buckets
   constexpr int kBk = SortLds<kLds>::kBuckets, kBkBits = SortLds<kLds>::kBucketBits, kBpt = kBk / kSortThreads;
@@ -1973,8 +2059,7 @@ __device__ __forceinline__ uint2 sort_tile(const Params& p, const uint32_t bid, 
   if (kGather) {
     const int T = p.g.T, R = p.rows;
     // XCD-aware order: neighbouring tiles' runs share cache lines in every region, so give each XCD (= each L2) a contiguous
-    // range of tiles
-    const int tg = xcd_remap((int)bid, (int)p.sort_blocks);
+    // range of tiles (the caller's `tg`)
     const int v = tg / T, t = tg - v * T;
     // De-phase the first resident round.  All its workgroups start together and would gather together (memory-bound, CUs
     // idle: 250 k small reads take 11 us when issued at once, 2-4 us per workgroup when spread out), then sort together
@@ -2575,12 +2660,12 @@ __global__ __launch_bounds__(kFwdThreads, (kLds == 2048 && kGather && !kExtra) ?
   // The sort phase is a chain of short instruction bursts between trips to memory and LDS; the blend phase of the other tiles of
   // the CU (de-phased: they are up to 5 us ahead) keeps the SIMDs issuing every cycle.  A wave in its sort phase goes first
   // when both are ready: its next request leaves at once and the blend waves lose nothing they would not lose later (-0.7 us).
+  const int tg = kGather ? fwd_tile_of(p, fwd_tile_word(p, bid)) : (int)bid;  // (one place for the sort and the blend)
   __builtin_amdgcn_s_setprio(2);
-  const uint2 rg = sort_tile<kGather, kLds>(p, bid, smem, red, sInfo);
+  const uint2 rg = sort_tile<kGather, kLds>(p, bid, tg, smem, red, sInfo);
   __builtin_amdgcn_s_setprio(0);
   if (bid == 0 && threadIdx.x == 0) *p.page_counter = (unsigned long long)p.call_tag << 32;  // the binning launch's (take_pages)
   __syncthreads();  // the list is this workgroup's own: its stores are visible to its waves from here on; the keys are dead
-  const int tg = kGather ? xcd_remap((int)bid, (int)p.sort_blocks) : (int)bid;
   const int v = tg / p.g.T;
   blend_tile<kExtra, kAlpha>(p, v, tg - v * p.g.T, rg, *reinterpret_cast<BlendLds*>(smem));
   if (kGather && threadIdx.x == 64 && rg.y - rg.x > p.status->max_list) atomicMax(&p.status->max_list, rg.y - rg.x);
@@ -2619,8 +2704,8 @@ static_assert(kPrefix % kFB == 0 && kPrefix >= 2 * kFB, "the prefix is whole bat
 
 // The rare paths of k_tile_fwd_prefix (inlined: as real calls - `noinline` - `Params` travels by reference, 480 B of scratch per lane
 // and 108-112 VGPRs for a path that is almost never taken: forward 84 us)
-__device__ __forceinline__ uint2 sort_tile_general_2048(const Params& p, const uint32_t bid, unsigned long long* smem, uint32_t* red, uint32_t* sInfo) {
-  return sort_tile<true, 2048>(p, bid, smem, red, sInfo);
+__device__ __forceinline__ uint2 sort_tile_general_2048(const Params& p, const uint32_t bid, const int tg, unsigned long long* smem, uint32_t* red, uint32_t* sInfo) {
+  return sort_tile<true, 2048>(p, bid, tg, smem, red, sInfo);
 }
 __device__ __forceinline__ void bitonic_whole_list(unsigned long long* sk, uint32_t* out, const int n) {
   int lgnp = 1;
@@ -2655,6 +2740,9 @@ __global__ __launch_bounds__(kFwdThreads, kCompact ? 6 : 4) void k_tile_fwd_pref
   __shared__ uint32_t sCount, sLongRuns, sLongKeys;
   const uint32_t bid = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // the workgroup's tile, asked for as the kernel's first memory operation: a word of its own, on its way while the de-phase
+  // groups sleep.  (The compact instance takes calls of more than one resident round: image order.)
+  const uint32_t tile_word = kCompact ? (uint32_t)xcd_remap((int)bid, (int)p.sort_blocks) : fwd_tile_word(p, bid);
   // (overflow is raised by tiles of THIS launch only - a tile that cannot place its list - and such a tile poisons its own pixels
   // whatever it read here; for everybody else the flag is a courtesy whose outcome depends on timing either way)
   uint32_t overflow_early = 0;
@@ -2675,12 +2763,12 @@ __global__ __launch_bounds__(kFwdThreads, kCompact ? 6 : 4) void k_tile_fwd_pref
   __builtin_amdgcn_s_setprio(2);
   GSR_STAMP(0);
   const int T = p.g.T, R = p.rows;
-  const int tg = xcd_remap((int)bid, (int)p.sort_blocks);
-  const int v = tg / T, t = tg - v * T;
   // (de-phasing of the first resident round: see sort_tile.  With this kernel's shorter gather 1 us between the four groups is
   // enough: sleeps of 16 / 24 / 32 / 40 / 64 gave 53.0 / 52.9 / 53.0 / 53.0 / 53.9 us for the forward; round 6: 16 - GSR_DEPHASE_SLEEP)
   if (bid < 1024u)
     for (int q = 0; q < (int)((bid >> kDephaseShift) % kDephaseGroups); ++q) __builtin_amdgcn_s_sleep(GSR_DEPHASE_SLEEP);
+  const int tg = fwd_tile_of(p, tile_word);
+  const int v = tg / T, t = tg - v * T;
   // ---- gather: column (v, :, t) of the pair matrix, one row per thread
   uint2 e0 = make_uint2(0u, 0u);
   uint32_t bb0 = 0;
@@ -2808,7 +2896,7 @@ __global__ __launch_bounds__(kFwdThreads, kCompact ? 6 : 4) void k_tile_fwd_pref
   bool bucketed = false;  // the keys sit in bucket order in `sk`, cur[b] = end of bucket b: positions are ranked on demand
   if (bad || n > p.stride) {  // workgroup-uniform: the general path, from the start
     __syncthreads();
-    const uint2 rg = sort_tile_general_2048(p, bid, smem, red, sInfo);
+    const uint2 rg = sort_tile_general_2048(p, bid, tg, smem, red, sInfo);
     obase = rg.x; n = rg.y - rg.x; ranked = n;
   } else {
     if (tid == 0) p.ranges[tg] = make_uint2(obase, obase + n);
@@ -3092,7 +3180,7 @@ __global__ __launch_bounds__(256) void k_cotangent_max(const Params p, uint32_t*
 // tiles out across the whole chip by load was measured - the gathers then miss, prologue 3.0 -> 4.1 us, no gain), but inside
 // the XCD they are dealt to its 32 CUs heaviest first, every other round mirrored.  Work of a tile = list entries the forward
 // walked (Params::tile_total); every workgroup finds its own tile: a selection by bisection over the <= 256 keys of its XCD, one wave, ballots only.
-constexpr int kBalanceMax = 256;  // tiles per XCD up to which the deal is computed (more: image order; later rounds balance themselves)
+// (kBalanceMax, deal_key, deal_position: beside xcd_remap, shared with the forward's deal.)
 
 // kAlpha (GsrBackwardOptions.dL_dalpha_img): a loss on the accumulated alpha A = 1 - T_final.  dA/dalpha_j = T_final / (1 - alpha_j) is the
 // background term's derivative with the sign turned, so dL/dA enters where the background does: Q starts from bg.g - g_A.
@@ -3115,19 +3203,15 @@ __global__ __launch_bounds__(kBwdThreads, 4) void k_blend_bwd(const Params p) {
     const int cnt = q8 + (xcd < r8 ? 1 : 0), base = t - k;  // this XCD's tiles: [base, base + cnt)
     if (cnt <= kBalanceMax) {
       if (wave == 0) {
-        // keys (walked + 1) << 8 | (255 - index): distinct, heavier first, equal loads in index order; up to four per lane.
-        // CORRECTNESS rests on the low 8 bits alone - they are distinct, so the deal is a bijection of the XCD's tiles whatever
-        // tile_total holds (walked counts after a normal forward; binning totals or anything else after an overflowed one) -
-        // the load only decides the ORDER; it is clamped so that the shift cannot drop its high bits (the order stays monotonic)
+        // keys (deal_key): up to four per lane; a bijection of the XCD's tiles whatever tile_total holds
         const uint32_t* tot = p.tile_total + (size_t)v * g.T + base;
         uint32_t key[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
           const int i = lane + 64 * c;
-          key[c] = i < cnt ? ((min(tot[i], 0xfffffeu) + 1u) << 8) | (uint32_t)(255 - i) : 0u;
+          key[c] = i < cnt ? deal_key(tot[i], i) : 0u;
         }
-        const int round = k >> 5, in = k & 31, len = cnt - (round << 5) < 32 ? cnt - (round << 5) : 32;
-        const int want = (round << 5) + ((round & 1) ? len - 1 - in : in);  // position of this block in heaviest-first order
+        const int want = deal_position(k, cnt);  // position of this block in heaviest-first order
         // the key at that position: the largest X with more than `want` keys >= X, bit by bit from the top bit of the largest key
         const uint32_t top = wave_max_u32(max(max(key[0], key[1]), max(key[2], key[3])));
         uint32_t X = 0;
@@ -4174,13 +4258,14 @@ int64_t gsr_capacity_for(const GsrDims* dims, uint64_t num_pairs, uint32_t max_l
   return (int64_t)(2 * (slots > num_pairs ? slots : num_pairs));
 }
 
-// Debug aid for tests: byte offsets of the sub-buffers inside bin (6) and img (2).
-int gsr_workspace_layout(const GsrDims* dims, int64_t* offsets8) {
-  if (!dims_ok(dims) || !offsets8) return GSR_ERR_INVALID_ARGUMENT;
+// Debug aid for tests: byte offsets of the sub-buffers inside bin (6), img (2) and, appended, bin's tile_order.
+int gsr_workspace_layout(const GsrDims* dims, int64_t* offsets9) {
+  if (!dims_ok(dims) || !offsets9) return GSR_ERR_INVALID_ARGUMENT;
   const Layout L = make_layout(*dims);
-  offsets8[0] = (int64_t)L.o_status; offsets8[1] = (int64_t)L.o_counts; offsets8[2] = (int64_t)L.o_total;
-  offsets8[3] = (int64_t)L.o_ranges; offsets8[4] = (int64_t)L.o_keys; offsets8[5] = (int64_t)L.o_list;
-  offsets8[6] = (int64_t)L.o_finalT; offsets8[7] = (int64_t)L.o_ncontrib;
+  offsets9[0] = (int64_t)L.o_status; offsets9[1] = (int64_t)L.o_counts; offsets9[2] = (int64_t)L.o_total;
+  offsets9[3] = (int64_t)L.o_ranges; offsets9[4] = (int64_t)L.o_keys; offsets9[5] = (int64_t)L.o_list;
+  offsets9[6] = (int64_t)L.o_finalT; offsets9[7] = (int64_t)L.o_ncontrib;
+  offsets9[8] = (int64_t)L.o_order;
   return GSR_OK;
 }
 
@@ -4276,7 +4361,9 @@ static int forward_impl(const GsrDims* dims, const GsrView* views, const float* 
   GSR_STAGE_DONE(0);
   GSR_MARK();
   if (fused_bin) {
-    const dim3 bgrid((unsigned)p.rows, (unsigned)V);
+    // the tile launch's deal: its table from kDealBlocks more workgroups of the binning launch, or from a launch of its own
+    if (fwd_deal_active(p) && !color_in_bin) hipLaunchKernelGGL(k_tile_order, dim3(kDealBlocks), dim3(256), 0, st, p);
+    const dim3 bgrid((unsigned)p.rows + (fwd_deal_active(p) && color_in_bin ? kDealBlocks : 0), (unsigned)V);
     const size_t shmem = bin_lds_bytes(p.g.T, color_in_bin);
     // (two plain workgroups per CU where the image's tile counters leave the LDS for it: LDS comes in 1280-byte steps)
     const bool two_per_cu = bin_two_per_cu(p.g, color_in_bin);

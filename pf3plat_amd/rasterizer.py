@@ -228,11 +228,11 @@ class HipBackend:
         return d
 
     def workspace_layout(self, dims: _lib.GsrDims):
-        offs = (ctypes.c_int64 * 8)()
+        offs = (ctypes.c_int64 * 9)()
         rc = self.lib.gsr_workspace_layout(ctypes.byref(self._sizing_dims(dims)), offs)
         if rc != 0:
             raise RuntimeError(f"gsr_workspace_layout failed (code {rc})")
-        return dict(zip(("status", "counts", "tile_total", "ranges", "keys", "point_list", "final_T", "n_contrib"),
+        return dict(zip(("status", "counts", "tile_total", "ranges", "keys", "point_list", "final_T", "n_contrib", "tile_order"),
                         [int(o) for o in offs]))
 
     def geom_layout(self, dims: _lib.GsrDims):

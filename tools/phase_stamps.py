@@ -155,6 +155,11 @@ def main():
     g2 = slots_raw(8192 + VT, VT)
     us = lambda a: (a & 0xffffffff).double() * 0.01
     tile_of_bid = torch.tensor([xcd_remap(bb, VT) for bb in range(VT)])
+    if V == 1 and 256 < T <= 1024 and rows + 8 <= 256:  # the deal (gsr_hip.hip fwd_deal_active): the table the last call's tile launch took its tiles from
+        dealt = plan["bin"][lay["tile_order"]: lay["tile_order"] + VT * 4].view(torch.int32).cpu().long()
+        moved = int((dealt != tile_of_bid).sum())
+        tile_of_bid = dealt
+        print(f"  tile order: dealt by the previous call's walked counts ({moved} of {VT} workgroups off image order)")
     pts_b = [us(sl[:, 0]), us(g2[:, 0]), us(g2[:, 1]), us(g2[:, 2]), us(sl[:, 1]), us(sl[:, 2]), us(sl[:, 3]), us(sl[:, 4]), us(sl[:, 5]), us(sl[:, 6])]
     ss = torch.zeros(VT, dtype=torch.float64)
     se = torch.zeros(VT, dtype=torch.float64)
