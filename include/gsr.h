@@ -532,6 +532,64 @@ int gsr_cost_volume_backward(int num_scenes, int num_views, int channels, int he
                              const float* features, const float* intrinsics, const float* extrinsics, const float* near,
                              const float* far, const float* dL_dcost, float* dL_dfeatures, void* scratch, void* stream);
 
+/* The encoder's coarse camera poses (reference src/model/encoder/encoder_costvolume.py:323-381: cv2.solvePnPRansac per pair and scene,
+ * then src/flow_util.py:623-743 camera_synchronization), forward only, three launches and no host synchronisation.
+ * Inputs, b scenes of 2 <= v <= 8 views of H x W pixels: xyz (b, v, 3, H, W) f32; intrinsics_px (b, v, 3, 3) f32 IN PIXEL UNITS, of
+ *   which fx = [0][0], fy = [1][1], cx = [0][2], cy = [1][2] are read; the match lists as gsr_pose_loss takes them (list l = p b + s,
+ *   pairs p = (i, j), i < j, in the order [(a, c) for a in range(v) for c in range(a + 1, v)]; ids_i, ids_j int64, weights f32 the
+ *   matcher's scores, offsets on the host and on the device); points_2d (M, 2) f32 or NULL, sub-pixel keypoints (x, y) in the pair's
+ *   first view - NULL: the 2-D point of match k is (ids_i[k] % W, ids_i[k] / W); hypotheses Hy >= 1 (the reference: 1000);
+ *   reprojection_error > 0 in pixels (5); confidence_min < 1 (0.5); seed.  An id outside [0, H W) is the caller's error; it is
+ *   clamped into the image, not followed out of the array.
+ * Per list (pair (i, j), scene s, n matches): X_k = xyz[s, j, :, ids_j[k]], u_k the 2-D point, K = intrinsics_px[s, i].  Sought is
+ *   (R, t) with u ~ pi(K (R X + t)); the list's output is the rigid inverse [R^T | -R^T t] (the reference's `relpose`).
+ *   1. Hypothesis t = 0 .. Hy-1 draws four matches, slot = 0 .. 3, index draw(seed, l, t, slot) mod n in uint32 arithmetic with
+ *        fmix(x): x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13; x *= 0xC2B2AE35; x ^= x >> 16
+ *        draw = fmix(fmix(fmix(seed ^ 0x9E3779B9 (l + 1)) ^ 0x85EBCA6B (t + 1)) ^ 0xC2B2AE35 (slot + 1)).
+ *      Duplicates are allowed and give a degenerate hypothesis.  A P3P solve in fp64 on the first three (the law of cosines on the
+ *      three rays; a quartic by Ferrari's resolvent, its real roots polished by two Newton steps; every root with both signs of the
+ *      depths, the equations' solutions behind the camera included) gives up to eight poses; the one under which the fourth point
+ *      has the smallest reprojection error is kept (the first of equals; the depth is judged by the score, not here).  A hypothesis
+ *      with no finite pose is skipped.  ALL Hy hypotheses are evaluated:
+ *      there is no early exit on a confidence as OpenCV's RANSAC has (its `confidence=0.9999`).
+ *   2. Score: the number of matches with (R X + t)_z > 0 and |pi - u|^2 < reprojection_error^2, the pose rounded to fp32 and the
+ *      test in fp32, written so that a NaN fails it.  The winner is the maximum of the words (score << 32) | (Hy - 1 - t) - an
+ *      integer maximum, independent of the order: the highest score, of equals the lowest t.
+ *   3. Refinement in fp64: three rounds of { the consensus set (the same test in fp64) under the current pose; ten Gauss-Newton steps
+ *      on sum |pi - u|^2 over that set, update R <- exp(w) R, t <- t + d, the 6 x 6 normal equations summed in fp64 in a fixed
+ *      order and solved by Cholesky }.  The consensus set under the final pose is the list's inlier count and, on request, `mask`
+ *      (M) uint8.
+ *   4. Failure gives the identity, inlier count 0 and a zero mask; status: 0 a pose, 1 n < 4 (gsr_pnp_min_matches), 2 the winner
+ *      explains fewer than 4 matches (or no hypothesis had a pose), 3 the refined pose is not finite.
+ *   5. confidence[l] = the mean of the list's weights (fp64 sum in a fixed order), 0 FOR AN EMPTY LIST - the reference has NaN there,
+ *      which poisons the whole batch: a deliberate difference; for pairs with j - i > 1 then relu(c - confidence_min) /
+ *      (1 - confidence_min) in fp32.
+ * gsr_pnp_ransac: launch 1 over (list, block of 256 hypotheses) - a lane solves one hypothesis, then the workgroup walks the list in
+ *   LDS stages of 1024 matches (3-D point + 2-D point, 20 bytes each; longer lists in several stages), every lane counting for its own
+ *   pose, and publishes the integer maximum of its words to its slot of `scratch` (gsr_pnp_ransac_scratch_bytes(b, v, Hy) bytes, 8 per
+ *   (list, block); host arithmetic, 0 for sizes the call refuses); launch 2, one workgroup per list, takes the maximum of the list's
+ *   slots, solves the winner again from its index (the same arithmetic, the same pose: no pose is stored), refines, and writes
+ *   pairwise (b, P, 4, 4) - row [s, p] -, inliers, status, confidence (P b, in list order) and mask.  Nothing proportional to Hy x n
+ *   exists.
+ * gsr_camera_sync: pairwise (b, P, 4, 4), confidence (P b) -> absolute (b, v, 4, 4): camera_synchronization at its default arguments,
+ *   one workgroup per scene: confidences normalised per column and the (4 v)^2 matrix formed in fp32 in the reference's order of
+ *   operations, converted to fp64, squared 10 times in LDS, block column 0 divided by its mass, the rotations projected onto SO(3)
+ *   as U diag(1, 1, det(U V^T)) V^T (8 sweeps of one-sided Jacobi), rounded once to fp32.  v = 2: camera_chaining (identity, then
+ *   P(i, i+1) times the pose before it, fp32).  A scene one of whose v masses is exactly 0 takes camera_chaining FOR THAT SCENE, decided
+ *   on the device; the reference decides for the whole batch after a host read: a difference for batches that mix such scenes.
+ * Every value is a pure function of the inputs and the seed - the same bits on every run; no floating-point atomics; every loop's
+ * trip count is fixed by the arguments (hypotheses, rounds, steps, sweeps, squarings, list lengths): no loop waits on data.
+ * Both: GSR_ERR_INVALID_ARGUMENT, nothing launched, on v < 2, v > 8, num_pairs != v (v - 1) / 2, b < 0, Hy < 1 or > 2^24, a
+ * non-positive extent, H W > 2^31 - 1, negative or decreasing offsets, a threshold that is not positive, confidence_min >= 1 or a NULL
+ * required pointer (mask, points_2d may be NULL; ids and weights when there is no match).  b == 0: nothing is launched. */
+int gsr_pnp_min_matches(void);
+size_t gsr_pnp_ransac_scratch_bytes(int num_scenes, int num_views, int hypotheses);
+int gsr_pnp_ransac(int num_scenes, int num_views, int height, int width, int num_pairs, const float* xyz, const float* intrinsics_px,
+                   const int64_t* ids_i, const int64_t* ids_j, const float* weights, const float* points_2d, const int32_t* offsets,
+                   const int32_t* offsets_device, int hypotheses, float reprojection_error, float confidence_min, uint32_t seed,
+                   void* scratch, float* pairwise, int32_t* inliers, int32_t* status, float* confidence, uint8_t* mask, void* stream);
+int gsr_camera_sync(int num_scenes, int num_views, const float* pairwise, const float* confidence, float* absolute, void* stream);
+
 /* Measurement aid: 1 when gsr_forward runs the colour pass inside the binning launch for these dims (two launches: binning +
  * colour, per-tile sort + blend), 0 when the colour pass is a launch of its own (images of more than 4608 8x8 tiles, more than
  * four views per set, the windowed binning path), negative on bad dims. */

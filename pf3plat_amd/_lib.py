@@ -311,6 +311,15 @@ def load():
     lib.gsr_cost_volume.argtypes = [ctypes.c_int] * 6 + [vp] * 8  # sizes; features, intrinsics, extrinsics, near, far, cost, scratch, stream
     lib.gsr_cost_volume_backward.restype = ctypes.c_int
     lib.gsr_cost_volume_backward.argtypes = [ctypes.c_int] * 6 + [vp] * 9  # ...; far, dL_dcost, dL_dfeatures, scratch, stream
+    lib.gsr_pnp_min_matches.restype = ctypes.c_int
+    lib.gsr_pnp_min_matches.argtypes = []
+    lib.gsr_pnp_ransac_scratch_bytes.restype = ctypes.c_size_t
+    lib.gsr_pnp_ransac_scratch_bytes.argtypes = [ctypes.c_int] * 3
+    lib.gsr_pnp_ransac.restype = ctypes.c_int  # sizes; xyz, intrinsics, ids_i, ids_j, weights, points_2d; host + device offsets; ...
+    lib.gsr_pnp_ransac.argtypes = ([ctypes.c_int] * 5 + [vp] * 6 + [i32p, vp, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_uint32]
+                                   + [vp] * 7)  # scratch, pairwise, inliers, status, confidence, mask, stream
+    lib.gsr_camera_sync.restype = ctypes.c_int
+    lib.gsr_camera_sync.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
     if lib.gsr_abi_version() != GSR_ABI_VERSION:
         raise RuntimeError(f"libgsr_hip.so ABI {lib.gsr_abi_version()} != expected {GSR_ABI_VERSION}; rebuild")
     _lib = lib
@@ -327,6 +336,7 @@ EXPORTED_SYMBOLS = (
     "gsr_image_metrics", "gsr_image_metrics_partials", "gsr_image_metrics_finish",
     "gsr_pose_loss", "gsr_pose_loss_backward", "gsr_pose_loss_units",
     "gsr_cost_volume", "gsr_cost_volume_backward", "gsr_cost_volume_scratch_bytes",
+    "gsr_pnp_ransac", "gsr_pnp_ransac_scratch_bytes", "gsr_pnp_min_matches", "gsr_camera_sync",
 )
 # The stages of GsrForwardOptions.stage_ms / GsrBackwardOptions.stage_ms as run_forward / run_backward(profile=True) key them (the
 # names a failed debug-mode stage is reported with are the library's: gsr_stage_name).  On images of up to 20 480 tiles (the fused binning path) "preprocess" is the whole binning

@@ -23,6 +23,7 @@
 //
 // Built with -ffp-contract=off: projection / EWA / SH arithmetic then evaluates the same expression
 // trees as the fp32 oracle (IEEE +,-,*,/ and sqrt are correctly rounded on both sides).
+#ifndef GSR_POSE_HOST_ONLY  // (the host check of the coarse-pose solver at the end of this file skips to it)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>
@@ -6345,3 +6346,719 @@ int gsr_cost_volume_backward(int num_scenes, int num_views, int channels, int he
 }
 
 }  // extern "C"
+
+#endif  // GSR_POSE_HOST_ONLY
+
+// ------------------------------------------------------------------------------------------------
+// Coarse camera poses (include/gsr.h states the definition): PnP RANSAC per match list - a P3P hypothesis per lane, scored by the
+// workgroup over points staged in LDS, the winner refined by Gauss-Newton on its consensus set - and the synchronisation of the
+// pairwise poses (gsr_pnp_ransac, gsr_camera_sync).  The minimal solver and the Gauss-Newton step are host + device functions
+// (namespace gsr::pnp) that a host program can check in fp64 without a GPU: a translation unit that defines GSR_POSE_HOST_ONLY (and
+// GSR_HD as `inline`, after <cmath> and <cstdint>) and includes this file gets that arithmetic alone - everything above this line,
+// and the kernels and entry points below it, are left out.
+#ifndef GSR_HD
+#define GSR_HD __host__ __device__ inline
+#endif
+
+namespace gsr {
+namespace pnp {
+
+constexpr int kMinMatches = 4;     // three matches for the P3P solve and one to choose among its poses
+constexpr int kRefineRounds = 3;   // consensus set, then kGnSteps Gauss-Newton steps on it
+constexpr int kGnSteps = 10;
+constexpr int kJacobiSweeps = 8;   // of the 3 x 3 one-sided Jacobi SVD
+constexpr int kSquarings = 10;
+constexpr int kMaxViews = 8;
+
+struct Pose {
+  double R[9];  // row-major
+  double t[3];
+};
+
+GSR_HD uint32_t fmix32(uint32_t x) {
+  x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
+  return x;
+}
+
+// The draw of hypothesis t's slot (0..3) in list l: three rounds of murmur3's finaliser; the index is draw % n.
+GSR_HD uint32_t draw(uint32_t seed, uint32_t l, uint32_t t, uint32_t slot) {
+  uint32_t x = fmix32(seed ^ (0x9E3779B9u * (l + 1u)));
+  x = fmix32(x ^ (0x85EBCA6Bu * (t + 1u)));
+  return fmix32(x ^ (0xC2B2AE35u * (slot + 1u)));
+}
+
+// The largest real root of x^3 + a2 x^2 + a1 x + a0 (closed form, then three Newton steps).
+GSR_HD double cubic_largest_root(double a2, double a1, double a0) {
+  const double Q = (3.0 * a1 - a2 * a2) / 9.0, R = (9.0 * a2 * a1 - 27.0 * a0 - 2.0 * a2 * a2 * a2) / 54.0;
+  const double D = Q * Q * Q + R * R;
+  double x;
+  if (D < 0.0) {  // three real roots
+    const double sq = sqrt(-Q);
+    double c = R / (sq * sq * sq);
+    c = c > 1.0 ? 1.0 : (c < -1.0 ? -1.0 : c);
+    x = 2.0 * sq * cos(acos(c) / 3.0) - a2 / 3.0;
+  } else {
+    const double s = sqrt(D);
+    x = cbrt(R + s) + cbrt(R - s) - a2 / 3.0;
+  }
+  for (int it = 0; it < 3; ++it) {
+    const double f = ((x + a2) * x + a1) * x + a0, d = (3.0 * x + 2.0 * a2) * x + a1;
+    if (fabs(d) > 1e-300) x -= f / d;
+  }
+  return x;
+}
+
+// The real roots of c[4] y^4 + ... + c[0] by Ferrari's resolvent, each polished by two Newton steps; their number (0..4).
+GSR_HD int quartic_real_roots(const double c[5], double roots[4]) {
+  const double B = c[3] / c[4], C = c[2] / c[4], D = c[1] / c[4], E = c[0] / c[4];
+  const double B2 = B * B;
+  const double p = C - 0.375 * B2, q = D - 0.5 * B * C + 0.125 * B2 * B, r = E - 0.25 * B * D + B2 * C / 16.0 - 3.0 * B2 * B2 / 256.0;
+  const double m = cubic_largest_root(p, 0.25 * p * p - r, -0.125 * q * q);
+  if (!(m > 0.0)) return 0;  // (q == 0 with no positive root of the resolvent, or a non-finite coefficient: no hypothesis)
+  const double s = sqrt(2.0 * m), h = 0.5 * p + m, k = q / (2.0 * s);
+  int n = 0;
+  const double d1 = s * s - 4.0 * (h + k), d2 = s * s - 4.0 * (h - k);
+  if (d1 >= 0.0) { const double w = sqrt(d1); roots[n++] = 0.5 * (s + w); roots[n++] = 0.5 * (s - w); }
+  if (d2 >= 0.0) { const double w = sqrt(d2); roots[n++] = 0.5 * (-s + w); roots[n++] = 0.5 * (-s - w); }
+  for (int i = 0; i < n; ++i) {
+    double y = roots[i] - 0.25 * B;
+    for (int it = 0; it < 2; ++it) {
+      const double f = (((y + B) * y + C) * y + D) * y + E, d = ((4.0 * y + 3.0 * B) * y + 2.0 * C) * y + D;
+      if (fabs(d) > 1e-300) y -= f / d;
+    }
+    roots[i] = y;
+  }
+  return n;
+}
+
+GSR_HD void cross3(const double a[3], const double b[3], double o[3]) {
+  o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0];
+}
+GSR_HD double dot3(const double a[3], const double b[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+
+// The right-handed orthonormal frame of a triangle, as the columns e1 e2 e3 (F[3 * r + c]).
+GSR_HD void triangle_frame(const double P0[3], const double P1[3], const double P2[3], double F[9]) {
+  double a[3], b[3], e3[3], e2[3];
+  for (int i = 0; i < 3; ++i) { a[i] = P1[i] - P0[i]; b[i] = P2[i] - P0[i]; }
+  const double na = sqrt(dot3(a, a));
+  for (int i = 0; i < 3; ++i) a[i] /= na;
+  cross3(a, b, e3);
+  const double n3 = sqrt(dot3(e3, e3));
+  for (int i = 0; i < 3; ++i) e3[i] /= n3;
+  cross3(e3, a, e2);
+  for (int i = 0; i < 3; ++i) { F[3 * i] = a[i]; F[3 * i + 1] = e2[i]; F[3 * i + 2] = e3[i]; }
+}
+
+// P3P: world points X[0..2], unit bearings f[0..2] in the camera -> up to eight poses (R, t) with s_i f_i = R X_i + t.
+// With the depths s1, s2 = x s1, s3 = y s1 and the law of cosines on the three sides, x is a rational function N(y) / D(y) and y a
+// root of the quartic N^2 - 2 cos(gamma) N D - p D^2 (the polynomials are multiplied out here, not typed in).  Every real root gives
+// two poses, s1 = +sqrt and s1 = -sqrt: a solution with negative depths is a solution of the equations as well, and the one the
+// data came from when the points lie behind the camera - the caller's fourth point chooses, the score's depth test judges.
+GSR_HD int p3p(const double X[3][3], const double f[3][3], Pose out[8]) {
+  double d12[3], d02[3], d01[3];
+  for (int i = 0; i < 3; ++i) { d12[i] = X[1][i] - X[2][i]; d02[i] = X[0][i] - X[2][i]; d01[i] = X[0][i] - X[1][i]; }
+  const double a2 = dot3(d12, d12), b2 = dot3(d02, d02), c2 = dot3(d01, d01);
+  const double ca = dot3(f[1], f[2]), cb = dot3(f[0], f[2]), cg = dot3(f[0], f[1]);
+  const double kc = c2 / b2, ka = a2 / b2;
+  const double p[3] = {kc - 1.0, -2.0 * cb * kc, kc};              // x^2 = 2 cg x + p(y)
+  const double q[3] = {-ka, 2.0 * cb * ka, 1.0 - ka};              // x^2 - 2 ca y x + q(y) = 0
+  const double N[3] = {-(p[0] + q[0]), -(p[1] + q[1]), -(p[2] + q[2])};
+  const double Dn[2] = {2.0 * cg, -2.0 * ca};                      // x = N(y) / D(y)
+  double quart[5] = {0, 0, 0, 0, 0};
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) quart[i + j] += N[i] * N[j];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 2; ++j) quart[i + j] -= 2.0 * cg * N[i] * Dn[j];
+  const double DD[3] = {Dn[0] * Dn[0], 2.0 * Dn[0] * Dn[1], Dn[1] * Dn[1]};
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) quart[i + j] -= p[i] * DD[j];
+  double ys[4];
+  const int nr = quartic_real_roots(quart, ys);
+  double FX[9];
+  triangle_frame(X[0], X[1], X[2], FX);
+  int n = 0;
+  for (int k = 0; k < nr; ++k) {
+    const double y = ys[k];
+    const double x = ((N[2] * y + N[1]) * y + N[0]) / (Dn[1] * y + Dn[0]);
+    const double w = 1.0 + y * y - 2.0 * y * cb;
+    if (!(w > 0.0)) continue;
+    for (int sign = 0; sign < 2; ++sign) {
+      const double s1 = sign ? -sqrt(b2 / w) : sqrt(b2 / w), s2 = x * s1, s3 = y * s1;
+      double P[3][3];
+      for (int i = 0; i < 3; ++i) { P[0][i] = s1 * f[0][i]; P[1][i] = s2 * f[1][i]; P[2][i] = s3 * f[2][i]; }
+      double FP[9];
+      triangle_frame(P[0], P[1], P[2], FP);
+      Pose& o = out[n];
+      for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) o.R[3 * r + c] = FP[3 * r] * FX[3 * c] + FP[3 * r + 1] * FX[3 * c + 1] + FP[3 * r + 2] * FX[3 * c + 2];
+      for (int r = 0; r < 3; ++r) o.t[r] = P[0][r] - (o.R[3 * r] * X[0][0] + o.R[3 * r + 1] * X[0][1] + o.R[3 * r + 2] * X[0][2]);
+      ++n;
+    }
+  }
+  return n;
+}
+
+struct Camera { double fx, fy, cx, cy; };
+
+GSR_HD bool pose_finite(const Pose& P) {
+  bool ok = true;
+  for (int i = 0; i < 9; ++i) ok = ok && (fabs(P.R[i]) <= 1.7e308);
+  for (int i = 0; i < 3; ++i) ok = ok && (fabs(P.t[i]) <= 1.7e308);
+  return ok;  // (a NaN fails the comparison)
+}
+
+// Squared reprojection error of X under P, and its depth; the caller tests `z > 0 && e2 < thr^2`, which a NaN fails.
+GSR_HD double reproj2(const Pose& P, const Camera& K, const double X[3], const double u[2], double* z) {
+  const double Y0 = P.R[0] * X[0] + P.R[1] * X[1] + P.R[2] * X[2] + P.t[0];
+  const double Y1 = P.R[3] * X[0] + P.R[4] * X[1] + P.R[5] * X[2] + P.t[1];
+  const double Y2 = P.R[6] * X[0] + P.R[7] * X[1] + P.R[8] * X[2] + P.t[2];
+  const double dx = K.fx * Y0 / Y2 + K.cx - u[0], dy = K.fy * Y1 / Y2 + K.cy - u[1];
+  *z = Y2;
+  return dx * dx + dy * dy;
+}
+
+// One hypothesis: P3P on the first three of four matches, the pose that reprojects the fourth best (the first of equals).
+GSR_HD bool hypothesis(const double X[4][3], const double u[4][2], const Camera& K, Pose* best) {
+  double f[3][3];
+  for (int i = 0; i < 3; ++i) {
+    const double bx = (u[i][0] - K.cx) / K.fx, by = (u[i][1] - K.cy) / K.fy;
+    const double inv = 1.0 / sqrt(bx * bx + by * by + 1.0);
+    f[i][0] = bx * inv; f[i][1] = by * inv; f[i][2] = inv;
+  }
+  Pose cand[8];
+  const int n = p3p(X, f, cand);
+  double best_e = 1.7e308;
+  bool found = false;
+  for (int k = 0; k < n; ++k) {
+    if (!pose_finite(cand[k])) continue;
+    double z;
+    const double e = reproj2(cand[k], K, X[3], u[3], &z);
+    if (e < best_e) { best_e = e; *best = cand[k]; found = true; }  // (a NaN fails the comparison)
+  }
+  return found;
+}
+
+// Gauss-Newton on sum |pi(K (R X + t)) - u|^2 with the update R <- exp(w) R, t <- t + d: one match's share of the upper triangle
+// of J^T J (21 numbers, row by row) and of J^T r (6), parameters (w, d).
+GSR_HD void gn_accumulate(const Pose& P, const Camera& K, const double X[3], const double u[2], double acc[27]) {
+  const double Q0 = P.R[0] * X[0] + P.R[1] * X[1] + P.R[2] * X[2];
+  const double Q1 = P.R[3] * X[0] + P.R[4] * X[1] + P.R[5] * X[2];
+  const double Q2 = P.R[6] * X[0] + P.R[7] * X[1] + P.R[8] * X[2];
+  const double Y0 = Q0 + P.t[0], Y1 = Q1 + P.t[1], Y2 = Q2 + P.t[2];
+  const double iz = 1.0 / Y2;
+  const double r0 = K.fx * Y0 * iz + K.cx - u[0], r1 = K.fy * Y1 * iz + K.cy - u[1];
+  // d pi / d Y
+  const double a0[3] = {K.fx * iz, 0.0, -K.fx * Y0 * iz * iz}, a1[3] = {0.0, K.fy * iz, -K.fy * Y1 * iz * iz};
+  // d Y / d w_k = e_k x Q, so a row of J is (Q x a)
+  double J0[6], J1[6];
+  J0[0] = Q1 * a0[2] - Q2 * a0[1];  J0[1] = Q2 * a0[0] - Q0 * a0[2];  J0[2] = Q0 * a0[1] - Q1 * a0[0];
+  J1[0] = Q1 * a1[2] - Q2 * a1[1];  J1[1] = Q2 * a1[0] - Q0 * a1[2];  J1[2] = Q0 * a1[1] - Q1 * a1[0];
+  for (int k = 0; k < 3; ++k) { J0[3 + k] = a0[k]; J1[3 + k] = a1[k]; }
+  int e = 0;
+  for (int i = 0; i < 6; ++i)
+    for (int j = i; j < 6; ++j) acc[e++] += J0[i] * J0[j] + J1[i] * J1[j];
+  for (int i = 0; i < 6; ++i) acc[21 + i] += J0[i] * r0 + J1[i] * r1;
+}
+
+// Solve the normal equations (Cholesky, no pivoting) and apply the step.  A matrix that is not positive definite gives a non-finite
+// pose, which the caller reports.
+GSR_HD void gn_step(Pose* P, const double acc[27]) {
+  double A[36], g[6];
+  int e = 0;
+  for (int i = 0; i < 6; ++i)
+    for (int j = i; j < 6; ++j) { A[6 * i + j] = acc[e]; A[6 * j + i] = acc[e]; ++e; }
+  for (int i = 0; i < 6; ++i) g[i] = -acc[21 + i];
+  for (int j = 0; j < 6; ++j) {  // A = L L^T, L in the lower triangle
+    double d = A[6 * j + j];
+    for (int k = 0; k < j; ++k) d -= A[6 * j + k] * A[6 * j + k];
+    d = sqrt(d);  // (NaN when d < 0)
+    A[6 * j + j] = d;
+    for (int i = j + 1; i < 6; ++i) {
+      double s = A[6 * i + j];
+      for (int k = 0; k < j; ++k) s -= A[6 * i + k] * A[6 * j + k];
+      A[6 * i + j] = s / d;
+    }
+  }
+  for (int i = 0; i < 6; ++i) {
+    double s = g[i];
+    for (int k = 0; k < i; ++k) s -= A[6 * i + k] * g[k];
+    g[i] = s / A[6 * i + i];
+  }
+  for (int i = 5; i >= 0; --i) {
+    double s = g[i];
+    for (int k = i + 1; k < 6; ++k) s -= A[6 * k + i] * g[k];
+    g[i] = s / A[6 * i + i];
+  }
+  const double wx = g[0], wy = g[1], wz = g[2];
+  const double th2 = wx * wx + wy * wy + wz * wz, th = sqrt(th2);
+  double ka, kb;  // exp(w) = I + ka [w]x + kb [w]x^2
+  if (th < 1e-8) { ka = 1.0; kb = 0.5; }
+  else { ka = sin(th) / th; kb = (1.0 - cos(th)) / th2; }
+  const double Kx[9] = {0.0, -wz, wy, wz, 0.0, -wx, -wy, wx, 0.0};
+  double E[9];
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) {
+      double k2 = 0.0;
+      for (int k = 0; k < 3; ++k) k2 += Kx[3 * r + k] * Kx[3 * k + c];
+      E[3 * r + c] = (r == c ? 1.0 : 0.0) + ka * Kx[3 * r + c] + kb * k2;
+    }
+  double Rn[9];
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) Rn[3 * r + c] = E[3 * r] * P->R[c] + E[3 * r + 1] * P->R[3 + c] + E[3 * r + 2] * P->R[6 + c];
+  for (int i = 0; i < 9; ++i) P->R[i] = Rn[i];
+  for (int i = 0; i < 3; ++i) P->t[i] += g[3 + i];
+}
+
+// The rotation nearest a 3 x 3 matrix as the reference projects it: U diag(1, 1, det(U V^T)) V^T of its SVD, the SVD by
+// kJacobiSweeps sweeps of one-sided Jacobi rotations; the factor det goes to the smallest singular value.
+GSR_HD void project_so3(const double Ain[9], double Rout[9]) {
+  double A[9], V[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  for (int i = 0; i < 9; ++i) A[i] = Ain[i];
+  for (int sweep = 0; sweep < kJacobiSweeps; ++sweep)
+    for (int p = 0; p < 2; ++p)
+      for (int q = p + 1; q < 3; ++q) {
+        double al = 0.0, be = 0.0, ga = 0.0;
+        for (int i = 0; i < 3; ++i) { al += A[3 * i + p] * A[3 * i + p]; be += A[3 * i + q] * A[3 * i + q]; ga += A[3 * i + p] * A[3 * i + q]; }
+        if (ga == 0.0) continue;
+        const double zeta = (be - al) / (2.0 * ga);
+        const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+        const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
+        for (int i = 0; i < 3; ++i) {
+          const double ap = A[3 * i + p], aq = A[3 * i + q];
+          A[3 * i + p] = c * ap - s * aq; A[3 * i + q] = s * ap + c * aq;
+          const double vp = V[3 * i + p], vq = V[3 * i + q];
+          V[3 * i + p] = c * vp - s * vq; V[3 * i + q] = s * vp + c * vq;
+        }
+      }
+  double sig[3], U[9];
+  for (int j = 0; j < 3; ++j) {
+    sig[j] = sqrt(A[j] * A[j] + A[3 + j] * A[3 + j] + A[6 + j] * A[6 + j]);
+    for (int i = 0; i < 3; ++i) U[3 * i + j] = sig[j] > 0.0 ? A[3 * i + j] / sig[j] : 0.0;
+  }
+  double M[9];
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) M[3 * r + c] = U[3 * r] * V[3 * c] + U[3 * r + 1] * V[3 * c + 1] + U[3 * r + 2] * V[3 * c + 2];
+  const double det = M[0] * (M[4] * M[8] - M[5] * M[7]) - M[1] * (M[3] * M[8] - M[5] * M[6]) + M[2] * (M[3] * M[7] - M[4] * M[6]);
+  int lo = 0;
+  if (sig[1] < sig[lo]) lo = 1;
+  if (sig[2] < sig[lo]) lo = 2;
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) Rout[3 * r + c] = M[3 * r + c] + (det - 1.0) * U[3 * r + lo] * V[3 * c + lo];
+}
+
+}  // namespace pnp
+}  // namespace gsr
+
+#ifndef GSR_POSE_HOST_ONLY
+namespace gsr {
+
+struct PnpArgs {
+  int B, V, H, W, L, hyp, nblk;
+  const float* xyz; const float* intr; const int64_t* ids_i; const int64_t* ids_j; const float* wgt; const float* pts2d;
+  const int32_t* offs;
+  uint32_t seed; float thr; float conf_min;
+  unsigned long long* best;
+  float* pairwise; int32_t* inliers; int32_t* status; float* conf; uint8_t* mask;
+};
+
+constexpr int kPnpThreads = 256;
+constexpr int kPnpStage = 1024;  // matches per LDS stage of the scoring kernel: 20 bytes each
+
+// List l -> its pair (i, j) and scene.
+__device__ inline void pnp_list_views(int l, int B, int V, int* s, int* pi, int* pj, int* pair) {
+  const int p = l / B;
+  *s = l - p * B; *pair = p;
+  int i = 0, left = p;
+  while (i < V - 2 && left >= V - 1 - i) { left -= V - 1 - i; ++i; }  // (at most V - 2 trips)
+  *pi = i; *pj = i + 1 + left;
+}
+
+struct PnpList {
+  const float* x; const int64_t* ids_i; const int64_t* ids_j; const float* pts2d;  // the second view's points; the list's entries
+  int64_t hw; int W;
+};
+
+__device__ inline void pnp_fetch(const PnpList& ls, int k, float X[3], float u[2]) {
+  int64_t idj = ls.ids_j[k];
+  idj = idj < 0 ? 0 : (idj >= ls.hw ? ls.hw - 1 : idj);  // (an id outside the image is the caller's error; it is not followed out of the array)
+  X[0] = ls.x[idj]; X[1] = ls.x[ls.hw + idj]; X[2] = ls.x[2 * ls.hw + idj];
+  if (ls.pts2d) { u[0] = ls.pts2d[2 * (int64_t)k]; u[1] = ls.pts2d[2 * (int64_t)k + 1]; }
+  else { const int64_t idi = ls.ids_i[k]; u[0] = (float)(idi % ls.W); u[1] = (float)(idi / ls.W); }
+}
+
+__device__ inline PnpList pnp_list(const PnpArgs& a, int l, int* s_out, int* far_out, pnp::Camera* K, int* begin, int* n) {
+  int s, pi, pj, pair;
+  pnp_list_views(l, a.B, a.V, &s, &pi, &pj, &pair);
+  const int64_t hw = (int64_t)a.H * a.W;
+  const int off = a.offs[l];
+  PnpList ls;
+  ls.x = a.xyz + ((int64_t)s * a.V + pj) * 3 * hw;
+  ls.ids_i = a.ids_i + off; ls.ids_j = a.ids_j + off; ls.pts2d = a.pts2d ? a.pts2d + 2 * (int64_t)off : nullptr;
+  ls.hw = hw; ls.W = a.W;
+  const float* k = a.intr + ((int64_t)s * a.V + pi) * 9;
+  K->fx = k[0]; K->fy = k[4]; K->cx = k[2]; K->cy = k[5];
+  *s_out = s; *far_out = (pj - pi > 1); *begin = off; *n = a.offs[l + 1] - off;
+  return ls;
+}
+
+__device__ inline bool pnp_solve_hypothesis(const PnpList& ls, const pnp::Camera& K, uint32_t seed, int l, int t, int n, pnp::Pose* P) {
+  double X[4][3], u[4][2];
+  for (int slot = 0; slot < 4; ++slot) {
+    const int k = (int)(pnp::draw(seed, (uint32_t)l, (uint32_t)t, (uint32_t)slot) % (uint32_t)n);
+    float Xf[3], uf[2];
+    pnp_fetch(ls, k, Xf, uf);
+    for (int c = 0; c < 3; ++c) X[slot][c] = Xf[c];
+    u[slot][0] = uf[0]; u[slot][1] = uf[1];
+  }
+  return pnp::hypothesis(X, u, K, P);
+}
+
+// Launch 1: workgroup (list, block of 256 hypotheses).  A lane solves its hypothesis in fp64; the workgroup then walks the list in
+// LDS stages, every lane counting the matches its own pose explains (fp32; all lanes read the same match: an LDS broadcast).
+__global__ void __launch_bounds__(kPnpThreads) k_pnp_hypotheses(PnpArgs a) {
+  __shared__ float stage[kPnpStage * 5];
+  __shared__ unsigned long long red[kPnpThreads];
+  const int tid = threadIdx.x, l = blockIdx.x / a.nblk, hb = blockIdx.x - l * a.nblk;
+  int s, far, begin, n;
+  pnp::Camera K;
+  const PnpList ls = pnp_list(a, l, &s, &far, &K, &begin, &n);
+  if (n < pnp::kMinMatches) {  // (uniform over the workgroup)
+    if (tid == 0) a.best[blockIdx.x] = 0ull;
+    return;
+  }
+  const int t = hb * kPnpThreads + tid;
+  pnp::Pose P;
+  bool ok = false;
+  if (t < a.hyp) ok = pnp_solve_hypothesis(ls, K, a.seed, l, t, n, &P);
+  float R[9], T[3];
+  for (int i = 0; i < 9; ++i) R[i] = (float)P.R[i];
+  for (int i = 0; i < 3; ++i) T[i] = (float)P.t[i];
+  const float fx = (float)K.fx, fy = (float)K.fy, cx = (float)K.cx, cy = (float)K.cy, thr2 = a.thr * a.thr;
+  unsigned count = 0;
+  for (int base = 0; base < n; base += kPnpStage) {
+    const int m = min(kPnpStage, n - base);
+    __syncthreads();
+    for (int k = tid; k < m; k += kPnpThreads) {
+      float X[3], u[2];
+      pnp_fetch(ls, base + k, X, u);
+      stage[5 * k] = X[0]; stage[5 * k + 1] = X[1]; stage[5 * k + 2] = X[2]; stage[5 * k + 3] = u[0]; stage[5 * k + 4] = u[1];
+    }
+    __syncthreads();
+    if (ok)
+      for (int k = 0; k < m; ++k) {
+        const float x = stage[5 * k], y = stage[5 * k + 1], z = stage[5 * k + 2];
+        const float Y0 = R[0] * x + R[1] * y + R[2] * z + T[0], Y1 = R[3] * x + R[4] * y + R[5] * z + T[1], Y2 = R[6] * x + R[7] * y + R[8] * z + T[2];
+        const float dx = fx * Y0 / Y2 + cx - stage[5 * k + 3], dy = fy * Y1 / Y2 + cy - stage[5 * k + 4];
+        count += (Y2 > 0.f && dx * dx + dy * dy < thr2) ? 1u : 0u;
+      }
+  }
+  red[tid] = ok ? (((unsigned long long)count << 32) | (unsigned)(a.hyp - 1 - t)) : 0ull;
+  __syncthreads();
+  for (int w = kPnpThreads / 2; w > 0; w >>= 1) {
+    if (tid < w) red[tid] = max(red[tid], red[tid + w]);
+    __syncthreads();
+  }
+  if (tid == 0) a.best[blockIdx.x] = red[0];
+}
+
+// Launch 2: one workgroup per list.  The winner is solved again from its index (the same arithmetic: the same pose), refined, and
+// the list's row of every output written.
+__global__ void __launch_bounds__(kPnpThreads) k_pnp_refine(PnpArgs a) {
+  __shared__ double red[27 * kPnpThreads];
+  __shared__ pnp::Pose pose, pose0;
+  __shared__ int state;
+  const int tid = threadIdx.x, l = blockIdx.x;
+  int s, far, begin, n;
+  pnp::Camera K;
+  const PnpList ls = pnp_list(a, l, &s, &far, &K, &begin, &n);
+  const double thr2 = (double)a.thr * (double)a.thr;
+
+  // the confidence: the mean score in fp64, in a fixed order
+  {
+    double sum = 0.0;
+    for (int k = tid; k < n; k += kPnpThreads) sum += (double)a.wgt[begin + k];
+    red[tid] = sum;
+    __syncthreads();
+    for (int w = kPnpThreads / 2; w > 0; w >>= 1) {
+      if (tid < w) red[tid] += red[tid + w];
+      __syncthreads();
+    }
+    if (tid == 0) {
+      float c = n > 0 ? (float)(red[0] / (double)n) : 0.f;
+      if (far) c = fmaxf(c - a.conf_min, 0.f) / (1.f - a.conf_min);
+      a.conf[l] = c;
+    }
+    __syncthreads();
+  }
+
+  if (tid == 0) {
+    int st = 0;
+    if (n < pnp::kMinMatches) st = 1;
+    else {
+      unsigned long long best = 0ull;
+      for (int k = 0; k < a.nblk; ++k) best = max(best, a.best[(int64_t)l * a.nblk + k]);
+      if ((unsigned)(best >> 32) < (unsigned)pnp::kMinMatches) st = 2;
+      else {
+        const int t = a.hyp - 1 - (int)(unsigned)(best & 0xffffffffull);
+        pnp::Pose P;
+        if (!pnp_solve_hypothesis(ls, K, a.seed, l, t, n, &P)) st = 2;
+        pose = P;
+      }
+    }
+    state = st;
+  }
+  __syncthreads();
+  int st = state;
+
+  if (st == 0) {
+    for (int round = 0; round < pnp::kRefineRounds; ++round) {
+      if (tid == 0) pose0 = pose;
+      __syncthreads();
+      for (int step = 0; step < pnp::kGnSteps; ++step) {
+        double acc[27];
+        for (int i = 0; i < 27; ++i) acc[i] = 0.0;
+        for (int k = tid; k < n; k += kPnpThreads) {
+          float Xf[3], uf[2];
+          pnp_fetch(ls, k, Xf, uf);
+          const double X[3] = {Xf[0], Xf[1], Xf[2]}, u[2] = {uf[0], uf[1]};
+          double z;
+          const double e2 = pnp::reproj2(pose0, K, X, u, &z);
+          if (z > 0.0 && e2 < thr2) pnp::gn_accumulate(pose, K, X, u, acc);
+        }
+        __syncthreads();  // (everybody has read `pose`; `red` is free)
+        for (int i = 0; i < 27; ++i) red[i * kPnpThreads + tid] = acc[i];
+        __syncthreads();
+        for (int w = kPnpThreads / 2; w > 0; w >>= 1) {
+          if (tid < w)
+            for (int i = 0; i < 27; ++i) red[i * kPnpThreads + tid] += red[i * kPnpThreads + tid + w];
+          __syncthreads();
+        }
+        if (tid == 0) {
+          double sum[27];
+          for (int i = 0; i < 27; ++i) sum[i] = red[i * kPnpThreads];
+          pnp::Pose P = pose;
+          pnp::gn_step(&P, sum);
+          pose = P;
+        }
+        __syncthreads();
+      }
+    }
+    if (!pnp::pose_finite(pose)) st = 3;
+  }
+
+  // the consensus set under the final pose
+  int count = 0;
+  for (int k = tid; k < n; k += kPnpThreads) {
+    bool in = false;
+    if (st == 0) {
+      float Xf[3], uf[2];
+      pnp_fetch(ls, k, Xf, uf);
+      const double X[3] = {Xf[0], Xf[1], Xf[2]}, u[2] = {uf[0], uf[1]};
+      double z;
+      const double e2 = pnp::reproj2(pose, K, X, u, &z);
+      in = z > 0.0 && e2 < thr2;
+    }
+    if (a.mask) a.mask[begin + k] = in ? 1 : 0;
+    count += in ? 1 : 0;
+  }
+  __syncthreads();
+  int* ired = reinterpret_cast<int*>(red);
+  ired[tid] = count;
+  __syncthreads();
+  for (int w = kPnpThreads / 2; w > 0; w >>= 1) {
+    if (tid < w) ired[tid] += ired[tid + w];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    a.inliers[l] = ired[0];
+    a.status[l] = st;
+    const int pairs = a.V * (a.V - 1) / 2, p = l / a.B;
+    float* o = a.pairwise + ((int64_t)s * pairs + p) * 16;
+    if (st != 0) {
+      for (int i = 0; i < 16; ++i) o[i] = (i % 5 == 0) ? 1.f : 0.f;
+    } else {  // the rigid inverse [R^T | -R^T t]
+      for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) o[4 * r + c] = (float)pose.R[3 * c + r];
+        o[4 * r + 3] = (float)(-(pose.R[r] * pose.t[0] + pose.R[3 + r] * pose.t[1] + pose.R[6 + r] * pose.t[2]));
+      }
+      o[12] = 0.f; o[13] = 0.f; o[14] = 0.f; o[15] = 1.f;
+    }
+  }
+}
+
+struct SyncArgs {
+  int B, V;
+  const float* pairwise; const float* conf; float* out;
+};
+
+// Launch 3: one workgroup per scene; the (4 v)^2 matrix and its square in LDS, fp64.  The matrix is formed in fp32 as the reference
+// forms it (it converts to fp64 afterwards), in the reference's order of operations.
+__global__ void __launch_bounds__(256) k_camera_sync(SyncArgs a) {
+  constexpr int MV = pnp::kMaxViews, MN = 4 * MV;
+  __shared__ double Lm[2][MN * MN];
+  __shared__ int chain;
+  const int tid = threadIdx.x, s = blockIdx.x, V = a.V, N = 4 * V, pairs = V * (V - 1) / 2;
+  const float* Ps = a.pairwise + (int64_t)s * pairs * 16;
+  float* out = a.out + (int64_t)s * V * 16;
+  if (tid == 0) chain = (V == 2) ? 1 : 0;
+  for (int e = tid; e < N * N; e += 256) Lm[0][e] = 0.0;
+  __syncthreads();
+  if (V > 2) {
+    if (tid == 0) {
+      float conf[MV][MV];
+      for (int i = 0; i < V; ++i)
+        for (int j = 0; j < V; ++j) conf[i][j] = 0.f;
+      int p = 0;
+      for (int i = 0; i < V; ++i)
+        for (int j = i + 1; j < V; ++j, ++p) {
+          const float c = a.conf[(int64_t)p * a.B + s];
+          conf[i][j] = c; conf[j][i] = c;
+          conf[i][i] = conf[i][i] + c / 2.f; conf[j][j] = conf[j][j] + c / 2.f;
+        }
+      for (int j = 0; j < V; ++j) {
+        float sum = conf[0][j];
+        for (int i = 1; i < V; ++i) sum += conf[i][j];
+        sum = fmaxf(sum, 1e-9f);
+        for (int i = 0; i < V; ++i) conf[i][j] = conf[i][j] / sum;
+      }
+      for (int i = 0; i < V; ++i)
+        for (int k = 0; k < 4; ++k) Lm[0][(4 * i + k) * N + 4 * i + k] = (double)conf[i][i];
+      p = 0;
+      for (int i = 0; i < V; ++i)
+        for (int j = i + 1; j < V; ++j, ++p) {
+          const float* P = Ps + p * 16;
+          float inv[16];
+          for (int r = 0; r < 3; ++r) {
+            for (int c = 0; c < 3; ++c) inv[4 * r + c] = P[4 * c + r];
+            float acc = (-1.f * P[r]) * P[3];           // ((-1 R^T) t)_r = sum_k (-R[k][r]) t_k
+            acc += (-1.f * P[4 + r]) * P[7];
+            acc += (-1.f * P[8 + r]) * P[11];
+            inv[4 * r + 3] = acc;
+          }
+          for (int c = 0; c < 4; ++c) inv[12 + c] = P[12 + c];
+          const float cij = conf[i][j], cji = conf[j][i];
+          for (int r = 0; r < 4; ++r)
+            for (int c = 0; c < 4; ++c) {
+              Lm[0][(4 * i + r) * N + 4 * j + c] = (double)(cij * inv[4 * r + c]);
+              Lm[0][(4 * j + r) * N + 4 * i + c] = (double)(cji * P[4 * r + c]);
+            }
+        }
+    }
+    __syncthreads();
+    int cur = 0;
+    for (int sq = 0; sq < pnp::kSquarings; ++sq) {
+      for (int e = tid; e < N * N; e += 256) {
+        const int r = e / N, c = e - r * N;
+        double acc = 0.0;
+        for (int k = 0; k < N; ++k) acc += Lm[cur][r * N + k] * Lm[cur][k * N + c];
+        Lm[cur ^ 1][e] = acc;
+      }
+      __syncthreads();
+      cur ^= 1;
+    }
+    // (kSquarings is even: the result is in Lm[0])
+    if (tid == 0) {
+      int zero = 0;
+      for (int i = 0; i < V; ++i) zero |= (Lm[0][(4 * i + 3) * N + 3] == 0.0) ? 1 : 0;
+      chain = zero;
+    }
+    __syncthreads();
+    if (!chain && tid < V) {
+      const int i = tid;
+      const double mass = fmax(Lm[0][(4 * i + 3) * N + 3], 1e-9);
+      double blk[16], Rp[9], R[9];
+      for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) blk[4 * r + c] = Lm[0][(4 * i + r) * N + c] / mass;
+      for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) Rp[3 * r + c] = blk[4 * r + c];
+      pnp::project_so3(Rp, R);
+      for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) blk[4 * r + c] = R[3 * r + c];
+      for (int e = 0; e < 16; ++e) out[16 * i + e] = (float)blk[e];
+    }
+  }
+  if (chain && tid == 0) {  // camera_chaining: identity, then P(i, i + 1) times the one before, in fp32
+    float cur[16];
+    for (int e = 0; e < 16; ++e) { cur[e] = (e % 5 == 0) ? 1.f : 0.f; out[e] = cur[e]; }
+    int p = 0;
+    for (int i = 0; i + 1 < V; ++i) {
+      const float* P = Ps + p * 16;
+      float nxt[16];
+      for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) {
+          float acc = P[4 * r] * cur[c];
+          for (int k = 1; k < 4; ++k) acc += P[4 * r + k] * cur[4 * k + c];
+          nxt[4 * r + c] = acc;
+        }
+      for (int e = 0; e < 16; ++e) { cur[e] = nxt[e]; out[16 * (i + 1) + e] = nxt[e]; }
+      p += V - 1 - i;  // pair (i + 1, i + 2) follows the V - 1 - i pairs that begin with i
+    }
+  }
+}
+
+static bool pnp_offsets_ok(int L, const int32_t* offsets) {
+  if (!offsets || offsets[0] < 0) return false;
+  for (int l = 0; l < L; ++l)
+    if (offsets[l + 1] < offsets[l]) return false;
+  return true;
+}
+
+static bool pnp_sizes_ok(int B, int V, int pairs, int hyp) {
+  if (B < 0 || V < 2 || V > pnp::kMaxViews || (int64_t)V * (V - 1) / 2 != pairs || hyp < 1 || hyp > (1 << 24)) return false;
+  const int64_t nblk = (hyp + kPnpThreads - 1) / kPnpThreads;
+  return (int64_t)B * pairs * nblk <= 0x7fffffff;
+}
+
+}  // namespace gsr
+
+extern "C" {
+
+int gsr_pnp_min_matches(void) { return gsr::pnp::kMinMatches; }
+
+size_t gsr_pnp_ransac_scratch_bytes(int num_scenes, int num_views, int hypotheses) {
+  const int pairs = num_views * (num_views - 1) / 2;
+  if (num_views < 2 || !gsr::pnp_sizes_ok(num_scenes, num_views, pairs, hypotheses)) return 0;
+  return (size_t)num_scenes * pairs * ((hypotheses + gsr::kPnpThreads - 1) / gsr::kPnpThreads) * sizeof(unsigned long long);
+}
+
+int gsr_pnp_ransac(int num_scenes, int num_views, int height, int width, int num_pairs, const float* xyz, const float* intrinsics_px,
+                   const int64_t* ids_i, const int64_t* ids_j, const float* weights, const float* points_2d, const int32_t* offsets,
+                   const int32_t* offsets_device, int hypotheses, float reprojection_error, float confidence_min, uint32_t seed,
+                   void* scratch, float* pairwise, int32_t* inliers, int32_t* status, float* confidence, uint8_t* mask, void* stream_) {
+  using namespace gsr;
+  if (!pnp_sizes_ok(num_scenes, num_views, num_pairs, hypotheses)) return GSR_ERR_INVALID_ARGUMENT;
+  if (height <= 0 || width <= 0 || (int64_t)height * width > 0x7fffffff) return GSR_ERR_INVALID_ARGUMENT;
+  const int L = num_scenes * num_pairs;
+  if (!pnp_offsets_ok(L, offsets)) return GSR_ERR_INVALID_ARGUMENT;
+  if (!(reprojection_error > 0.f) || !(confidence_min < 1.f)) return GSR_ERR_INVALID_ARGUMENT;
+  if (L == 0) return GSR_OK;
+  if (!xyz || !intrinsics_px || !offsets_device || !scratch || !pairwise || !inliers || !status || !confidence) return GSR_ERR_INVALID_ARGUMENT;
+  if (offsets[L] > offsets[0] && (!ids_i || !ids_j || !weights)) return GSR_ERR_INVALID_ARGUMENT;
+  hipStream_t st = static_cast<hipStream_t>(stream_);
+  PnpArgs a{};
+  a.B = num_scenes; a.V = num_views; a.H = height; a.W = width; a.L = L; a.hyp = hypotheses;
+  a.nblk = (hypotheses + kPnpThreads - 1) / kPnpThreads;
+  a.xyz = xyz; a.intr = intrinsics_px; a.ids_i = ids_i; a.ids_j = ids_j; a.wgt = weights; a.pts2d = points_2d; a.offs = offsets_device;
+  a.seed = seed; a.thr = reprojection_error; a.conf_min = confidence_min;
+  a.best = static_cast<unsigned long long*>(scratch);
+  a.pairwise = pairwise; a.inliers = inliers; a.status = status; a.conf = confidence; a.mask = mask;
+  hipLaunchKernelGGL(k_pnp_hypotheses, dim3((unsigned)(L * a.nblk)), dim3(kPnpThreads), 0, st, a);
+  GSR_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_pnp_refine, dim3((unsigned)L), dim3(kPnpThreads), 0, st, a);
+  GSR_CHECK(hipGetLastError());
+  return GSR_OK;
+}
+
+int gsr_camera_sync(int num_scenes, int num_views, const float* pairwise, const float* confidence, float* absolute, void* stream_) {
+  using namespace gsr;
+  if (num_scenes < 0 || num_views < 2 || num_views > pnp::kMaxViews) return GSR_ERR_INVALID_ARGUMENT;
+  if (num_scenes == 0) return GSR_OK;
+  if (!pairwise || !confidence || !absolute) return GSR_ERR_INVALID_ARGUMENT;
+  SyncArgs a{num_scenes, num_views, pairwise, confidence, absolute};
+  hipLaunchKernelGGL(k_camera_sync, dim3((unsigned)num_scenes), dim3(256), 0, static_cast<hipStream_t>(stream_), a);
+  GSR_CHECK(hipGetLastError());
+  return GSR_OK;
+}
+
+}  // extern "C"
+#endif  // GSR_POSE_HOST_ONLY

@@ -1,0 +1,166 @@
+"""The encoder's coarse camera poses on the device (reference src/model/encoder/encoder_costvolume.py:323-381 and
+src/flow_util.py:623-743; the definition is stated in include/gsr.h): `pnp_ransac` replaces the loop of `cv2.solvePnPRansac` calls
+over (pair, scene) - and its copies to the host and back - with two launches (gsr_pnp_ransac), `synchronize_cameras` replaces
+`camera_synchronization` with one (gsr_camera_sync), and `coarse_poses` is the chain: three launches, no host synchronisation, no
+gradient (the reference's poses come back from numpy).  There is no CPU fallback."""
+from __future__ import annotations
+
+import ctypes
+from dataclasses import dataclass
+from typing import Optional
+
+import torch
+from torch import Tensor
+
+from . import _lib
+from .losses import PackedCorrespondences, pack_correspondences
+from .rasterizer import _on_device, _stream_ptr
+
+MIN_MATCHES = 4  # a P3P solve on three matches and one to choose its root (gsr_pnp_min_matches)
+MAX_VIEWS = 8
+STATUS_OK, STATUS_TOO_FEW_MATCHES, STATUS_NO_CONSENSUS, STATUS_NOT_FINITE = 0, 1, 2, 3
+
+
+@dataclass
+class CoarsePoses:
+    pairwise: Tensor    # (b, P, 4, 4): the reference's pw_relpose_list, pairs in the pack's order
+    absolute: Tensor    # (b, v, 4, 4): the reference's sync_abspose
+    confidence: Tensor  # (P b,) in the list order of the pack: what the synchronisation weighs the pairs with
+    inliers: Tensor     # (P b,) int32
+    status: Tensor      # (P b,) int32: STATUS_*
+    mask: Optional[Tensor] = None  # (M,) uint8, on request
+
+
+def pack_matches(corr) -> PackedCorrespondences:
+    """`pack_correspondences` without confidences: the reference's {(i, j): [(id_i, id_j, score) per scene]} as the kernels read it,
+    with zeros where the confidences go.  `coarse_poses` returns the confidences; `dataclasses.replace(packed, conf=...)` puts them
+    into the pack for the pose loss."""
+    pairs = sorted(corr.keys())
+    if not pairs:
+        raise ValueError("pack_matches: no pairs")
+    scores = corr[pairs[0]][0][2] if len(corr[pairs[0]]) else None
+    dev = scores.device if scores is not None else None
+    conf = {p: torch.zeros(len(corr[p]), dtype=torch.float32, device=dev) for p in pairs}
+    return pack_correspondences(corr, conf)
+
+
+def _f32(t: Tensor) -> Tensor:
+    t = t.detach()
+    return t if t.dtype == torch.float32 and t.is_contiguous() else t.to(torch.float32).contiguous()
+
+
+def _pnp_args(xyz, intrinsics_px, packed, points_2d, hypotheses, reprojection_error, confidence_min):
+    """The shape checks (before the device is looked at and before the library is loaded), then the device check."""
+    if xyz.dim() != 5 or xyz.shape[2] != 3:
+        raise ValueError(f"pnp_ransac: expected xyz (b, v, 3, h, w), got {tuple(xyz.shape)}")
+    b, v, _, h, w = xyz.shape
+    if v < 2 or v > MAX_VIEWS:
+        raise ValueError(f"pnp_ransac: needs 2 to {MAX_VIEWS} views, got {v}")
+    if tuple(intrinsics_px.shape) != (b, v, 3, 3):
+        raise ValueError(f"pnp_ransac: expected intrinsics_px (b, v, 3, 3) = ({b}, {v}, 3, 3), got {tuple(intrinsics_px.shape)}")
+    if packed.num_scenes != b or packed.num_pairs != v * (v - 1) // 2 or len(packed.offsets) != b * packed.num_pairs + 1:
+        raise ValueError(f"pnp_ransac: the matches are packed for {packed.num_scenes} scenes and {packed.num_pairs} pairs, "
+                         f"the points are of {b} scenes and {v} views ({v * (v - 1) // 2} pairs)")
+    total = packed.offsets[-1]
+    if points_2d is not None and tuple(points_2d.shape) != (total, 2):
+        raise ValueError(f"pnp_ransac: expected points_2d (M, 2) = ({total}, 2), got {tuple(points_2d.shape)}")
+    if int(hypotheses) < 1 or int(hypotheses) > 1 << 24:
+        raise ValueError(f"pnp_ransac: needs 1 to 2^24 hypotheses, got {hypotheses}")
+    if not float(reprojection_error) > 0.0:
+        raise ValueError(f"pnp_ransac: needs a positive reprojection_error, got {reprojection_error}")
+    if not float(confidence_min) < 1.0:
+        raise ValueError(f"pnp_ransac: needs confidence_min < 1, got {confidence_min}")
+    if h * w > 0x7fffffff:
+        raise ValueError("pnp_ransac: more than 2^31 - 1 pixels in a view")
+    tensors = [xyz, intrinsics_px, packed.ids_i, packed.ids_j, packed.weights, packed.offsets_device]
+    if points_2d is not None:
+        tensors.append(points_2d)
+    if not all(t.is_cuda for t in tensors):
+        raise RuntimeError("pf3plat_amd pose: tensors must be on a ROCm device (there is no CPU fallback path)")
+    if any(t.device != xyz.device for t in tensors):
+        raise RuntimeError("pnp_ransac: every tensor must be on the same device")
+    return b, v, h, w
+
+
+def _pnp(xyz, intrinsics_px, packed, points_2d, hypotheses, reprojection_error, confidence_min, seed, return_mask):
+    b, v, h, w = _pnp_args(xyz, intrinsics_px, packed, points_2d, hypotheses, reprojection_error, confidence_min)
+    lib = _lib.load()
+    dev = xyz.device
+    pairs, lists, total = packed.num_pairs, b * packed.num_pairs, packed.offsets[-1]
+    x, k = _f32(xyz), _f32(intrinsics_px)
+    pts = None if points_2d is None else _f32(points_2d)
+    ids_i, ids_j, wgt = packed.ids_i.contiguous(), packed.ids_j.contiguous(), _f32(packed.weights)
+    if ids_i.dtype != torch.int64 or ids_j.dtype != torch.int64:
+        raise ValueError("pnp_ransac: the packed ids are int64")
+    scratch = torch.empty(max(int(lib.gsr_pnp_ransac_scratch_bytes(b, v, int(hypotheses))) // 8, 1), dtype=torch.int64, device=dev)
+    pairwise = torch.empty((b, pairs, 4, 4), dtype=torch.float32, device=dev)
+    inliers = torch.empty(lists, dtype=torch.int32, device=dev)
+    status = torch.empty(lists, dtype=torch.int32, device=dev)
+    conf = torch.empty(lists, dtype=torch.float32, device=dev)
+    mask = torch.empty(total, dtype=torch.uint8, device=dev) if return_mask else None
+    n = len(packed.offsets)
+    host = (ctypes.c_int32 * n)(*packed.offsets)
+    with _on_device(dev):
+        rc = lib.gsr_pnp_ransac(b, v, h, w, pairs, x.data_ptr(), k.data_ptr(), ids_i.data_ptr(), ids_j.data_ptr(), wgt.data_ptr(),
+                                None if pts is None else pts.data_ptr(), host, packed.offsets_device.data_ptr(), int(hypotheses),
+                                float(reprojection_error), float(confidence_min), int(seed) & 0xffffffff, scratch.data_ptr(),
+                                pairwise.data_ptr(), inliers.data_ptr(), status.data_ptr(), conf.data_ptr(),
+                                None if mask is None else mask.data_ptr(), _stream_ptr(dev))
+    if rc != 0:
+        raise RuntimeError(f"gsr_pnp_ransac failed with code {rc}")
+    return pairwise, inliers, status, conf, mask
+
+
+@torch.no_grad()
+def pnp_ransac(xyz: Tensor, intrinsics_px: Tensor, packed: PackedCorrespondences, *, points_2d: Optional[Tensor] = None,
+               hypotheses: int = 1000, reprojection_error: float = 5.0, seed: int = 0, return_mask: bool = False):
+    """xyz (b, v, 3, h, w), pixel-unit intrinsics (b, v, 3, 3), the packed match lists -> (pairwise (b, P, 4, 4), inliers (P b,) int32,
+    status (P b,) int32[, mask (M,) uint8]): per list the pose of the pair as the reference's `relpose` - the inverse of what
+    cv2.solvePnPRansac returns for the second view's 3-D points and the first view's 2-D points -, P3P RANSAC over `hypotheses` draws
+    and Gauss-Newton on the consensus set as include/gsr.h defines them; identity, 0 inliers and a status > 0 where there is no pose.
+    `points_2d` (M, 2): sub-pixel keypoints (x, y) in the order of the pack; None: the pixel of `ids_i`.  Two launches, no host
+    synchronisation; the same bits on every call with the same seed."""
+    pairwise, inliers, status, _conf, mask = _pnp(xyz, intrinsics_px, packed, points_2d, hypotheses, reprojection_error, 0.5, seed, return_mask)
+    return (pairwise, inliers, status, mask) if return_mask else (pairwise, inliers, status)
+
+
+@torch.no_grad()
+def synchronize_cameras(pairwise: Tensor, confidence: Tensor, num_views: int) -> Tensor:
+    """pairwise (b, P, 4, 4), confidence (P b,) in list order (pair-major), the number of views -> (b, v, 4, 4): the reference's
+    `camera_synchronization(Ps, confidence, v)` at its default arguments in one launch; a scene whose mass has a zero entry is
+    chained, by itself (include/gsr.h)."""
+    v = int(num_views)
+    if v < 2 or v > MAX_VIEWS:
+        raise ValueError(f"synchronize_cameras: needs 2 to {MAX_VIEWS} views, got {num_views}")
+    pairs = v * (v - 1) // 2
+    if pairwise.dim() != 4 or tuple(pairwise.shape[1:]) != (pairs, 4, 4):
+        raise ValueError(f"synchronize_cameras: expected pairwise (b, {pairs}, 4, 4), got {tuple(pairwise.shape)}")
+    b = pairwise.shape[0]
+    if tuple(confidence.shape) != (pairs * b,):
+        raise ValueError(f"synchronize_cameras: expected confidence (P b,) = ({pairs * b},), got {tuple(confidence.shape)}")
+    if not (pairwise.is_cuda and confidence.is_cuda):
+        raise RuntimeError("pf3plat_amd pose: tensors must be on a ROCm device (there is no CPU fallback path)")
+    if pairwise.device != confidence.device:
+        raise RuntimeError("synchronize_cameras: every tensor must be on the same device")
+    lib = _lib.load()
+    dev = pairwise.device
+    pw, cf = _f32(pairwise), _f32(confidence)
+    out = torch.empty((b, v, 4, 4), dtype=torch.float32, device=dev)
+    with _on_device(dev):
+        rc = lib.gsr_camera_sync(b, v, pw.data_ptr(), cf.data_ptr(), out.data_ptr(), _stream_ptr(dev))
+    if rc != 0:
+        raise RuntimeError(f"gsr_camera_sync failed with code {rc}")
+    return out
+
+
+@torch.no_grad()
+def coarse_poses(xyz: Tensor, intrinsics_px: Tensor, packed: PackedCorrespondences, *, points_2d: Optional[Tensor] = None,
+                 hypotheses: int = 1000, reprojection_error: float = 5.0, confidence_min: float = 0.5, seed: int = 0,
+                 return_mask: bool = False) -> CoarsePoses:
+    """The whole block: `pnp_ransac` per list, the lists' confidences (the mean score; for pairs of views that are not neighbours
+    relu(c - confidence_min) / (1 - confidence_min); 0 for an empty list) and `synchronize_cameras`.  Three launches, no host
+    synchronisation."""
+    pairwise, inliers, status, conf, mask = _pnp(xyz, intrinsics_px, packed, points_2d, hypotheses, reprojection_error, confidence_min,
+                                                 seed, return_mask)
+    absolute = synchronize_cameras(pairwise, conf, xyz.shape[1])
+    return CoarsePoses(pairwise, absolute, conf, inliers, status, mask)
