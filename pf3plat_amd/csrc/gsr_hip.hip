@@ -3,7 +3,7 @@
 // Replaces, behind the same operator surface, the external CUDA extension the reference calls at
 // src/model/decoder/cuda_splatting.py:113-124 (forward) and through autograd (backward).  The
 // arithmetic it must reproduce is restated in oracle/gsr_oracle.hpp; this
-// file is not a translation of the CUDA package's structure:
+// library is not a translation of the CUDA package's structure:
 //
 //   * one launch chain renders V views (grid.y / per-view tile ranges) instead of one chain per view;
 //   * tiles are 8x8 pixels = ONE 64-lane wavefront per tile: no block barriers in the blend loops,
@@ -23,837 +23,26 @@
 //
 // Built with -ffp-contract=off: projection / EWA / SH arithmetic then evaluates the same expression
 // trees as the fp32 oracle (IEEE +,-,*,/ and sqrt are correctly rounded on both sides).
-#ifndef GSR_POSE_HOST_ONLY  // (the host check of the coarse-pose solver at the end of this file skips to it)
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <algorithm>
-#include <atomic>
-#include <type_traits>
-
-#include "../../include/gsr.h"
-
-// Measurement-only switches (tools/ablate.py builds its own library with -DGSR_ABLATE): ablation bits that make results
-// WRONG on purpose and device-side phase stamps.  The product library is compiled without them - the branches do not
-// exist in it, and dims_ok() rejects the bits.
-#ifdef GSR_ABLATE
-#define GSR_ABL(flags, bit) (((flags) & (bit)) != 0)
-#else
-#define GSR_ABL(flags, bit) false
-#endif
+//
+// The library is ONE translation unit: this file holds the rasterizer and includes the headers below - the operators at its end,
+// in the order their text always had, which is the order of the kernels in the code object and with it their addresses
+// (tools/compare_code_objects.py is the gate for a change that must not move them).  Every header includes what it uses and
+// compiles alone (tools/check_headers.py).
+//
+//   gsr_common.h       GSR_ABL, constants, GeomRec / PreRec / Grid / Layout / Params, choose_chunk, make_layout, small device helpers,
+//                      GSR_CHECK, dispatch_bools
+//   gsr_hip.hip        K1 preprocess and binning, k_color, the windowed chain; K5 per-tile sort, K6 / K2 forward tile kernels; B1 / B2
+//                      backward (preprocess_bwd.inc, twice), pose reductions; camera set-up; dims_ok, base_params, covariance
+//                      kernels, forward_impl / backward_impl, the rasterizer's entry points
+//   gsr_image.h        image loss and evaluation metrics           }
+//   gsr_adapter.h      Gaussian adapter                            }  operators next to the raster path, each with its
+//   gsr_pose_loss.h    pose loss                                   }  kernels and its own entry points
+//   gsr_cost_volume.h  plane-sweep cost volume                     }
+//   gsr_pnp_solver.h   namespace gsr::pnp: host + device arithmetic of the coarse-pose solver (a host program includes it alone)
+//   gsr_coarse_pose.h  PnP RANSAC kernels, k_camera_sync, entry points
+#include "gsr_common.h"
 
 namespace gsr {
-
-constexpr int kChunkMax = 2048;   // most Gaussians per binning workgroup (= one row of the per-view count matrix)
-constexpr int kChunkMin = 1024;    // ... unless ONE round of smaller chunks (down to kChunkSmall) still fits the chip: see choose_chunk
-constexpr int kChunkSmall = 512;
-constexpr int kCUs = 256;
-// de-phasing of a tile launch's first resident round (sort_tile, k_tile_fwd_prefix): group = the workgroup's residency slot on its CU
-constexpr int kDephaseShift = 8, kDephaseGroups = 4;
-constexpr int kBinThreads = 1024; // threads of a binning workgroup (count / emit)
-constexpr int kTileWindow = 8192; // tiles histogrammed in LDS at a time by a binning workgroup of the WINDOWED chain (32 KiB, static)
-#ifndef GSR_FUSED_MAX_TILES
-#define GSR_FUSED_MAX_TILES 20480
-#endif
-// most tiles of an image that takes the fused binning launch (k_preprocess_bin: its per-tile counters are dynamic LDS, T x 4 bytes
-// next to the 64 KB record-transpose / pair-staging area and ~10 KB of static LDS); larger images take the windowed chain.
-// (Round 2 stopped at 8192; one 1024 x 1024 view of the 300 k scene: 236 us through the windowed chain, 187 us this way.)
-constexpr int kFusedMaxTiles = GSR_FUSED_MAX_TILES;
-static_assert(kFusedMaxTiles % 1024 == 0 && kFusedMaxTiles >= kTileWindow && 65536 + kFusedMaxTiles * 4 + 10400 <= 160 * 1024, "LDS of the fused binning launch");
-constexpr int kSortThreads = 256; // threads cooperating on one tile's sort
-constexpr int kPage = 1024;        // pairs per page of the key buffer: a binning workgroup's private region is whole pages
-constexpr int kSlotStride = 8192 + 136;  // keys between the fixed slots of consecutive binning workgroups: NOT a multiple of the memory
-                                        // channel interleave - the sort reads the same tile from every slot at once, and with a
-                                        // power-of-two stride all those reads landed on one channel (gather 16 us instead of 3)
-constexpr int kStagePairs = 8192;  // pairs a binning workgroup collects in LDS (the 64 KB record-transpose area) before one linear copy-out
-constexpr float kNear = 0.2f;     // [EXT] auxiliary.h in_frustum: p_view.z <= 0.2f culls
-
-struct __attribute__((aligned(32))) GeomRec {  // 32 B per (view, Gaussian): everything the blends gather, nothing else
-  float4 q0;  // x, y, conic a, conic b
-  float4 q1;  // conic c, opacity, extra channel, bits(radius)
-};
-// What preprocess_one produces: the record plus the footprint word q3 = bits(hit mask lo), bits(hit mask hi),
-// bits(window origin: sx0 | sy0 << 12 | big << 31), depth.  The mask lists the 8x8 tiles this splat must be listed in, over
-// the 8x8-tile window whose top-left tile is (sx0, sy0) (bit = (sy - sy0) * 8 + (sx - sx0)); footprints wider than 8 tiles set
-// `big` and are re-derived from the record by the binning kernels.  The fused binning launch consumes q3 from registers; only
-// the windowed chain (k_preprocess -> k_count / k_emit) keeps it in memory (Params::aux, 16 B per (view, Gaussian)).
-struct PreRec {
-  float4 q0, q1, q3;
-};
-// The view-dependent colour lives in its own array (float4 per (view, Gaussian): r, g, b, bits(clamp mask)) because it is
-// produced by the colour pass (k_color / color_unit), not by the geometry/binning kernel.
-
-typedef unsigned long long ull2 __attribute__((ext_vector_type(2), aligned(8)));  // two keys, 8-byte aligned
-
-struct Grid {
-  int W, H, gx16, gy16, sgx, sgy, sw, sh, T;  // sw/sh: 8x8 tiles that contain at least one pixel
-};
-
-__host__ __device__ inline Grid make_grid(int W, int H) {
-  Grid g;
-  g.W = W; g.H = H;
-  g.gx16 = (W + 15) / 16; g.gy16 = (H + 15) / 16;
-  g.sgx = 2 * g.gx16; g.sgy = 2 * g.gy16;
-  g.sw = (W + 7) / 8; g.sh = (H + 7) / 8;
-  g.T = g.sgx * g.sgy;
-  return g;
-}
-
-struct Layout {
-  size_t geom_bytes, bin_bytes, img_bytes;
-  size_t o_aux, o_rgbc, o_rows, o_shj;  // o_aux: 0 = none (fused binning path)  // in geom (only with GSR_FLAG_BACKWARD_FOLLOWS: o_rows screen-space gradient rows, o_shj d rgb / d direction)
-  size_t o_status, o_counts, o_total, o_ranges, o_keys, o_list, o_blk, o_blktot, o_order;  // in bin
-  size_t key_slots;  // keys: one fixed slot of kStagePairs keys per binning workgroup, then ...
-  size_t key_pages;  // ... a pool of pages of kPage keys (regions / scratch too long for a slot)
-  size_t stride;     // fused binning: entries of the index list owned by every (view, tile)
-  size_t o_finalT, o_ncontrib;                                   // in img
-};
-
-static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-// Gaussians per binning workgroup.  The binning kernels are latency/VALU bound per workgroup, so the chip is fullest
-// when one round of workgroups covers all CUs: the chunk (a multiple of 64 in [kChunkMin, kChunkMax]) that minimises
-// rounds x chunk, the larger one on ties (fewer rows in the count matrix).
-// Chunks above kChunkPrefer are not considered: a workgroup stages its pairs in LDS (kStagePairs = 8192) for one linear copy-out,
-// and at the ~4.2 pairs per Gaussian of PF3plat-shaped scenes a 2048-Gaussian chunk lists ~8600 - past the staging area, every
-// pair then leaves as an 8-byte store of its own (measured: 48 views x 131 072 Gaussians chose 2048 by a tie and the binning
-// launch took 2437 us instead of ~600).
-constexpr int kChunkPrefer = 1600;
-#ifndef GSR_BIN_TWO
-#define GSR_BIN_TWO 1  // 0: measurement builds without the two-per-CU instance of the plain binning launch
-#endif
-#ifndef GSR_CIB_MAX_VPS
-#define GSR_CIB_MAX_VPS 4  // most views per set whose colour pass runs inside the binning launch (see color_in_bin_for)
-#endif
-// (a launch whose workgroups sit two to a CU - the plain binning launch of a small image, k_preprocess_bin<false, false, 2048> - has
-// twice the slots per round: 8 views of 300 k Gaussians then take 1600-Gaussian chunks, three rounds, instead of 1344, four)
-// ONE statement of "which binning launch will this call take", shared by the chunk choice (host arithmetic at sizing time) and by
-// forward_impl (defined behind bin_lds_bytes, next to the launch): the colour pass inside the binning launch as far as the call's
-// dims say (forward_impl adds what only the device knows: whether it granted the LDS attribute), and whether the plain launch's
-// workgroups sit two to a CU (LDS in 1280-byte steps: images of up to 1496 tiles).
-static bool color_in_bin_by_dims(const GsrDims& d, const Grid& g);
-static bool bin_two_per_cu(const Grid& g, bool color_in_bin);
-// A round of binning workgroups costs its chunk AND a fixed part (prologue, scan, pair walk, copy-out: ~6 of the 23 us a 1600-Gaussian
-// workgroup lives) - in Gaussians.  It only decides between chunk sizes that need different numbers of rounds: PF3plat's training batch
-// (4 scenes x 3 views x 131 072: 984 workgroups of 1600 in four rounds, against 1536 of 1024 in six as the plain product chose) forward
-// 300 -> 292 us; 0 / 400 / 800 measured, forced 1344 / 1408 / 1472 (whole passes of the eleven binning waves) are slower than 1600.
-#ifndef GSR_CHUNK_FIXED
-#define GSR_CHUNK_FIXED 400
-#endif
-static int choose_chunk(const GsrDims& d) {
-  const long long V = d.num_views > 0 ? d.num_views : 1, N = d.num_gaussians > 0 ? d.num_gaussians : 1;
-  const Grid g = make_grid(d.width, d.height);
-  const bool plain_two = bin_two_per_cu(g, color_in_bin_by_dims(d, g));
-  const long long slots = plain_two ? 2 * kCUs : kCUs;
-  long long best_cost = -1;
-  int best = kChunkPrefer;
-  for (int c = kChunkPrefer; c >= kChunkSmall; c -= 64) {
-    const long long blocks = V * ((N + c - 1) / c), cost = ((blocks + slots - 1) / slots) * (c + GSR_CHUNK_FIXED);
-    // chunks below kChunkMin only while a single round of workgroups holds them all: one 131 072-Gaussian view (configs[4]'s share of
-    // a GPU, PF3plat's native size) took 128 workgroups of 1024 - half the chip idle through the whole binning launch (19.5 us); 256
-    // workgroups of 512 are one projection pass per wave instead of two.  With several rounds the per-workgroup prologue, scan and
-    // copy-out are paid per round: there the larger chunks stay.
-    if (c < kChunkMin && blocks > slots) break;
-    if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = c; }
-  }
-  return best;
-}
-
-// Does a forward that announces its backward (GSR_FLAG_BACKWARD_FOLLOWS) save d rgb / d direction per (view, Gaussian) for it?
-// The rows are 48 bytes per view and Gaussian, written by the colour pass and read back by k_preprocess_bwd; the alternative - the
-// backward reads the harmonics again and re-derives them - is 12 K bytes per Gaussian ONCE for all views of its set, fewer bytes from
-// three views per set on.  Measured (fwd + bwd, saved / re-derived): one view 124.8 / 135.8 us, two 107 / 116 per view, three views of
-// 131 072 Gaussians 73.0 / 75.0, eight views 86.4 / 89.7 - the re-derivation is arithmetic in a launch that has none to spare; always saved.
-#ifndef GSR_SHJ_MAX_VIEWS
-#define GSR_SHJ_MAX_VIEWS (1 << 30)
-#endif
-static inline bool saves_jacobian(const GsrDims& d) {
-  return (d.flags & GSR_FLAG_BACKWARD_FOLLOWS) && d.sh_coeffs > 0 && d.views_per_set <= GSR_SHJ_MAX_VIEWS;
-}
-
-static Layout make_layout(const GsrDims& d) {
-  Layout L;
-  const Grid g = make_grid(d.width, d.height);
-  const size_t V = d.num_views, N = d.num_gaussians, VT = V * (size_t)g.T;
-  const size_t cap = d.pair_capacity > 0 ? (size_t)d.pair_capacity : 0;
-  const bool windowed = g.T > kFusedMaxTiles || (d.flags & GSR_FLAG_WINDOWED_BINNING) != 0;
-  // every sub-array of `geom` starts on a 2 MiB boundary: the backward kernels gather / scatter by Gaussian index into three of
-  // them at once, and with the arrays packed at 256-byte granularity the 300 k-Gaussian training step was 2-3 us slower for
-  // some sizes of the first array than for others (measured: 143.5-144.2 us packed, 141.4-142.6 aligned)
-#ifndef GSR_GEOM_ALIGN
-#define GSR_GEOM_ALIGN 2097152
-#endif
-  constexpr size_t kGA = GSR_GEOM_ALIGN;
-  const size_t rec_bytes = align_up(V * N * sizeof(GeomRec), kGA);
-  L.o_aux = windowed ? rec_bytes : 0;
-  L.o_rgbc = rec_bytes + (windowed ? align_up(V * N * sizeof(float4), kGA) : 0);
-  L.o_rows = L.o_rgbc + align_up(V * N * sizeof(float4), kGA);
-  L.o_shj = L.o_rows + ((d.flags & GSR_FLAG_BACKWARD_FOLLOWS)
-                            ? align_up((d.flags & GSR_FLAG_DETERMINISTIC) ? V * N * GSR_SCREEN_GRAD_FLOATS * 8 + V * 4  // (det_max_words)
-                                                                          : V * N * GSR_SCREEN_GRAD_FLOATS * 4, kGA) : 0);
-  L.geom_bytes = L.o_shj + (saves_jacobian(d) ? align_up(V * N * 3 * sizeof(float4), 256) : 0);
-  size_t o = 0;
-  L.o_status = o; o = align_up(o + sizeof(GsrStatus), 256);
-  const size_t rows = (N + choose_chunk(d) - 1) / choose_chunk(d);
-  L.o_counts = o; o = align_up(o + V * (rows > 0 ? rows : 1) * (size_t)(g.T + 8) * 8, 256);  // uint2 (offset, count); rows padded by 8
-  L.o_total = o; o = align_up(o + VT * 4, 256);
-  L.o_ranges = o; o = align_up(o + VT * 8, 256);
-  // keys: a fixed slot per binning workgroup (all it needs unless it lists more than kStagePairs pairs), then a page pool
-  // for the longer regions and for the contiguous scratch of per-tile lists too long for the LDS sort
-  const size_t blocks = V * (rows > 0 ? rows : 1);
-  L.key_slots = blocks * (size_t)kSlotStride;
-  L.key_pages = (cap + kPage - 1) / kPage + 64;  // (capacity = 2 x pairs, what gsr_capacity_for returns, holds every pair twice)
-  L.o_keys = o; o = align_up(o + (L.key_slots + L.key_pages * kPage) * 8 + 64, 256);  // + padding: 16-byte reads may overrun a run by one key
-  L.o_list = o; o = align_up(o + cap * 4, 256);
-  L.o_blk = o; o = align_up(o + blocks * 4, 256);
-  L.o_blktot = o; o = align_up(o + blocks * 4, 256);
-  L.o_order = o; o = align_up(o + VT * 4, 256);  // tile_order (device side: tile_order_of - directly behind blk_total)
-  L.stride = VT > 0 ? cap / (2 * VT) : 0;  // half of the index list in per-tile slots, the rest a shared tail (longer lists)
-  L.bin_bytes = o;
-  const size_t px = V * (size_t)d.height * d.width;
-  L.o_finalT = 0;
-  L.o_ncontrib = align_up(px * 4, 256);
-  L.img_bytes = align_up(L.o_ncontrib + px * 4, 256);
-  return L;
-}
-
-struct Params {
-  GsrDims d;
-  Grid g;
-  int rows;   // binning chunks per view = ceil(N / chunk)
-  int chunk;  // Gaussians per binning workgroup (choose_chunk)
-  const GsrView* views;
-  const float *means, *cov6, *opac, *colors, *extra;
-  const float* frames;   // scale/rotation input form (GsrForwardOptions.scale_rot): cov6 points at (S, N, 7) records, frames at
-  int num_frames;        // (S, F, 3, 3) rotations (nullable) applied to the Gaussians of each of the F equal groups of a set
-  int scale_rot;         // 1: that form is in use
-  float* out_color;
-  float* out_extra;
-  union {
-    int32_t* radii;              // forward
-    const float* dL_dalpha_img;  // backward - (V, H, W), or null (shares the forward-only pointer's storage: see out_alpha)
-  };
-  GeomRec* geom;
-  float4* aux;  // footprint words of the windowed binning chain (null on the fused path)
-  float4* rgbc;
-  float4* grad_rows;  // forward with GSR_FLAG_BACKWARD_FOLLOWS: the rows the geometry kernels zero-fill (else null)
-  float4* shj;        // same flag, SH colours: d rgb / d (unit view direction) of every (view, Gaussian), 3 x float4 = rows x, y, z
-                      // (r, g, b, -): saved by the colour pass so that the backward need not read the harmonics again (else null)
-  GsrStatus* status;
-  uint32_t* counts;      // windowed path: u32 count matrix; fused path: the same storage as uint2 (offset, count)
-  uint2* pair_mat;
-  uint32_t* blk_base;    // fused path: first key of every binning workgroup's region (0xffffffff: not stored)
-  uint32_t* blk_total;   // fused path: pairs listed by every binning workgroup
-  uint32_t key_pages;    // pages in the pool behind the fixed slots
-  uint32_t pool_off;     // first key of the pool
-  uint32_t stride;       // index-list entries owned by every (view, tile)
-  uint32_t tail_off, tail_cap;  // the rest of the index list: lists longer than `stride`, bump-allocated
-  uint32_t* tail_counter;
-  unsigned long long* page_counter;  // in the status block: (call tag << 32) | pool pages handed out so far by the binning launch
-  unsigned long long* page_counter_tiles;  // same form, by the tile launch (its pages are the upper half of the pool)
-  uint32_t call_tag;       // unique per gsr_forward call of this process: a counter left by another call reads as zero
-  uint32_t sort_blocks;    // workgroups of the tile launch = views x tiles
-  uint32_t color_units;    // colour units per set = ceil(N / 64)
-  uint32_t* tile_total;
-  uint2* ranges;
-  unsigned long long* keys;
-  uint32_t* point_list;
-  float* final_T;
-  uint32_t* n_contrib;
-  // backward only
-  const float *dL_dcolor, *dL_dextra_img;
-  float* scratch;
-  float *dL_dmeans, *dL_dcov6, *dL_dopac, *dL_dcolors, *dL_dextra, *dL_dmeans2D;  // (scale_rot: dL_dcov6 is (S, N, 7))
-  // accumulated alpha (GsrForwardOptions.out_alpha / GsrBackwardOptions.dL_dalpha_img; read by the kAlpha instances only).  The struct keeps its size and
-  // every field its offset - kernels that take their arguments from it, copy it or carry an argument behind it are then the code
-  // they were - so the two pointers share the storage of one that only the OTHER direction's kernels read.  (A backward kernel that
-  // ever needs `radii`, or a forward kernel `pose_partials`, takes that pointer out of its union first.)
-  union {
-    float* pose_partials;  // backward - camera gradients requested: [view][preprocess_bwd workgroup][DPP row 0..3][kPoseFloats]
-    float* out_alpha;      // forward - (V, H, W) 1 - final_T, or null
-  };
-};
-static_assert(sizeof(Params) == 464, "Params as the kernels without kAlpha were built around it");
-
-// ------------------------------------------------------------------------------------------------
-// small device helpers
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-// Inclusive prefix sum over the 64 lanes of a wave, DPP only (no LDS permutes): Hillis-Steele inside each 16-lane row
-// (row_shr 1, 2, 4, 8; lanes shifted in from outside the row read 0), then lane 15 of row 0 / 2 into rows 1 / 3
-// (row_bcast15) and lane 31 into rows 2 and 3 (row_bcast31).
-template <int CTRL, int ROW_MASK, bool BOUND>
-__device__ __forceinline__ uint32_t dpp_take_u32(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, BOUND);
-}
-__device__ __forceinline__ uint32_t wave_inclusive_scan_u32(uint32_t v) {
-  v += dpp_take_u32<0x111, 0xf, true>(v);   // row_shr:1
-  v += dpp_take_u32<0x112, 0xf, true>(v);   // row_shr:2
-  v += dpp_take_u32<0x114, 0xf, true>(v);   // row_shr:4
-  v += dpp_take_u32<0x118, 0xf, true>(v);   // row_shr:8
-  v += dpp_take_u32<0x142, 0xa, false>(v);  // row_bcast15 -> rows 1 and 3
-  v += dpp_take_u32<0x143, 0xc, false>(v);  // row_bcast31 -> rows 2 and 3
-  return v;
-}
-// Maximum over the 64 lanes of a wave (every lane active), DPP rotations inside the 16-lane rows, then the four row results
-// through scalar registers.
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp_row_max_u32(uint32_t v) {
-  const uint32_t o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false);
-  return o > v ? o : v;
-}
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-  v = dpp_row_max_u32<0x128>(v);  // row_ror:8
-  v = dpp_row_max_u32<0x124>(v);  // row_ror:4
-  v = dpp_row_max_u32<0x122>(v);  // row_ror:2
-  v = dpp_row_max_u32<0x121>(v);  // row_ror:1
-  const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)v, 0), r1 = (uint32_t)__builtin_amdgcn_readlane((int)v, 16);
-  const uint32_t r2 = (uint32_t)__builtin_amdgcn_readlane((int)v, 32), r3 = (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
-  const uint32_t a = r0 > r1 ? r0 : r1, b = r2 > r3 ? r2 : r3;
-  return a > b ? a : b;
-}
-
-// What the colour pass reads of a view: fetched through the CONSTANT address space, i.e. by scalar loads (s_load_dword, the scalar
-// cache) into scalar registers - the records are written by an earlier launch and wave-uniform here.  As a plain `p.views[v]` read
-// the compiler issues a per-lane global load, and every unit's evaluation then starts by waiting a memory round trip for it
-// under the colour stream.  The colour waves of the binning launch ask for the first view's values BEFORE they wait for the
-// unit's rows (cam_lite early, `cam0`), so the values are there when the rows are.
-struct CamLite { float scale, cx, cy, cz; };
-__device__ __forceinline__ CamLite cam_lite(const GsrView* views, int v_uniform) {
-  typedef const __attribute__((address_space(4))) float* cptr;
-  cptr c = reinterpret_cast<cptr>(reinterpret_cast<uintptr_t>(views + v_uniform));
-  return CamLite{c[40], c[32], c[33], c[34]};  // GsrView: scale at float 40, campos at 32..34
-}
-
-// The whole record that way (fields that are not used cost nothing): for the kernels whose lanes all work on one view at a time.
-__device__ __forceinline__ GsrView view_const(const GsrView* views, int v_uniform) {
-  typedef const __attribute__((address_space(4))) float* cptr;
-  cptr c = reinterpret_cast<cptr>(reinterpret_cast<uintptr_t>(views + __builtin_amdgcn_readfirstlane(v_uniform)));
-  GsrView o;
-  float* f = reinterpret_cast<float*>(&o);
-#pragma unroll
-  for (int k = 0; k < (int)(sizeof(GsrView) / 4); ++k) f[k] = c[k];
-  return o;
-}
-
-// XCD-aware tile order: workgroup b runs on XCD b % 8 (observed dispatch order; speed only), so give
-// each XCD a contiguous run of tiles - neighbouring tiles gather the same splat records from one L2.
-__device__ __forceinline__ int xcd_remap(int b, int n) {
-  const int q = n >> 3, r = n & 7;
-  const int xcd = b & 7, k = b >> 3;
-  const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return base + k;
-}
-
-// ---- The deal of an XCD's tiles to its 32 CUs by load: heaviest first, every other round of 32 mirrored (k_blend_bwd has the
-// measurements).  Shared by k_blend_bwd, which finds its tile from the forward's walked counts, and by the single view's forward
-// tile launch, which takes its tile from a table (tile_order) the binning launch builds from what the PREVIOUS forward walked.
-constexpr int kBalanceMax = 256;  // tiles per XCD up to which the deal is computed (more: image order; later rounds balance themselves)
-// keys (load + 1) << 8 | (255 - index): distinct, heavier first, equal loads in index order.  CORRECTNESS rests on the low 8 bits
-// alone - they are distinct, so the deal is a bijection of the XCD's tiles whatever the counts hold (walked counts after a normal
-// forward; binning totals or anything else after an overflowed one, or in a fresh workspace) - the load only decides the ORDER; it
-// is clamped so that the shift cannot drop its high bits (the order stays monotonic)
-__device__ __forceinline__ uint32_t deal_key(uint32_t load, int index) {
-  return ((min(load, 0xfffffeu) + 1u) << 8) | (uint32_t)(255 - index);
-}
-// position in heaviest-first order that the XCD's k-th workgroup takes; its own inverse (the k of the workgroup that takes position k)
-__device__ __forceinline__ int deal_position(int k, int cnt) {
-  const int round = k >> 5, in = k & 31, len = cnt - (round << 5) < 32 ? cnt - (round << 5) : 32;
-  return (round << 5) + ((round & 1) ? len - 1 - in : in);
-}
-// The forward's deal: one view whose tile workgroups are all resident at once (four per CU) - what a CU is busy for is then the sum
-// of its up to four tiles, and nothing rebalances it.  Every other call keeps xcd_remap's image order: several views, more tiles
-// than one round, no more tiles than CUs (nothing to balance) - or a binning launch without kDealBlocks idle CUs for the table's
-// builders (below): they would be a second round of that launch (one 131 072-Gaussian view, 256 binning workgroups: binning
-// 16.7 -> 19.7 us for a tile launch 2.3 us shorter).
-constexpr int kDealBlocks = 8;  // one builder workgroup per XCD
-__host__ __device__ __forceinline__ bool fwd_deal_active(const Params& p) {
-  return p.d.num_views == 1 && p.g.T > kCUs && p.g.T <= 4 * kCUs && p.rows + kDealBlocks <= kCUs;
-}
-// tile_order: one word per (view, tile), behind blk_total in `bin` (make_layout: o_order)
-__device__ __forceinline__ uint32_t* tile_order_of(const Params& p) {
-  return p.blk_total + ((((size_t)p.d.num_views * p.rows * 4 + 255) & ~(size_t)255) >> 2);
-}
-// K1's side: wave c (0 ... 3) of a workgroup ranks keys 64 c ... 64 c + 63 of XCD `xcd` among the XCD's <= kBalanceMax keys - the
-// keys pass as lane broadcasts, no LDS, no barrier - and stores tile_order[block] = tile for the workgroups that take them.
-__device__ __forceinline__ void build_tile_order_wave(const Params& p, const int xcd, const int c, const int lane) {
-  const int T = p.g.T, cnt = (T >> 3) + (xcd < (T & 7) ? 1 : 0), base = xcd_remap(xcd, T);  // this XCD's tiles: [base, base + cnt)
-  if (cnt > kBalanceMax || 64 * c >= cnt) return;
-  const uint32_t* tot = p.tile_total + base;
-  uint32_t key[4], mine = 0;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int i = lane + 64 * q;
-    key[q] = i < cnt ? deal_key(tot[i], i) : 0u;  // (0: below every key)
-    mine = q == c ? key[q] : mine;
-  }
-  int rank = 0;  // keys above mine = my position in heaviest-first order
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    if (64 * q >= cnt) break;
-#pragma unroll 8
-    for (int j = 0; j < 64; ++j) rank += (uint32_t)__builtin_amdgcn_readlane((int)key[q], j) > mine ? 1 : 0;
-  }
-  const int i = lane + 64 * c;
-  if (i < cnt) tile_order_of(p)[(deal_position(rank, cnt) << 3) | xcd] = (uint32_t)(base + i);
-}
-// Who builds it: kDealBlocks workgroups of the fused binning launch BEHIND its `rows` binning workgroups, one per XCD's table (the
-// tile launch runs after that kernel, the previous call's tile launch - which left the counts - before it).  They are workgroups of
-// their own because the launch has compute units to spare for them - 247 binning workgroups on 256 CUs in the 300 k view - and
-// none of its own waves has: built by the binning waves of rows 0 ... 7 in their tail, under the harmonics stream, the same table
-// made the launch 1.0 us longer (23.9 -> 24.9 us; a trip to memory and ~400 VALU instructions per wave on SIMDs the colour waves fill).
-// A single view that takes the binning launch WITHOUT colour waves (a device that does not grant it the LDS) gets the table from
-// a launch of its own, k_tile_order, in front: those instances stay the code they were (the two-per-CU one spills with it).
-__device__ __forceinline__ void build_tile_order(const Params& p, const int xcd, const int w, const int lane) {
-  if (w < 4) build_tile_order_wave(p, xcd, w, lane);
-}
-__global__ __launch_bounds__(256) void k_tile_order(const Params p) {
-  build_tile_order(p, (int)blockIdx.x, (int)(threadIdx.x >> 6), (int)(threadIdx.x & 63));
-}
-// K2's side: the (view, tile) of workgroup `bid` of a gathering tile launch, in two steps so that a kernel can ask for the word at
-// its start and look at it where it first needs the tile.  The dealt tile is read from the table - never from tile_total itself,
-// which tiles of the same launch overwrite - and is clamped: whatever the word holds, the tile exists.  A VECTOR load (the
-// relaxed atomic keeps it one): the scalar loads of a wave return in any order, so the next wait for one of them - the status
-// word thread 0 asks for - would wait for this word too, one round trip behind the other.
-__device__ __forceinline__ uint32_t fwd_tile_word(const Params& p, const uint32_t bid) {
-  if (!fwd_deal_active(p)) return (uint32_t)xcd_remap((int)bid, (int)p.sort_blocks);
-  return __hip_atomic_load(tile_order_of(p) + bid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ int fwd_tile_of(const Params& p, const uint32_t word) {
-  return (int)min((uint32_t)__builtin_amdgcn_readfirstlane((int)word), p.sort_blocks - 1u);
-}
-
-// Real-SH polynomial basis and its x/y/z partials, visited in coefficient order with compile-time k.
-// Same expression trees as oracle/gsr_oracle.hpp sh_basis / sh_basis_grad ([EXT] forward.cu
-// computeColorFromSH, backward.cu computeColorFromSH; band 4 per SURVEY.md Appendix A.1).
-template <class F>
-__device__ __forceinline__ void sh_visit(int deg, float x, float y, float z, F&& f) {
-  constexpr float C0 = 0.28209479177387814f, C1 = 0.4886025119029199f;
-  constexpr float C20 = 1.0925484305920792f, C21 = -1.0925484305920792f, C22 = 0.31539156525252005f,
-                  C23 = -1.0925484305920792f, C24 = 0.5462742152960396f;
-  constexpr float C30 = -0.5900435899266435f, C31 = 2.890611442640554f, C32 = -0.4570457994644658f,
-                  C33 = 0.3731763325901154f, C34 = -0.4570457994644658f, C35 = 1.445305721320277f,
-                  C36 = -0.5900435899266435f;
-  constexpr float C40 = 2.5033429417967046f, C41 = -1.7701307697799304f, C42 = 0.9461746957575601f,
-                  C43 = -0.6690465435572892f, C44 = 0.10578554691520431f, C45 = -0.6690465435572892f,
-                  C46 = 0.47308734787878004f, C47 = -1.7701307697799304f, C48 = 0.6258357354491761f;
-  f(0, C0, 0.f, 0.f, 0.f);
-  if (deg > 0) {
-    f(1, -C1 * y, 0.f, -C1, 0.f);
-    f(2, C1 * z, 0.f, 0.f, C1);
-    f(3, -C1 * x, -C1, 0.f, 0.f);
-    if (deg > 1) {
-      const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-      f(4, C20 * xy, C20 * y, C20 * x, 0.f);
-      f(5, C21 * yz, 0.f, C21 * z, C21 * y);
-      f(6, C22 * (2.f * zz - xx - yy), C22 * -2.f * x, C22 * -2.f * y, C22 * 4.f * z);
-      f(7, C23 * xz, C23 * z, 0.f, C23 * x);
-      f(8, C24 * (xx - yy), C24 * 2.f * x, C24 * -2.f * y, 0.f);
-      if (deg > 2) {
-        f(9, C30 * y * (3.f * xx - yy), C30 * 6.f * xy, C30 * (3.f * xx - 3.f * yy), 0.f);
-        f(10, C31 * xy * z, C31 * yz, C31 * xz, C31 * xy);
-        f(11, C32 * y * (4.f * zz - xx - yy), C32 * -2.f * xy, C32 * (4.f * zz - xx - 3.f * yy), C32 * 8.f * yz);
-        f(12, C33 * z * (2.f * zz - 3.f * xx - 3.f * yy), C33 * -6.f * xz, C33 * -6.f * yz,
-          C33 * (6.f * zz - 3.f * xx - 3.f * yy));
-        f(13, C34 * x * (4.f * zz - xx - yy), C34 * (4.f * zz - 3.f * xx - yy), C34 * -2.f * xy, C34 * 8.f * xz);
-        f(14, C35 * z * (xx - yy), C35 * 2.f * xz, C35 * -2.f * yz, C35 * (xx - yy));
-        f(15, C36 * x * (xx - 3.f * yy), C36 * (3.f * xx - 3.f * yy), C36 * -6.f * xy, 0.f);
-        if (deg > 3) {
-          f(16, C40 * xy * (xx - yy), C40 * (3.f * xx * y - yy * y), C40 * (xx * x - 3.f * x * yy), 0.f);
-          f(17, C41 * yz * (3.f * xx - yy), C41 * 6.f * xy * z, C41 * z * (3.f * xx - 3.f * yy), C41 * y * (3.f * xx - yy));
-          f(18, C42 * xy * (7.f * zz - 1.f), C42 * y * (7.f * zz - 1.f), C42 * x * (7.f * zz - 1.f), C42 * 14.f * xy * z);
-          f(19, C43 * yz * (7.f * zz - 3.f), 0.f, C43 * z * (7.f * zz - 3.f), C43 * y * (21.f * zz - 3.f));
-          f(20, C44 * (zz * (35.f * zz - 30.f) + 3.f), 0.f, 0.f, C44 * (140.f * zz * z - 60.f * z));
-          f(21, C45 * xz * (7.f * zz - 3.f), C45 * z * (7.f * zz - 3.f), 0.f, C45 * x * (21.f * zz - 3.f));
-          f(22, C46 * (xx - yy) * (7.f * zz - 1.f), C46 * 2.f * x * (7.f * zz - 1.f), C46 * -2.f * y * (7.f * zz - 1.f),
-            C46 * 14.f * z * (xx - yy));
-          f(23, C47 * xz * (xx - 3.f * yy), C47 * z * (3.f * xx - 3.f * yy), C47 * -6.f * xy * z, C47 * x * (xx - 3.f * yy));
-          f(24, C48 * (xx * (xx - 3.f * yy) - yy * (3.f * xx - yy)), C48 * (4.f * xx * x - 12.f * x * yy),
-            C48 * (4.f * yy * y - 12.f * xx * y), 0.f);
-        }
-      }
-    }
-  }
-}
-
-// Input layouts (GsrDims.flags): covariances as 6 floats xx,xy,xz,yy,yz,zz (the rasterizer's cov3D_precomp) or, with
-// GSR_FLAG_COV_3X3, as the full symmetric 3x3 PF3plat carries (only its upper triangle is read, and only the upper
-// triangle receives gradient - exactly what the reference's fancy-index gather does, cuda_splatting.py:115,123);
-// SH as (N, M, 3) (the rasterizer's shs) or, with GSR_FLAG_SH_PLANAR, as PF3plat's harmonics (N, 3, M).
-__device__ __forceinline__ void load_cov6(const float* cov, size_t gi, bool c9, float* o) {
-  if (c9) {
-    const float* c = cov + 9 * gi;
-    o[0] = c[0]; o[1] = c[1]; o[2] = c[2]; o[3] = c[4]; o[4] = c[5]; o[5] = c[8];
-  } else {
-    const float* c = cov + 6 * gi;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) o[k] = c[k];
-  }
-}
-
-// Scale / rotation input form: what PF3plat's GaussianAdapter does between its raw network outputs and the covariance it
-// hands to the decoder (reference src/model/encoder/common/gaussians.py:8-44 quaternion_to_matrix + build_covariance,
-// gaussian_adapter.py:79-83 rotation into world space), evaluated on load instead of materialising (N, 3, 3) matrices:
-//   record = scale (x, y, z), quaternion (x, y, z, w);   two_s = 2 / (|q|^2 + 1e-8);   Rq from the quaternion;
-//   M = F Rq  (F: camera-to-world rotation of the Gaussian's source view, optional);   Sigma = M diag(s^2) M^T.
-__device__ __forceinline__ void sr_matrix(const float* sr, const float* F, float* M, float& ts) {
-  const float i = sr[3], j = sr[4], k = sr[5], r = sr[6];
-  ts = 2.f / (i * i + j * j + k * k + r * r + 1e-8f);
-  const float Rq[9] = {1.f - ts * (j * j + k * k), ts * (i * j - k * r), ts * (i * k + j * r),
-                       ts * (i * j + k * r), 1.f - ts * (i * i + k * k), ts * (j * k - i * r),
-                       ts * (i * k - j * r), ts * (j * k + i * r), 1.f - ts * (i * i + j * j)};
-  if (F) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-      for (int b = 0; b < 3; ++b) M[3 * a + b] = F[3 * a] * Rq[b] + F[3 * a + 1] * Rq[3 + b] + F[3 * a + 2] * Rq[6 + b];
-  } else {
-#pragma unroll
-    for (int a = 0; a < 9; ++a) M[a] = Rq[a];
-  }
-}
-__device__ __forceinline__ void cov6_from_sr(const float* sr, const float* F, float* o) {
-  float M[9], ts;
-  sr_matrix(sr, F, M, ts);
-  const float s0 = sr[0] * sr[0], s1 = sr[1] * sr[1], s2 = sr[2] * sr[2];
-  auto S = [&](int a, int b) { return M[3 * a] * s0 * M[3 * b] + M[3 * a + 1] * s1 * M[3 * b + 1] + M[3 * a + 2] * s2 * M[3 * b + 2]; };
-  o[0] = S(0, 0); o[1] = S(0, 1); o[2] = S(0, 2); o[3] = S(1, 1); o[4] = S(1, 2); o[5] = S(2, 2);
-}
-// dL/d(record) from dL/dcov6 (doubled off-diagonals, as the raster backward produces them)
-__device__ __forceinline__ void sr_backward(const float* sr, const float* F, const float* dc, float* dsr) {
-  float M[9], ts;
-  sr_matrix(sr, F, M, ts);
-  const float G[9] = {dc[0], 0.5f * dc[1], 0.5f * dc[2], 0.5f * dc[1], dc[3], 0.5f * dc[4], 0.5f * dc[2], 0.5f * dc[4], dc[5]};
-  float dM[9];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float m[3] = {M[k], M[3 + k], M[6 + k]};  // column k of M
-    float Gm[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) Gm[a] = G[3 * a] * m[0] + G[3 * a + 1] * m[1] + G[3 * a + 2] * m[2];
-    dsr[k] = 2.f * sr[k] * (m[0] * Gm[0] + m[1] * Gm[1] + m[2] * Gm[2]);
-    const float s2 = 2.f * sr[k] * sr[k];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) dM[3 * a + k] = s2 * Gm[a];
-  }
-  float D[9];  // dL/dRq = F^T dL/dM
-  if (F) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-      for (int b = 0; b < 3; ++b) D[3 * a + b] = F[a] * dM[b] + F[3 + a] * dM[3 + b] + F[6 + a] * dM[6 + b];
-  } else {
-#pragma unroll
-    for (int a = 0; a < 9; ++a) D[a] = dM[a];
-  }
-  const float i = sr[3], j = sr[4], k = sr[5], r = sr[6];
-  // Rq = I + two_s P(q):  dL/dq = two_s sum D : dP/dq  -  two_s^2 q sum D : P
-  const float DP = D[0] * -(j * j + k * k) + D[1] * (i * j - k * r) + D[2] * (i * k + j * r) + D[3] * (i * j + k * r) +
-                   D[4] * -(i * i + k * k) + D[5] * (j * k - i * r) + D[6] * (i * k - j * r) + D[7] * (j * k + i * r) +
-                   D[8] * -(i * i + j * j);
-  const float di = D[1] * j + D[2] * k + D[3] * j - 2.f * i * D[4] - r * D[5] + k * D[6] + r * D[7] - 2.f * i * D[8];
-  const float dj = -2.f * j * D[0] + i * D[1] + r * D[2] + i * D[3] + k * D[5] - r * D[6] + k * D[7] - 2.f * j * D[8];
-  const float dk = -2.f * k * D[0] - r * D[1] + i * D[2] + r * D[3] - 2.f * k * D[4] + j * D[5] + i * D[6] + j * D[7];
-  const float dr = -k * D[1] + j * D[2] + k * D[3] - i * D[5] - j * D[6] + i * D[7];
-  const float c = ts * ts * DP;
-  dsr[3] = ts * di - c * i; dsr[4] = ts * dj - c * j; dsr[5] = ts * dk - c * k; dsr[6] = ts * dr - c * r;
-}
-// The covariance of Gaussian i of `set` in whichever input form the call uses
-__device__ __forceinline__ void load_covariance(const Params& p, int set, int i, size_t gi, float* o) {
-  if (p.scale_rot) {
-    const int N = p.d.num_gaussians;
-    const float* F = p.frames ? p.frames + ((size_t)set * p.num_frames + (size_t)i / (size_t)(N / p.num_frames)) * 9 : nullptr;
-    cov6_from_sr(p.cov6 + 7 * gi, F, o);
-  } else {
-    load_cov6(p.cov6, gi, (p.d.flags & GSR_FLAG_COV_3X3) != 0, o);
-  }
-}
-
-// GSR_FLAG_SH_IN_FRAME: the harmonics of Gaussian i of `set` are in the coordinates of G = F = frames[set, i / (N / F)], or, with
-// GSR_FLAG_SH_FRAME_E3NN, of G = M F M^T (M = Z P, P: (x, y, z) -> (z, x, y), Z = diag(-1, -1, 1)).  Evaluating them at the
-// view direction d' = G^T d is the same as evaluating rotate_sh(harmonics, F, basis) at d.  T receives G^T row by row (T[3k + j]
-// = G[j][k]); the direction gradient goes back to world coordinates as dd = T^T dd'.  M is a signed permutation, so the e3nn
-// form is a re-indexing with signs: G[j][k] = s_j s_k F[pi_j][pi_k], pi = (2, 0, 1), s = (-1, -1, 1).  The lanes of a unit read
-// the same 36 bytes unless a group boundary falls inside the unit (one cache line per load instruction either way).
-__device__ __forceinline__ void load_dir_frame(const Params& p, int set, int i, float (&T)[9]) {
-  const int N = p.d.num_gaussians;
-  const int f = min(i, N - 1) / (N / p.num_frames);
-  const float* F = p.frames + ((size_t)set * p.num_frames + f) * 9;
-  float R[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) R[k] = F[k];
-  if (p.d.flags & GSR_FLAG_SH_FRAME_E3NN) {
-    const int pi[3] = {2, 0, 1};
-    const float s[3] = {-1.f, -1.f, 1.f};
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-#pragma unroll
-      for (int k = 0; k < 3; ++k) T[3 * k + j] = s[j] * s[k] * R[3 * pi[j] + pi[k]];
-  } else {
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-#pragma unroll
-      for (int k = 0; k < 3; ++k) T[3 * k + j] = R[3 * j + k];
-  }
-}
-// d' = T d (the direction in the harmonics' frame); in place
-__device__ __forceinline__ void dir_to_frame(const float (&T)[9], float& x, float& y, float& z) {
-  const float a = T[0] * x + T[1] * y + T[2] * z, b = T[3] * x + T[4] * y + T[5] * z, c = T[6] * x + T[7] * y + T[8] * z;
-  x = a; y = b; z = c;
-}
-// dd = T^T dd' (a gradient w.r.t. the frame's direction back to world coordinates); in place
-__device__ __forceinline__ void grad_to_world(const float (&T)[9], float& x, float& y, float& z) {
-  const float a = T[0] * x + T[3] * y + T[6] * z, b = T[1] * x + T[4] * y + T[7] * z, c = T[2] * x + T[5] * y + T[8] * z;
-  x = a; y = b; z = c;
-}
-
-// Built-in extra channel (GsrDims.flags bits 4-6, GSR_EXTRA_*): the scalar the reference's depth render blends
-// (cuda_splatting.py:238-251) - camera-space z in UN-normalised units (z_scaled / scale), mapped by the mode - and its
-// derivative w.r.t. z for the backward chain.  near/far are the caller's un-normalised values (GsrView.near/far).
-__device__ __forceinline__ float extra_from_depth(int mode, float z, float nr, float fr, float& dfdz) {
-  const float eps = 1e-10f;
-  if (mode == GSR_EXTRA_DEPTH) { dfdz = 1.f; return z; }
-  if (mode == GSR_EXTRA_DISPARITY) { const float r = 1.f / z; dfdz = -r * r; return r; }
-  if (mode == GSR_EXTRA_RELATIVE_DISPARITY) {  // depth_to_relative_disparity, conversions.py:17-27
-    const float dn = 1.f / (nr + eps), df = 1.f / (fr + eps), d = 1.f / (z + eps);
-    const float k = 1.f / (dn - df + eps);
-    dfdz = d * d * k;
-    return 1.f - (d - df) * k;
-  }
-  dfdz = 0.f;  // GSR_EXTRA_LOG: the reference's min(near).max(far).log() is the constant log(far) (cuda_splatting.py:251)
-  return logf(fmaxf(fminf(z, nr), fr));
-}
-
-// EWA projection pieces shared by forward and backward ([EXT] forward.cu computeCov2D);
-// same expression trees as oracle cov2d_parts.
-struct Cov2D {
-  float t0, t1, t2;
-  float M[6];
-  float a, b, c;
-  float fx, fy;
-  bool xcl, ycl;
-};
-
-__device__ __forceinline__ void cov2d_parts(const float mx, const float my, const float mz, const float* cov6,
-                                            const GsrView& cam, int W, int H, Cov2D& o) {
-  const float* v = cam.viewmatrix;
-  float t0 = v[0] * mx + v[4] * my + v[8] * mz + v[12];
-  float t1 = v[1] * mx + v[5] * my + v[9] * mz + v[13];
-  const float t2 = v[2] * mx + v[6] * my + v[10] * mz + v[14];
-  const float limx = 1.3f * cam.tanfovx, limy = 1.3f * cam.tanfovy;
-  const float txtz = t0 / t2, tytz = t1 / t2;
-  o.xcl = (txtz < -limx) || (txtz > limx);
-  o.ycl = (tytz < -limy) || (tytz > limy);
-  t0 = fminf(limx, fmaxf(-limx, txtz)) * t2;
-  t1 = fminf(limy, fmaxf(-limy, tytz)) * t2;
-  o.t0 = t0; o.t1 = t1; o.t2 = t2;
-  o.fx = (float)W / (2.f * cam.tanfovx);
-  o.fy = (float)H / (2.f * cam.tanfovy);
-  const float J00 = o.fx / t2, J02 = -(o.fx * t0) / (t2 * t2);
-  const float J11 = o.fy / t2, J12 = -(o.fy * t1) / (t2 * t2);
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    o.M[j] = J00 * v[4 * j + 0] + J02 * v[4 * j + 2];
-    o.M[3 + j] = J11 * v[4 * j + 1] + J12 * v[4 * j + 2];
-  }
-  const float S[9] = {cov6[0], cov6[1], cov6[2], cov6[1], cov6[3], cov6[4], cov6[2], cov6[4], cov6[5]};
-  float MS[6];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-      MS[3 * i + j] = o.M[3 * i + 0] * S[0 * 3 + j] + o.M[3 * i + 1] * S[1 * 3 + j] + o.M[3 * i + 2] * S[2 * 3 + j];
-  o.a = MS[0] * o.M[0] + MS[1] * o.M[1] + MS[2] * o.M[2] + 0.3f;
-  o.b = MS[0] * o.M[3] + MS[1] * o.M[4] + MS[2] * o.M[5];
-  o.c = MS[3] * o.M[3] + MS[4] * o.M[4] + MS[5] * o.M[5] + 0.3f;
-}
-
-// Footprint of one projected Gaussian over the 8x8-tile grid.  The candidate range is the reference's
-// 16x16-tile rect ([EXT] auxiliary.h getRect) expressed in 8x8 tiles, clipped to the image and to the
-// axis-aligned bounds of the ellipse {q <= tau}, q = a dx^2 + 2 b dx dy + c dy^2, tau = 2 ln(255 o):
-// outside it alpha = o exp(-q/2) < 1/255 and the blend would skip the pixel anyway.
-struct Foot {
-  float cx, cy, A, B, C, tau, nBiC, nBiA;  // nBiC = -B/C, nBiA = -B/A
-  float detc, hx, hy;                          // conic determinant, half extents of the ellipse {q <= tau}
-  bool convex;
-  int sx0, sx1, sy0, sy1;
-};
-
-__device__ __forceinline__ int f2i_clamped(float f) { return (int)fminf(1e9f, fmaxf(-1e9f, f)); }
-
-__device__ __forceinline__ void ref_rect16(float x, float y, float r, const Grid& g, int& rx0, int& ry0, int& rx1, int& ry1) {
-  rx0 = min(g.gx16, max(0, f2i_clamped((x - r) / 16.f)));
-  ry0 = min(g.gy16, max(0, f2i_clamped((y - r) / 16.f)));
-  rx1 = min(g.gx16, max(0, f2i_clamped((x + r + 15.f) / 16.f)));
-  ry1 = min(g.gy16, max(0, f2i_clamped((y + r + 15.f) / 16.f)));
-}
-
-__device__ __forceinline__ Foot make_foot(float x, float y, float A, float B, float C, float o, float r, const Grid& g) {
-  Foot f;
-  f.cx = x; f.cy = y; f.A = A; f.B = B; f.C = C;
-  // Hardware reciprocal / square root / log2 (about 1 ulp) are enough here: every test built on the footprint carries a margin
-  // orders of magnitude above that, and the count and emit passes see bit-identical values either way.
-  f.nBiC = -B * __builtin_amdgcn_rcpf(C); f.nBiA = -B * __builtin_amdgcn_rcpf(A);
-  int rx0, ry0, rx1, ry1;
-  ref_rect16(x, y, r, g, rx0, ry0, rx1, ry1);
-  f.sx0 = 2 * rx0; f.sy0 = 2 * ry0;
-  f.sx1 = min(2 * rx1, g.sw); f.sy1 = min(2 * ry1, g.sh);
-  const float tau = (2.f * 0.6931471805599453f) * __builtin_amdgcn_logf(255.f * o);  // 2 ln(255 o)
-  f.tau = tau + 1e-4f * fabsf(tau) + 0.02f;  // margin >> fp32 error of the blend's own power evaluation
-  const float detc = A * C - B * B;
-  f.convex = (A > 0.f) && (C > 0.f) && (detc > 0.f) && (detc < 3.0e38f);
-  f.detc = detc; f.hx = 0.f; f.hy = 0.f;
-  if (!(f.tau >= 0.f)) {  // opacity < 1/255 (or NaN): alpha < 1/255 everywhere
-    f.sx1 = f.sx0; f.sy1 = f.sy0;
-  } else if (f.convex) {
-    f.detc = detc;
-    const float rdet = __builtin_amdgcn_rcpf(detc);
-    f.hx = __builtin_amdgcn_sqrtf(f.tau * C * rdet); f.hy = __builtin_amdgcn_sqrtf(f.tau * A * rdet);
-    const float hx = f.hx + 0.5f, hy = f.hy + 0.5f;
-    f.sx0 = max(f.sx0, f2i_clamped(floorf((x - hx) * 0.125f)));
-    f.sx1 = min(f.sx1, f2i_clamped(floorf((x + hx) * 0.125f)) + 1);
-    f.sy0 = max(f.sy0, f2i_clamped(floorf((y - hy) * 0.125f)));
-    f.sy1 = min(f.sy1, f2i_clamped(floorf((y + hy) * 0.125f)) + 1);
-  }
-  return f;
-}
-
-// Exact minimum of q over the pixel-centre box of 8x8 tile (sx, sy); true if some pixel may reach alpha >= 1/255.
-__device__ __forceinline__ bool subtile_hit(const Foot& f, int sx, int sy, const Grid& g) {
-  if (!f.convex) return true;
-  const float dx0 = (float)(8 * sx) - f.cx, dx1 = (float)min(8 * sx + 7, g.W - 1) - f.cx;
-  const float dy0 = (float)(8 * sy) - f.cy, dy1 = (float)min(8 * sy + 7, g.H - 1) - f.cy;
-  const bool inx = (dx0 <= 0.f) && (dx1 >= 0.f), iny = (dy0 <= 0.f) && (dy1 >= 0.f);
-  if (inx && iny) return true;
-  auto qx = [&](float dxe) {
-    const float ys = fminf(fmaxf(f.nBiC * dxe, dy0), dy1);
-    return f.A * dxe * dxe + 2.f * f.B * dxe * ys + f.C * ys * ys;
-  };
-  auto qy = [&](float dye) {
-    const float xs = fminf(fmaxf(f.nBiA * dye, dx0), dx1);
-    return f.A * xs * xs + 2.f * f.B * xs * dye + f.C * dye * dye;
-  };
-  const float qmin = fminf(fminf(qx(dx0), qx(dx1)), fminf(qy(dy0), qy(dy1)));
-  return qmin <= f.tau;
-}
-
-// All hit tiles of one row of 8x8 tiles at once: the ellipse {q <= tau} cut by the row's band of pixel centres is convex,
-// so its x-projection is an interval [xl, xr]; xr(y) = (-B y + sqrt(A tau - det y^2)) / A is concave with its maximum at the
-// ellipse's rightmost point y_r = -B hx / C, hence the band maximum sits at y_r clamped into the band (xl symmetrically).
-// Returns the bits (relative to f.sx0) of the tiles whose pixel-centre span meets that interval - the same set the
-// per-tile box minimum (subtile_hit) accepts, at the cost of two square roots per row instead of ~50 ops per tile.
-__device__ __forceinline__ uint32_t row_hit_bits(const Foot& f, int sy, const Grid& g) {
-  const int w = f.sx1 - f.sx0;
-  const uint32_t all = w >= 32 ? 0xffffffffu : ((1u << w) - 1u);
-  if (!f.convex) return all;
-  const float ya = fmaxf((float)(8 * sy) - f.cy, -f.hy), yb = fminf((float)min(8 * sy + 7, g.H - 1) - f.cy, f.hy);
-  if (ya > yb) return 0u;
-  const float yrt = f.nBiC * f.hx;  // y of the rightmost point; the leftmost is at -yrt
-  const float yr = fminf(fmaxf(yrt, ya), yb), yl = fminf(fmaxf(-yrt, ya), yb);
-  const float inva = __builtin_amdgcn_rcpf(f.A), at = f.A * f.tau;
-  const float xr = (-f.B * yr + __builtin_amdgcn_sqrtf(fmaxf(0.f, at - f.detc * yr * yr))) * inva + 1e-3f;
-  const float xl = (-f.B * yl - __builtin_amdgcn_sqrtf(fmaxf(0.f, at - f.detc * yl * yl))) * inva - 1e-3f;
-  const int lo = max(f.sx0, f2i_clamped(ceilf((xl + f.cx - 7.f) * 0.125f)));
-  const int hi = min(f.sx1 - 1, f2i_clamped(floorf((xr + f.cx) * 0.125f)));
-  if (hi < lo) return 0u;
-  const int n = hi - lo + 1;
-  return (n >= 32 ? 0xffffffffu : ((1u << n) - 1u)) << (lo - f.sx0);
-}
-
-// Walks of a footprint wider than the mask window: by one lane, or by all 64 lanes of a wave (wave-uniform foot).
-template <class F>
-__device__ __forceinline__ void big_walk_lane(const Foot& ft, const Grid& g, F&& f) {
-  for (int sy = ft.sy0; sy < ft.sy1; ++sy)
-    for (int sx = ft.sx0; sx < ft.sx1; ++sx)
-      if (subtile_hit(ft, sx, sy, g)) f(sy * g.sgx + sx);
-}
-template <class F>
-__device__ __forceinline__ void big_walk_wave(const Foot& ft, const Grid& g, int lane, F&& f) {
-  const int w = ft.sx1 - ft.sx0, cnt = w * (ft.sy1 - ft.sy0);
-  for (int c = lane; c < cnt; c += 64) {
-    const int dy = c / w, sx = ft.sx0 + (c - dy * w), sy = ft.sy0 + dy;
-    if (subtile_hit(ft, sx, sy, g)) f(sy * g.sgx + sx);
-  }
-}
-constexpr int kBigList = 256;  // deferred wide footprints per binning workgroup (more are walked in line)
-
-__device__ __forceinline__ Foot foot_of_record(const GeomRec* rec, const Grid& g) {
-  const float4 q0 = rec->q0, q1 = rec->q1;
-  return make_foot(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, (float)(__float_as_uint(q1.w) & 0x0fffffffu), g);
-}
-// Walks the (tile) pairs of one Gaussian from its record's q3 word (hit mask, origin, depth).
-template <class F, class B>
-__device__ __forceinline__ void walk_pairs(const Params& p, const float4 q3, int i, int t0, int t1, F&& f, B&& big) {
-  const Grid& g = p.g;
-  const uint32_t origin = __float_as_uint(q3.z);
-  unsigned long long m = ((unsigned long long)__float_as_uint(q3.y) << 32) | __float_as_uint(q3.x);
-  const int sx0 = (int)(origin & 0xfffu), sy0 = (int)((origin >> 12) & 0xfffu);
-  while (m) {
-    const int b = __ffsll((long long)m) - 1;
-    m &= m - 1;
-    const int t = (sy0 + (b >> 3)) * g.sgx + sx0 + (b & 7);
-    if (t >= t0 && t < t1) f(i, t, q3.w);
-  }
-  if (origin & 0x80000000u) big(i);  // footprint wider than the 8x8-tile mask window
-}
-template <class F>
-__device__ __forceinline__ void for_each_pair(const Params& p, int v, int row, int tid, int t0, int t1, F&& f) {
-  const int N = p.d.num_gaussians;
-  const int end = min(N, (row + 1) * p.chunk);
-  for (int i = row * p.chunk + tid; i < end; i += kBinThreads) {
-    const GeomRec* rec = p.geom + (size_t)v * N + i;
-    const float4 q3 = p.aux[(size_t)v * N + i];
-    walk_pairs(p, q3, i, t0, t1, f, [&](int) {
-      const Foot ft = foot_of_record(rec, p.g);
-      big_walk_lane(ft, p.g, [&](int t) { if (t >= t0 && t < t1) f(i, t, q3.w); });
-    });
-  }
-}
-
-// Wave-cooperative copy of `cnt` rows of `rowf` floats from global to LDS (row stride ldstride floats).
-__device__ __forceinline__ void stage_rows(float* lds, const float* src, int cnt, int rowf, int ldstride, int lane) {
-  const int total = cnt * rowf;
-  if (ldstride == rowf) {
-    if ((((uintptr_t)src) & 15) == 0) {
-      const int n4 = total >> 2;
-      for (int k = lane; k < n4; k += 64) reinterpret_cast<float4*>(lds)[k] = reinterpret_cast<const float4*>(src)[k];
-      for (int k = (n4 << 2) + lane; k < total; k += 64) lds[k] = src[k];
-    } else {
-      for (int k = lane; k < total; k += 64) lds[k] = src[k];
-    }
-  } else {
-    for (int k = lane; k < total; k += 64) {
-      const int row = k / rowf;
-      lds[row * ldstride + (k - row * rowf)] = src[k];
-    }
-  }
-}
-__device__ __forceinline__ void unstage_rows(float* dst, const float* lds, int cnt, int rowf, int ldstride, int lane) {
-  const int total = cnt * rowf;
-  if (ldstride == rowf) {
-    if ((((uintptr_t)dst) & 15) == 0) {
-      const int n4 = total >> 2;
-      // streaming stores: the dense SH gradient (300 B per Gaussian, written once, not read again by this library) should not
-      // push the arrays the next forward streams (the harmonics themselves) out of the Infinity Cache: fwd + bwd steps -3 us
-      typedef float f4v_ __attribute__((ext_vector_type(4)));
-      for (int k = lane; k < n4; k += 64) {
-        const float4 x = reinterpret_cast<const float4*>(lds)[k];
-        __builtin_nontemporal_store(f4v_{x.x, x.y, x.z, x.w}, reinterpret_cast<f4v_*>(dst) + k);
-      }
-      for (int k = (n4 << 2) + lane; k < total; k += 64) dst[k] = lds[k];
-    } else {
-      for (int k = lane; k < total; k += 64) dst[k] = lds[k];
-    }
-  } else {
-    for (int k = lane; k < total; k += 64) {
-      const int row = k / rowf;
-      dst[k] = lds[row * ldstride + (k - row * rowf)];
-    }
-  }
-}
 
 // ------------------------------------------------------------------------------------------------
 // K1: preprocess ([EXT] forward.cu preprocessCUDA; oracle preprocess()), split in two parts that have nothing in common
@@ -4045,21 +3234,6 @@ static Params base_params(const GsrDims* d, const GsrView* views, const float* m
   return p;
 }
 
-#define GSR_CHECK(expr)                       \
-  do {                                        \
-    if ((expr) != hipSuccess) return GSR_ERR_LAUNCH; \
-  } while (0)
-
-// Run-time bools as compile-time constants: dispatch_bools(f, a, b) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}).  A generic
-// lambda f names a kernel's template arguments once, where it is launched; every combination of its bools is instantiated.
-template <class F>
-static inline void dispatch_bools(F&& f) { f(); }
-template <class F, class... Bools>
-static inline void dispatch_bools(F&& f, bool b, Bools... rest) {
-  if (b) dispatch_bools([&](auto... cs) { f(std::true_type{}, cs...); }, rest...);
-  else dispatch_bools([&](auto... cs) { f(std::false_type{}, cs...); }, rest...);
-}
-
 }  // namespace gsr
 
 using namespace gsr;
@@ -4645,2420 +3819,10 @@ int gsr_cov_from_scale_rot_backward(int64_t n, const float* scales, const float*
 
 }  // extern "C"
 
-// ------------------------------------------------------------------------------------------------
-// Image losses next to the raster path: the reference's photometric terms - LossMse (src/loss/loss_mse.py:23-36:
-// weight x mean squared error), LossMultiSSIM (src/loss/loss_multissim.py:24-83: weight x (1 - mean SSIM map), 11 x 11 Gaussian
-// window, sigma 1.5, zero padding, C1 = 0.01^2, C2 = 0.03^2) and the clipped squared error behind compute_psnr
-// (src/evaluation/metrics.py:11-19) - evaluated in ONE launch that also writes dL/dprediction in the (image, 3, H, W) layout
-// gsr_backward reads as dL_dcolor.  In torch the SSIM term alone is five depthwise convolutions forward and their
-// transposes backward (dozens of launches on images this small).
-//   SSIM map S = A B / (C D),  A = 2 mu1 mu2 + C1,  B = 2 sigma12 + C2,  C = mu1^2 + mu2^2 + C1,  D = sigma1^2 + sigma2^2 + C2,
-//   with mu = w * x, sigma1^2 = w * x1^2 - mu1^2, sigma12 = w * x1 x2 - mu1 mu2 (w * . = windowed mean).  For the prediction x1:
-//   dS/dx1(p) = [w * dmu](p) + 2 x1(p) [w * a](p) + x2(p) [w * b](p)   (the window is symmetric), where at every map position
-//   a = dS/d(w*x1^2) = -A B / (C D^2),  b = dS/d(w*x1x2) = 2 A / (C D),
-//   dmu = dS/dmu1 = 2 mu2 (B - A) / (C D) - 2 mu1 A B / (C^2 D) + 2 mu1 A B / (C D^2).
-// One workgroup = one 16 x 16 tile of one channel of one image: inputs on the 36 x 36 halo region -> five windowed means on
-// 26 x 26 (separable) -> S, a, b, dmu there (zero outside the image: those map positions do not exist) -> three windowed sums
-// back on 16 x 16.  Partial sums (squared error, clipped squared error, SSIM map) go to one slot per workgroup: the caller adds
-// them up (deterministic).
-// ------------------------------------------------------------------------------------------------
-namespace gsr {
-constexpr int kLossTile = 16, kLossR = 5, kLossMid = kLossTile + 2 * kLossR, kLossIn = kLossTile + 4 * kLossR;  // 16, 26, 36
-
-// LDS planes, row strides multiples of four floats so that a thread reads the 14 inputs of FOUR adjacent outputs of an 11-tap pass
-// as four 16-byte words (the first form read every tap as a float of its own: 80 k LDS reads per workgroup, 33 us for three
-// 256 x 256 images): inputs 36 x 40 (two planes), first horizontal pass 36 x 28 (five planes), a / b / dmu 26 x 28 (three planes,
-// over the inputs - dead by then, a thread keeps its own pixel's two values), second horizontal pass 26 x 16 (three planes, over
-// the first one's).  31.7 KB: five workgroups per CU.
-constexpr int kLossXS = 40, kLossHS = 28, kLossBS = 16;
-__global__ __launch_bounds__(256) void k_image_loss(int H, int W, const float* __restrict__ pred, const float* __restrict__ target,
-                                                    float mse_scale, float ssim_scale, float* __restrict__ grad, float* __restrict__ partials) {
-  __shared__ __attribute__((aligned(16))) float sX[2 * kLossIn * kLossXS];
-  __shared__ __attribute__((aligned(16))) float sH[5 * kLossIn * kLossHS];
-  static_assert(3 * kLossMid * kLossHS <= 2 * kLossIn * kLossXS && 3 * kLossMid * kLossBS <= 5 * kLossIn * kLossHS, "aliased planes fit");
-  float* const x1 = sX;
-  float* const x2 = sX + kLossIn * kLossXS;
-  auto hz = [&](int k, int r) { return sH + (k * kLossIn + r) * kLossHS; };   // x1, x2, x1^2, x2^2, x1 x2 after the horizontal pass
-  auto mp = [&](int k, int r) { return sX + (k * kLossMid + r) * kLossHS; };  // a, b, dmu on the 26 x 26 region
-  auto hb = [&](int k, int r) { return sH + (k * kLossMid + r) * kLossBS; };  // their horizontal pass
-  __shared__ float red[3][4];
-  const int tid = threadIdx.x, img_c = blockIdx.z;   // image * 3 + channel
-  const int ox = blockIdx.x * kLossTile, oy = blockIdx.y * kLossTile;
-  const float* p1 = pred + (size_t)img_c * H * W;
-  const float* p2 = target + (size_t)img_c * H * W;
-  // window: exp(-(k - 5)^2 / (2 sigma^2)) normalised, sigma = 1.5 (loss_multissim.py:50-52), as the reference computes it in fp32
-  float wgt[11];
-  {
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < 11; ++k) { wgt[k] = expf(-(float)((k - 5) * (k - 5)) / 4.5f); s += wgt[k]; }
-#pragma unroll
-    for (int k = 0; k < 11; ++k) wgt[k] /= s;
-  }
-  for (int e = tid; e < kLossIn * kLossXS; e += 256) {
-    const int r = e / kLossXS, c = e - r * kLossXS, y = oy - 2 * kLossR + r, x = ox - 2 * kLossR + c;
-    const bool in = c < kLossIn && x >= 0 && x < W && y >= 0 && y < H;
-    x1[e] = in ? p1[(size_t)y * W + x] : 0.f;
-    x2[e] = in ? p2[(size_t)y * W + x] : 0.f;
-  }
-  __syncthreads();
-  // ---- horizontal pass of the five products: row r, output columns 4 j .. 4 j + 3 (columns 26, 27 are padding)
-  if (tid < kLossIn * (kLossHS / 4)) {
-    const int r = tid / (kLossHS / 4), j = tid - r * (kLossHS / 4);
-    float a[16], b[16];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float4 va = *reinterpret_cast<const float4*>(x1 + r * kLossXS + 4 * j + 4 * q);
-      const float4 vb = *reinterpret_cast<const float4*>(x2 + r * kLossXS + 4 * j + 4 * q);
-      a[4 * q] = va.x; a[4 * q + 1] = va.y; a[4 * q + 2] = va.z; a[4 * q + 3] = va.w;
-      b[4 * q] = vb.x; b[4 * q + 1] = vb.y; b[4 * q + 2] = vb.z; b[4 * q + 3] = vb.w;
-    }
-    float o[5][4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      float s1 = 0, s2 = 0, s11 = 0, s22 = 0, s12 = 0;
-#pragma unroll
-      for (int k = 0; k < 11; ++k) {
-        const float av = a[u + k], bv = b[u + k], w = wgt[k];
-        s1 += w * av; s2 += w * bv; s11 += w * (av * av); s22 += w * (bv * bv); s12 += w * (av * bv);
-      }
-      o[0][u] = s1; o[1][u] = s2; o[2][u] = s11; o[3][u] = s22; o[4][u] = s12;
-    }
-#pragma unroll
-    for (int k = 0; k < 5; ++k) *reinterpret_cast<float4*>(hz(k, r) + 4 * j) = make_float4(o[k][0], o[k][1], o[k][2], o[k][3]);
-  }
-  // this thread's own pixel of the tile (the last phase needs it; the inputs' planes are overwritten before)
-  const float own1 = x1[(tid / kLossTile + 2 * kLossR) * kLossXS + tid % kLossTile + 2 * kLossR];
-  const float own2 = x2[(tid / kLossTile + 2 * kLossR) * kLossXS + tid % kLossTile + 2 * kLossR];
-  __syncthreads();
-  // ---- vertical pass + the SSIM terms: column c, output rows 4 g .. 4 g + 3 (rows >= 26 do not exist)
-  float sum_s = 0.f;
-  constexpr float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-  if (tid < ((kLossMid + 3) / 4) * kLossMid) {
-    const int g = tid / kLossMid, c = tid - g * kLossMid;
-    float acc[5][4];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-      float col[14];
-#pragma unroll
-      for (int q = 0; q < 14; ++q) col[q] = hz(k, min(4 * g + q, kLossIn - 1))[c];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        float t = 0.f;
-#pragma unroll
-        for (int q = 0; q < 11; ++q) t += wgt[q] * col[u + q];
-        acc[k][u] = t;
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int r = 4 * g + u, y = oy - kLossR + r, x = ox - kLossR + c;
-      if (r >= kLossMid) continue;
-      const float mu1 = acc[0][u], mu2 = acc[1][u], s11 = acc[2][u], s22 = acc[3][u], s12 = acc[4][u];
-      float a = 0.f, b = 0.f, dmu = 0.f;
-      if (x >= 0 && x < W && y >= 0 && y < H) {
-        const float A = 2.f * mu1 * mu2 + C1, B = 2.f * (s12 - mu1 * mu2) + C2;
-        const float C = mu1 * mu1 + mu2 * mu2 + C1, D = (s11 - mu1 * mu1) + (s22 - mu2 * mu2) + C2;
-        const float iC = 1.f / C, iD = 1.f / D, AB = A * B;
-        a = -AB * iC * iD * iD;
-        b = 2.f * A * iC * iD;
-        dmu = 2.f * mu2 * (B - A) * iC * iD - 2.f * mu1 * AB * iC * iC * iD + 2.f * mu1 * AB * iC * iD * iD;
-        if (r >= kLossR && r < kLossR + kLossTile && c >= kLossR && c < kLossR + kLossTile) sum_s += AB * iC * iD;  // this tile's own pixels
-      }
-      mp(0, r)[c] = a; mp(1, r)[c] = b; mp(2, r)[c] = dmu;
-    }
-  }
-  __syncthreads();
-  // ---- horizontal pass of a, b, dmu: row r, output columns 4 j .. 4 j + 3 (hb lies over hz: dead since the barrier)
-  if (tid < kLossMid * (kLossTile / 4)) {
-    const int r = tid / (kLossTile / 4), j = tid - r * (kLossTile / 4);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      float v[16];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float4 t = *reinterpret_cast<const float4*>(mp(k, r) + 4 * j + 4 * q);
-        v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
-      }
-      float o[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        float t = 0.f;
-#pragma unroll
-        for (int q = 0; q < 11; ++q) t += wgt[q] * v[u + q];
-        o[u] = t;
-      }
-      *reinterpret_cast<float4*>(hb(k, r) + 4 * j) = make_float4(o[0], o[1], o[2], o[3]);
-    }
-  }
-  __syncthreads();
-  float sum_se = 0.f, sum_ce = 0.f;
-  {
-    const int r = tid / kLossTile, c = tid - r * kLossTile, y = oy + r, x = ox + c;
-    if (x < W && y < H) {
-      float wa = 0, wb = 0, wm = 0;
-#pragma unroll
-      for (int k = 0; k < 11; ++k) { const float w = wgt[k]; wa += w * hb(0, r + k)[c]; wb += w * hb(1, r + k)[c]; wm += w * hb(2, r + k)[c]; }
-      const float v1 = own1, v2 = own2;
-      const float d = v1 - v2;
-      sum_se = d * d;
-      const float dc = fminf(fmaxf(v2, 0.f), 1.f) - fminf(fmaxf(v1, 0.f), 1.f);
-      sum_ce = dc * dc;
-      if (grad) grad[(size_t)img_c * H * W + (size_t)y * W + x] = mse_scale * 2.f * d - ssim_scale * (wm + 2.f * v1 * wa + v2 * wb);
-    }
-  }
-  sum_se = wave_sum(sum_se); sum_ce = wave_sum(sum_ce); sum_s = wave_sum(sum_s);
-  if ((tid & 63) == 0) { red[0][tid >> 6] = sum_se; red[1][tid >> 6] = sum_ce; red[2][tid >> 6] = sum_s; }
-  __syncthreads();
-  if (tid < 3) {
-    const size_t slot = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    partials[slot * 4 + tid] = red[tid][0] + red[tid][1] + red[tid][2] + red[tid][3];
-    if (tid == 0) partials[slot * 4 + 3] = 0.f;
-  }
-}
-
-// The slots of k_image_loss added up in a fixed order by ONE workgroup (a few thousand slots: a 256 x 256 image has 768): per image
-// (sums[i][0..3]: squared error, clipped squared error, SSIM map, 0) and over the batch -> totals[0..2] = loss, mean squared
-// error, mean SSIM.  No atomics, nothing between workgroups: the result is the same bits every time.
-__global__ __launch_bounds__(1024) void k_image_loss_finish(int slots_per_image, int num_images, const float* __restrict__ partials,
-                                                            float mse_weight, float ssim_weight, float inv_count, float* __restrict__ sums,
-                                                            float* __restrict__ totals) {
-  __shared__ float red[3][16];
-  const int tid = threadIdx.x;
-  float se = 0.f, sm = 0.f;
-  for (int img = 0; img < num_images; ++img) {
-    const float* ps = partials + (size_t)img * slots_per_image * 4;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-    for (int k = tid; k < slots_per_image; k += 1024) {
-      const float4 v = *reinterpret_cast<const float4*>(ps + 4 * k);
-      a0 += v.x; a1 += v.y; a2 += v.z;
-    }
-    a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2);
-    if ((tid & 63) == 0) { red[0][tid >> 6] = a0; red[1][tid >> 6] = a1; red[2][tid >> 6] = a2; }
-    __syncthreads();
-    if (tid == 0) {
-      float t[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        float x = 0.f;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) x += red[c][q];
-        t[c] = x;
-        sums[img * 4 + c] = x;
-      }
-      sums[img * 4 + 3] = 0.f;
-      se += t[0]; sm += t[2];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    const float mse = se * inv_count, ssim = sm * inv_count;
-    totals[0] = mse_weight * mse + ssim_weight * (1.f - ssim);
-    totals[1] = mse;
-    totals[2] = ssim;
-    totals[3] = 0.f;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Evaluation metrics (reference src/evaluation/metrics.py:11-19 compute_psnr and :36-52 compute_ssim): the SSIM there is
-// skimage.metrics.structural_similarity(gt, hat, win_size=11, gaussian_weights=True, channel_axis=0, data_range=1.0) per image,
-// NOT the loss's SSIM above.  Same window (11 taps, sigma 1.5, separable), but: the image is extended by reflection about its
-// edge (index -1 - j reads j, H + j reads H - 1 - j; scipy's mode="reflect") instead of zeros; the covariances are the sample ones,
-// cn = 121 / 120 times the population ones; the map S = (2 ux uy + C1)(2 vxy + C2) / ((ux^2 + uy^2 + C1)(vx + vy + C2)) is averaged
-// over the interior 5 <= row < H - 5, 5 <= col < W - 5 of each channel, and an image's value is the mean of its three channels'.
-// Forward only: one workgroup = one 16 x 16 tile of one channel of one image; both images on the 26 x 26 halo region through the
-// reflected index -> the five products' horizontal 11-tap pass on 26 x 16 -> the vertical pass, S and the tile's interior sum by the
-// first wave.  Slots as k_image_loss writes them: squared error, squared error of the inputs clipped to [0, 1], sum of S over the
-// tile's interior pixels, 0.
-// LDS: inputs 26 rows x 48 floats (a 16-lane group of the 16-byte reads covers rows r, r + 3, r + 5, r + 6 or r + 1, r + 2,
-// r + 4, r + 7, four lanes and 16 floats each: at 48 floats a row those start 0, 16, 48, 32 or 48, 32, 0, 16 floats into the 64
-// banks - no conflict; at 28 they would overlap); horizontal pass 26 rows x 20 floats (a 32-lane half of the column reads is two
-// row groups, 4 x 20 = 80 floats = 16 banks of 32 apart).  20.4 KB and 88 VGPRs: five workgroups per CU, by the registers.
-// ------------------------------------------------------------------------------------------------
-constexpr int kMetXS = 48, kMetHS = 20;
-__global__ __launch_bounds__(256) void k_image_metrics(int H, int W, const float* __restrict__ truth, const float* __restrict__ pred,
-                                                       float* __restrict__ smap, float* __restrict__ partials) {
-  __shared__ __attribute__((aligned(16))) float sX[2 * kLossMid * kMetXS];
-  __shared__ __attribute__((aligned(16))) float sH[5 * kLossMid * kMetHS];
-  static_assert(kMetXS % 4 == 0 && kMetHS % 4 == 0 && kMetXS >= kLossMid + 2 && kMetHS >= kLossTile, "16-byte rows");
-  float* const x1 = sX;
-  float* const x2 = sX + kLossMid * kMetXS;
-  auto hz = [&](int k, int r) { return sH + (k * kLossMid + r) * kMetHS; };  // x, y, x^2, y^2, x y after the horizontal pass
-  __shared__ float red[3][4];
-  const int tid = threadIdx.x, img_c = blockIdx.z;  // image * 3 + channel
-  const int ox = blockIdx.x * kLossTile, oy = blockIdx.y * kLossTile;
-  const float* p1 = truth + (size_t)img_c * H * W;
-  const float* p2 = pred + (size_t)img_c * H * W;
-  float wgt[11];  // the window of k_image_loss
-  {
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < 11; ++k) { wgt[k] = expf(-(float)((k - 5) * (k - 5)) / 4.5f); s += wgt[k]; }
-#pragma unroll
-    for (int k = 0; k < 11; ++k) wgt[k] /= s;
-  }
-  // Both images are staged minus ONE number, the ground truth at the tile's centre: the variances and the covariance do not
-  // depend on it, and where the image is nearly constant around the tile (rendered backgrounds) uxx - ux^2 no longer cancels
-  // seven digits against C2 = 9e-4 - the float32 rounding that costs the unshifted form 1e-4 per pixel of S there.
-  const float shift = p1[(size_t)min(oy + kLossTile / 2, H - 1) * W + min(ox + kLossTile / 2, W - 1)];
-  // Rows of 28: columns 26, 27 are read by the 16-byte loads and never used.  One reflection lands inside the image for every tap
-  // of a pixel inside it (H, W >= 11); the taps of the tile's pixels beyond the image's edge may not, hence the clamp.
-  for (int e = tid; e < kLossMid * (kLossMid + 2); e += 256) {
-    const int r = e / (kLossMid + 2), c = e - r * (kLossMid + 2);
-    int y = oy - kLossR + r, x = ox - kLossR + c;
-    y = y < 0 ? -1 - y : (y >= H ? 2 * H - 1 - y : y);
-    x = x < 0 ? -1 - x : (x >= W ? 2 * W - 1 - x : x);
-    y = min(max(y, 0), H - 1);
-    x = min(max(x, 0), W - 1);
-    const bool in = c < kLossMid;
-    x1[r * kMetXS + c] = in ? p1[(size_t)y * W + x] - shift : 0.f;
-    x2[r * kMetXS + c] = in ? p2[(size_t)y * W + x] - shift : 0.f;
-  }
-  __syncthreads();
-  // ---- horizontal pass of the five products: row r, output columns 4 j .. 4 j + 3
-  if (tid < kLossMid * (kLossTile / 4)) {
-    const int r = tid / (kLossTile / 4), j = tid - r * (kLossTile / 4);
-    float a[16], b[16];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float4 va = *reinterpret_cast<const float4*>(x1 + r * kMetXS + 4 * j + 4 * q);
-      const float4 vb = *reinterpret_cast<const float4*>(x2 + r * kMetXS + 4 * j + 4 * q);
-      a[4 * q] = va.x; a[4 * q + 1] = va.y; a[4 * q + 2] = va.z; a[4 * q + 3] = va.w;
-      b[4 * q] = vb.x; b[4 * q + 1] = vb.y; b[4 * q + 2] = vb.z; b[4 * q + 3] = vb.w;
-    }
-    float o[5][4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      float s1 = 0, s2 = 0, s11 = 0, s22 = 0, s12 = 0;
-#pragma unroll
-      for (int k = 0; k < 11; ++k) {
-        const float av = a[u + k], bv = b[u + k], w = wgt[k];
-        s1 += w * av; s2 += w * bv; s11 += w * (av * av); s22 += w * (bv * bv); s12 += w * (av * bv);
-      }
-      o[0][u] = s1; o[1][u] = s2; o[2][u] = s11; o[3][u] = s22; o[4][u] = s12;
-    }
-#pragma unroll
-    for (int k = 0; k < 5; ++k) *reinterpret_cast<float4*>(hz(k, r) + 4 * j) = make_float4(o[k][0], o[k][1], o[k][2], o[k][3]);
-  }
-  // ---- the two squared errors of this thread's own pixel
-  float sum_se = 0.f, sum_ce = 0.f;
-  {
-    const int r = tid / kLossTile, c = tid - r * kLossTile;
-    if (ox + c < W && oy + r < H) {  // (from memory, not from the shifted planes: the same bits as k_image_loss's)
-      const float v1 = p1[(size_t)(oy + r) * W + ox + c], v2 = p2[(size_t)(oy + r) * W + ox + c];
-      const float d = v1 - v2;
-      sum_se = d * d;
-      const float dc = fminf(fmaxf(v2, 0.f), 1.f) - fminf(fmaxf(v1, 0.f), 1.f);
-      sum_ce = dc * dc;
-    }
-  }
-  __syncthreads();
-  // ---- vertical pass + S: column c, output rows 4 g .. 4 g + 3 of the tile (the first wave)
-  float sum_s = 0.f;
-  if (tid < kLossTile * (kLossTile / 4)) {
-    constexpr float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f, cn = 121.f / 120.f;
-    const int g = tid / kLossTile, c = tid - g * kLossTile;
-    float acc[5][4];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-      float col[14];
-#pragma unroll
-      for (int q = 0; q < 14; ++q) col[q] = hz(k, 4 * g + q)[c];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        float t = 0.f;
-#pragma unroll
-        for (int q = 0; q < 11; ++q) t += wgt[q] * col[u + q];
-        acc[k][u] = t;
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int y = oy + 4 * g + u, x = ox + c;
-      if (x >= W || y >= H) continue;
-      const float sx = acc[0][u], sy = acc[1][u], ux = sx + shift, uy = sy + shift;
-      const float vx = cn * (acc[2][u] - sx * sx), vy = cn * (acc[3][u] - sy * sy), vxy = cn * (acc[4][u] - sx * sy);
-      const float S = ((2.f * ux * uy + C1) * (2.f * vxy + C2)) / ((ux * ux + uy * uy + C1) * (vx + vy + C2));
-      if (smap) smap[((size_t)img_c * H + y) * W + x] = S;
-      if (y >= kLossR && y < H - kLossR && x >= kLossR && x < W - kLossR) sum_s += S;
-    }
-  }
-  sum_se = wave_sum(sum_se); sum_ce = wave_sum(sum_ce); sum_s = wave_sum(sum_s);
-  if ((tid & 63) == 0) { red[0][tid >> 6] = sum_se; red[1][tid >> 6] = sum_ce; red[2][tid >> 6] = sum_s; }
-  __syncthreads();
-  if (tid < 3) {
-    const size_t slot = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    partials[slot * 4 + tid] = red[tid][0] + red[tid][1] + red[tid][2] + red[tid][3];
-    if (tid == 0) partials[slot * 4 + 3] = 0.f;
-  }
-}
-
-// The slots of k_image_metrics added up as k_image_loss_finish adds them (one workgroup, fixed order, an image's sums independent
-// of the other images) and finished: metrics (4, num_images) = SSIM (the interior sum / interior_count), PSNR
-// (-10 log10(clipped squared error / pixel_count), +inf for equal images), the interior sum of S, the clipped squared error.
-__global__ __launch_bounds__(1024) void k_image_metrics_finish(int slots_per_image, int num_images, const float* __restrict__ partials,
-                                                               float interior_count, float pixel_count, float* __restrict__ metrics) {
-  __shared__ float red[2][16];
-  const int tid = threadIdx.x;
-  for (int img = 0; img < num_images; ++img) {
-    const float* ps = partials + (size_t)img * slots_per_image * 4;
-    float a1 = 0.f, a2 = 0.f;
-    for (int k = tid; k < slots_per_image; k += 1024) {
-      const float4 v = *reinterpret_cast<const float4*>(ps + 4 * k);
-      a1 += v.y; a2 += v.z;
-    }
-    a1 = wave_sum(a1); a2 = wave_sum(a2);
-    if ((tid & 63) == 0) { red[0][tid >> 6] = a1; red[1][tid >> 6] = a2; }
-    __syncthreads();
-    if (tid == 0) {
-      float ce = 0.f, s = 0.f;
-#pragma unroll
-      for (int q = 0; q < 16; ++q) { ce += red[0][q]; s += red[1][q]; }
-      metrics[img] = s / interior_count;
-      metrics[num_images + img] = -10.f * log10f(ce / pixel_count);
-      metrics[2 * (size_t)num_images + img] = s;
-      metrics[3 * (size_t)num_images + img] = ce;
-    }
-    __syncthreads();
-  }
-}
-}  // namespace gsr
-
-extern "C" {
-
-size_t gsr_image_loss_partials(int num_images, int height, int width) {
-  if (num_images <= 0 || height <= 0 || width <= 0) return 0;
-  return (size_t)num_images * 3 * ((height + gsr::kLossTile - 1) / gsr::kLossTile) * ((width + gsr::kLossTile - 1) / gsr::kLossTile);
-}
-
-int gsr_image_loss(int num_images, int height, int width, const float* prediction, const float* target, float mse_weight,
-                   float ssim_weight, float* dL_dprediction, float* partials, void* stream_) {
-  if (num_images < 0 || height <= 0 || width <= 0) return GSR_ERR_INVALID_ARGUMENT;
-  if (num_images == 0) return GSR_OK;
-  if (!prediction || !target || !partials || (size_t)num_images * 3 > 65535) return GSR_ERR_INVALID_ARGUMENT;
-  const double count = (double)num_images * 3.0 * height * width;  // both reference losses average over every element
-  const dim3 grid((unsigned)((width + gsr::kLossTile - 1) / gsr::kLossTile), (unsigned)((height + gsr::kLossTile - 1) / gsr::kLossTile),
-                  (unsigned)num_images * 3u);
-  hipLaunchKernelGGL(gsr::k_image_loss, grid, dim3(256), 0, static_cast<hipStream_t>(stream_), height, width, prediction, target,
-                     (float)(mse_weight / count), (float)(ssim_weight / count), dL_dprediction, partials);
-  GSR_CHECK(hipGetLastError());
-  return GSR_OK;
-}
-
-int gsr_image_loss_finish(int num_images, int height, int width, const float* partials, float mse_weight, float ssim_weight,
-                          float* sums, float* totals, void* stream_) {
-  if (num_images <= 0 || height <= 0 || width <= 0 || !partials || !sums || !totals) return GSR_ERR_INVALID_ARGUMENT;
-  const int slots = (int)(gsr_image_loss_partials(num_images, height, width) / (size_t)num_images);
-  const double count = (double)num_images * 3.0 * height * width;
-  hipLaunchKernelGGL(gsr::k_image_loss_finish, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream_), slots, num_images,
-                     partials, mse_weight, ssim_weight, (float)(1.0 / count), sums, totals);
-  GSR_CHECK(hipGetLastError());
-  return GSR_OK;
-}
-
-size_t gsr_image_metrics_partials(int num_images, int height, int width) {
-  if (num_images <= 0 || height < 2 * gsr::kLossR + 1 || width < 2 * gsr::kLossR + 1 || (size_t)num_images * 3 > 65535) return 0;
-  return gsr_image_loss_partials(num_images, height, width);
-}
-
-int gsr_image_metrics(int num_images, int height, int width, const float* ground_truth, const float* prediction, float* ssim_map,
-                      float* partials, void* stream_) {
-  if (num_images < 0 || height < 2 * gsr::kLossR + 1 || width < 2 * gsr::kLossR + 1) return GSR_ERR_INVALID_ARGUMENT;
-  if (num_images == 0) return GSR_OK;
-  if (!ground_truth || !prediction || !partials || (size_t)num_images * 3 > 65535) return GSR_ERR_INVALID_ARGUMENT;
-  const dim3 grid((unsigned)((width + gsr::kLossTile - 1) / gsr::kLossTile), (unsigned)((height + gsr::kLossTile - 1) / gsr::kLossTile),
-                  (unsigned)num_images * 3u);
-  hipLaunchKernelGGL(gsr::k_image_metrics, grid, dim3(256), 0, static_cast<hipStream_t>(stream_), height, width, ground_truth,
-                     prediction, ssim_map, partials);
-  GSR_CHECK(hipGetLastError());
-  return GSR_OK;
-}
-
-int gsr_image_metrics_finish(int num_images, int height, int width, const float* partials, float* metrics, void* stream_) {
-  const size_t total = gsr_image_metrics_partials(num_images, height, width);
-  if (total == 0 || !partials || !metrics) return GSR_ERR_INVALID_ARGUMENT;
-  const double interior = 3.0 * (height - 2 * gsr::kLossR) * (double)(width - 2 * gsr::kLossR);
-  hipLaunchKernelGGL(gsr::k_image_metrics_finish, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream_),
-                     (int)(total / (size_t)num_images), num_images, partials, (float)interior, (float)(3.0 * height * width), metrics);
-  GSR_CHECK(hipGetLastError());
-  return GSR_OK;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------------
-// Gaussian adapter: the step right in front of the raster path - per-pixel network outputs to means,
-// scale + quaternion records and masked harmonics (reference src/model/encoder/common/gaussian_adapter.py:60-87 with
-// get_world_rays of projection.py) - as ONE launch in each direction instead of the ~25 elementwise torch kernels, the per-Gaussian
-// 3 x 3 solve and the split / broadcast copies of pf3plat_amd/adapter.py.  A workgroup takes kAdaptBlock consecutive Gaussians of
-// ONE group (scene x source view): every thread builds the group's K^-1, R, t and scale multiplier from uniform loads (in fp64:
-// a few dozen operations per thread against ~340 B of traffic per Gaussian); the block's raw rows - one contiguous stretch of
-// the input when the row stride is the row width or the 84 of the encoder's `gaussians[..., 2:]` slice - are staged in LDS with
-// 16-byte loads (the LDS image is shifted by the stretch's misalignment so both sides stay aligned), the 7-float heads are read
-// from there by the block's first wave, and the 3 M harmonics floats of the block leave as one contiguous stream of 16-byte
-// stores, the band mask chosen by column.  The backward recomputes everything from the forward's inputs (nothing is saved),
-// assembles the block's dL/draw rows in LDS and writes them with streaming 16-byte stores; the camera-to-world gradient is one
-// wave-reduced row of 12 floats per workgroup, added up in a fixed order by k_adapt_pose_reduce: the same bits on every run.
-// When the intrinsics want a gradient (gsr_adapt_backward_ex with dL_dintrinsics) a second instance of the backward appends ten
-// sums to that row - the cotangents of K^-1 (9) and of the scale multiplier (1) - and k_adapt_camera_reduce, launched in place of
-// k_adapt_pose_reduce, carries them back to K in fp64 (formulas: include/gsr.h).  Still two launches.
-// ------------------------------------------------------------------------------------------------
-namespace gsr {
-constexpr int kAdaptBlock = 64;       // Gaussians per workgroup
-constexpr int kAdaptThreads = 256;
-constexpr int kAdaptPoseFloats = 12;  // sum of dmean (x) (depth ray) (9), sum of dmean (3)
-constexpr int kAdaptIntrFloats = 10;  // behind them when intrinsics want a gradient: sum of d_p (x) (u, v, 1) (9), cotangent of AdaptGroup::mult (1)
-constexpr int kAdaptSlack = 8;        // a row stride of up to this many floats over the row width is streamed gaps included
-
-struct AdaptArgs {
-  int G, P, stride, lstride, height, width;
-  float lo, hi, eps;
-  const float *ext, *intr, *coords, *depths, *raw;
-  float *means, *scale_rot, *harm;
-  const float *d_means, *d_sr, *d_harm;
-  float *d_raw, *d_depths, *d_coords, *partials;
-};
-
-struct AdaptGroup {
-  float kinv[9], rot[9], t[3], mult;
-};
-
-// K^-1 (adjugate / determinant), camera-to-world rotation and centre, and 0.1 x sum(K[:2, :2]^-1 (1 / w, 1 / h)) of one group
-__device__ __forceinline__ AdaptGroup adapt_group(const float* __restrict__ e, const float* __restrict__ k, int h, int w) {
-  AdaptGroup o;
-  const double a = k[0], b = k[1], c = k[2], d = k[3], ee = k[4], f = k[5], g = k[6], hh = k[7], i = k[8];
-  const double c00 = ee * i - f * hh, c01 = c * hh - b * i, c02 = b * f - c * ee;
-  const double c10 = f * g - d * i, c11 = a * i - c * g, c12 = c * d - a * f;
-  const double c20 = d * hh - ee * g, c21 = b * g - a * hh, c22 = a * ee - b * d;
-  const double inv = 1.0 / (a * c00 + b * c10 + c * c20);
-  o.kinv[0] = (float)(c00 * inv); o.kinv[1] = (float)(c01 * inv); o.kinv[2] = (float)(c02 * inv);
-  o.kinv[3] = (float)(c10 * inv); o.kinv[4] = (float)(c11 * inv); o.kinv[5] = (float)(c12 * inv);
-  o.kinv[6] = (float)(c20 * inv); o.kinv[7] = (float)(c21 * inv); o.kinv[8] = (float)(c22 * inv);
-  const double px = (double)(1.0f / (float)w), py = (double)(1.0f / (float)h);
-  o.mult = (float)(0.1 * ((ee * px - b * py) + (a * py - d * px)) / c22);
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    o.rot[3 * r] = e[4 * r]; o.rot[3 * r + 1] = e[4 * r + 1]; o.rot[3 * r + 2] = e[4 * r + 2];
-    o.t[r] = e[4 * r + 3];
-  }
-  return o;
-}
-
-// band l of the harmonics is scaled by 0.1 x 0.25^l, the DC term by 1 (gaussian_adapter.py:40-44); m: coefficient index in [0, 25)
-__device__ __forceinline__ float adapt_mask(int m) {
-  return m == 0 ? 1.f : m < 4 ? 0.1f * 0.25f : m < 9 ? 0.1f * 0.0625f : m < 16 ? 0.1f * 0.015625f : 0.1f * 0.00390625f;
-}
-
-// The per-Gaussian arithmetic both directions share: unit ray through the pixel, the sigmoid of the scale features, quaternion norm
-struct AdaptPoint {
-  float p[3], n, denom, ray[3], sig[3], qn, qd;
-};
-__device__ __forceinline__ AdaptPoint adapt_point(const AdaptGroup& grp, float u, float v, const float* head) {
-  AdaptPoint o;
-#pragma unroll
-  for (int r = 0; r < 3; ++r) o.p[r] = grp.kinv[3 * r] * u + grp.kinv[3 * r + 1] * v + grp.kinv[3 * r + 2];
-  o.n = sqrtf(o.p[0] * o.p[0] + o.p[1] * o.p[1] + o.p[2] * o.p[2]);
-  o.denom = fmaxf(o.n, 1e-12f);  // F.normalize
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    o.ray[r] = o.p[r] / o.denom;
-    o.sig[r] = 1.f / (1.f + expf(-head[r]));
-  }
-  o.qn = sqrtf(head[3] * head[3] + head[4] * head[4] + head[5] * head[5] + head[6] * head[6]);
-  return o;
-}
-
-template <int D>
-__global__ __launch_bounds__(kAdaptThreads) void k_adapt_fwd(const AdaptArgs a) {
-  constexpr int M = (D + 1) * (D + 1), C = 3 * M, ROWF = 7 + C;
-  extern __shared__ __attribute__((aligned(16))) float adapt_lds[];
-  const int nb = (a.P + kAdaptBlock - 1) / kAdaptBlock;
-  const int g = (int)blockIdx.x / nb, r0 = ((int)blockIdx.x - g * nb) * kAdaptBlock;
-  const int cnt = min(kAdaptBlock, a.P - r0), tid = threadIdx.x;
-  const size_t first = (size_t)g * a.P + r0;
-  const float* __restrict__ src = a.raw + first * (size_t)a.stride;
-  int sh = 0;
-  if (a.lstride == a.stride) {  // the block's rows as one stretch of the input, gaps between rows included
-    sh = (int)(((uintptr_t)src >> 2) & 3);
-    float* img = adapt_lds + sh;
-    const int total = (cnt - 1) * a.stride + ROWF;  // ends with the last row: nothing behind it is read
-    const int head = min(total, (4 - sh) & 3);
-    if (tid < head) img[tid] = src[tid];
-    const int n4 = (total - head) >> 2;
-    const float4* __restrict__ s4 = reinterpret_cast<const float4*>(src + head);
-    float4* d4 = reinterpret_cast<float4*>(img + head);
-#pragma unroll 6
-    for (int k = tid; k < n4; k += kAdaptThreads) d4[k] = s4[k];
-    for (int k = head + (n4 << 2) + tid; k < total; k += kAdaptThreads) img[k] = src[k];
-  } else {  // rows far apart: row by row into a compact image
-    for (int e = tid; e < cnt * ROWF; e += kAdaptThreads) {
-      const int row = e / ROWF, col = e - row * ROWF;
-      adapt_lds[e] = src[(size_t)row * a.stride + col];
-    }
-  }
-  const AdaptGroup grp = adapt_group(a.ext + (size_t)g * 16, a.intr + (size_t)g * 9, a.height, a.width);
-  __syncthreads();
-  const float* img = adapt_lds + sh;
-  if (tid < cnt) {
-    const float* head = img + tid * a.lstride;
-    const size_t gi = first + tid;
-    const float u = a.coords[2 * gi], v = a.coords[2 * gi + 1], dep = a.depths[gi];
-    float hd[7];
-#pragma unroll
-    for (int k = 0; k < 7; ++k) hd[k] = head[k];
-    const AdaptPoint pt = adapt_point(grp, u, v, hd);
-    const float fp = dep * grp.mult, qd = pt.qn + a.eps;
-    float* mo = a.means + 3 * gi;
-    float* so = a.scale_rot + 7 * gi;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      const float dir = grp.rot[3 * r] * pt.ray[0] + grp.rot[3 * r + 1] * pt.ray[1] + grp.rot[3 * r + 2] * pt.ray[2];
-      mo[r] = grp.t[r] + dir * dep;
-      so[r] = (a.lo + (a.hi - a.lo) * pt.sig[r]) * fp;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) so[3 + k] = hd[3 + k] / qd;
-  }
-  // the block's harmonics: cnt x 3 M consecutive output floats
-  float* __restrict__ out = a.harm + first * C;
-  const int total = cnt * C;
-  const auto value = [&](int e) {
-    const int row = e / C, col = e - row * C;
-    return img[row * a.lstride + 7 + col] * adapt_mask(col % M);
-  };
-  if ((((uintptr_t)out) & 15) == 0) {
-    const int n4 = total >> 2;
-    for (int k = tid; k < n4; k += kAdaptThreads)
-      reinterpret_cast<float4*>(out)[k] = make_float4(value(4 * k), value(4 * k + 1), value(4 * k + 2), value(4 * k + 3));
-    for (int e = (n4 << 2) + tid; e < total; e += kAdaptThreads) out[e] = value(e);
-  } else {
-    for (int e = tid; e < total; e += kAdaptThreads) out[e] = value(e);
-  }
-}
-
-// KG: the intrinsics want a gradient - the partial row is kAdaptPoseFloats + kAdaptIntrFloats wide; everything else is the same code
-template <int D, bool KG>
-__global__ __launch_bounds__(kAdaptThreads) void k_adapt_bwd(const AdaptArgs a) {
-  constexpr int M = (D + 1) * (D + 1), C = 3 * M, ROWF = 7 + C;
-  constexpr int PARTF = kAdaptPoseFloats + (KG ? kAdaptIntrFloats : 0);
-  __shared__ __attribute__((aligned(16))) float rows[kAdaptBlock * ROWF];  // the block's dL/draw rows
-  const int nb = (a.P + kAdaptBlock - 1) / kAdaptBlock;
-  const int g = (int)blockIdx.x / nb, blk = (int)blockIdx.x - g * nb, r0 = blk * kAdaptBlock;
-  const int cnt = min(kAdaptBlock, a.P - r0), tid = threadIdx.x;
-  const size_t first = (size_t)g * a.P + r0;
-  // harmonics: dL/draw = mask x dL/dharmonics (zeros without a cotangent), one contiguous input stream
-  const int total = cnt * C;
-  const float* __restrict__ gh = a.d_harm ? a.d_harm + first * C : nullptr;
-  const auto put = [&](int e, float x) {
-    const int row = e / C, col = e - row * C;
-    rows[row * ROWF + 7 + col] = x * adapt_mask(col % M);
-  };
-  if (gh && (((uintptr_t)gh) & 15) == 0) {
-    const int n4 = total >> 2;
-#pragma unroll 5
-    for (int k = tid; k < n4; k += kAdaptThreads) {
-      const float4 x = reinterpret_cast<const float4*>(gh)[k];
-      put(4 * k, x.x); put(4 * k + 1, x.y); put(4 * k + 2, x.z); put(4 * k + 3, x.w);
-    }
-    for (int e = (n4 << 2) + tid; e < total; e += kAdaptThreads) put(e, gh[e]);
-  } else {
-    for (int e = tid; e < total; e += kAdaptThreads) put(e, gh ? gh[e] : 0.f);
-  }
-  if (tid < 64) {  // one wave: the 7-float heads, depth, pixel offsets, and the group's camera gradient
-    float pose[kAdaptPoseFloats];
-#pragma unroll
-    for (int k = 0; k < kAdaptPoseFloats; ++k) pose[k] = 0.f;
-    float kg[kAdaptIntrFloats];  // (dead code without KG)
-#pragma unroll
-    for (int k = 0; k < kAdaptIntrFloats; ++k) kg[k] = 0.f;
-    if (tid < cnt) {
-      const AdaptGroup grp = adapt_group(a.ext + (size_t)g * 16, a.intr + (size_t)g * 9, a.height, a.width);
-      const size_t gi = first + tid;
-      const float* __restrict__ head = a.raw + gi * (size_t)a.stride;
-      float hd[7], gs[7], gm[3];
-#pragma unroll
-      for (int k = 0; k < 7; ++k) {
-        hd[k] = head[k];
-        gs[k] = a.d_sr ? a.d_sr[7 * gi + k] : 0.f;
-      }
-#pragma unroll
-      for (int k = 0; k < 3; ++k) gm[k] = a.d_means ? a.d_means[3 * gi + k] : 0.f;
-      const float u = a.coords[2 * gi], v = a.coords[2 * gi + 1], dep = a.depths[gi];
-      const AdaptPoint pt = adapt_point(grp, u, v, hd);
-      const float fp = dep * grp.mult, range = a.hi - a.lo;
-      float* row = rows + tid * ROWF;
-      float d_dep = 0.f, d_ray[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        const float dir = grp.rot[3 * r] * pt.ray[0] + grp.rot[3 * r + 1] * pt.ray[1] + grp.rot[3 * r + 2] * pt.ray[2];
-        d_dep += gm[r] * dir + gs[r] * (a.lo + range * pt.sig[r]) * grp.mult;
-        row[r] = gs[r] * fp * range * (pt.sig[r] * (1.f - pt.sig[r]));
-        const float d_dir = gm[r] * dep;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          d_ray[c] += grp.rot[3 * r + c] * d_dir;
-          pose[3 * r + c] = gm[r] * (dep * pt.ray[c]);
-        }
-        pose[9 + r] = gm[r];
-      }
-      a.d_depths[gi] = d_dep;
-      // through the normalisation (the norm's own gradient is taken as 0 where it was clamped, as torch does) and K^-1
-      const float along = pt.n > 1e-12f ? pt.ray[0] * d_ray[0] + pt.ray[1] * d_ray[1] + pt.ray[2] * d_ray[2] : 0.f;
-      float d_u = 0.f, d_v = 0.f;
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        const float d_p = (d_ray[r] - pt.ray[r] * along) / pt.denom;
-        d_u += d_p * grp.kinv[3 * r];
-        d_v += d_p * grp.kinv[3 * r + 1];
-        if constexpr (KG) {
-          kg[3 * r] = d_p * u; kg[3 * r + 1] = d_p * v; kg[3 * r + 2] = d_p;
-        }
-      }
-      if constexpr (KG) {
-        float d_fp = 0.f;
-#pragma unroll
-        for (int r = 0; r < 3; ++r) d_fp += gs[r] * (a.lo + range * pt.sig[r]);
-        kg[9] = dep * d_fp;
-      }
-      a.d_coords[2 * gi] = d_u;
-      a.d_coords[2 * gi + 1] = d_v;
-      // q / (|q| + eps): a zero quaternion takes the norm's gradient as 0 (torch's norm backward)
-      const float qd = pt.qn + a.eps;
-      const float qg = hd[3] * gs[3] + hd[4] * gs[4] + hd[5] * gs[5] + hd[6] * gs[6];
-      const float back = pt.qn > 0.f ? qg / (qd * qd * pt.qn) : 0.f;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) row[3 + k] = gs[3 + k] / qd - hd[3 + k] * back;
-    }
-    if (a.partials) {
-#pragma unroll
-      for (int k = 0; k < kAdaptPoseFloats; ++k) pose[k] = wave_sum(pose[k]);
-      if (tid < kAdaptPoseFloats) {
-        float mine = 0.f;
-#pragma unroll
-        for (int k = 0; k < kAdaptPoseFloats; ++k) mine = tid == k ? pose[k] : mine;
-        a.partials[((size_t)g * nb + blk) * PARTF + tid] = mine;
-      }
-      if constexpr (KG) {
-#pragma unroll
-        for (int k = 0; k < kAdaptIntrFloats; ++k) kg[k] = wave_sum(kg[k]);
-        if (tid >= kAdaptPoseFloats && tid < PARTF) {
-          float mine = 0.f;
-#pragma unroll
-          for (int k = 0; k < kAdaptIntrFloats; ++k) mine = tid == kAdaptPoseFloats + k ? kg[k] : mine;
-          a.partials[((size_t)g * nb + blk) * PARTF + tid] = mine;
-        }
-      }
-    }
-  }
-  __syncthreads();
-  // streaming stores, like the dense gradients of k_preprocess_bwd (unstage_rows): written once, read next by autograd
-  float* __restrict__ dst = a.d_raw + first * ROWF;
-  const int out_total = cnt * ROWF;
-  if ((((uintptr_t)dst) & 15) == 0) {
-    typedef float f4v_ __attribute__((ext_vector_type(4)));
-    const int n4 = out_total >> 2;
-    for (int k = tid; k < n4; k += kAdaptThreads) {
-      const float4 x = reinterpret_cast<const float4*>(rows)[k];
-      __builtin_nontemporal_store(f4v_{x.x, x.y, x.z, x.w}, reinterpret_cast<f4v_*>(dst) + k);
-    }
-    for (int k = (n4 << 2) + tid; k < out_total; k += kAdaptThreads) dst[k] = rows[k];
-  } else {
-    for (int k = tid; k < out_total; k += kAdaptThreads) dst[k] = rows[k];
-  }
-}
-
-// dL/dextrinsics (G, 4, 4) from the per-workgroup rows: block g adds the nb rows of group g in a fixed order (252 threads = 21 rows x
-// 12 columns per step, then the 21 partial rows one after the other).  Rows 0-2 x columns 0-2: sum of dmean (x) (depth ray); column 3:
-// sum of dmean; bottom row zero.
-__global__ __launch_bounds__(256) void k_adapt_pose_reduce(const float* __restrict__ partials, int nb, float* __restrict__ d_ext) {
-  __shared__ float part[21][kAdaptPoseFloats];
-  const int g = blockIdx.x, tid = threadIdx.x, k = tid % kAdaptPoseFloats, r = tid / kAdaptPoseFloats;
-  const float* base = partials + (size_t)g * nb * kAdaptPoseFloats;
-  if (r < 21) {
-    float acc = 0.f;
-    for (int i = r; i < nb; i += 21) acc += base[(size_t)i * kAdaptPoseFloats + k];
-    part[r][k] = acc;
-  }
-  __syncthreads();
-  if (tid < 16) {
-    const int row = tid >> 2, col = tid & 3;
-    float sum = 0.f;
-    if (row < 3) {
-      const int idx = col < 3 ? 3 * row + col : 9 + row;
-      for (int j = 0; j < 21; ++j) sum += part[j][idx];
-    }
-    d_ext[(size_t)g * 16 + tid] = sum;
-  }
-}
-
-// The same sum over rows of kAdaptPoseFloats + kAdaptIntrFloats floats (k_adapt_bwd<D, true>): dL/dextrinsics from the first 12
-// columns in exactly k_adapt_pose_reduce's order (the same bits), and dL/dintrinsics (G, 3, 3) from the other ten, added up in
-// fp64 in the same fixed order and carried through K^-1 and the scale multiplier of adapt_group in fp64:
-//   dL/dK = -K^-T Ginv K^-T,   dL/dK[:2, :2] += -0.1 g_mult (K2^-T 1) (K2^-1 q)^T,   K2 = K[:2, :2], q = (1 / w, 1 / h)
-__global__ __launch_bounds__(256) void k_adapt_camera_reduce(const float* __restrict__ partials, int nb, const float* __restrict__ intr, int h, int w,
-                                                             float* __restrict__ d_ext, float* __restrict__ d_intr) {
-  constexpr int PARTF = kAdaptPoseFloats + kAdaptIntrFloats;
-  __shared__ float part[21][kAdaptPoseFloats];
-  __shared__ double parti[21][kAdaptIntrFloats];
-  __shared__ double tot[kAdaptIntrFloats];
-  const int g = blockIdx.x, tid = threadIdx.x, k = tid % kAdaptPoseFloats, r = tid / kAdaptPoseFloats;
-  const float* base = partials + (size_t)g * nb * PARTF;
-  if (r < 21) {
-    float acc = 0.f;
-    for (int i = r; i < nb; i += 21) acc += base[(size_t)i * PARTF + k];
-    part[r][k] = acc;
-    if (k < kAdaptIntrFloats) {
-      double wide = 0.0;
-      for (int i = r; i < nb; i += 21) wide += (double)base[(size_t)i * PARTF + kAdaptPoseFloats + k];
-      parti[r][k] = wide;
-    }
-  }
-  __syncthreads();
-  if (tid < 16) {
-    const int row = tid >> 2, col = tid & 3;
-    float sum = 0.f;
-    if (row < 3) {
-      const int idx = col < 3 ? 3 * row + col : 9 + row;
-      for (int j = 0; j < 21; ++j) sum += part[j][idx];
-    }
-    d_ext[(size_t)g * 16 + tid] = sum;
-  } else if (tid >= 64 && tid < 64 + kAdaptIntrFloats) {
-    double sum = 0.0;
-    for (int j = 0; j < 21; ++j) sum += parti[j][tid - 64];
-    tot[tid - 64] = sum;
-  }
-  __syncthreads();
-  if (tid < 9) {
-    const float* kk = intr + (size_t)g * 9;
-    const double a = kk[0], b = kk[1], c = kk[2], d = kk[3], ee = kk[4], f = kk[5], gg = kk[6], hh = kk[7], i = kk[8];
-    double inv[9] = {ee * i - f * hh, c * hh - b * i, b * f - c * ee, f * gg - d * i, a * i - c * gg, c * d - a * f,
-                     d * hh - ee * gg, b * gg - a * hh, a * ee - b * d};
-    const double det2 = inv[8], rdet = 1.0 / (a * inv[0] + b * inv[3] + c * inv[6]);
-#pragma unroll
-    for (int j = 0; j < 9; ++j) inv[j] *= rdet;
-    const int row = tid / 3, col = tid - 3 * row;
-    // -(K^-T Ginv K^-T)[row][col] = -sum_rc K^-1[r][row] Ginv[r][c] K^-1[col][c]
-    double sum = 0.0;
-#pragma unroll
-    for (int rr = 0; rr < 3; ++rr) {
-      double t = 0.0;
-#pragma unroll
-      for (int cc = 0; cc < 3; ++cc) t += tot[3 * rr + cc] * inv[3 * col + cc];
-      sum += inv[3 * rr + row] * t;
-    }
-    sum = -sum;
-    if (row < 2 && col < 2) {
-      const double px = (double)(1.0f / (float)w), py = (double)(1.0f / (float)h);
-      const double ones[2] = {(ee - d) / det2, (a - b) / det2};               // K2^-T (1, 1)
-      const double q[2] = {(ee * px - b * py) / det2, (a * py - d * px) / det2};  // K2^-1 (1 / w, 1 / h)
-      sum -= 0.1 * tot[9] * ones[row] * q[col];
-    }
-    d_intr[(size_t)g * 9 + tid] = (float)sum;
-  }
-}
-
-static bool adapt_sizes_ok(int G, int P, int sh_degree, int64_t stride, int height, int width) {
-  if (G < 0 || P < 0 || sh_degree < 0 || sh_degree > 4 || height <= 0 || width <= 0) return false;
-  const int rowf = 7 + 3 * (sh_degree + 1) * (sh_degree + 1);
-  if (stride < rowf || stride > (int64_t)1 << 24) return false;
-  const int64_t blocks = (int64_t)G * (((int64_t)P + kAdaptBlock - 1) / kAdaptBlock);
-  return blocks <= 0x7fffffff;
-}
-
-template <template <int> class Launch>
-static void adapt_dispatch(int degree, const AdaptArgs& a, hipStream_t st) {
-  switch (degree) {
-    case 0: Launch<0>::go(a, st); break;
-    case 1: Launch<1>::go(a, st); break;
-    case 2: Launch<2>::go(a, st); break;
-    case 3: Launch<3>::go(a, st); break;
-    default: Launch<4>::go(a, st); break;
-  }
-}
-static unsigned adapt_grid(const AdaptArgs& a) { return (unsigned)a.G * (unsigned)((a.P + kAdaptBlock - 1) / kAdaptBlock); }
-template <int D>
-struct AdaptFwdLaunch {
-  static void go(const AdaptArgs& a, hipStream_t st) {
-    constexpr int ROWF = 7 + 3 * (D + 1) * (D + 1);
-    const size_t floats = a.lstride == a.stride ? (size_t)(kAdaptBlock - 1) * a.stride + ROWF + 4 : (size_t)kAdaptBlock * ROWF;
-    hipLaunchKernelGGL(k_adapt_fwd<D>, dim3(adapt_grid(a)), dim3(kAdaptThreads), floats * sizeof(float), st, a);
-  }
-};
-template <int D>
-struct AdaptBwdLaunch {
-  static void go(const AdaptArgs& a, hipStream_t st) {
-    hipLaunchKernelGGL((k_adapt_bwd<D, false>), dim3(adapt_grid(a)), dim3(kAdaptThreads), 0, st, a);
-  }
-};
-template <int D>
-struct AdaptBwdIntrLaunch {
-  static void go(const AdaptArgs& a, hipStream_t st) {
-    hipLaunchKernelGGL((k_adapt_bwd<D, true>), dim3(adapt_grid(a)), dim3(kAdaptThreads), 0, st, a);
-  }
-};
-}  // namespace gsr
-
-extern "C" {
-
-size_t gsr_adapt_partials_bytes_ex(int num_groups, int gaussians_per_group, int with_intrinsics) {
-  if (num_groups <= 0 || gaussians_per_group <= 0) return 0;
-  const int rowf = gsr::kAdaptPoseFloats + (with_intrinsics ? gsr::kAdaptIntrFloats : 0);
-  return (size_t)num_groups * (size_t)((gaussians_per_group + gsr::kAdaptBlock - 1) / gsr::kAdaptBlock) * rowf * sizeof(float);
-}
-size_t gsr_adapt_partials_bytes(int num_groups, int gaussians_per_group) { return gsr_adapt_partials_bytes_ex(num_groups, gaussians_per_group, 0); }
-
-int gsr_adapt(int num_groups, int gaussians_per_group, int sh_degree, const float* extrinsics, const float* intrinsics,
-              const float* coordinates, const float* depths, const float* raw, int64_t raw_row_stride, float scale_min,
-              float scale_max, int height, int width, float eps, float* means, float* scale_rot, float* harmonics, void* stream_) {
-  using namespace gsr;
-  if (!adapt_sizes_ok(num_groups, gaussians_per_group, sh_degree, raw_row_stride, height, width)) return GSR_ERR_INVALID_ARGUMENT;
-  if (num_groups == 0 || gaussians_per_group == 0) return GSR_OK;
-  if (!extrinsics || !intrinsics || !coordinates || !depths || !raw || !means || !scale_rot || !harmonics) return GSR_ERR_INVALID_ARGUMENT;
-  const int rowf = 7 + 3 * (sh_degree + 1) * (sh_degree + 1);
-  AdaptArgs a{};
-  a.G = num_groups; a.P = gaussians_per_group; a.stride = (int)raw_row_stride;
-  a.lstride = raw_row_stride - rowf <= kAdaptSlack ? (int)raw_row_stride : rowf;
-  a.height = height; a.width = width; a.lo = scale_min; a.hi = scale_max; a.eps = eps;
-  a.ext = extrinsics; a.intr = intrinsics; a.coords = coordinates; a.depths = depths; a.raw = raw;
-  a.means = means; a.scale_rot = scale_rot; a.harm = harmonics;
-  adapt_dispatch<AdaptFwdLaunch>(sh_degree, a, static_cast<hipStream_t>(stream_));
-  GSR_CHECK(hipGetLastError());
-  return GSR_OK;
-}
-
-int gsr_adapt_backward(int num_groups, int gaussians_per_group, int sh_degree, const float* extrinsics, const float* intrinsics,
-                       const float* coordinates, const float* depths, const float* raw, int64_t raw_row_stride, float scale_min,
-                       float scale_max, int height, int width, float eps, const float* dL_dmeans, const float* dL_dscale_rot,
-                       const float* dL_dharmonics, float* dL_draw, float* dL_ddepths, float* dL_dcoordinates, float* dL_dextrinsics,
-                       float* partials, void* stream_) {
-  return gsr_adapt_backward_ex(num_groups, gaussians_per_group, sh_degree, extrinsics, intrinsics, coordinates, depths, raw, raw_row_stride, scale_min,
-                               scale_max, height, width, eps, dL_dmeans, dL_dscale_rot, dL_dharmonics, dL_draw, dL_ddepths, dL_dcoordinates,
-                               dL_dextrinsics, nullptr, partials, stream_);
-}
-
-int gsr_adapt_backward_ex(int num_groups, int gaussians_per_group, int sh_degree, const float* extrinsics, const float* intrinsics,
-                          const float* coordinates, const float* depths, const float* raw, int64_t raw_row_stride, float scale_min,
-                          float scale_max, int height, int width, float eps, const float* dL_dmeans, const float* dL_dscale_rot,
-                          const float* dL_dharmonics, float* dL_draw, float* dL_ddepths, float* dL_dcoordinates, float* dL_dextrinsics,
-                          float* dL_dintrinsics, float* partials, void* stream_) {
-  using namespace gsr;
-  if (!adapt_sizes_ok(num_groups, gaussians_per_group, sh_degree, raw_row_stride, height, width)) return GSR_ERR_INVALID_ARGUMENT;
-  if (num_groups == 0 || gaussians_per_group == 0) return GSR_OK;
-  if (!extrinsics || !intrinsics || !coordinates || !depths || !raw || !dL_draw || !dL_ddepths || !dL_dcoordinates || !dL_dextrinsics || !partials)
-    return GSR_ERR_INVALID_ARGUMENT;
-  hipStream_t st = static_cast<hipStream_t>(stream_);
-  AdaptArgs a{};
-  a.G = num_groups; a.P = gaussians_per_group; a.stride = (int)raw_row_stride; a.lstride = a.stride;
-  a.height = height; a.width = width; a.lo = scale_min; a.hi = scale_max; a.eps = eps;
-  a.ext = extrinsics; a.intr = intrinsics; a.coords = coordinates; a.depths = depths; a.raw = raw;
-  a.d_means = dL_dmeans; a.d_sr = dL_dscale_rot; a.d_harm = dL_dharmonics;
-  a.d_raw = dL_draw; a.d_depths = dL_ddepths; a.d_coords = dL_dcoordinates; a.partials = partials;
-  const int nb = (gaussians_per_group + kAdaptBlock - 1) / kAdaptBlock;
-  if (dL_dintrinsics) {
-    adapt_dispatch<AdaptBwdIntrLaunch>(sh_degree, a, st);
-    GSR_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_adapt_camera_reduce, dim3((unsigned)num_groups), dim3(256), 0, st, partials, nb, intrinsics, height, width, dL_dextrinsics,
-                       dL_dintrinsics);
-  } else {
-    adapt_dispatch<AdaptBwdLaunch>(sh_degree, a, st);
-    GSR_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_adapt_pose_reduce, dim3((unsigned)num_groups), dim3(256), 0, st, partials, nb, dL_dextrinsics);
-  }
-  GSR_CHECK(hipGetLastError());
-  return GSR_OK;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------------
-// Pose loss (reference src/loss/loss_pose.py:28-129, the fourth loss of the training step; definition: include/gsr.h): per match of a
-// ragged list per (pair, scene) a 3D residual |Rt x_i - x_j| and a reprojection residual through depth, K_i^-1, Rt and K_j.  Work is
-// cut into units of kPoseUnit consecutive matches of ONE list, one workgroup per unit (the L1 normalisation of the scores is linear,
-// so a unit only needs its own three sums); every thread builds the list's Rt (fp64: P_j P_i^-1, general 3 x 3 inverse), K_i^-1 and
-// K_j from uniform loads, then takes one match: two int64 ids, a score, seven gathered floats.  k_pose_loss_finish - one workgroup,
-// a wave per list, fp64, fixed shuffle tree - adds the rows of each list and then the lists.  The backward recomputes everything
-// from the inputs (nothing per match is saved), adds dL/dxyz and dL/ddepth into zero-filled arrays with float atomics and writes
-// one row of 12 floats (dL/dRt) per unit; k_pose_loss_pose_reduce, a wave per (scene, view), sums the rows of each list in fp64 and
-// carries them to the poses, through the inverse for the first view of a pair, its pairs in their fixed order.
-// The four kernels are templates (one instance each, <kPoseUnit>) for the code object's layout alone: a plain kernel is emitted in
-// front of every template instance, and four new ones there moved the raster kernels 28 KB against the kernels in front of them -
-// the headline benchmark lost 0.25 % in six rounds of seven.  As instances they come last and nothing else moves against anything.
-// ------------------------------------------------------------------------------------------------
-namespace gsr {
-constexpr int kPoseUnit = 256;        // matches per workgroup, one per thread
-constexpr int kPoseFwdFloats = 4;     // a unit's forward row: sum |w|, sum w r3, sum huber(r2) / delta, 0
-constexpr int kPoseBwdFloats = 12;    // a unit's backward row: dL/dRt, rows 0-2 x (R columns 0-2, t)
-constexpr int kPoseListFloats = 4;    // a list's row: conf L3, L2, the backward's 3D factor, sum |w|
-constexpr float kPoseDelta = 0.01f;   // the Huber threshold of the 2D term
-constexpr float kPoseHomEps = 1e-6f;  // from_homogeneous's epsilon
-
-struct PoseLossArgs {
-  int B, V, H, W, L;
-  const float *xyz, *depth, *poses, *intr;
-  const int64_t *ids_i, *ids_j;
-  const float *wgt, *conf;
-  const int32_t* offs;
-  float w2d, w3d;
-  float *partials, *lists, *out;                 // forward
-  const float* d_loss;                           // backward: the upstream cotangent, one float on the device
-  float *d_xyz, *d_depth, *d_poses;
-};
-
-struct PoseList {
-  int list, s, i, j, begin, end;
-  float R[9], t[3], Kj[9];      // Rt of the list (i -> j), K_j
-  double Rd[9], td[3], Kid[9];  // Rt before its rounding to float and K_i^-1: the reprojection chain (pose_match) runs in fp64
-};
-
-__device__ __forceinline__ int pose_units_of(int m0, int m1) { return (m1 - m0 + kPoseUnit - 1) / kPoseUnit; }
-
-__device__ __forceinline__ void pose_pair_of(int p, int V, int& i, int& j) {
-  i = 0;
-  while (p >= V - 1 - i) { p -= V - 1 - i; ++i; }
-  j = i + 1 + p;
-}
-
-// inverse of a 3 x 3 (row-major) in fp64, by the adjugate
-__device__ __forceinline__ void pose_inv3(const double* m, double* inv) {
-  const double a = m[0], b = m[1], c = m[2], d = m[3], e = m[4], f = m[5], g = m[6], h = m[7], i = m[8];
-  inv[0] = e * i - f * h; inv[1] = c * h - b * i; inv[2] = b * f - c * e;
-  inv[3] = f * g - d * i; inv[4] = a * i - c * g; inv[5] = c * d - a * f;
-  inv[6] = d * h - e * g; inv[7] = b * g - a * h; inv[8] = a * e - b * d;
-  const double rdet = 1.0 / (a * inv[0] + b * inv[3] + c * inv[6]);
-#pragma unroll
-  for (int k = 0; k < 9; ++k) inv[k] *= rdet;
-}
-
-// The top three rows of the affine inverse of a pose (rows of 4 floats): A = [R^-1 | -R^-1 t], 12 doubles, rows of 4.
-__device__ __forceinline__ void pose_affine_inverse(const float* P, double* A) {
-  double r[9], ri[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) r[k] = (double)P[4 * (k / 3) + k % 3];
-  pose_inv3(r, ri);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    A[4 * k] = ri[3 * k]; A[4 * k + 1] = ri[3 * k + 1]; A[4 * k + 2] = ri[3 * k + 2];
-    A[4 * k + 3] = -(ri[3 * k] * (double)P[3] + ri[3 * k + 1] * (double)P[7] + ri[3 * k + 2] * (double)P[11]);
-  }
-}
-
-// Which list a unit belongs to and that list's matrices; all of it uniform over the workgroup.
-__device__ __forceinline__ void pose_list_of_unit(const PoseLossArgs& a, int unit, PoseList& c) {
-  int l = 0, first = 0, m0 = a.offs[0], m1 = m0;
-  for (; l < a.L; ++l) {
-    m1 = a.offs[l + 1];
-    const int n = pose_units_of(m0, m1);
-    if (unit < first + n) break;
-    first += n;
-    m0 = m1;
-  }
-  c.list = l;
-  c.begin = m0 + (unit - first) * kPoseUnit;
-  c.end = min(c.begin + kPoseUnit, m1);
-  const int p = l / a.B;
-  c.s = l - p * a.B;
-  pose_pair_of(p, a.V, c.i, c.j);
-  const float* Pj = a.poses + ((size_t)c.s * a.V + c.j) * 16;
-  if (c.i == 0) {  // the reference's shortcut: poses[s, 0] is taken as the identity, whatever it holds
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { c.R[3 * k] = Pj[4 * k]; c.R[3 * k + 1] = Pj[4 * k + 1]; c.R[3 * k + 2] = Pj[4 * k + 2]; c.t[k] = Pj[4 * k + 3]; }
-#pragma unroll
-    for (int k = 0; k < 9; ++k) c.Rd[k] = (double)c.R[k];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) c.td[k] = (double)c.t[k];
-  } else {
-    double A[12];
-    pose_affine_inverse(a.poses + ((size_t)c.s * a.V + c.i) * 16, A);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const double x = Pj[4 * k], y = Pj[4 * k + 1], z = Pj[4 * k + 2];
-#pragma unroll
-      for (int q = 0; q < 3; ++q) { c.Rd[3 * k + q] = x * A[q] + y * A[4 + q] + z * A[8 + q]; c.R[3 * k + q] = (float)c.Rd[3 * k + q]; }
-      c.td[k] = x * A[3] + y * A[7] + z * A[11] + (double)Pj[4 * k + 3];
-      c.t[k] = (float)c.td[k];
-    }
-  }
-  const float* Ki = a.intr + ((size_t)c.s * a.V + c.i) * 9;
-  const float* Kj = a.intr + ((size_t)c.s * a.V + c.j) * 9;
-  double k64[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) { k64[k] = (double)Ki[k]; c.Kj[k] = Kj[k]; }
-  pose_inv3(k64, c.Kid);
-}
-
-struct PoseMatch {
-  float xi[3], y[3], r3;          // x_i, R x_i + t - x_j, its norm
-  float ray[3], P[3], uz, q[2];   // K_i^-1 (c, 1), depth x ray, (K_j Q)_z + eps, the projection
-  float e[2], r2;                 // q - c(id_j), its norm
-};
-
-__device__ __forceinline__ void pose_match(const PoseLossArgs& a, const PoseList& c, uint32_t ia, uint32_t ib, PoseMatch& m) {
-  const size_t hw = (size_t)a.H * a.W;
-  const float* xi = a.xyz + ((size_t)c.s * a.V + c.i) * 3 * hw + ia;
-  const float* xj = a.xyz + ((size_t)c.s * a.V + c.j) * 3 * hw + ib;
-  m.xi[0] = xi[0]; m.xi[1] = xi[hw]; m.xi[2] = xi[2 * hw];
-  const float xj0 = xj[0], xj1 = xj[hw], xj2 = xj[2 * hw];
-  const float d = a.depth[((size_t)c.s * a.V + c.i) * hw + ia];
-  const float xjv[3] = {xj0, xj1, xj2};
-#pragma unroll
-  for (int k = 0; k < 3; ++k) m.y[k] = c.R[3 * k] * m.xi[0] + c.R[3 * k + 1] * m.xi[1] + c.R[3 * k + 2] * m.xi[2] + c.t[k] - xjv[k];
-  m.r3 = sqrtf(m.y[0] * m.y[0] + m.y[1] * m.y[1] + m.y[2] * m.y[2]);
-  const uint32_t W = (uint32_t)a.W;
-  const uint32_t ya = ia / W, yb = ib / W;
-  const float fw = (float)a.W, fh = (float)a.H;
-  const float cx = ((float)(ia - ya * W) + 0.5f) / fw, cy = ((float)ya + 0.5f) / fh;
-  const float bx = ((float)(ib - yb * W) + 0.5f) / fw, by = ((float)yb + 0.5f) / fh;
-  // The reprojection in fp64, from the float32 pixel centres to the residual: where the poses are near the identity q and c(id_j)
-  // agree to 1e-3 and float32 would keep four digits of their difference (and of the 2D term and its gradient, list after list:
-  // much of that rounding sits in Rt and K_i^-1, common to a list's matches).  What the backward reads comes out as floats.
-  const double eps = 1e-6;
-  double ray[3], P[3], Q[3], u[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) { ray[k] = c.Kid[3 * k] * (double)cx + c.Kid[3 * k + 1] * (double)cy + c.Kid[3 * k + 2]; P[k] = ray[k] * (double)d; }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) Q[k] = (c.Rd[3 * k] * P[0] + c.Rd[3 * k + 1] * P[1] + c.Rd[3 * k + 2] * P[2] + c.td[k]) / (1.0 + eps);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) u[k] = (double)c.Kj[3 * k] * Q[0] + (double)c.Kj[3 * k + 1] * Q[1] + (double)c.Kj[3 * k + 2] * Q[2];
-  const double uz = u[2] + eps, q0 = u[0] / uz, q1 = u[1] / uz, e0 = q0 - (double)bx, e1 = q1 - (double)by;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) { m.ray[k] = (float)ray[k]; m.P[k] = (float)P[k]; }
-  m.uz = (float)uz;
-  m.q[0] = (float)q0; m.q[1] = (float)q1;
-  m.e[0] = (float)e0; m.e[1] = (float)e1;
-  m.r2 = (float)sqrt(e0 * e0 + e1 * e1);
-}
-
-template <int kUnit>
-__global__ __launch_bounds__(kPoseUnit) void k_pose_loss_fwd(const PoseLossArgs a) {
-  __shared__ float red[3][kPoseUnit / 64];
-  PoseList c;
-  pose_list_of_unit(a, (int)blockIdx.x, c);
-  const int tid = threadIdx.x, at = c.begin + tid;
-  float sw = 0.f, s3 = 0.f, s2 = 0.f;
-  if (at < c.end) {
-    PoseMatch m;
-    pose_match(a, c, (uint32_t)a.ids_i[at], (uint32_t)a.ids_j[at], m);
-    const float w = a.wgt[at];
-    sw = fabsf(w);
-    s3 = w * m.r3;
-    s2 = (m.r2 <= kPoseDelta ? 0.5f * m.r2 * m.r2 : kPoseDelta * (m.r2 - 0.5f * kPoseDelta)) / kPoseDelta;
-  }
-  sw = wave_sum(sw); s3 = wave_sum(s3); s2 = wave_sum(s2);
-  if ((tid & 63) == 0) { red[0][tid >> 6] = sw; red[1][tid >> 6] = s3; red[2][tid >> 6] = s2; }
-  __syncthreads();
-  if (tid < kPoseFwdFloats) a.partials[(size_t)blockIdx.x * kPoseFwdFloats + tid] = tid < 3 ? red[tid][0] + red[tid][1] + red[tid][2] + red[tid][3] : 0.f;
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
-// One workgroup of 16 waves; wave q takes lists q, q + 16, ...: the rows of a list added in fp64 (lane k the rows k, k + 64, ...,
-// then the xor tree: a fixed order), so a list's row does not depend on the other lists.  Then the first wave adds the lists the
-// same way.  lists[l] = (conf L3 term, L2 term, w3d conf / (max(sum |w|, 1e-12) L), sum |w|); out = (loss, mean L3, mean L2, 0).
-template <int kUnit>
-__global__ __launch_bounds__(1024) void k_pose_loss_finish(const PoseLossArgs a) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  int first = 0;
-  for (int base = 0; base < a.L; base += 16) {
-    const int mine = (lane < 16 && base + lane < a.L) ? pose_units_of(a.offs[base + lane], a.offs[base + lane + 1]) : 0;
-    int before = 0, total = 0, count = 0;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int n = __shfl(mine, q, 64);
-      if (q < wv) before += n;
-      if (q == wv) count = n;
-      total += n;
-    }
-    const int l = base + wv;
-    if (l < a.L) {
-      const float* rows = a.partials + (size_t)(first + before) * kPoseFwdFloats;
-      double sw = 0.0, s3 = 0.0, s2 = 0.0;
-      for (int k = lane; k < count; k += 64) {
-        const float4 v = *reinterpret_cast<const float4*>(rows + (size_t)k * kPoseFwdFloats);
-        sw += (double)v.x; s3 += (double)v.y; s2 += (double)v.z;
-      }
-      sw = wave_sum_f64(sw); s3 = wave_sum_f64(s3); s2 = wave_sum_f64(s2);
-      if (lane == 0) {
-        const double conf = (double)a.conf[l], den = fmax(sw, 1e-12);
-        float* o = a.lists + (size_t)l * kPoseListFloats;
-        o[0] = (float)(conf * s3 / den);
-        o[1] = (float)s2;
-        o[2] = (float)((double)a.w3d * conf / (den * (double)a.L));
-        o[3] = (float)sw;
-      }
-    }
-    first += total;
-  }
-  __syncthreads();
-  if (wv == 0) {
-    double t3 = 0.0, t2 = 0.0;
-    for (int l = lane; l < a.L; l += 64) { t3 += (double)a.lists[(size_t)l * kPoseListFloats]; t2 += (double)a.lists[(size_t)l * kPoseListFloats + 1]; }
-    t3 = wave_sum_f64(t3); t2 = wave_sum_f64(t2);
-    if (lane == 0) {
-      const double m3 = a.L > 0 ? t3 / (double)a.L : 0.0, m2 = a.L > 0 ? t2 / (double)a.L : 0.0;
-      a.out[0] = (float)((double)a.w3d * m3 + (double)a.w2d * m2);
-      a.out[1] = (float)m3;
-      a.out[2] = (float)m2;
-      a.out[3] = 0.f;
-    }
-  }
-}
-
-template <int kUnit>
-__global__ __launch_bounds__(kPoseUnit) void k_pose_loss_bwd(const PoseLossArgs a) {
-  __shared__ float red[kPoseUnit / 64][kPoseBwdFloats];
-  PoseList c;
-  pose_list_of_unit(a, (int)blockIdx.x, c);
-  const int tid = threadIdx.x, at = c.begin + tid;
-  const float up = a.d_loss[0];
-  const float f3 = up * a.lists[(size_t)c.list * kPoseListFloats + 2];  // dL / d(sum w r3) of this list
-  const float f2 = up * a.w2d / (float)a.L;                             // dL / d(sum huber / delta)
-  float g[kPoseBwdFloats];
-#pragma unroll
-  for (int k = 0; k < kPoseBwdFloats; ++k) g[k] = 0.f;
-  if (at < c.end) {
-    PoseMatch m;
-    const uint32_t ia = (uint32_t)a.ids_i[at], ib = (uint32_t)a.ids_j[at];
-    pose_match(a, c, ia, ib, m);
-    const size_t hw = (size_t)a.H * a.W;
-    // 3D term: w r3, r3 = |y|; the norm's gradient at y = 0 is 0
-    const float s3 = m.r3 > 0.f ? f3 * a.wgt[at] / m.r3 : 0.f;
-    const float gy[3] = {s3 * m.y[0], s3 * m.y[1], s3 * m.y[2]};
-    // 2D term: huber(r2) / delta, r2 = |e|: d/de = e / delta on the quadratic side, e / r2 on the linear one
-    const float s2 = m.r2 <= kPoseDelta ? f2 / kPoseDelta : f2 / m.r2;
-    const float dq[2] = {s2 * m.e[0], s2 * m.e[1]};
-    const float du[3] = {dq[0] / m.uz, dq[1] / m.uz, -(dq[0] * m.q[0] + dq[1] * m.q[1]) / m.uz};
-    float dY[3], dP[3], dxi[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) dY[k] = (c.Kj[k] * du[0] + c.Kj[3 + k] * du[1] + c.Kj[6 + k] * du[2]) / (1.f + kPoseHomEps);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      dP[k] = c.R[k] * dY[0] + c.R[3 + k] * dY[1] + c.R[6 + k] * dY[2];
-      dxi[k] = c.R[k] * gy[0] + c.R[3 + k] * gy[1] + c.R[6 + k] * gy[2];
-    }
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-#pragma unroll
-      for (int q = 0; q < 3; ++q) g[4 * r + q] = gy[r] * m.xi[q] + dY[r] * m.P[q];
-      g[4 * r + 3] = gy[r] + dY[r];
-    }
-    float* di = a.d_xyz + ((size_t)c.s * a.V + c.i) * 3 * hw + ia;
-    float* dj = a.d_xyz + ((size_t)c.s * a.V + c.j) * 3 * hw + ib;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { unsafeAtomicAdd(di + k * hw, dxi[k]); unsafeAtomicAdd(dj + k * hw, -gy[k]); }
-    unsafeAtomicAdd(a.d_depth + ((size_t)c.s * a.V + c.i) * hw + ia, dP[0] * m.ray[0] + dP[1] * m.ray[1] + dP[2] * m.ray[2]);
-  }
-#pragma unroll
-  for (int k = 0; k < kPoseBwdFloats; ++k) g[k] = wave_sum(g[k]);
-  if ((tid & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < kPoseBwdFloats; ++k) red[tid >> 6][k] = g[k];
-  }
-  __syncthreads();
-  if (tid < kPoseBwdFloats) a.partials[(size_t)blockIdx.x * kPoseBwdFloats + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
-}
-
-// dL/dposes (B, V, 4, 4), one wave per (scene, view u): for each pair (i, j) holding u, in the pairs' order, lane k < 12 adds
-// entry k of the list's rows in fp64 (G = dL/dRt), then entry (r, c) of the view's top three rows receives
-//   u == j:          (G A4^T)[r][c], A4 = P_i^-1 (the identity when i == 0: the shortcut);
-//   u == i, i > 0:   -(A^T (P_j^T G)[:3] A4^T)[r][c]     (Rt = P_j P_i^-1, d(P^-1) = -P^-1 dP P^-1; rows of A4 above its last);
-//   u == i == 0:     nothing (the shortcut never reads poses[s, 0]).
-// The bottom row is written as zeros.
-template <int kUnit>
-__global__ __launch_bounds__(64) void k_pose_loss_pose_reduce(const PoseLossArgs a) {
-  __shared__ double G[kPoseBwdFloats];
-  const int lane = threadIdx.x, s = (int)blockIdx.x / a.V, u = (int)blockIdx.x - s * a.V;
-  const int r = (lane >> 2) % 3, col = lane & 3;
-  double acc = 0.0;
-  const int pairs = a.V * (a.V - 1) / 2;
-  for (int p = 0; p < pairs; ++p) {
-    int i, j;
-    pose_pair_of(p, a.V, i, j);
-    if (i != u && j != u) continue;  // (uniform)
-    const int l = p * a.B + s;
-    int before = 0;
-    for (int q = lane; q < l; q += 64) before += pose_units_of(a.offs[q], a.offs[q + 1]);
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) before += __shfl_xor(before, m, 64);
-    const int count = pose_units_of(a.offs[l], a.offs[l + 1]);
-    __syncthreads();
-    if (lane < kPoseBwdFloats) {
-      double sum = 0.0;
-      const float* rows = a.partials + (size_t)before * kPoseBwdFloats + lane;
-      for (int k = 0; k < count; ++k) sum += (double)rows[(size_t)k * kPoseBwdFloats];
-      G[lane] = sum;
-    }
-    __syncthreads();
-    if (i == 0) {
-      if (u == j) acc += G[4 * r + col];
-      continue;
-    }
-    double A[16];
-    pose_affine_inverse(a.poses + ((size_t)s * a.V + i) * 16, A);
-    A[12] = 0.0; A[13] = 0.0; A[14] = 0.0; A[15] = 1.0;
-    if (u == j) {
-#pragma unroll
-      for (int m = 0; m < 4; ++m) acc += G[4 * r + m] * A[4 * col + m];
-    } else {
-      const float* Pj = a.poses + ((size_t)s * a.V + j) * 16;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        double t = 0.0;  // (dA A4^T)[k][col], dA[k][m] = sum_q P_j[q][k] G[q][m]
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-          const double dA = (double)Pj[k] * G[m] + (double)Pj[4 + k] * G[4 + m] + (double)Pj[8 + k] * G[8 + m];
-          t += dA * A[4 * col + m];
-        }
-        acc -= A[4 * k + r] * t;
-      }
-    }
-  }
-  if (lane < 16) a.d_poses[(size_t)blockIdx.x * 16 + lane] = lane < 12 ? (float)acc : 0.f;
-}
-
-// Host side: the unit count of a set of lists, -1 for offsets that are not a monotone sequence from a non-negative start.
-static int64_t pose_units_host(int num_lists, const int32_t* offsets) {
-  if (num_lists < 0 || !offsets || offsets[0] < 0) return -1;
-  int64_t units = 0;
-  for (int l = 0; l < num_lists; ++l) {
-    if (offsets[l + 1] < offsets[l]) return -1;
-    units += ((int64_t)offsets[l + 1] - offsets[l] + kPoseUnit - 1) / kPoseUnit;
-  }
-  return units;
-}
-
-// Everything the two entry points check alike; the unit count, or -1.
-static int64_t pose_args_ok(int B, int V, int H, int W, int pairs, const void* xyz, const void* depth, const void* poses, const void* intr,
-                            const void* ids_i, const void* ids_j, const void* wgt, const void* conf, const int32_t* offsets, const void* offsets_dev) {
-  if (B < 0 || V < 2 || H <= 0 || W <= 0 || (int64_t)H * W > 0x7fffffff || (int64_t)V * (V - 1) / 2 != pairs) return -1;
-  if ((int64_t)B * pairs > 0x7fffff || (int64_t)B * V > 0x7fffffff) return -1;
-  if (!offsets) return -1;
-  const int L = B * pairs;
-  const int64_t units = pose_units_host(L, offsets);
-  if (units < 0 || units > 0x7fffffff) return -1;
-  if (L > 0 && (!xyz || !depth || !poses || !intr || !conf || !offsets_dev)) return -1;
-  if (L > 0 && offsets[L] > offsets[0] && (!ids_i || !ids_j || !wgt)) return -1;
-  return units;
-}
-}  // namespace gsr
-
-extern "C" {
-
-int64_t gsr_pose_loss_units(int num_lists, const int32_t* offsets) { return gsr::pose_units_host(num_lists, offsets); }
-
-int gsr_pose_loss(int num_scenes, int num_views, int height, int width, int num_pairs, const float* xyz, const float* depth, const float* poses,
-                  const float* intrinsics, const int64_t* ids_i, const int64_t* ids_j, const float* weights, const float* conf,
-                  const int32_t* offsets, const int32_t* offsets_device, float weight_2d, float weight_3d, float* partials, float* lists,
-                  float* out, void* stream_) {
-  using namespace gsr;
-  const int64_t units = pose_args_ok(num_scenes, num_views, height, width, num_pairs, xyz, depth, poses, intrinsics, ids_i, ids_j, weights, conf,
-                                     offsets, offsets_device);
-  if (units < 0 || !out || (num_scenes > 0 && !lists) || (units > 0 && !partials)) return GSR_ERR_INVALID_ARGUMENT;
-  hipStream_t st = static_cast<hipStream_t>(stream_);
-  PoseLossArgs a{};
-  a.B = num_scenes; a.V = num_views; a.H = height; a.W = width; a.L = num_scenes * num_pairs;
-  a.xyz = xyz; a.depth = depth; a.poses = poses; a.intr = intrinsics; a.ids_i = ids_i; a.ids_j = ids_j; a.wgt = weights; a.conf = conf;
-  a.offs = offsets_device; a.w2d = weight_2d; a.w3d = weight_3d; a.partials = partials; a.lists = lists; a.out = out;
-  if (units > 0) {
-    hipLaunchKernelGGL(k_pose_loss_fwd<kPoseUnit>, dim3((unsigned)units), dim3(kPoseUnit), 0, st, a);
-    GSR_CHECK(hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_pose_loss_finish<kPoseUnit>, dim3(1), dim3(1024), 0, st, a);
-  GSR_CHECK(hipGetLastError());
-  return GSR_OK;
-}
-
-int gsr_pose_loss_backward(int num_scenes, int num_views, int height, int width, int num_pairs, const float* xyz, const float* depth,
-                           const float* poses, const float* intrinsics, const int64_t* ids_i, const int64_t* ids_j, const float* weights,
-                           const float* conf, const int32_t* offsets, const int32_t* offsets_device, float weight_2d, float weight_3d,
-                           const float* lists, const float* dL_dloss, float* dL_dxyz, float* dL_ddepth, float* dL_dposes, float* partials,
-                           void* stream_) {
-  using namespace gsr;
-  const int64_t units = pose_args_ok(num_scenes, num_views, height, width, num_pairs, xyz, depth, poses, intrinsics, ids_i, ids_j, weights, conf,
-                                     offsets, offsets_device);
-  if (units < 0 || (units > 0 && !partials)) return GSR_ERR_INVALID_ARGUMENT;
-  if (num_scenes == 0) return GSR_OK;
-  if (!lists || !dL_dloss || !dL_dxyz || !dL_ddepth || !dL_dposes) return GSR_ERR_INVALID_ARGUMENT;
-  hipStream_t st = static_cast<hipStream_t>(stream_);
-  PoseLossArgs a{};
-  a.B = num_scenes; a.V = num_views; a.H = height; a.W = width; a.L = num_scenes * num_pairs;
-  a.xyz = xyz; a.depth = depth; a.poses = poses; a.intr = intrinsics; a.ids_i = ids_i; a.ids_j = ids_j; a.wgt = weights; a.conf = conf;
-  a.offs = offsets_device; a.w2d = weight_2d; a.w3d = weight_3d; a.partials = partials; a.lists = const_cast<float*>(lists);
-  a.d_loss = dL_dloss; a.d_xyz = dL_dxyz; a.d_depth = dL_ddepth; a.d_poses = dL_dposes;
-  const size_t pixels = (size_t)num_scenes * num_views * height * width;
-  GSR_CHECK(hipMemsetAsync(dL_dxyz, 0, pixels * 3 * sizeof(float), st));
-  GSR_CHECK(hipMemsetAsync(dL_ddepth, 0, pixels * sizeof(float), st));
-  if (units > 0) {
-    hipLaunchKernelGGL(k_pose_loss_bwd<kPoseUnit>, dim3((unsigned)units), dim3(kPoseUnit), 0, st, a);
-    GSR_CHECK(hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_pose_loss_pose_reduce<kPoseUnit>, dim3((unsigned)(num_scenes * num_views)), dim3(64), 0, st, a);
-  GSR_CHECK(hipGetLastError());
-  return GSR_OK;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------------
-// Plane-sweep cost volume (reference src/model/encoder/costvolume/depth_predictor_multiview.py:28-141, 321-343; definition:
-// include/gsr.h): cost[(i s), d, p] = 1 / ((v - 1) sqrt(c)) sum_k f_i[:, p] . bilinear(f_j, proj_k(p, depth_d)).  The warped features
-// (v b, c, D, h, w) never exist: a wave takes one pixel p of one row (i, s), walks the candidates and reads each tap as ONE contiguous
-// channel row of a channels-last staging copy of the features, (b, v, h, w, Cp) floats, Cp = c rounded up to 4 and the pad zero
-// (k_cv_transpose<0>; a row is 1 KB at c = 256 and every float4 of it aligned).  Set-up per (row, other view), every thread, fp64,
-// uniform loads: P = E_j^-1 E_i (affine inverse), M = K R_P K^-1, K t_P; per pixel a = M (x, y, 1) in fp64; per sample
-// q = depth a + K t in fp32 and two divisions.  The 64 lanes form px, py of 64 candidates at once; the walk then takes one candidate
-// at a time with readlane, so px, py, the inside test and the tap addresses are scalars and every branch on them is uniform.
-// A tap is inside by a comparison of FLOATS (NaN and +-inf compare false); only an inside tap is converted to an integer.
-// Forward: workgroup = 16 consecutive pixels of one row, wave w pixels w, w + 4, ...; lane l holds float4 l of a 256-channel pass
-// (the first pass's reference feature stays in registers); 64 candidates x 16 pixels go through LDS to leave as 64-byte segments.
-// Backward: one launch over the same walk with channel = pass + 64 m + lane (every atomic instruction adds 256 contiguous bytes of a
-// row).  dL/df_i[:, p] = sum_k sum_d G[d, p] warp: registers, one row add at the end.  dL/df_j is the scatter: the contribution of a
-// tap is (G[d, p] weight) f_i[:, p] - a SCALAR times a row that is fixed for the walk - so the four scalars of consecutive candidates
-// with the same base pixel are summed in scalar registers and a row leaves the CU only when the walk moves on to another base
-// pixel.  Both go with float atomics into a zero-filled channels-last gradient (b, v, h, w, Cp), which k_cv_transpose<1> returns
-// as (b, v, c, h, w).  Templates for the code object's layout alone, as the pose loss above.
-// ------------------------------------------------------------------------------------------------
-namespace gsr {
-constexpr int kCvPix = 16;       // pixels of a forward workgroup
-constexpr int kCvPass = 256;     // channels of one pass of a wave
-constexpr float kCvMinZ = 1e-3f;  // the reference's clamp_min_depth
-
-struct CostVolArgs {
-  int B, V, C, Cp, H, W, D;
-  const float *feat, *intr, *extr, *near, *far;
-  float* fcl;      // (B, V, H, W, Cp) channels-last features
-  float* cost;     // forward: (V B, D, H, W)
-  const float* g;  // backward: dL/dcost
-  float* gcl;      // backward: (B, V, H, W, Cp) channels-last gradient, zero-filled
-  float* d_feat;   // backward: (B, V, C, H, W)
-  float scale;     // 1 / ((V - 1) sqrt(C))
-};
-
-// kDir 0: features (img, C, HW) -> fcl (img, HW, Cp), pad channels zero; kDir 1: gcl (img, HW, Cp) -> d_feat (img, C, HW).
-template <int kDir>
-__global__ __launch_bounds__(256) void k_cv_transpose(const CostVolArgs a) {
-  __shared__ float tile[32][33];
-  const int HW = a.H * a.W, tpx = (HW + 31) / 32, tch = (a.Cp + 31) / 32;
-  unsigned bid = blockIdx.x;
-  const int p0 = (int)(bid % (unsigned)tpx) * 32;
-  bid /= (unsigned)tpx;
-  const int c0 = (int)(bid % (unsigned)tch) * 32;
-  const size_t img = bid / (unsigned)tch;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  if (kDir == 0) {
-    const float* src = a.feat + img * (size_t)a.C * HW;
-    for (int r = ty; r < 32; r += 8) tile[r][tx] = (c0 + r < a.C && p0 + tx < HW) ? src[(size_t)(c0 + r) * HW + p0 + tx] : 0.f;
-    __syncthreads();
-    float* dst = a.fcl + img * (size_t)HW * a.Cp;
-    for (int r = ty; r < 32; r += 8)
-      if (p0 + r < HW && c0 + tx < a.Cp) dst[(size_t)(p0 + r) * a.Cp + c0 + tx] = tile[tx][r];
-  } else {
-    const float* src = a.gcl + img * (size_t)HW * a.Cp;
-    for (int r = ty; r < 32; r += 8) tile[r][tx] = (p0 + r < HW && c0 + tx < a.C) ? src[(size_t)(p0 + r) * a.Cp + c0 + tx] : 0.f;
-    __syncthreads();
-    float* dst = a.d_feat + img * (size_t)a.C * HW;
-    for (int r = ty; r < 32; r += 8)
-      if (c0 + r < a.C && p0 + tx < HW) dst[(size_t)(c0 + r) * HW + p0 + tx] = tile[tx][r];
-  }
-}
-
-// torch.linspace(0, 1, D) in float32: from the start below the middle, from the end above it.
-__device__ __forceinline__ float cv_lin(int d, int D) {
-  if (D < 2) return 0.f;
-  const float step = 1.f / (float)(D - 1);
-  return d < D / 2 ? (float)d * step : 1.f - (float)(D - 1 - d) * step;
-}
-
-// The candidate depth of a lane: 1 / (1 / far + lin (1 / near - 1 / far)), fp64 from the float32 bounds and lin.
-__device__ __forceinline__ float cv_depth(const CostVolArgs& a, size_t cam, int d) {
-  const double dmin = 1.0 / (double)a.far[cam], dmax = 1.0 / (double)a.near[cam];
-  return (float)(1.0 / (dmin + (double)cv_lin(d, a.D) * (dmax - dmin)));
-}
-
-// M = K R_P K^-1 and K t_P of row (i, s) against view j, P = E_j^-1 E_i, K = intrinsics[s, i] with row 0 x W, row 1 x H; fp64, uniform.
-__device__ __forceinline__ void cv_setup(const CostVolArgs& a, int s, int i, int j, double* M, double* kt) {
-  const float* Ei = a.extr + ((size_t)s * a.V + i) * 16;
-  double A[12], R[9], t[3], K[9], Ki[9], KR[9];
-  pose_affine_inverse(a.extr + ((size_t)s * a.V + j) * 16, A);
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) R[3 * r + c] = A[4 * r] * (double)Ei[c] + A[4 * r + 1] * (double)Ei[4 + c] + A[4 * r + 2] * (double)Ei[8 + c];
-    t[r] = A[4 * r] * (double)Ei[3] + A[4 * r + 1] * (double)Ei[7] + A[4 * r + 2] * (double)Ei[11] + A[4 * r + 3];
-  }
-  const float* Kn = a.intr + ((size_t)s * a.V + i) * 9;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) { K[c] = (double)Kn[c] * (double)a.W; K[3 + c] = (double)Kn[3 + c] * (double)a.H; K[6 + c] = (double)Kn[6 + c]; }
-  pose_inv3(K, Ki);
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) KR[3 * r + c] = K[3 * r] * R[c] + K[3 * r + 1] * R[3 + c] + K[3 * r + 2] * R[6 + c];
-    kt[r] = K[3 * r] * t[0] + K[3 * r + 1] * t[1] + K[3 * r + 2] * t[2];
-  }
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) M[3 * r + c] = KR[3 * r] * Ki[c] + KR[3 * r + 1] * Ki[3 + c] + KR[3 * r + 2] * Ki[6 + c];
-  }
-}
-
-// This lane's sample position for pixel (x, y): q = depth M (x, y, 1) + K t; px = q_x / max(q_z, 1e-3), py likewise.
-__device__ __forceinline__ void cv_project(const double* M, const double* kt, int x, int y, float depth, float& px, float& py) {
-  const float ax = (float)(M[0] * (double)x + M[1] * (double)y + M[2]), ay = (float)(M[3] * (double)x + M[4] * (double)y + M[5]);
-  const float az = (float)(M[6] * (double)x + M[7] * (double)y + M[8]);
-  const float qx = depth * ax + (float)kt[0], qy = depth * ay + (float)kt[1], qz = depth * az + (float)kt[2];
-  const float z = fmaxf(qz, kCvMinZ);  // (a NaN q_z gives the clamp: the sample then lands wherever q_x / 1e-3 does)
-  px = qx / z;
-  py = qy / z;
-}
-
-// The four taps of a sample (x0 y0, x1 y0, x0 y1, x1 y1): weights, and the pixel index y W + x of the taps that are inside; -1 outside.
-struct CvTaps {
-  float w[4];
-  int at[4];
-};
-
-// false: no tap inside (nothing may be read or added).  The comparisons are on floats - false for NaN, true for no value outside
-// [0, W - 1] x [0, H - 1] - and only what passed them is converted: x0 in [-1, W - 1], y0 in [-1, H - 1].
-__device__ __forceinline__ bool cv_taps(float px, float py, int W, int H, CvTaps& t) {
-  const float x0 = floorf(px), y0 = floorf(py), x1 = x0 + 1.f, y1 = y0 + 1.f;
-  const float wm1 = (float)(W - 1), hm1 = (float)(H - 1);
-  const bool ix0 = x0 >= 0.f && x0 <= wm1, ix1 = x1 >= 0.f && x1 <= wm1, iy0 = y0 >= 0.f && y0 <= hm1, iy1 = y1 >= 0.f && y1 <= hm1;
-  if (!((ix0 || ix1) && (iy0 || iy1))) return false;
-  const int xi = ix0 ? (int)x0 : -1, yi = iy0 ? (int)y0 : -1;  // (an x0 that is not inside while x1 is, is -1)
-  const float wx1 = px - x0, wx0 = x1 - px, wy1 = py - y0, wy0 = y1 - py;
-  t.w[0] = wx0 * wy0; t.w[1] = wx1 * wy0; t.w[2] = wx0 * wy1; t.w[3] = wx1 * wy1;
-  t.at[0] = (ix0 && iy0) ? yi * W + xi : -1;
-  t.at[1] = (ix1 && iy0) ? yi * W + xi + 1 : -1;
-  t.at[2] = (ix0 && iy1) ? (yi + 1) * W + xi : -1;
-  t.at[3] = (ix1 && iy1) ? (yi + 1) * W + xi + 1 : -1;
-  return true;
-}
-
-__device__ __forceinline__ float cv_lane_value(float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); }
-
-template <int kUnit>
-__global__ __launch_bounds__(256) void k_cost_volume_fwd(const CostVolArgs a) {
-  __shared__ float tile[64][kCvPix + 1];
-  const int HW = a.H * a.W, groups = (HW + kCvPix - 1) / kCvPix;
-  const int row = (int)(blockIdx.x / (unsigned)groups), p0 = (int)(blockIdx.x - (unsigned)row * (unsigned)groups) * kCvPix;
-  const int i = row / a.B, s = row - i * a.B;
-  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const size_t cam = (size_t)s * a.V + i;
-  const float* fi = a.fcl + cam * (size_t)HW * a.Cp;
-  const int c4 = lane * 4;
-  for (int d0 = 0; d0 < a.D; d0 += 64) {
-    const int nd = min(64, a.D - d0);
-    const float depth = cv_depth(a, cam, min(d0 + lane, a.D - 1));
-    float res[kCvPix / 4];
-#pragma unroll
-    for (int q = 0; q < kCvPix / 4; ++q) res[q] = 0.f;
-    for (int k = 1; k < a.V; ++k) {
-      const int j = (i + k) % a.V;
-      double M[9], kt[3];
-      cv_setup(a, s, i, j, M, kt);
-      const float* fj = a.fcl + ((size_t)s * a.V + j) * (size_t)HW * a.Cp;
-#pragma unroll
-      for (int q = 0; q < kCvPix / 4; ++q) {
-        const int p = p0 + wv + 4 * q;
-        if (p >= HW) continue;  // (uniform over the wave)
-        const int y = p / a.W, x = p - y * a.W;
-        float px, py;
-        cv_project(M, kt, x, y, depth, px, py);
-        const float* ref = fi + (size_t)p * a.Cp;
-        const float4 ref0 = c4 < a.Cp ? *reinterpret_cast<const float4*>(ref + c4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int dd = 0; dd < nd; ++dd) {
-          CvTaps t;
-          if (!cv_taps(cv_lane_value(px, dd), cv_lane_value(py, dd), a.W, a.H, t)) continue;  // (scalars: uniform)
-          float part = 0.f;
-          for (int c = c4; c < a.Cp; c += kCvPass) {
-            const float4 r = c == c4 ? ref0 : *reinterpret_cast<const float4*>(ref + c);
-            float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-            for (int n = 0; n < 4; ++n) {
-              if (t.at[n] < 0) continue;
-              const float4 f = *reinterpret_cast<const float4*>(fj + (size_t)t.at[n] * a.Cp + c);
-              w.x += t.w[n] * f.x; w.y += t.w[n] * f.y; w.z += t.w[n] * f.z; w.w += t.w[n] * f.w;
-            }
-            part += r.x * w.x + r.y * w.y + r.z * w.z + r.w * w.w;
-          }
-          part = wave_sum(part);
-          if (lane == dd) res[q] += part;
-        }
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < kCvPix / 4; ++q) tile[lane][wv + 4 * q] = res[q] * a.scale;
-    __syncthreads();
-    for (int e = tid; e < 64 * kCvPix; e += 256) {
-      const int dd = e / kCvPix, pp = e - dd * kCvPix;
-      if (dd < nd && p0 + pp < HW) a.cost[((size_t)row * a.D + d0 + dd) * HW + p0 + pp] = tile[dd][pp];
-    }
-    __syncthreads();
-  }
-}
-
-// Adds coef[n] x ref[m] to the channel rows of the (up to four) taps of base pixel `at`; channel c0 + 64 m + lane.
-__device__ __forceinline__ void cv_flush(float* gj, const int* at, float* coef, const float* ref, int c0, int lane, int C, int Cp) {
-#pragma unroll
-  for (int n = 0; n < 4; ++n) {
-    if (at[n] >= 0 && coef[n] != 0.f) {  // (scalars: uniform)
-      float* rowp = gj + (size_t)at[n] * Cp + c0 + lane;
-#pragma unroll
-      for (int m = 0; m < 4; ++m)
-        if (c0 + 64 * m + lane < C) unsafeAtomicAdd(rowp + 64 * m, coef[n] * ref[m]);
-    }
-    coef[n] = 0.f;
-  }
-}
-
-template <int kUnit>
-__global__ __launch_bounds__(256) void k_cost_volume_bwd(const CostVolArgs a) {
-  const int HW = a.H * a.W, groups = (HW + 3) / 4;
-  const int row = (int)(blockIdx.x / (unsigned)groups);
-  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int p = (int)(blockIdx.x - (unsigned)row * (unsigned)groups) * 4 + wv;
-  if (p >= HW) return;  // (uniform over the wave; no barrier below)
-  const int i = row / a.B, s = row - i * a.B;
-  const size_t cam = (size_t)s * a.V + i;
-  const int y = p / a.W, x = p - y * a.W;
-  const float* ref_row = a.fcl + (cam * (size_t)HW + p) * a.Cp;
-  float* gi = a.gcl + (cam * (size_t)HW + p) * a.Cp;
-  for (int c0 = 0; c0 < a.C; c0 += kCvPass) {
-    float ref[4], acc[4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) { ref[m] = c0 + 64 * m + lane < a.C ? ref_row[c0 + 64 * m + lane] : 0.f; acc[m] = 0.f; }
-    for (int k = 1; k < a.V; ++k) {
-      const int j = (i + k) % a.V;
-      double M[9], kt[3];
-      cv_setup(a, s, i, j, M, kt);
-      const float* fj = a.fcl + ((size_t)s * a.V + j) * (size_t)HW * a.Cp;
-      float* gj = a.gcl + ((size_t)s * a.V + j) * (size_t)HW * a.Cp;
-      int cur[4] = {-1, -1, -1, -1};
-      float coef[4] = {0.f, 0.f, 0.f, 0.f};
-      for (int d0 = 0; d0 < a.D; d0 += 64) {
-        const int nd = min(64, a.D - d0);
-        const int d = min(d0 + lane, a.D - 1);
-        float px, py;
-        cv_project(M, kt, x, y, cv_depth(a, cam, d), px, py);
-        const float gl = a.g[((size_t)row * a.D + d) * HW + p] * a.scale;
-        for (int dd = 0; dd < nd; ++dd) {
-          CvTaps t;
-          if (!cv_taps(cv_lane_value(px, dd), cv_lane_value(py, dd), a.W, a.H, t)) continue;  // (scalars: uniform)
-          const float g = cv_lane_value(gl, dd);
-          if (t.at[0] != cur[0] || t.at[1] != cur[1] || t.at[2] != cur[2] || t.at[3] != cur[3]) {
-            cv_flush(gj, cur, coef, ref, c0, lane, a.C, a.Cp);
-#pragma unroll
-            for (int n = 0; n < 4; ++n) cur[n] = t.at[n];
-          }
-#pragma unroll
-          for (int n = 0; n < 4; ++n) {
-            if (t.at[n] < 0) continue;
-            const float gw = g * t.w[n];
-            coef[n] += gw;
-            const float* src = fj + (size_t)t.at[n] * a.Cp + c0 + lane;
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-              if (c0 + 64 * m + lane < a.C) acc[m] += gw * src[64 * m];
-          }
-        }
-      }
-      cv_flush(gj, cur, coef, ref, c0, lane, a.C, a.Cp);
-    }
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-      if (c0 + 64 * m + lane < a.C) unsafeAtomicAdd(gi + c0 + 64 * m + lane, acc[m]);
-  }
-}
-
-// The checks of the three entry points: 0 when the sizes are in range, and Cp.
-static bool cv_sizes_ok(int B, int V, int C, int H, int W, int D, int64_t* cp) {
-  if (B < 0 || V < 2 || C < 1 || H < 2 || W < 2 || D < 1) return false;
-  const int64_t Cp = ((int64_t)C + 3) / 4 * 4, lim = 0x7fffffff;
-  const int64_t rows = (int64_t)B * V, hw = (int64_t)H * W;
-  if (rows > lim || hw > lim || rows * hw > lim || rows * hw * Cp > lim || rows * hw * (int64_t)D > lim) return false;
-  *cp = Cp;
-  return true;
-}
-}  // namespace gsr
-
-extern "C" {
-
-size_t gsr_cost_volume_scratch_bytes(int num_scenes, int num_views, int channels, int height, int width, int backward) {
-  int64_t cp;
-  if (!gsr::cv_sizes_ok(num_scenes, num_views, channels, height, width, 1, &cp)) return 0;
-  return (size_t)num_scenes * num_views * height * width * (size_t)cp * sizeof(float) * (backward ? 2 : 1);
-}
-
-int gsr_cost_volume(int num_scenes, int num_views, int channels, int height, int width, int num_depth_candidates, const float* features,
-                    const float* intrinsics, const float* extrinsics, const float* near, const float* far, float* cost, void* scratch,
-                    void* stream_) {
-  using namespace gsr;
-  int64_t cp;
-  if (!cv_sizes_ok(num_scenes, num_views, channels, height, width, num_depth_candidates, &cp)) return GSR_ERR_INVALID_ARGUMENT;
-  if (!features || !intrinsics || !extrinsics || !near || !far || !cost || !scratch) return GSR_ERR_INVALID_ARGUMENT;
-  if (num_scenes == 0) return GSR_OK;
-  hipStream_t st = static_cast<hipStream_t>(stream_);
-  CostVolArgs a{};
-  a.B = num_scenes; a.V = num_views; a.C = channels; a.Cp = (int)cp; a.H = height; a.W = width; a.D = num_depth_candidates;
-  a.feat = features; a.intr = intrinsics; a.extr = extrinsics; a.near = near; a.far = far;
-  a.fcl = static_cast<float*>(scratch); a.cost = cost;
-  a.scale = (float)(1.0 / ((double)(num_views - 1) * sqrt((double)channels)));
-  const int64_t hw = (int64_t)height * width, rows = (int64_t)num_scenes * num_views;
-  const int64_t tblocks = (hw + 31) / 32 * ((cp + 31) / 32) * rows, blocks = (hw + kCvPix - 1) / kCvPix * rows;
-  hipLaunchKernelGGL(k_cv_transpose<0>, dim3((unsigned)tblocks), dim3(256), 0, st, a);
-  GSR_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_cost_volume_fwd<kCvPix>, dim3((unsigned)blocks), dim3(256), 0, st, a);
-  GSR_CHECK(hipGetLastError());
-  return GSR_OK;
-}
-
-int gsr_cost_volume_backward(int num_scenes, int num_views, int channels, int height, int width, int num_depth_candidates,
-                             const float* features, const float* intrinsics, const float* extrinsics, const float* near, const float* far,
-                             const float* dL_dcost, float* dL_dfeatures, void* scratch, void* stream_) {
-  using namespace gsr;
-  int64_t cp;
-  if (!cv_sizes_ok(num_scenes, num_views, channels, height, width, num_depth_candidates, &cp)) return GSR_ERR_INVALID_ARGUMENT;
-  if (!features || !intrinsics || !extrinsics || !near || !far || !dL_dcost || !dL_dfeatures || !scratch) return GSR_ERR_INVALID_ARGUMENT;
-  if (num_scenes == 0) return GSR_OK;
-  hipStream_t st = static_cast<hipStream_t>(stream_);
-  const int64_t hw = (int64_t)height * width, rows = (int64_t)num_scenes * num_views;
-  const size_t floats = (size_t)(rows * hw * cp);
-  CostVolArgs a{};
-  a.B = num_scenes; a.V = num_views; a.C = channels; a.Cp = (int)cp; a.H = height; a.W = width; a.D = num_depth_candidates;
-  a.feat = features; a.intr = intrinsics; a.extr = extrinsics; a.near = near; a.far = far;
-  a.fcl = static_cast<float*>(scratch); a.gcl = a.fcl + floats; a.g = dL_dcost; a.d_feat = dL_dfeatures;
-  a.scale = (float)(1.0 / ((double)(num_views - 1) * sqrt((double)channels)));
-  const int64_t tblocks = (hw + 31) / 32 * ((cp + 31) / 32) * rows, blocks = (hw + 3) / 4 * rows;
-  GSR_CHECK(hipMemsetAsync(a.gcl, 0, floats * sizeof(float), st));
-  hipLaunchKernelGGL(k_cv_transpose<0>, dim3((unsigned)tblocks), dim3(256), 0, st, a);
-  GSR_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_cost_volume_bwd<kCvPix>, dim3((unsigned)blocks), dim3(256), 0, st, a);
-  GSR_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_cv_transpose<1>, dim3((unsigned)tblocks), dim3(256), 0, st, a);
-  GSR_CHECK(hipGetLastError());
-  return GSR_OK;
-}
-
-}  // extern "C"
-
-#endif  // GSR_POSE_HOST_ONLY
-
-// ------------------------------------------------------------------------------------------------
-// Coarse camera poses (include/gsr.h states the definition): PnP RANSAC per match list - a P3P hypothesis per lane, scored by the
-// workgroup over points staged in LDS, the winner refined by Gauss-Newton on its consensus set - and the synchronisation of the
-// pairwise poses (gsr_pnp_ransac, gsr_camera_sync).  The minimal solver and the Gauss-Newton step are host + device functions
-// (namespace gsr::pnp) that a host program can check in fp64 without a GPU: a translation unit that defines GSR_POSE_HOST_ONLY (and
-// GSR_HD as `inline`, after <cmath> and <cstdint>) and includes this file gets that arithmetic alone - everything above this line,
-// and the kernels and entry points below it, are left out.
-#ifndef GSR_HD
-#define GSR_HD __host__ __device__ inline
-#endif
-
-namespace gsr {
-namespace pnp {
-
-constexpr int kMinMatches = 4;     // three matches for the P3P solve and one to choose among its poses
-constexpr int kRefineRounds = 3;   // consensus set, then kGnSteps Gauss-Newton steps on it
-constexpr int kGnSteps = 10;
-constexpr int kJacobiSweeps = 8;   // of the 3 x 3 one-sided Jacobi SVD
-constexpr int kSquarings = 10;
-constexpr int kMaxViews = 8;
-
-struct Pose {
-  double R[9];  // row-major
-  double t[3];
-};
-
-GSR_HD uint32_t fmix32(uint32_t x) {
-  x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
-  return x;
-}
-
-// The draw of hypothesis t's slot (0..3) in list l: three rounds of murmur3's finaliser; the index is draw % n.
-GSR_HD uint32_t draw(uint32_t seed, uint32_t l, uint32_t t, uint32_t slot) {
-  uint32_t x = fmix32(seed ^ (0x9E3779B9u * (l + 1u)));
-  x = fmix32(x ^ (0x85EBCA6Bu * (t + 1u)));
-  return fmix32(x ^ (0xC2B2AE35u * (slot + 1u)));
-}
-
-// The largest real root of x^3 + a2 x^2 + a1 x + a0 (closed form, then three Newton steps).
-GSR_HD double cubic_largest_root(double a2, double a1, double a0) {
-  const double Q = (3.0 * a1 - a2 * a2) / 9.0, R = (9.0 * a2 * a1 - 27.0 * a0 - 2.0 * a2 * a2 * a2) / 54.0;
-  const double D = Q * Q * Q + R * R;
-  double x;
-  if (D < 0.0) {  // three real roots
-    const double sq = sqrt(-Q);
-    double c = R / (sq * sq * sq);
-    c = c > 1.0 ? 1.0 : (c < -1.0 ? -1.0 : c);
-    x = 2.0 * sq * cos(acos(c) / 3.0) - a2 / 3.0;
-  } else {
-    const double s = sqrt(D);
-    x = cbrt(R + s) + cbrt(R - s) - a2 / 3.0;
-  }
-  for (int it = 0; it < 3; ++it) {
-    const double f = ((x + a2) * x + a1) * x + a0, d = (3.0 * x + 2.0 * a2) * x + a1;
-    if (fabs(d) > 1e-300) x -= f / d;
-  }
-  return x;
-}
-
-// The real roots of c[4] y^4 + ... + c[0] by Ferrari's resolvent, each polished by two Newton steps; their number (0..4).
-GSR_HD int quartic_real_roots(const double c[5], double roots[4]) {
-  const double B = c[3] / c[4], C = c[2] / c[4], D = c[1] / c[4], E = c[0] / c[4];
-  const double B2 = B * B;
-  const double p = C - 0.375 * B2, q = D - 0.5 * B * C + 0.125 * B2 * B, r = E - 0.25 * B * D + B2 * C / 16.0 - 3.0 * B2 * B2 / 256.0;
-  const double m = cubic_largest_root(p, 0.25 * p * p - r, -0.125 * q * q);
-  if (!(m > 0.0)) return 0;  // (q == 0 with no positive root of the resolvent, or a non-finite coefficient: no hypothesis)
-  const double s = sqrt(2.0 * m), h = 0.5 * p + m, k = q / (2.0 * s);
-  int n = 0;
-  const double d1 = s * s - 4.0 * (h + k), d2 = s * s - 4.0 * (h - k);
-  if (d1 >= 0.0) { const double w = sqrt(d1); roots[n++] = 0.5 * (s + w); roots[n++] = 0.5 * (s - w); }
-  if (d2 >= 0.0) { const double w = sqrt(d2); roots[n++] = 0.5 * (-s + w); roots[n++] = 0.5 * (-s - w); }
-  for (int i = 0; i < n; ++i) {
-    double y = roots[i] - 0.25 * B;
-    for (int it = 0; it < 2; ++it) {
-      const double f = (((y + B) * y + C) * y + D) * y + E, d = ((4.0 * y + 3.0 * B) * y + 2.0 * C) * y + D;
-      if (fabs(d) > 1e-300) y -= f / d;
-    }
-    roots[i] = y;
-  }
-  return n;
-}
-
-GSR_HD void cross3(const double a[3], const double b[3], double o[3]) {
-  o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0];
-}
-GSR_HD double dot3(const double a[3], const double b[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
-
-// The right-handed orthonormal frame of a triangle, as the columns e1 e2 e3 (F[3 * r + c]).
-GSR_HD void triangle_frame(const double P0[3], const double P1[3], const double P2[3], double F[9]) {
-  double a[3], b[3], e3[3], e2[3];
-  for (int i = 0; i < 3; ++i) { a[i] = P1[i] - P0[i]; b[i] = P2[i] - P0[i]; }
-  const double na = sqrt(dot3(a, a));
-  for (int i = 0; i < 3; ++i) a[i] /= na;
-  cross3(a, b, e3);
-  const double n3 = sqrt(dot3(e3, e3));
-  for (int i = 0; i < 3; ++i) e3[i] /= n3;
-  cross3(e3, a, e2);
-  for (int i = 0; i < 3; ++i) { F[3 * i] = a[i]; F[3 * i + 1] = e2[i]; F[3 * i + 2] = e3[i]; }
-}
-
-// P3P: world points X[0..2], unit bearings f[0..2] in the camera -> up to eight poses (R, t) with s_i f_i = R X_i + t.
-// With the depths s1, s2 = x s1, s3 = y s1 and the law of cosines on the three sides, x is a rational function N(y) / D(y) and y a
-// root of the quartic N^2 - 2 cos(gamma) N D - p D^2 (the polynomials are multiplied out here, not typed in).  Every real root gives
-// two poses, s1 = +sqrt and s1 = -sqrt: a solution with negative depths is a solution of the equations as well, and the one the
-// data came from when the points lie behind the camera - the caller's fourth point chooses, the score's depth test judges.
-GSR_HD int p3p(const double X[3][3], const double f[3][3], Pose out[8]) {
-  double d12[3], d02[3], d01[3];
-  for (int i = 0; i < 3; ++i) { d12[i] = X[1][i] - X[2][i]; d02[i] = X[0][i] - X[2][i]; d01[i] = X[0][i] - X[1][i]; }
-  const double a2 = dot3(d12, d12), b2 = dot3(d02, d02), c2 = dot3(d01, d01);
-  const double ca = dot3(f[1], f[2]), cb = dot3(f[0], f[2]), cg = dot3(f[0], f[1]);
-  const double kc = c2 / b2, ka = a2 / b2;
-  const double p[3] = {kc - 1.0, -2.0 * cb * kc, kc};              // x^2 = 2 cg x + p(y)
-  const double q[3] = {-ka, 2.0 * cb * ka, 1.0 - ka};              // x^2 - 2 ca y x + q(y) = 0
-  const double N[3] = {-(p[0] + q[0]), -(p[1] + q[1]), -(p[2] + q[2])};
-  const double Dn[2] = {2.0 * cg, -2.0 * ca};                      // x = N(y) / D(y)
-  double quart[5] = {0, 0, 0, 0, 0};
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) quart[i + j] += N[i] * N[j];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 2; ++j) quart[i + j] -= 2.0 * cg * N[i] * Dn[j];
-  const double DD[3] = {Dn[0] * Dn[0], 2.0 * Dn[0] * Dn[1], Dn[1] * Dn[1]};
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) quart[i + j] -= p[i] * DD[j];
-  double ys[4];
-  const int nr = quartic_real_roots(quart, ys);
-  double FX[9];
-  triangle_frame(X[0], X[1], X[2], FX);
-  int n = 0;
-  for (int k = 0; k < nr; ++k) {
-    const double y = ys[k];
-    const double x = ((N[2] * y + N[1]) * y + N[0]) / (Dn[1] * y + Dn[0]);
-    const double w = 1.0 + y * y - 2.0 * y * cb;
-    if (!(w > 0.0)) continue;
-    for (int sign = 0; sign < 2; ++sign) {
-      const double s1 = sign ? -sqrt(b2 / w) : sqrt(b2 / w), s2 = x * s1, s3 = y * s1;
-      double P[3][3];
-      for (int i = 0; i < 3; ++i) { P[0][i] = s1 * f[0][i]; P[1][i] = s2 * f[1][i]; P[2][i] = s3 * f[2][i]; }
-      double FP[9];
-      triangle_frame(P[0], P[1], P[2], FP);
-      Pose& o = out[n];
-      for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) o.R[3 * r + c] = FP[3 * r] * FX[3 * c] + FP[3 * r + 1] * FX[3 * c + 1] + FP[3 * r + 2] * FX[3 * c + 2];
-      for (int r = 0; r < 3; ++r) o.t[r] = P[0][r] - (o.R[3 * r] * X[0][0] + o.R[3 * r + 1] * X[0][1] + o.R[3 * r + 2] * X[0][2]);
-      ++n;
-    }
-  }
-  return n;
-}
-
-struct Camera { double fx, fy, cx, cy; };
-
-GSR_HD bool pose_finite(const Pose& P) {
-  bool ok = true;
-  for (int i = 0; i < 9; ++i) ok = ok && (fabs(P.R[i]) <= 1.7e308);
-  for (int i = 0; i < 3; ++i) ok = ok && (fabs(P.t[i]) <= 1.7e308);
-  return ok;  // (a NaN fails the comparison)
-}
-
-// Squared reprojection error of X under P, and its depth; the caller tests `z > 0 && e2 < thr^2`, which a NaN fails.
-GSR_HD double reproj2(const Pose& P, const Camera& K, const double X[3], const double u[2], double* z) {
-  const double Y0 = P.R[0] * X[0] + P.R[1] * X[1] + P.R[2] * X[2] + P.t[0];
-  const double Y1 = P.R[3] * X[0] + P.R[4] * X[1] + P.R[5] * X[2] + P.t[1];
-  const double Y2 = P.R[6] * X[0] + P.R[7] * X[1] + P.R[8] * X[2] + P.t[2];
-  const double dx = K.fx * Y0 / Y2 + K.cx - u[0], dy = K.fy * Y1 / Y2 + K.cy - u[1];
-  *z = Y2;
-  return dx * dx + dy * dy;
-}
-
-// One hypothesis: P3P on the first three of four matches, the pose that reprojects the fourth best (the first of equals).
-GSR_HD bool hypothesis(const double X[4][3], const double u[4][2], const Camera& K, Pose* best) {
-  double f[3][3];
-  for (int i = 0; i < 3; ++i) {
-    const double bx = (u[i][0] - K.cx) / K.fx, by = (u[i][1] - K.cy) / K.fy;
-    const double inv = 1.0 / sqrt(bx * bx + by * by + 1.0);
-    f[i][0] = bx * inv; f[i][1] = by * inv; f[i][2] = inv;
-  }
-  Pose cand[8];
-  const int n = p3p(X, f, cand);
-  double best_e = 1.7e308;
-  bool found = false;
-  for (int k = 0; k < n; ++k) {
-    if (!pose_finite(cand[k])) continue;
-    double z;
-    const double e = reproj2(cand[k], K, X[3], u[3], &z);
-    if (e < best_e) { best_e = e; *best = cand[k]; found = true; }  // (a NaN fails the comparison)
-  }
-  return found;
-}
-
-// Gauss-Newton on sum |pi(K (R X + t)) - u|^2 with the update R <- exp(w) R, t <- t + d: one match's share of the upper triangle
-// of J^T J (21 numbers, row by row) and of J^T r (6), parameters (w, d).
-GSR_HD void gn_accumulate(const Pose& P, const Camera& K, const double X[3], const double u[2], double acc[27]) {
-  const double Q0 = P.R[0] * X[0] + P.R[1] * X[1] + P.R[2] * X[2];
-  const double Q1 = P.R[3] * X[0] + P.R[4] * X[1] + P.R[5] * X[2];
-  const double Q2 = P.R[6] * X[0] + P.R[7] * X[1] + P.R[8] * X[2];
-  const double Y0 = Q0 + P.t[0], Y1 = Q1 + P.t[1], Y2 = Q2 + P.t[2];
-  const double iz = 1.0 / Y2;
-  const double r0 = K.fx * Y0 * iz + K.cx - u[0], r1 = K.fy * Y1 * iz + K.cy - u[1];
-  // d pi / d Y
-  const double a0[3] = {K.fx * iz, 0.0, -K.fx * Y0 * iz * iz}, a1[3] = {0.0, K.fy * iz, -K.fy * Y1 * iz * iz};
-  // d Y / d w_k = e_k x Q, so a row of J is (Q x a)
-  double J0[6], J1[6];
-  J0[0] = Q1 * a0[2] - Q2 * a0[1];  J0[1] = Q2 * a0[0] - Q0 * a0[2];  J0[2] = Q0 * a0[1] - Q1 * a0[0];
-  J1[0] = Q1 * a1[2] - Q2 * a1[1];  J1[1] = Q2 * a1[0] - Q0 * a1[2];  J1[2] = Q0 * a1[1] - Q1 * a1[0];
-  for (int k = 0; k < 3; ++k) { J0[3 + k] = a0[k]; J1[3 + k] = a1[k]; }
-  int e = 0;
-  for (int i = 0; i < 6; ++i)
-    for (int j = i; j < 6; ++j) acc[e++] += J0[i] * J0[j] + J1[i] * J1[j];
-  for (int i = 0; i < 6; ++i) acc[21 + i] += J0[i] * r0 + J1[i] * r1;
-}
-
-// Solve the normal equations (Cholesky, no pivoting) and apply the step.  A matrix that is not positive definite gives a non-finite
-// pose, which the caller reports.
-GSR_HD void gn_step(Pose* P, const double acc[27]) {
-  double A[36], g[6];
-  int e = 0;
-  for (int i = 0; i < 6; ++i)
-    for (int j = i; j < 6; ++j) { A[6 * i + j] = acc[e]; A[6 * j + i] = acc[e]; ++e; }
-  for (int i = 0; i < 6; ++i) g[i] = -acc[21 + i];
-  for (int j = 0; j < 6; ++j) {  // A = L L^T, L in the lower triangle
-    double d = A[6 * j + j];
-    for (int k = 0; k < j; ++k) d -= A[6 * j + k] * A[6 * j + k];
-    d = sqrt(d);  // (NaN when d < 0)
-    A[6 * j + j] = d;
-    for (int i = j + 1; i < 6; ++i) {
-      double s = A[6 * i + j];
-      for (int k = 0; k < j; ++k) s -= A[6 * i + k] * A[6 * j + k];
-      A[6 * i + j] = s / d;
-    }
-  }
-  for (int i = 0; i < 6; ++i) {
-    double s = g[i];
-    for (int k = 0; k < i; ++k) s -= A[6 * i + k] * g[k];
-    g[i] = s / A[6 * i + i];
-  }
-  for (int i = 5; i >= 0; --i) {
-    double s = g[i];
-    for (int k = i + 1; k < 6; ++k) s -= A[6 * k + i] * g[k];
-    g[i] = s / A[6 * i + i];
-  }
-  const double wx = g[0], wy = g[1], wz = g[2];
-  const double th2 = wx * wx + wy * wy + wz * wz, th = sqrt(th2);
-  double ka, kb;  // exp(w) = I + ka [w]x + kb [w]x^2
-  if (th < 1e-8) { ka = 1.0; kb = 0.5; }
-  else { ka = sin(th) / th; kb = (1.0 - cos(th)) / th2; }
-  const double Kx[9] = {0.0, -wz, wy, wz, 0.0, -wx, -wy, wx, 0.0};
-  double E[9];
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) {
-      double k2 = 0.0;
-      for (int k = 0; k < 3; ++k) k2 += Kx[3 * r + k] * Kx[3 * k + c];
-      E[3 * r + c] = (r == c ? 1.0 : 0.0) + ka * Kx[3 * r + c] + kb * k2;
-    }
-  double Rn[9];
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) Rn[3 * r + c] = E[3 * r] * P->R[c] + E[3 * r + 1] * P->R[3 + c] + E[3 * r + 2] * P->R[6 + c];
-  for (int i = 0; i < 9; ++i) P->R[i] = Rn[i];
-  for (int i = 0; i < 3; ++i) P->t[i] += g[3 + i];
-}
-
-// The rotation nearest a 3 x 3 matrix as the reference projects it: U diag(1, 1, det(U V^T)) V^T of its SVD, the SVD by
-// kJacobiSweeps sweeps of one-sided Jacobi rotations; the factor det goes to the smallest singular value.
-GSR_HD void project_so3(const double Ain[9], double Rout[9]) {
-  double A[9], V[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-  for (int i = 0; i < 9; ++i) A[i] = Ain[i];
-  for (int sweep = 0; sweep < kJacobiSweeps; ++sweep)
-    for (int p = 0; p < 2; ++p)
-      for (int q = p + 1; q < 3; ++q) {
-        double al = 0.0, be = 0.0, ga = 0.0;
-        for (int i = 0; i < 3; ++i) { al += A[3 * i + p] * A[3 * i + p]; be += A[3 * i + q] * A[3 * i + q]; ga += A[3 * i + p] * A[3 * i + q]; }
-        if (ga == 0.0) continue;
-        const double zeta = (be - al) / (2.0 * ga);
-        const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-        const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-        for (int i = 0; i < 3; ++i) {
-          const double ap = A[3 * i + p], aq = A[3 * i + q];
-          A[3 * i + p] = c * ap - s * aq; A[3 * i + q] = s * ap + c * aq;
-          const double vp = V[3 * i + p], vq = V[3 * i + q];
-          V[3 * i + p] = c * vp - s * vq; V[3 * i + q] = s * vp + c * vq;
-        }
-      }
-  double sig[3], U[9];
-  for (int j = 0; j < 3; ++j) {
-    sig[j] = sqrt(A[j] * A[j] + A[3 + j] * A[3 + j] + A[6 + j] * A[6 + j]);
-    for (int i = 0; i < 3; ++i) U[3 * i + j] = sig[j] > 0.0 ? A[3 * i + j] / sig[j] : 0.0;
-  }
-  double M[9];
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) M[3 * r + c] = U[3 * r] * V[3 * c] + U[3 * r + 1] * V[3 * c + 1] + U[3 * r + 2] * V[3 * c + 2];
-  const double det = M[0] * (M[4] * M[8] - M[5] * M[7]) - M[1] * (M[3] * M[8] - M[5] * M[6]) + M[2] * (M[3] * M[7] - M[4] * M[6]);
-  int lo = 0;
-  if (sig[1] < sig[lo]) lo = 1;
-  if (sig[2] < sig[lo]) lo = 2;
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) Rout[3 * r + c] = M[3 * r + c] + (det - 1.0) * U[3 * r + lo] * V[3 * c + lo];
-}
-
-}  // namespace pnp
-}  // namespace gsr
-
-#ifndef GSR_POSE_HOST_ONLY
-namespace gsr {
-
-struct PnpArgs {
-  int B, V, H, W, L, hyp, nblk;
-  const float* xyz; const float* intr; const int64_t* ids_i; const int64_t* ids_j; const float* wgt; const float* pts2d;
-  const int32_t* offs;
-  uint32_t seed; float thr; float conf_min;
-  unsigned long long* best;
-  float* pairwise; int32_t* inliers; int32_t* status; float* conf; uint8_t* mask;
-};
-
-constexpr int kPnpThreads = 256;
-constexpr int kPnpStage = 1024;  // matches per LDS stage of the scoring kernel: 20 bytes each
-
-// List l -> its pair (i, j) and scene.
-__device__ inline void pnp_list_views(int l, int B, int V, int* s, int* pi, int* pj, int* pair) {
-  const int p = l / B;
-  *s = l - p * B; *pair = p;
-  int i = 0, left = p;
-  while (i < V - 2 && left >= V - 1 - i) { left -= V - 1 - i; ++i; }  // (at most V - 2 trips)
-  *pi = i; *pj = i + 1 + left;
-}
-
-struct PnpList {
-  const float* x; const int64_t* ids_i; const int64_t* ids_j; const float* pts2d;  // the second view's points; the list's entries
-  int64_t hw; int W;
-};
-
-__device__ inline void pnp_fetch(const PnpList& ls, int k, float X[3], float u[2]) {
-  int64_t idj = ls.ids_j[k];
-  idj = idj < 0 ? 0 : (idj >= ls.hw ? ls.hw - 1 : idj);  // (an id outside the image is the caller's error; it is not followed out of the array)
-  X[0] = ls.x[idj]; X[1] = ls.x[ls.hw + idj]; X[2] = ls.x[2 * ls.hw + idj];
-  if (ls.pts2d) { u[0] = ls.pts2d[2 * (int64_t)k]; u[1] = ls.pts2d[2 * (int64_t)k + 1]; }
-  else { const int64_t idi = ls.ids_i[k]; u[0] = (float)(idi % ls.W); u[1] = (float)(idi / ls.W); }
-}
-
-__device__ inline PnpList pnp_list(const PnpArgs& a, int l, int* s_out, int* far_out, pnp::Camera* K, int* begin, int* n) {
-  int s, pi, pj, pair;
-  pnp_list_views(l, a.B, a.V, &s, &pi, &pj, &pair);
-  const int64_t hw = (int64_t)a.H * a.W;
-  const int off = a.offs[l];
-  PnpList ls;
-  ls.x = a.xyz + ((int64_t)s * a.V + pj) * 3 * hw;
-  ls.ids_i = a.ids_i + off; ls.ids_j = a.ids_j + off; ls.pts2d = a.pts2d ? a.pts2d + 2 * (int64_t)off : nullptr;
-  ls.hw = hw; ls.W = a.W;
-  const float* k = a.intr + ((int64_t)s * a.V + pi) * 9;
-  K->fx = k[0]; K->fy = k[4]; K->cx = k[2]; K->cy = k[5];
-  *s_out = s; *far_out = (pj - pi > 1); *begin = off; *n = a.offs[l + 1] - off;
-  return ls;
-}
-
-__device__ inline bool pnp_solve_hypothesis(const PnpList& ls, const pnp::Camera& K, uint32_t seed, int l, int t, int n, pnp::Pose* P) {
-  double X[4][3], u[4][2];
-  for (int slot = 0; slot < 4; ++slot) {
-    const int k = (int)(pnp::draw(seed, (uint32_t)l, (uint32_t)t, (uint32_t)slot) % (uint32_t)n);
-    float Xf[3], uf[2];
-    pnp_fetch(ls, k, Xf, uf);
-    for (int c = 0; c < 3; ++c) X[slot][c] = Xf[c];
-    u[slot][0] = uf[0]; u[slot][1] = uf[1];
-  }
-  return pnp::hypothesis(X, u, K, P);
-}
-
-// Launch 1: workgroup (list, block of 256 hypotheses).  A lane solves its hypothesis in fp64; the workgroup then walks the list in
-// LDS stages, every lane counting the matches its own pose explains (fp32; all lanes read the same match: an LDS broadcast).
-__global__ void __launch_bounds__(kPnpThreads) k_pnp_hypotheses(PnpArgs a) {
-  __shared__ float stage[kPnpStage * 5];
-  __shared__ unsigned long long red[kPnpThreads];
-  const int tid = threadIdx.x, l = blockIdx.x / a.nblk, hb = blockIdx.x - l * a.nblk;
-  int s, far, begin, n;
-  pnp::Camera K;
-  const PnpList ls = pnp_list(a, l, &s, &far, &K, &begin, &n);
-  if (n < pnp::kMinMatches) {  // (uniform over the workgroup)
-    if (tid == 0) a.best[blockIdx.x] = 0ull;
-    return;
-  }
-  const int t = hb * kPnpThreads + tid;
-  pnp::Pose P;
-  bool ok = false;
-  if (t < a.hyp) ok = pnp_solve_hypothesis(ls, K, a.seed, l, t, n, &P);
-  float R[9], T[3];
-  for (int i = 0; i < 9; ++i) R[i] = (float)P.R[i];
-  for (int i = 0; i < 3; ++i) T[i] = (float)P.t[i];
-  const float fx = (float)K.fx, fy = (float)K.fy, cx = (float)K.cx, cy = (float)K.cy, thr2 = a.thr * a.thr;
-  unsigned count = 0;
-  for (int base = 0; base < n; base += kPnpStage) {
-    const int m = min(kPnpStage, n - base);
-    __syncthreads();
-    for (int k = tid; k < m; k += kPnpThreads) {
-      float X[3], u[2];
-      pnp_fetch(ls, base + k, X, u);
-      stage[5 * k] = X[0]; stage[5 * k + 1] = X[1]; stage[5 * k + 2] = X[2]; stage[5 * k + 3] = u[0]; stage[5 * k + 4] = u[1];
-    }
-    __syncthreads();
-    if (ok)
-      for (int k = 0; k < m; ++k) {
-        const float x = stage[5 * k], y = stage[5 * k + 1], z = stage[5 * k + 2];
-        const float Y0 = R[0] * x + R[1] * y + R[2] * z + T[0], Y1 = R[3] * x + R[4] * y + R[5] * z + T[1], Y2 = R[6] * x + R[7] * y + R[8] * z + T[2];
-        const float dx = fx * Y0 / Y2 + cx - stage[5 * k + 3], dy = fy * Y1 / Y2 + cy - stage[5 * k + 4];
-        count += (Y2 > 0.f && dx * dx + dy * dy < thr2) ? 1u : 0u;
-      }
-  }
-  red[tid] = ok ? (((unsigned long long)count << 32) | (unsigned)(a.hyp - 1 - t)) : 0ull;
-  __syncthreads();
-  for (int w = kPnpThreads / 2; w > 0; w >>= 1) {
-    if (tid < w) red[tid] = max(red[tid], red[tid + w]);
-    __syncthreads();
-  }
-  if (tid == 0) a.best[blockIdx.x] = red[0];
-}
-
-// Launch 2: one workgroup per list.  The winner is solved again from its index (the same arithmetic: the same pose), refined, and
-// the list's row of every output written.
-__global__ void __launch_bounds__(kPnpThreads) k_pnp_refine(PnpArgs a) {
-  __shared__ double red[27 * kPnpThreads];
-  __shared__ pnp::Pose pose, pose0;
-  __shared__ int state;
-  const int tid = threadIdx.x, l = blockIdx.x;
-  int s, far, begin, n;
-  pnp::Camera K;
-  const PnpList ls = pnp_list(a, l, &s, &far, &K, &begin, &n);
-  const double thr2 = (double)a.thr * (double)a.thr;
-
-  // the confidence: the mean score in fp64, in a fixed order
-  {
-    double sum = 0.0;
-    for (int k = tid; k < n; k += kPnpThreads) sum += (double)a.wgt[begin + k];
-    red[tid] = sum;
-    __syncthreads();
-    for (int w = kPnpThreads / 2; w > 0; w >>= 1) {
-      if (tid < w) red[tid] += red[tid + w];
-      __syncthreads();
-    }
-    if (tid == 0) {
-      float c = n > 0 ? (float)(red[0] / (double)n) : 0.f;
-      if (far) c = fmaxf(c - a.conf_min, 0.f) / (1.f - a.conf_min);
-      a.conf[l] = c;
-    }
-    __syncthreads();
-  }
-
-  if (tid == 0) {
-    int st = 0;
-    if (n < pnp::kMinMatches) st = 1;
-    else {
-      unsigned long long best = 0ull;
-      for (int k = 0; k < a.nblk; ++k) best = max(best, a.best[(int64_t)l * a.nblk + k]);
-      if ((unsigned)(best >> 32) < (unsigned)pnp::kMinMatches) st = 2;
-      else {
-        const int t = a.hyp - 1 - (int)(unsigned)(best & 0xffffffffull);
-        pnp::Pose P;
-        if (!pnp_solve_hypothesis(ls, K, a.seed, l, t, n, &P)) st = 2;
-        pose = P;
-      }
-    }
-    state = st;
-  }
-  __syncthreads();
-  int st = state;
-
-  if (st == 0) {
-    for (int round = 0; round < pnp::kRefineRounds; ++round) {
-      if (tid == 0) pose0 = pose;
-      __syncthreads();
-      for (int step = 0; step < pnp::kGnSteps; ++step) {
-        double acc[27];
-        for (int i = 0; i < 27; ++i) acc[i] = 0.0;
-        for (int k = tid; k < n; k += kPnpThreads) {
-          float Xf[3], uf[2];
-          pnp_fetch(ls, k, Xf, uf);
-          const double X[3] = {Xf[0], Xf[1], Xf[2]}, u[2] = {uf[0], uf[1]};
-          double z;
-          const double e2 = pnp::reproj2(pose0, K, X, u, &z);
-          if (z > 0.0 && e2 < thr2) pnp::gn_accumulate(pose, K, X, u, acc);
-        }
-        __syncthreads();  // (everybody has read `pose`; `red` is free)
-        for (int i = 0; i < 27; ++i) red[i * kPnpThreads + tid] = acc[i];
-        __syncthreads();
-        for (int w = kPnpThreads / 2; w > 0; w >>= 1) {
-          if (tid < w)
-            for (int i = 0; i < 27; ++i) red[i * kPnpThreads + tid] += red[i * kPnpThreads + tid + w];
-          __syncthreads();
-        }
-        if (tid == 0) {
-          double sum[27];
-          for (int i = 0; i < 27; ++i) sum[i] = red[i * kPnpThreads];
-          pnp::Pose P = pose;
-          pnp::gn_step(&P, sum);
-          pose = P;
-        }
-        __syncthreads();
-      }
-    }
-    if (!pnp::pose_finite(pose)) st = 3;
-  }
-
-  // the consensus set under the final pose
-  int count = 0;
-  for (int k = tid; k < n; k += kPnpThreads) {
-    bool in = false;
-    if (st == 0) {
-      float Xf[3], uf[2];
-      pnp_fetch(ls, k, Xf, uf);
-      const double X[3] = {Xf[0], Xf[1], Xf[2]}, u[2] = {uf[0], uf[1]};
-      double z;
-      const double e2 = pnp::reproj2(pose, K, X, u, &z);
-      in = z > 0.0 && e2 < thr2;
-    }
-    if (a.mask) a.mask[begin + k] = in ? 1 : 0;
-    count += in ? 1 : 0;
-  }
-  __syncthreads();
-  int* ired = reinterpret_cast<int*>(red);
-  ired[tid] = count;
-  __syncthreads();
-  for (int w = kPnpThreads / 2; w > 0; w >>= 1) {
-    if (tid < w) ired[tid] += ired[tid + w];
-    __syncthreads();
-  }
-  if (tid == 0) {
-    a.inliers[l] = ired[0];
-    a.status[l] = st;
-    const int pairs = a.V * (a.V - 1) / 2, p = l / a.B;
-    float* o = a.pairwise + ((int64_t)s * pairs + p) * 16;
-    if (st != 0) {
-      for (int i = 0; i < 16; ++i) o[i] = (i % 5 == 0) ? 1.f : 0.f;
-    } else {  // the rigid inverse [R^T | -R^T t]
-      for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) o[4 * r + c] = (float)pose.R[3 * c + r];
-        o[4 * r + 3] = (float)(-(pose.R[r] * pose.t[0] + pose.R[3 + r] * pose.t[1] + pose.R[6 + r] * pose.t[2]));
-      }
-      o[12] = 0.f; o[13] = 0.f; o[14] = 0.f; o[15] = 1.f;
-    }
-  }
-}
-
-struct SyncArgs {
-  int B, V;
-  const float* pairwise; const float* conf; float* out;
-};
-
-// Launch 3: one workgroup per scene; the (4 v)^2 matrix and its square in LDS, fp64.  The matrix is formed in fp32 as the reference
-// forms it (it converts to fp64 afterwards), in the reference's order of operations.
-__global__ void __launch_bounds__(256) k_camera_sync(SyncArgs a) {
-  constexpr int MV = pnp::kMaxViews, MN = 4 * MV;
-  __shared__ double Lm[2][MN * MN];
-  __shared__ int chain;
-  const int tid = threadIdx.x, s = blockIdx.x, V = a.V, N = 4 * V, pairs = V * (V - 1) / 2;
-  const float* Ps = a.pairwise + (int64_t)s * pairs * 16;
-  float* out = a.out + (int64_t)s * V * 16;
-  if (tid == 0) chain = (V == 2) ? 1 : 0;
-  for (int e = tid; e < N * N; e += 256) Lm[0][e] = 0.0;
-  __syncthreads();
-  if (V > 2) {
-    if (tid == 0) {
-      float conf[MV][MV];
-      for (int i = 0; i < V; ++i)
-        for (int j = 0; j < V; ++j) conf[i][j] = 0.f;
-      int p = 0;
-      for (int i = 0; i < V; ++i)
-        for (int j = i + 1; j < V; ++j, ++p) {
-          const float c = a.conf[(int64_t)p * a.B + s];
-          conf[i][j] = c; conf[j][i] = c;
-          conf[i][i] = conf[i][i] + c / 2.f; conf[j][j] = conf[j][j] + c / 2.f;
-        }
-      for (int j = 0; j < V; ++j) {
-        float sum = conf[0][j];
-        for (int i = 1; i < V; ++i) sum += conf[i][j];
-        sum = fmaxf(sum, 1e-9f);
-        for (int i = 0; i < V; ++i) conf[i][j] = conf[i][j] / sum;
-      }
-      for (int i = 0; i < V; ++i)
-        for (int k = 0; k < 4; ++k) Lm[0][(4 * i + k) * N + 4 * i + k] = (double)conf[i][i];
-      p = 0;
-      for (int i = 0; i < V; ++i)
-        for (int j = i + 1; j < V; ++j, ++p) {
-          const float* P = Ps + p * 16;
-          float inv[16];
-          for (int r = 0; r < 3; ++r) {
-            for (int c = 0; c < 3; ++c) inv[4 * r + c] = P[4 * c + r];
-            float acc = (-1.f * P[r]) * P[3];           // ((-1 R^T) t)_r = sum_k (-R[k][r]) t_k
-            acc += (-1.f * P[4 + r]) * P[7];
-            acc += (-1.f * P[8 + r]) * P[11];
-            inv[4 * r + 3] = acc;
-          }
-          for (int c = 0; c < 4; ++c) inv[12 + c] = P[12 + c];
-          const float cij = conf[i][j], cji = conf[j][i];
-          for (int r = 0; r < 4; ++r)
-            for (int c = 0; c < 4; ++c) {
-              Lm[0][(4 * i + r) * N + 4 * j + c] = (double)(cij * inv[4 * r + c]);
-              Lm[0][(4 * j + r) * N + 4 * i + c] = (double)(cji * P[4 * r + c]);
-            }
-        }
-    }
-    __syncthreads();
-    int cur = 0;
-    for (int sq = 0; sq < pnp::kSquarings; ++sq) {
-      for (int e = tid; e < N * N; e += 256) {
-        const int r = e / N, c = e - r * N;
-        double acc = 0.0;
-        for (int k = 0; k < N; ++k) acc += Lm[cur][r * N + k] * Lm[cur][k * N + c];
-        Lm[cur ^ 1][e] = acc;
-      }
-      __syncthreads();
-      cur ^= 1;
-    }
-    // (kSquarings is even: the result is in Lm[0])
-    if (tid == 0) {
-      int zero = 0;
-      for (int i = 0; i < V; ++i) zero |= (Lm[0][(4 * i + 3) * N + 3] == 0.0) ? 1 : 0;
-      chain = zero;
-    }
-    __syncthreads();
-    if (!chain && tid < V) {
-      const int i = tid;
-      const double mass = fmax(Lm[0][(4 * i + 3) * N + 3], 1e-9);
-      double blk[16], Rp[9], R[9];
-      for (int r = 0; r < 4; ++r)
-        for (int c = 0; c < 4; ++c) blk[4 * r + c] = Lm[0][(4 * i + r) * N + c] / mass;
-      for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) Rp[3 * r + c] = blk[4 * r + c];
-      pnp::project_so3(Rp, R);
-      for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) blk[4 * r + c] = R[3 * r + c];
-      for (int e = 0; e < 16; ++e) out[16 * i + e] = (float)blk[e];
-    }
-  }
-  if (chain && tid == 0) {  // camera_chaining: identity, then P(i, i + 1) times the one before, in fp32
-    float cur[16];
-    for (int e = 0; e < 16; ++e) { cur[e] = (e % 5 == 0) ? 1.f : 0.f; out[e] = cur[e]; }
-    int p = 0;
-    for (int i = 0; i + 1 < V; ++i) {
-      const float* P = Ps + p * 16;
-      float nxt[16];
-      for (int r = 0; r < 4; ++r)
-        for (int c = 0; c < 4; ++c) {
-          float acc = P[4 * r] * cur[c];
-          for (int k = 1; k < 4; ++k) acc += P[4 * r + k] * cur[4 * k + c];
-          nxt[4 * r + c] = acc;
-        }
-      for (int e = 0; e < 16; ++e) { cur[e] = nxt[e]; out[16 * (i + 1) + e] = nxt[e]; }
-      p += V - 1 - i;  // pair (i + 1, i + 2) follows the V - 1 - i pairs that begin with i
-    }
-  }
-}
-
-static bool pnp_offsets_ok(int L, const int32_t* offsets) {
-  if (!offsets || offsets[0] < 0) return false;
-  for (int l = 0; l < L; ++l)
-    if (offsets[l + 1] < offsets[l]) return false;
-  return true;
-}
-
-static bool pnp_sizes_ok(int B, int V, int pairs, int hyp) {
-  if (B < 0 || V < 2 || V > pnp::kMaxViews || (int64_t)V * (V - 1) / 2 != pairs || hyp < 1 || hyp > (1 << 24)) return false;
-  const int64_t nblk = (hyp + kPnpThreads - 1) / kPnpThreads;
-  return (int64_t)B * pairs * nblk <= 0x7fffffff;
-}
-
-}  // namespace gsr
-
-extern "C" {
-
-int gsr_pnp_min_matches(void) { return gsr::pnp::kMinMatches; }
-
-size_t gsr_pnp_ransac_scratch_bytes(int num_scenes, int num_views, int hypotheses) {
-  const int pairs = num_views * (num_views - 1) / 2;
-  if (num_views < 2 || !gsr::pnp_sizes_ok(num_scenes, num_views, pairs, hypotheses)) return 0;
-  return (size_t)num_scenes * pairs * ((hypotheses + gsr::kPnpThreads - 1) / gsr::kPnpThreads) * sizeof(unsigned long long);
-}
-
-int gsr_pnp_ransac(int num_scenes, int num_views, int height, int width, int num_pairs, const float* xyz, const float* intrinsics_px,
-                   const int64_t* ids_i, const int64_t* ids_j, const float* weights, const float* points_2d, const int32_t* offsets,
-                   const int32_t* offsets_device, int hypotheses, float reprojection_error, float confidence_min, uint32_t seed,
-                   void* scratch, float* pairwise, int32_t* inliers, int32_t* status, float* confidence, uint8_t* mask, void* stream_) {
-  using namespace gsr;
-  if (!pnp_sizes_ok(num_scenes, num_views, num_pairs, hypotheses)) return GSR_ERR_INVALID_ARGUMENT;
-  if (height <= 0 || width <= 0 || (int64_t)height * width > 0x7fffffff) return GSR_ERR_INVALID_ARGUMENT;
-  const int L = num_scenes * num_pairs;
-  if (!pnp_offsets_ok(L, offsets)) return GSR_ERR_INVALID_ARGUMENT;
-  if (!(reprojection_error > 0.f) || !(confidence_min < 1.f)) return GSR_ERR_INVALID_ARGUMENT;
-  if (L == 0) return GSR_OK;
-  if (!xyz || !intrinsics_px || !offsets_device || !scratch || !pairwise || !inliers || !status || !confidence) return GSR_ERR_INVALID_ARGUMENT;
-  if (offsets[L] > offsets[0] && (!ids_i || !ids_j || !weights)) return GSR_ERR_INVALID_ARGUMENT;
-  hipStream_t st = static_cast<hipStream_t>(stream_);
-  PnpArgs a{};
-  a.B = num_scenes; a.V = num_views; a.H = height; a.W = width; a.L = L; a.hyp = hypotheses;
-  a.nblk = (hypotheses + kPnpThreads - 1) / kPnpThreads;
-  a.xyz = xyz; a.intr = intrinsics_px; a.ids_i = ids_i; a.ids_j = ids_j; a.wgt = weights; a.pts2d = points_2d; a.offs = offsets_device;
-  a.seed = seed; a.thr = reprojection_error; a.conf_min = confidence_min;
-  a.best = static_cast<unsigned long long*>(scratch);
-  a.pairwise = pairwise; a.inliers = inliers; a.status = status; a.conf = confidence; a.mask = mask;
-  hipLaunchKernelGGL(k_pnp_hypotheses, dim3((unsigned)(L * a.nblk)), dim3(kPnpThreads), 0, st, a);
-  GSR_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_pnp_refine, dim3((unsigned)L), dim3(kPnpThreads), 0, st, a);
-  GSR_CHECK(hipGetLastError());
-  return GSR_OK;
-}
-
-int gsr_camera_sync(int num_scenes, int num_views, const float* pairwise, const float* confidence, float* absolute, void* stream_) {
-  using namespace gsr;
-  if (num_scenes < 0 || num_views < 2 || num_views > pnp::kMaxViews) return GSR_ERR_INVALID_ARGUMENT;
-  if (num_scenes == 0) return GSR_OK;
-  if (!pairwise || !confidence || !absolute) return GSR_ERR_INVALID_ARGUMENT;
-  SyncArgs a{num_scenes, num_views, pairwise, confidence, absolute};
-  hipLaunchKernelGGL(k_camera_sync, dim3((unsigned)num_scenes), dim3(256), 0, static_cast<hipStream_t>(stream_), a);
-  GSR_CHECK(hipGetLastError());
-  return GSR_OK;
-}
-
-}  // extern "C"
-#endif  // GSR_POSE_HOST_ONLY
+// The operators next to the raster path (see the map at the top of this file).
+#include "gsr_image.h"
+#include "gsr_adapter.h"
+#include "gsr_pose_loss.h"
+#include "gsr_cost_volume.h"
+#include "gsr_pnp_solver.h"
+#include "gsr_coarse_pose.h"

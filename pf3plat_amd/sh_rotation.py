@@ -13,7 +13,7 @@ Two conventions, selected by `basis`:
       positive: `sh_1 = (x, y, z)`, `sh_2_0 = sqrt(15) x z`, ..., `sh_2_4 = sqrt(15)/2 (z^2 - x^2)`) with the y axis as polar
       axis:  Y_e(x, y, z) = W(z, x, y)  (component order m = -l..l);
     - `D(R) Y_e(d) = Y_e(R d)` is the matrix `wigner_D(l, *matrix_to_angles(R))` (e3nn's equivariance statement).
-  The rasterizer's basis B (csrc/gsr_hip.hip `sh_visit`) is W WITH the phase: B_lm = (-1)^m W_lm.  Hence, with the permutation
+  The rasterizer's basis B (csrc/gsr_common.h `sh_visit`) is W WITH the phase: B_lm = (-1)^m W_lm.  Hence, with the permutation
   P: (x, y, z) -> (z, x, y) and S = diag((-1)^m):   D_e3nn(R) = S D_B(P R P^T) S,   D_B being the exact representation matrix in
   the rasterizer's basis that the "rasterizer" mode builds.  **Unpinned**: no e3nn output could be recorded in this container;
   tests/test_sh_rotation.py checks the consequences that can be checked without it (band 1 equals R itself in (x, y, z) order as

@@ -68,7 +68,7 @@ def _with_sh_frame(cfg: RasterConfig, sh_frame):
 
 def cov6_in_kernel_order(records, frames=None):
     """(S, N, 7) scale + quaternion (x, y, z, w) records [+ (S, F, 3, 3) frames] -> (S, N, 6) fp32 covariances, in the kernels' operation
-    order (gsr_hip.hip cov6_from_sr: Rq from the un-normalised quaternion, M = F Rq, Sigma = M diag(s^2) M^T; IEEE fp32, nothing
+    order (gsr_common.h cov6_from_sr: Rq from the un-normalised quaternion, M = F Rq, Sigma = M diag(s^2) M^T; IEEE fp32, nothing
     contracted).  The oracle side of the scale / rotation form rasterizes these: both sides then project the same covariance bits - the
     conic of a thin Gaussian amplifies a one-ulp difference in its covariance by its condition number, past the 1e-5 of
     check_preprocess between two correct fp32 builds.  The formula itself is pinned to oracle/adapter.py's (fp64) by tests/test_sr_cases.py."""

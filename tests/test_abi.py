@@ -71,7 +71,19 @@ def test_source_stamp_covers_every_file_the_library_is_built_from(tmp_path):
         f.write(b"\n")
     assert stamp() == before
     # (preprocess_bwd.inc: the text of k_preprocess_bwd, which gsr_hip.hip compiles twice)
-    assert {os.path.basename(s) for s in _lib.hip_sources()} == {"gsr_hip.hip", "preprocess_bwd.inc", "gsr.h"}
+    assert {os.path.basename(s) for s in _lib.hip_sources()} == {
+        "gsr_hip.hip", "gsr_common.h", "gsr_image.h", "gsr_adapter.h", "gsr_pose_loss.h", "gsr_cost_volume.h", "gsr_pnp_solver.h",
+        "gsr_coarse_pose.h", "preprocess_bwd.inc", "gsr.h"}
+    # ... and the stamp's file set IS the include graph of gsr_hip.hip: no file in csrc/ that changes the stamp without being
+    # compiled, no include the stamp misses (includes resolve relative to the including file)
+    reached, todo = set(), [os.path.realpath(_lib.SRC)]
+    while todo:
+        path = todo.pop()
+        if path not in reached:
+            reached.add(path)
+            with open(path) as f:
+                todo += [os.path.realpath(os.path.join(os.path.dirname(path), inc)) for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', f.read(), re.M)]
+    assert reached == {os.path.realpath(s) for s in _lib.hip_sources()}
 
 
 def test_oracle_twin_is_rebuilt_by_content_of_its_sources(tmp_path):
@@ -159,7 +171,7 @@ def test_workspace_sizes_and_validation():
 
 
 def test_binning_chunk_follows_the_shape_of_the_call():
-    """Gaussians per binning workgroup (choose_chunk, csrc/gsr_hip.hip), read back from the layout: the pair matrix holds views x rows x
+    """Gaussians per binning workgroup (choose_chunk, csrc/gsr_common.h), read back from the layout: the pair matrix holds views x rows x
     (tiles + 8) entries of 8 bytes between `counts` and `tile_total`.  One round of workgroups on the 256 CUs where it exists (the
     headline: 247 of 1216; configs[3]: 82 x 3 of 1600; one 131 072-Gaussian view: 256 of 512) - and for calls of several rounds (PF3plat's
     training batch: 4 scenes x 3 views) the chunk whose rounds cost least with the fixed part of a round counted: 1600, not 1024."""

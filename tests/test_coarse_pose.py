@@ -23,6 +23,7 @@ from tests import pnp_ref as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURES = os.path.join(ROOT, "tests", "golden", "pose_sync_fixtures.npz")
+SOLVER = os.path.join(os.path.dirname(_lib.SRC), "gsr_pnp_solver.h")
 M = pose.MIN_MATCHES
 INVALID = -1  # GSR_ERR_INVALID_ARGUMENT of include/gsr.h
 ROT_BOUND = 4 * 1.85e-9    # measured: 1.848e-9 rad (edges[2], n = 65)
@@ -176,7 +177,10 @@ def test_symbols_are_declared_exported_and_listed():
         assert name in _lib.EXPORTED_SYMBOLS and hasattr(exported, name) and f"{name}(" in header, name
     assert lib.gsr_pnp_ransac.restype is ctypes.c_int and len(lib.gsr_pnp_ransac.argtypes) == 24
     assert lib.gsr_camera_sync.restype is ctypes.c_int and len(lib.gsr_camera_sync.argtypes) == 6
-    assert "k_pnp_hypotheses" in open(_lib.SRC).read() and _lib.SRC in _lib.hip_sources()  # the content stamp of the build covers the kernels
+    kernels = os.path.join(os.path.dirname(_lib.SRC), "gsr_coarse_pose.h")
+    assert "k_pnp_hypotheses" in open(kernels).read() and kernels in _lib.hip_sources()  # the content stamp of the build covers the kernels
+    for path in _lib.hip_sources():  # the solver's header serves host and device as it is: no macro cuts a host build out of the library's text
+        assert "GSR_POSE_HOST_ONLY" not in open(path).read(), path
 
 
 def test_entry_points_refuse_invalid_sizes():
@@ -258,10 +262,6 @@ def test_pack_matches_is_pack_correspondences_without_confidences():
 
 
 HOST_WRAPPER = """
-#include <cmath>
-#include <cstdint>
-#define GSR_HD inline
-#define GSR_POSE_HOST_ONLY 1
 #include "%s"
 using namespace gsr::pnp;
 extern "C" int host_quartic(const double* c, double* roots) { return quartic_real_roots(c, roots); }
@@ -300,7 +300,7 @@ def test_host_build_of_the_solver_in_float64(tmp_path):
     cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++")
     assert cxx, "no C++ compiler (the build needs one as well)"
     src, lib_path = tmp_path / "host_pnp.cpp", tmp_path / "host_pnp.so"
-    src.write_text(HOST_WRAPPER % _lib.SRC)  # (with GSR_POSE_HOST_ONLY the file is its host + device arithmetic alone)
+    src.write_text(HOST_WRAPPER % SOLVER)  # (the header is the host + device arithmetic alone and needs nothing else)
     subprocess.run([cxx, "-O1", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", str(src), "-o", str(lib_path)], check=True)
     host = ctypes.CDLL(str(lib_path))
     ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)

@@ -146,8 +146,8 @@ def test_cov_backward_writes_only_the_outputs_it_is_given(n):
 # mark_visible
 # --------------------------------------------------------------------------------------------------------------------------
 def near_threshold_from_source():
-    """kNear of pf3plat_amd/csrc/gsr_hip.hip: `present = !(camera depth <= kNear)`, the forward's cull (in_frustum) with the same constant."""
-    src = open(os.path.join(os.path.dirname(_lib.SRC), "gsr_hip.hip")).read()
+    """kNear of pf3plat_amd/csrc/gsr_common.h: `present = !(camera depth <= kNear)`, the forward's cull (in_frustum) with the same constant."""
+    src = open(os.path.join(os.path.dirname(_lib.SRC), "gsr_common.h")).read()
     (value,) = re.findall(r"constexpr float kNear = ([0-9.]+)f;", src)
     return np.float32(value)
 

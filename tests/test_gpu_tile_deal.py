@@ -1,4 +1,4 @@
-"""`-m gpu`: the forward tile launch's deal (pf3plat_amd/csrc/gsr_hip.hip: build_tile_order, fwd_tile_of).  One view whose tiles fill
+"""`-m gpu`: the forward tile launch's deal (pf3plat_amd/csrc/gsr_common.h: build_tile_order, fwd_tile_of).  One view whose tiles fill
 no more than the first resident round takes its tile -> workgroup order from a table (`tile_order` in the `bin` workspace) that the
 binning launch builds from the walked counts (`tile_total`) the plan's PREVIOUS forward left: an XCD's tiles dealt to its compute
 units heaviest first, every other round of 32 mirrored - k_blend_bwd's order.  Whatever the counts hold, placement must be a

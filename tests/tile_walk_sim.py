@@ -4,7 +4,7 @@ uses the oracle's projected records).  What it answers, without a GPU:
     `tile_total`; batches of 32) - the reason the tile launch ranks only a prefix of each list (DESIGN 3.1, round 4);
   * whether anything the binning launch could accumulate per tile WITHOUT the depth order predicts that walk (it does
     not), and what a load-informed tile -> CU deal would gain with each predictor.
-The 8x8 membership rule restated here is the library's (make_foot / subtile_hit in gsr_hip.hip): reference 16x16 rect, clipped to
+The 8x8 membership rule restated here is the library's (make_foot / subtile_hit in gsr_common.h): reference 16x16 rect, clipped to
 the ellipse {q <= 2 ln(255 o)} and to tiles whose pixel-centre box comes within that ellipse.
 usage: python -m tests.tile_walk_sim [seed=2] [n=300000]"""
 from __future__ import annotations

@@ -32,7 +32,7 @@ for _ in range(4):
     be.run_forward(plan, vb, *ins)
 torch.cuda.synchronize()
 lay = be.workspace_layout(plan["dims"])
-slots = 512 if V > 4 else 256  # (two plain binning workgroups per CU for images of up to 1496 tiles: choose_chunk in gsr_hip.hip)
+slots = 512 if V > 4 else 256  # (two plain binning workgroups per CU for images of up to 1496 tiles: choose_chunk in gsr_common.h)
 chunk = min(range(1600, 1023, -64), key=lambda c: ((V * ((n + c - 1) // c) + slots - 1) // slots) * (c + 400))
 rows = (n + chunk - 1) // chunk
 cap = int(plan["dims"].pair_capacity)

@@ -34,7 +34,7 @@ T = 1024
 
 
 def choose_chunk(n, v, slots=256):
-    """-> (chunk, False): the library's choose_chunk (csrc/gsr_hip.hip).  (The flag named round 6's set binning launch, measured and dropped.)"""
+    """-> (chunk, False): the library's choose_chunk (csrc/gsr_common.h).  (The flag named round 6's set binning launch, measured and dropped.)"""
     best, best_cost = 1600, None
     for c in range(1600, 511, -64):
         blocks = v * -(-n // c)
@@ -155,7 +155,7 @@ def main():
     g2 = slots_raw(8192 + VT, VT)
     us = lambda a: (a & 0xffffffff).double() * 0.01
     tile_of_bid = torch.tensor([xcd_remap(bb, VT) for bb in range(VT)])
-    if V == 1 and 256 < T <= 1024 and rows + 8 <= 256:  # the deal (gsr_hip.hip fwd_deal_active): the table the last call's tile launch took its tiles from
+    if V == 1 and 256 < T <= 1024 and rows + 8 <= 256:  # the deal (gsr_common.h fwd_deal_active): the table the last call's tile launch took its tiles from
         dealt = plan["bin"][lay["tile_order"]: lay["tile_order"] + VT * 4].view(torch.int32).cpu().long()
         moved = int((dealt != tile_of_bid).sum())
         tile_of_bid = dealt

@@ -1,5 +1,5 @@
 """Measurement aid (GPU box): consecutive single-view forwards of ONE scene through ONE plan while the camera moves a little
-between calls - what the tile launch's deal (gsr_hip.hip: build_tile_order) sees in real use, where its hint, the previous call's
+between calls - what the tile launch's deal (gsr_common.h: build_tile_order) sees in real use, where its hint, the previous call's
 walked counts, is close but not exact.  Printed beside the identical-frame loop (the benchmark's headline: the hint is exact) and
 beside a loop that alternates two far-apart cameras (every hint from another view).
 
