@@ -25,6 +25,7 @@
 #include <atomic>
 #include <chrono>
 #include <cmath>
+#include <cstring>
 #include <map>
 #include <mutex>
 #include <set>
@@ -122,19 +123,13 @@ void rc_check(int rc, const char* what, bool backward) {
   throw std::runtime_error(msg);
 }
 
-// The call shape (pf3plat_amd.rasterizer.RasterConfig, field for field)
+// The call shape (pf3plat_amd.rasterizer.RasterConfig, field for field: kCfgFields below is the one statement of names and order)
 struct Cfg {
   int num_views = 0, num_sets = 0, views_per_set = 0, num_gaussians = 0, height = 0, width = 0, sh_degree = 0, sh_coeffs = 0, max_sh_eval = 4;
   int has_extra = 0, flags = 0, scale_rot = 0;
   int alpha = 0;  // the accumulated-alpha image is wanted (GsrForwardOptions.out_alpha / GsrBackwardOptions.dL_dalpha_img); not part of the dims: it sizes nothing
-  auto tie() const { return std::tie(num_views, num_sets, views_per_set, num_gaussians, height, width, sh_degree, sh_coeffs, max_sh_eval, has_extra, flags, scale_rot, alpha); }
-  bool operator<(const Cfg& o) const { return tie() < o.tie(); }
   // the dims of the sizing helpers: without the GSR_FLAG_SH_IN_FRAME bits, which only the launches take (they size nothing)
-  GsrDims dims(int64_t capacity) const {
-    GsrDims d = launch_dims(capacity);
-    d.flags &= ~kShFrameBits;
-    return d;
-  }
+  GsrDims dims(int64_t capacity) const { GsrDims d = launch_dims(capacity); d.flags &= ~kShFrameBits; return d; }
   GsrDims launch_dims(int64_t capacity) const {
     GsrDims d;
     d.abi_version = GSR_ABI_VERSION; d.num_views = num_views; d.num_sets = num_sets; d.views_per_set = views_per_set;
@@ -145,27 +140,54 @@ struct Cfg {
   static constexpr int kShFrameBits = GSR_FLAG_SH_IN_FRAME | GSR_FLAG_SH_FRAME_E3NN;
   int extra_mode() const { return (flags >> 4) & 7; }
 };
-Cfg cfg_from(const std::vector<int64_t>& v) {
-  TORCH_CHECK(v.size() == 13, "cfg: 13 integers expected");
-  Cfg c;
-  c.num_views = (int)v[0]; c.num_sets = (int)v[1]; c.views_per_set = (int)v[2]; c.num_gaussians = (int)v[3]; c.height = (int)v[4];
-  c.width = (int)v[5]; c.sh_degree = (int)v[6]; c.sh_coeffs = (int)v[7]; c.max_sh_eval = (int)v[8]; c.has_extra = (int)v[9];
-  c.flags = (int)v[10]; c.scale_rot = (int)v[11]; c.alpha = v[12] != 0;
-  return c;
+// Cfg's fields, in the dataclass's order (exported as CFG_FIELDS): what crosses to and from Python by name, and what orders two call shapes
+struct CfgField { const char* name; int Cfg::*member; bool is_bool; };
+constexpr CfgField kCfgFields[] = {
+    {"num_views", &Cfg::num_views, false}, {"num_sets", &Cfg::num_sets, false}, {"views_per_set", &Cfg::views_per_set, false}, {"num_gaussians", &Cfg::num_gaussians, false},
+    {"height", &Cfg::height, false}, {"width", &Cfg::width, false}, {"sh_degree", &Cfg::sh_degree, false}, {"sh_coeffs", &Cfg::sh_coeffs, false},
+    {"max_sh_eval", &Cfg::max_sh_eval, false}, {"has_extra", &Cfg::has_extra, true}, {"flags", &Cfg::flags, false}, {"scale_rot", &Cfg::scale_rot, true}, {"alpha", &Cfg::alpha, true}};
+bool operator<(const Cfg& a, const Cfg& b) {
+  for (const CfgField& f : kCfgFields) if (a.*f.member != b.*f.member) return a.*f.member < b.*f.member;
+  return false;
 }
-std::vector<int64_t> dims_vec(const GsrDims& d) {
-  return {d.abi_version, d.num_views, d.num_sets, d.views_per_set, d.num_gaussians, d.height, d.width, d.sh_degree, d.sh_coeffs,
-          d.max_sh_eval, d.has_extra, d.flags, d.pair_capacity};
-}
-GsrDims dims_from(const std::vector<int64_t>& v) {
-  TORCH_CHECK(v.size() == 13, "dims: 13 integers expected");
-  GsrDims d;
-  d.abi_version = (int)v[0]; d.num_views = (int)v[1]; d.num_sets = (int)v[2]; d.views_per_set = (int)v[3]; d.num_gaussians = (int)v[4];
-  d.height = (int)v[5]; d.width = (int)v[6]; d.sh_degree = (int)v[7]; d.sh_coeffs = (int)v[8]; d.max_sh_eval = (int)v[9];
-  d.has_extra = (int)v[10]; d.flags = (int)v[11]; d.pair_capacity = v[12];
-  return d;
-}
-
+}  // namespace
+// How the two structs cross the binding: the call shape as any object with RasterConfig's attributes (-> a RasterConfig), the dims as any
+// buffer of sizeof(GsrDims) bytes, which the ctypes mirror pf3plat_amd._lib.GsrDims is (-> one of those).  Anything else is a TypeError.
+namespace pybind11::detail {
+template <> struct type_caster<Cfg> {
+  PYBIND11_TYPE_CASTER(Cfg, const_name("RasterConfig"));
+  bool load(handle src, bool) {
+    for (const CfgField& f : kCfgFields) {
+      if (!hasattr(src, f.name)) return false;
+      const object a = getattr(src, f.name);
+      make_caster<int> as_int;  // (refuses floats; a bool field takes a bool or an integer, as RasterConfig's callers write them)
+      if (f.is_bool ? !PyLong_Check(a.ptr()) : !as_int.load(a, true)) return false;
+      value.*f.member = f.is_bool ? PyObject_IsTrue(a.ptr()) : (int)as_int;
+    }
+    return true;
+  }
+  static handle cast(const Cfg& c, return_value_policy, handle) {
+    dict kw;
+    for (const CfgField& f : kCfgFields) kw[f.name] = f.is_bool ? object(bool_(c.*f.member != 0)) : object(int_(c.*f.member));
+    return module_::import("pf3plat_amd.rasterizer").attr("RasterConfig")(**kw).release();
+  }
+};
+template <> struct type_caster<GsrDims> {
+  PYBIND11_TYPE_CASTER(GsrDims, const_name("GsrDims"));
+  bool load(handle src, bool) {
+    Py_buffer view;
+    if (!PyObject_CheckBuffer(src.ptr()) || PyObject_GetBuffer(src.ptr(), &view, PyBUF_SIMPLE) != 0) { PyErr_Clear(); return false; }
+    const bool fits = view.len == (Py_ssize_t)sizeof(GsrDims);
+    if (fits) std::memcpy(&value, view.buf, sizeof(GsrDims));
+    PyBuffer_Release(&view);
+    return fits;
+  }
+  static handle cast(const GsrDims& d, return_value_policy, handle) {
+    return module_::import("pf3plat_amd._lib").attr("GsrDims").attr("from_buffer_copy")(bytes(reinterpret_cast<const char*>(&d), sizeof d)).release();
+  }
+};
+}  // namespace pybind11::detail
+namespace {
 // The per-group rotations of the scale / rotation form: (sets, F, 3, 3) fp32 contiguous, or undefined
 Tensor frames_arg(const Cfg& cfg, const Tensor& frames) {
   if (!frames.defined()) return frames;
@@ -663,33 +685,30 @@ class Backend : public std::enable_shared_from_this<Backend> {
 };
 
 // ---- autograd ---------------------------------------------------------------------------------------------------------------
-struct BackendHolder : torch::CustomClassHolder {
-  std::shared_ptr<Backend> be;
-};
-
 struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
+  // What the node keeps besides its saved tensors, under one capsule (any intrusive_ptr target, no class registration needed).  It lives with
+  // the node (freed with the graph), past a first backward: a second one (retain_graph=True, several autograd.grad calls) runs on the same workspaces.
+  struct State : torch::CustomClassHolder {
+    Cfg cfg;
+    Saved ws;  // the workspaces and the token of the forward
+    Tensor frames;  // (undefined: none)
+    std::shared_ptr<Backend> holder;  // (keeps the backend alive for as long as a graph can call back into it)
+    size_t viewbuf_edge = 0;  // (needs_input_grad counts the Tensor arguments that are there: the camera records' position among them)
+    int64_t camera_gradient = 1;
+    bool want_means2d = false, rows_fresh = false;  // rows_fresh: the accumulator rows were zero-filled by the forward, usable once
+  };
   // inputs: means, cov, opac, colors, extra (may be undefined), means2d (may be undefined: only its gradient is wanted), viewbuf
   // (optional inputs travel as std::optional: the engine records layout / device of every Tensor argument, an undefined one has none)
   static torch::autograd::variable_list forward(torch::autograd::AutogradContext* ctx, Tensor means, Tensor cov, Tensor opac, Tensor colors,
                                                 c10::optional<Tensor> extra_o, c10::optional<Tensor> means2d_o, Tensor viewbuf, c10::optional<Tensor> frames_o,
-                                                c10::intrusive_ptr<BackendHolder> holder, std::vector<int64_t> cfgv, int64_t camera_gradient) {
+                                                std::shared_ptr<Backend> holder, Cfg cfg, int64_t camera_gradient) {
     const Tensor extra = extra_o.has_value() ? *extra_o : Tensor(), means2d = means2d_o.has_value() ? *means2d_o : Tensor();
-    const Tensor frames = frames_o.has_value() ? *frames_o : Tensor();
-    // (needs_input_grad counts the Tensor arguments that are there: the camera records' position among them)
-    ctx->saved_data["viewbuf_edge"] = (int64_t)(4 + (extra.defined() ? 1 : 0) + (means2d.defined() ? 1 : 0));
-    const Cfg cfg = cfg_from(cfgv);
-    ForwardOut o = holder->be->forward(cfg, viewbuf, means, cov, opac, colors, extra, frames, -1, false);
-    ctx->saved_data["cfg"] = cfgv;
-    ctx->saved_data["dims"] = dims_vec(o.saved.dims);
-    ctx->saved_data["geom"] = o.saved.geom;
-    ctx->saved_data["bin"] = o.saved.bin;
-    ctx->saved_data["img"] = o.saved.img;
-    ctx->saved_data["token"] = o.saved.token;
-    ctx->saved_data["rows_fresh"] = (cfg.flags & GSR_FLAG_BACKWARD_FOLLOWS) != 0;  // accumulator rows zero-filled by the forward, usable once
-    ctx->saved_data["want_means2d"] = means2d.defined();
-    ctx->saved_data["camera_gradient"] = camera_gradient;
-    ctx->saved_data["frames"] = frames.defined() ? frames : Tensor();
-    ctx->saved_data["holder"] = c10::IValue::make_capsule(holder);  // (a capsule: any intrusive_ptr target, no class registration needed)
+    auto st = c10::make_intrusive<State>();
+    st->cfg = cfg; st->holder = holder; st->camera_gradient = camera_gradient; st->frames = frames_o.has_value() ? *frames_o : Tensor();
+    st->viewbuf_edge = 4 + (extra.defined() ? 1 : 0) + (means2d.defined() ? 1 : 0);
+    st->want_means2d = means2d.defined(); st->rows_fresh = (cfg.flags & GSR_FLAG_BACKWARD_FOLLOWS) != 0;
+    ForwardOut o = holder->forward(cfg, viewbuf, means, cov, opac, colors, extra, st->frames, -1, false);
+    st->ws = o.saved; ctx->saved_data["state"] = c10::IValue::make_capsule(st);
     ctx->save_for_backward({means, cov, opac, colors, extra.defined() ? extra : at::empty({0}, means.options()), viewbuf});
     Tensor extra_img = o.extra_img;
     ctx->mark_non_differentiable({o.radii});
@@ -709,30 +728,19 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
   static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx, torch::autograd::variable_list grads) {
     const auto saved = ctx->get_saved_variables();
     const Tensor &means = saved[0], &cov = saved[1], &opac = saved[2], &colors = saved[3], &viewbuf = saved[5];
-    const Cfg cfg = cfg_from(ctx->saved_data["cfg"].toIntVector());
+    const auto st = c10::static_intrusive_pointer_cast<State>(ctx->saved_data["state"].toCapsule());
+    const Cfg& cfg = st->cfg;
     Tensor extra = saved[4], g_color = grads[0], g_extra = grads[1];
     if (!cfg.has_extra) { extra = Tensor(); g_extra = Tensor(); }
     else if (cfg.extra_mode()) extra = Tensor();  // built-in mode: no extra array; its gradient is folded into d_means by the backward kernel
     if (!g_color.defined()) g_color = at::zeros({cfg.num_views, 3, cfg.height, cfg.width}, means.options().dtype(at::kFloat));
-    Saved ws;
-    ws.valid = true;
-    ws.dims = dims_from(ctx->saved_data["dims"].toIntVector());
-    ws.geom = ctx->saved_data["geom"].toTensor();
-    ws.bin = ctx->saved_data["bin"].toTensor();
-    ws.img = ctx->saved_data["img"].toTensor();
-    ws.token = ctx->saved_data["token"].toInt();
-    auto holder = c10::static_intrusive_pointer_cast<BackendHolder>(ctx->saved_data["holder"].toCapsule());
-    const bool cam = ctx->needs_input_grad((size_t)ctx->saved_data["viewbuf_edge"].toInt());  // cameras being learned (PF3plat's pose refinement): opt-in, SURVEY 8f-3
+    const bool cam = ctx->needs_input_grad(st->viewbuf_edge);  // cameras being learned (PF3plat's pose refinement): opt-in, SURVEY 8f-3
     // (GSR_FLAG_FOV_GRADIENT in the call's flags - saved.dims carry it into the backward's launch and the partials' size - implies
     // the full camera gradient: the depth term alone has no tan-fov columns)
-    const int want_views = cam ? ((ctx->saved_data["camera_gradient"].toInt() == 2 && !(cfg.flags & GSR_FLAG_FOV_GRADIENT)) ? 2 : 1) : 0;
-    const c10::IValue& fr = ctx->saved_data["frames"];
-    std::vector<Tensor> g = holder->be->backward(cfg, ws, viewbuf, means, cov, opac, colors, extra, g_color, g_extra, ctx->saved_data["want_means2d"].toBool(),
-                                                 ctx->saved_data["rows_fresh"].toBool(), fr.isTensor() ? fr.toTensor() : Tensor(), want_views,
-                                                 (cfg.alpha && grads.size() > 3) ? grads[3] : Tensor());
-    ctx->saved_data["rows_fresh"] = false;
-    // the workspaces stay with ctx (freed with the graph): a second backward (retain_graph=True, several autograd.grad calls over one
-    // render) runs on them again, as upstream's Function can
+    const int want_views = cam ? ((st->camera_gradient == 2 && !(cfg.flags & GSR_FLAG_FOV_GRADIENT)) ? 2 : 1) : 0;
+    std::vector<Tensor> g = st->holder->backward(cfg, st->ws, viewbuf, means, cov, opac, colors, extra, g_color, g_extra, st->want_means2d, st->rows_fresh,
+                                                 st->frames, want_views, (cfg.alpha && grads.size() > 3) ? grads[3] : Tensor());
+    st->rows_fresh = false;  // (the workspaces stay: a second backward runs on them again, as upstream's Function can)
     return {g[0], g[1], g[2], g[3], g[4], g[5], g[6], Tensor(), Tensor(), Tensor(), Tensor()};
   }
 };
@@ -778,24 +786,27 @@ std::tuple<Tensor, Tensor> setup_views_backward_ex(const Tensor& viewbuf, const 
 }
 
 struct SetupViewsFn : public torch::autograd::Function<SetupViewsFn> {
+  struct State : torch::CustomClassHolder { at::ScalarType ext_dtype, intr_dtype; };  // what the two gradients are handed back as
   static Tensor forward(torch::autograd::AutogradContext* ctx, Tensor extrinsics, Tensor intrinsics, Tensor near, Tensor far, Tensor background, bool scale_invariant) {
     Tensor vb = setup_views_raw(extrinsics, intrinsics, near, far, background, scale_invariant);
     ctx->save_for_backward({vb, intrinsics});
-    ctx->saved_data["dtype"] = (int64_t)extrinsics.scalar_type();
-    ctx->saved_data["intr_dtype"] = (int64_t)intrinsics.scalar_type();
+    auto st = c10::make_intrusive<State>();
+    st->ext_dtype = extrinsics.scalar_type(); st->intr_dtype = intrinsics.scalar_type();
+    ctx->saved_data["state"] = c10::IValue::make_capsule(st);
     return vb;
   }
   static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx, torch::autograd::variable_list grads) {
     const auto saved = ctx->get_saved_variables();
+    const auto st = c10::static_intrusive_pointer_cast<State>(ctx->saved_data["state"].toCapsule());
     const bool want_ext = ctx->needs_input_grad(0), want_intr = ctx->needs_input_grad(1);
     Tensor d_ext, d_intr;
     if (want_intr) {
       std::tie(d_ext, d_intr) = setup_views_backward_ex(saved[0], saved[1], grads[0], want_ext, true);
-      d_intr = d_intr.to((at::ScalarType)ctx->saved_data["intr_dtype"].toInt()).reshape(saved[1].sizes());
+      d_intr = d_intr.to(st->intr_dtype).reshape(saved[1].sizes());
     } else if (want_ext) {
       d_ext = setup_views_backward(saved[0], grads[0]);
     }
-    if (d_ext.defined()) d_ext = d_ext.to((at::ScalarType)ctx->saved_data["dtype"].toInt());
+    if (d_ext.defined()) d_ext = d_ext.to(st->ext_dtype);
     return {d_ext, d_intr, Tensor(), Tensor(), Tensor(), Tensor()};
   }
 };
@@ -907,6 +918,11 @@ bool rows_evenly_spaced(const Tensor& t, int64_t* row_stride) {
   return true;
 }
 struct AdaptFn : public torch::autograd::Function<AdaptFn> {
+  struct State : torch::CustomClassHolder {  // the forward's launch arguments, for the backward's launch, and the shapes two gradients go back in
+    int64_t g, p, row_stride, degree, height, width;
+    double lo, hi, eps;
+    std::vector<int64_t> raw_sizes, coord_sizes;  // (of raw and coordinates as they were given)
+  };
   static torch::autograd::variable_list forward(torch::autograd::AutogradContext* ctx, Tensor extrinsics, Tensor intrinsics, Tensor coordinates, Tensor depths,
                                                 Tensor raw_in, double lo, double hi, int64_t height, int64_t width, double eps, int64_t degree) {
     check_device({&extrinsics, &intrinsics, &coordinates, &depths, &raw_in});
@@ -933,18 +949,17 @@ struct AdaptFn : public torch::autograd::Function<AdaptFn> {
                                (int)height, (int)width, (float)eps, means.data_ptr<float>(), records.data_ptr<float>(), harmonics.data_ptr<float>(), stream_of(ext.device()));
     if (rc != 0) throw std::runtime_error("gsr_adapt failed with code " + std::to_string(rc));
     ctx->save_for_backward({ext, intr, coords, dep, raw});
-    ctx->saved_data["shape"] = std::vector<int64_t>{g, p, row_stride, degree, height, width};
-    ctx->saved_data["scalars"] = std::vector<double>{lo, hi, eps};
-    ctx->saved_data["raw_sizes"] = raw_in.sizes().vec();
-    ctx->saved_data["coord_sizes"] = coordinates.sizes().vec();
+    auto st = c10::make_intrusive<State>();
+    st->g = g; st->p = p; st->row_stride = row_stride; st->degree = degree; st->height = height; st->width = width; st->lo = lo; st->hi = hi; st->eps = eps;
+    st->raw_sizes = raw_in.sizes().vec(); st->coord_sizes = coordinates.sizes().vec();
+    ctx->saved_data["state"] = c10::IValue::make_capsule(st);
     return {means, records, harmonics};
   }
   static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx, torch::autograd::variable_list grads) {
     const auto saved = ctx->get_saved_variables();
     const Tensor &ext = saved[0], &intr = saved[1], &coords = saved[2], &dep = saved[3], &raw = saved[4];
-    const auto shape = ctx->saved_data["shape"].toIntVector();
-    const auto scal = ctx->saved_data["scalars"].toDoubleVector();
-    const int64_t g = shape[0], p = shape[1], stride = shape[2], degree = shape[3], m = (degree + 1) * (degree + 1);
+    const auto st = c10::static_intrusive_pointer_cast<State>(ctx->saved_data["state"].toCapsule());
+    const int64_t g = st->g, p = st->p, degree = st->degree, m = (degree + 1) * (degree + 1);
     check_device({&grads[0], &grads[1], &grads[2]});
     const Tensor d_means = f32c(grads[0]), d_rec = f32c(grads[1]), d_harm = f32c(grads[2]);
     Tensor d_raw = at::empty({g, p, 7 + 3 * m}, ext.options()), d_dep = at::empty({g, p}, ext.options()), d_coords = at::empty({g, p, 2}, ext.options());
@@ -954,13 +969,12 @@ struct AdaptFn : public torch::autograd::Function<AdaptFn> {
     const bool want_intr = ctx->needs_input_grad(1);
     Tensor d_intr = !want_intr ? Tensor() : g * p > 0 ? at::empty({g, 3, 3}, ext.options()) : at::zeros({g, 3, 3}, ext.options());
     Tensor partials = at::empty({(int64_t)g_abi.adapt_partials_bytes_ex((int)g, (int)p, want_intr ? 1 : 0)}, ext.options().dtype(at::kByte));
-    const int rc = g_abi.adapt_backward_ex((int)g, (int)p, (int)degree, fptr(ext), fptr(intr), fptr(coords), fptr(dep), fptr(raw), stride, (float)scal[0], (float)scal[1],
-                                        (int)shape[4], (int)shape[5], (float)scal[2], fptr(d_means), fptr(d_rec), fptr(d_harm), d_raw.data_ptr<float>(),
+    const int rc = g_abi.adapt_backward_ex((int)g, (int)p, (int)degree, fptr(ext), fptr(intr), fptr(coords), fptr(dep), fptr(raw), st->row_stride, (float)st->lo, (float)st->hi,
+                                        (int)st->height, (int)st->width, (float)st->eps, fptr(d_means), fptr(d_rec), fptr(d_harm), d_raw.data_ptr<float>(),
                                         d_dep.data_ptr<float>(), d_coords.data_ptr<float>(), d_ext.data_ptr<float>(), fptr_mut(d_intr),
                                         reinterpret_cast<float*>(partials.data_ptr<uint8_t>()), stream_of(ext.device()));
     if (rc != 0) throw std::runtime_error("gsr_adapt_backward_ex failed with code " + std::to_string(rc));
-    return {d_ext, d_intr, d_coords.reshape(ctx->saved_data["coord_sizes"].toIntVector()), d_dep, d_raw.reshape(ctx->saved_data["raw_sizes"].toIntVector()),
-            Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+    return {d_ext, d_intr, d_coords.reshape(st->coord_sizes), d_dep, d_raw.reshape(st->raw_sizes), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
   }
 };
 std::tuple<Tensor, Tensor, Tensor> adapt(const Tensor& extrinsics, const Tensor& intrinsics, const Tensor& coordinates, const Tensor& depths, const Tensor& raw, double lo,
@@ -971,9 +985,8 @@ std::tuple<Tensor, Tensor, Tensor> adapt(const Tensor& extrinsics, const Tensor&
 
 // ---- what Python calls ------------------------------------------------------------------------------------------------------
 struct PyBackend {
-  c10::intrusive_ptr<BackendHolder> holder;
-  PyBackend() : holder(c10::make_intrusive<BackendHolder>()) { holder->be = std::make_shared<Backend>(); }
-  Backend& be() { return *holder->be; }
+  std::shared_ptr<Backend> holder = std::make_shared<Backend>();
+  Backend& be() { return *holder; }
 };
 
 pybind11::dict status_dict(const Status& st) {
@@ -987,50 +1000,35 @@ pybind11::dict status_dict(const Status& st) {
 // (color, extra_img (undefined without the extra channel), radii): the differentiable operator - an autograd node only when the call
 // announces a backward.  Runs WITHOUT the GIL (the callers below release it around their work and take it back to build the result):
 // a blocking forward polls its status block for as long as its kernels run, and other Python threads - a data loader's pin-memory
-// thread - must not stand still meanwhile.
-struct RasterOut { Tensor color, extra_img, radii, alpha_img; };
-RasterOut rasterize_impl(PyBackend& pb, const Tensor& means, const Tensor& cov, const Tensor& opac, const Tensor& colors, const c10::optional<Tensor>& extra,
-                         const c10::optional<Tensor>& means2d, const Tensor& viewbuf, const std::vector<int64_t>& cfgv, const c10::optional<Tensor>& frames,
-                         int64_t camera_gradient) {
-  const Cfg cfg = cfg_from(cfgv);
+// thread - must not stand still meanwhile.  (`saved` of the result stays empty: the node keeps the workspaces.)
+ForwardOut rasterize_impl(PyBackend& pb, const Tensor& means, const Tensor& cov, const Tensor& opac, const Tensor& colors, const c10::optional<Tensor>& extra,
+                          const c10::optional<Tensor>& means2d, const Tensor& viewbuf, const Cfg& cfg, const c10::optional<Tensor>& frames, int64_t camera_gradient) {
   const Tensor ex = extra.has_value() ? *extra : Tensor(), fr = frames.has_value() ? *frames : Tensor();
-  RasterOut r;
-  if (!(cfg.flags & GSR_FLAG_BACKWARD_FOLLOWS)) {  // nothing here can be differentiated: no autograd node, no saved workspaces
-    ForwardOut o = pb.be().forward(cfg, viewbuf, means, cov, opac, colors, ex, fr, -1, true);
-    r.color = o.color; r.extra_img = o.extra_img; r.radii = o.radii; r.alpha_img = o.alpha_img;
-  } else {
-    auto out = RasterizeFn::apply(means, cov, opac, colors, extra, means2d, viewbuf, frames, pb.holder, cfgv, camera_gradient);
-    r.color = out[0]; r.radii = out[2];
-    if (cfg.has_extra) r.extra_img = out[1];
-    if (cfg.alpha) r.alpha_img = out[3];
-  }
-  return r;
+  // nothing here can be differentiated: no autograd node, no saved workspaces
+  if (!(cfg.flags & GSR_FLAG_BACKWARD_FOLLOWS)) return pb.be().forward(cfg, viewbuf, means, cov, opac, colors, ex, fr, -1, true);
+  auto out = RasterizeFn::apply(means, cov, opac, colors, extra, means2d, viewbuf, frames, pb.holder, cfg, camera_gradient);
+  return {out[0], cfg.has_extra ? out[1] : Tensor(), out[2], {}, cfg.alpha ? out[3] : Tensor()};
 }
 pybind11::object or_none(const Tensor& t) { return t.defined() ? pybind11::cast(t) : pybind11::none(); }
-pybind11::tuple raster_tuple(const RasterOut& r) {
+pybind11::tuple raster_tuple(const ForwardOut& r) {
   if (r.alpha_img.defined()) return pybind11::make_tuple(r.color, or_none(r.extra_img), r.radii, r.alpha_img);  // (only a call that asked for alpha gets four)
   return pybind11::make_tuple(r.color, or_none(r.extra_img), r.radii);
 }
 pybind11::tuple rasterize(PyBackend& pb, const Tensor& means, const Tensor& cov, const Tensor& opac, const Tensor& colors, const c10::optional<Tensor>& extra,
-                          const c10::optional<Tensor>& means2d, const Tensor& viewbuf, const std::vector<int64_t>& cfgv, const c10::optional<Tensor>& frames,
-                          int64_t camera_gradient) {
-  RasterOut r;
-  {
-    pybind11::gil_scoped_release nogil;
-    r = rasterize_impl(pb, means, cov, opac, colors, extra, means2d, viewbuf, cfgv, frames, camera_gradient);
-  }
+                          const c10::optional<Tensor>& means2d, const Tensor& viewbuf, const Cfg& cfg, const c10::optional<Tensor>& frames, int64_t camera_gradient) {
+  const ForwardOut r = [&] { pybind11::gil_scoped_release nogil; return rasterize_impl(pb, means, cov, opac, colors, extra, means2d, viewbuf, cfg, frames, camera_gradient); }();
   return raster_tuple(r);
 }
 
 // The call shape of `rasterize_views`, stated ONCE: argument checks (message for message what the Python surface documents), dtype /
-// contiguity normalisation, the thirteen integers of the call shape and its flags (GSR_FLAG_BACKWARD_FOLLOWS when something can be
-// differentiated).  Touches no device: `rasterize_views` below runs it in front of the operator, and `pf3plat_amd.rasterizer` runs the
-// SAME function (bound as `prepare_call`) in front of any other backend object - the tests slide the CPU oracle under the host wrappers
-// that way - so the two paths cannot drift apart.
+// contiguity normalisation, the call shape and its flags (GSR_FLAG_BACKWARD_FOLLOWS when something can be differentiated).  Touches no
+// device: `rasterize_views` below runs it in front of the operator, and `pf3plat_amd.rasterizer` runs the SAME function (bound as
+// `prepare_call`) in front of any other backend object - the tests slide the CPU oracle under the host wrappers that way - so the two
+// paths cannot drift apart.
 struct Prepared {
   Tensor means, cov, opac, colors, viewbuf;
   c10::optional<Tensor> extra, frames;
-  std::vector<int64_t> cfgv;
+  Cfg cfg;  // (alpha stays off: the caller's to set)
 };
 Prepared prepare_call(const Tensor& means_in, const Tensor& cov_in, const Tensor& opac_in, const Tensor& colors_in, const Tensor& viewbuf_in, int64_t h, int64_t w,
                       int64_t sh_degree, bool use_sh, int64_t views_per_set, const c10::optional<Tensor>& extra_in, const c10::optional<Tensor>& means2d,
@@ -1040,8 +1038,7 @@ Prepared prepare_call(const Tensor& means_in, const Tensor& cov_in, const Tensor
   const int64_t s = means_in.size(0), n = means_in.size(1), v = viewbuf_in.size(0);
   if (v != s * views_per_set) throw pybind11::value_error(std::to_string(v) + " views != " + std::to_string(s) + " sets x " + std::to_string(views_per_set) + " views per set");
   p.means = f32c(means_in); p.cov = f32c(cov_in); p.opac = f32c(opac_in); p.colors = f32c(colors_in);
-  const Tensor& cov = p.cov;
-  const Tensor& colors = p.colors;
+  const Tensor &cov = p.cov, &colors = p.colors;
   if (extra_in.has_value() && extra_in->defined()) p.extra = f32c(*extra_in);
   if (use_sh && colors.dim() != 4) throw pybind11::value_error("shs must be (sets, N, M, 3) or (sets, N, 3, M)");
   const auto shape_str = [](const Tensor& t) { std::ostringstream o; o << t.sizes(); return o.str(); };
@@ -1073,7 +1070,9 @@ Prepared prepare_call(const Tensor& means_in, const Tensor& cov_in, const Tensor
     if (!use_sh) throw pybind11::value_error("sh_frame needs use_sh=True (harmonics)");
     flags |= GSR_FLAG_SH_IN_FRAME | (sh_frame == 2 ? GSR_FLAG_SH_FRAME_E3NN : 0);
   }
-  p.cfgv = {v, s, views_per_set, n, h, w, sh_degree, m, max_sh_eval, has_extra ? 1 : 0, flags, scale_rot ? 1 : 0, 0 /* Cfg::alpha: the caller's to set */};
+  Cfg& c = p.cfg;
+  c.num_views = (int)v; c.num_sets = (int)s; c.views_per_set = (int)views_per_set; c.num_gaussians = (int)n; c.height = (int)h; c.width = (int)w;
+  c.sh_degree = (int)sh_degree; c.sh_coeffs = (int)m; c.max_sh_eval = (int)max_sh_eval; c.has_extra = has_extra; c.flags = (int)flags; c.scale_rot = scale_rot;
   p.viewbuf = f32c(viewbuf_in);
   return p;
 }
@@ -1084,15 +1083,15 @@ pybind11::tuple rasterize_views(PyBackend& pb, const Tensor& means_in, const Ten
                                 const c10::optional<Tensor>& means2d, int64_t max_sh_eval, bool sh_planar, bool cov_3x3, int64_t extra_mode, bool debug,
                                 bool prefiltered, int64_t deterministic, bool scale_rot, const c10::optional<Tensor>& frames_in, int64_t camera_gradient,
                                 int64_t sh_frame, bool return_alpha, bool intrinsics_gradients) {
-  RasterOut result;
+  ForwardOut result;
   {
   pybind11::gil_scoped_release nogil;
   Prepared p = prepare_call(means_in, cov_in, opac_in, colors_in, viewbuf_in, h, w, sh_degree, use_sh, views_per_set, extra_in, means2d, max_sh_eval, sh_planar,
                                   cov_3x3, extra_mode, debug, prefiltered, deterministic, scale_rot, frames_in, camera_gradient, sh_frame);
-  p.cfgv[12] = return_alpha;  // (Cfg::alpha)
+  p.cfg.alpha = return_alpha;
   // the tan-fov columns of the camera gradient (GSR_FLAG_FOV_GRADIENT): only where a backward will ask for the camera gradient at all
-  if (intrinsics_gradients && (p.cfgv[10] & GSR_FLAG_BACKWARD_FOLLOWS) && viewbuf_in.requires_grad()) p.cfgv[10] |= GSR_FLAG_FOV_GRADIENT;
-  result = rasterize_impl(pb, p.means, p.cov, p.opac, p.colors, p.extra, means2d, p.viewbuf, p.cfgv, p.frames, camera_gradient);
+  if (intrinsics_gradients && (p.cfg.flags & GSR_FLAG_BACKWARD_FOLLOWS) && viewbuf_in.requires_grad()) p.cfg.flags |= GSR_FLAG_FOV_GRADIENT;
+  result = rasterize_impl(pb, p.means, p.cov, p.opac, p.colors, p.extra, means2d, p.viewbuf, p.cfg, p.frames, camera_gradient);
   }
   return raster_tuple(result);
 }
@@ -1115,23 +1114,24 @@ pybind11::tuple rasterize_one_view(PyBackend& pb, int64_t height, int64_t width,
   const Tensor& col_in = use_sh ? *shs : *colors_precomp;
   if (use_sh && col_in.dim() != 3) throw pybind11::value_error("shs must be (N, M, 3)");
   TORCH_CHECK(cov3d.numel() == 6 * n && opacities.numel() == n, "cov3D_precomp must hold (N, 6) values and opacities N");
-  int64_t flags = (debug ? GSR_FLAG_DEBUG : 0) | (prefiltered ? GSR_FLAG_PREFILTERED : 0) | (at::globalContext().deterministicAlgorithms() ? GSR_FLAG_DETERMINISTIC : 0);
+  Cfg cfg;  // V = 1, S = 1; (N, M, 3) harmonics or (N, 3) colours
+  cfg.num_views = cfg.num_sets = cfg.views_per_set = 1; cfg.num_gaussians = (int)n; cfg.height = (int)height; cfg.width = (int)width;
+  cfg.sh_degree = (int)sh_degree; cfg.sh_coeffs = use_sh ? (int)col_in.size(1) : 0;
+  cfg.flags = (debug ? GSR_FLAG_DEBUG : 0) | (prefiltered ? GSR_FLAG_PREFILTERED : 0) | (at::globalContext().deterministicAlgorithms() ? GSR_FLAG_DETERMINISTIC : 0);
   const bool grad = at::GradMode::is_enabled() && (means3d.requires_grad() || cov3d.requires_grad() || opacities.requires_grad() || col_in.requires_grad() ||
                                                    (means2d.has_value() && means2d->defined() && means2d->requires_grad()));
   if (!grad) {
     // nothing can be differentiated (the reference's inference loop): the arrays go to the library as they are - the call shape says
     // V = 1, S = 1 - and the image / radii are allocated in the shapes the operator returns: no view op on either side of the call
-    const std::vector<int64_t> cfgv{1, 1, 1, n, height, width, sh_degree, use_sh ? col_in.size(1) : 0, 4, 0, flags, 0, 0};
-    ForwardOut o = pb.be().forward(cfg_from(cfgv), viewbuf, f32c(means3d), f32c(cov3d), f32c(opacities), f32c(col_in), Tensor(), Tensor(), -1, true, true);
+    ForwardOut o = pb.be().forward(cfg, viewbuf, f32c(means3d), f32c(cov3d), f32c(opacities), f32c(col_in), Tensor(), Tensor(), -1, true, true);
     out_color = o.color; out_radii = o.radii;
   } else {
-  flags |= GSR_FLAG_BACKWARD_FOLLOWS;  // the forward zero-fills the backward's accumulator rows on its way
+  cfg.flags |= GSR_FLAG_BACKWARD_FOLLOWS;  // the forward zero-fills the backward's accumulator rows on its way
   const Tensor means = f32c(means3d.unsqueeze(0)), cov = f32c(cov3d.reshape({n, 6}).unsqueeze(0)), opac = f32c(opacities.reshape({n}).unsqueeze(0));
   const Tensor colors = f32c(col_in.unsqueeze(0));
   c10::optional<Tensor> m2;
   if (means2d.has_value() && means2d->defined()) m2 = means2d->unsqueeze(0);
-  const std::vector<int64_t> cfgv{1, 1, 1, n, height, width, sh_degree, use_sh ? colors.size(2) : 0, 4, 0, flags, 0, 0};
-  RasterOut r = rasterize_impl(pb, means, cov, opac, colors, c10::nullopt, m2, viewbuf, cfgv, c10::nullopt, 1);
+  ForwardOut r = rasterize_impl(pb, means, cov, opac, colors, c10::nullopt, m2, viewbuf, cfg, c10::nullopt, 1);
   out_color = r.color.select(0, 0); out_radii = r.radii.select(0, 0);
   }
   }
@@ -1143,6 +1143,11 @@ pybind11::tuple rasterize_one_view(PyBackend& pb, int64_t height, int64_t width,
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "torch-facing binding of libgsr_hip.so (include/gsr.h): compiled autograd function, status policy, camera set-up";
   m.def("init", &init, "dlopen the raster library and resolve the C ABI");
+  pybind11::list fields;
+  for (const CfgField& f : kCfgFields) fields.append(f.name);
+  m.attr("CFG_FIELDS") = pybind11::tuple(fields);  // RasterConfig's fields, in order, as this file states them
+  m.def("launch_dims", [](const Cfg& cfg, int64_t capacity) { return cfg.launch_dims(capacity); }, "the GsrDims a launch of this call shape takes");
+  m.def("call_shape", [](const Cfg& cfg) { return cfg; }, "the RasterConfig of any object with its fields (through Cfg and back)");
   pybind11::class_<PyBackend>(m, "Backend")
       .def(pybind11::init<>())
       .def_property("sync_policy", [](PyBackend& b) { return b.be().sync_policy == Backend::SyncPolicy::lazy ? "lazy" : "sync"; },
@@ -1169,9 +1174,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def_property_readonly("last_status", [](PyBackend& b) -> pybind11::object { return b.be().has_status() ? pybind11::object(status_dict(b.be().last_status())) : pybind11::none(); })
       .def_property_readonly("workspace_cache_size", [](PyBackend& b) { return b.be().workspace_cache_size(); })
       .def("set_capacity_hint", [](PyBackend& b, const ShapeKey& k, int64_t v) { b.be().set_capacity_hint(k, v); })
-      .def("capacity_for", [](PyBackend& b, const std::vector<int64_t>& cfgv, int64_t num_pairs, int max_list, double headroom) {
+      .def("capacity_for", [](PyBackend& b, const Cfg& cfg, int64_t num_pairs, int max_list, double headroom) {
              Status st; st.num_pairs = num_pairs; st.max_list = max_list;
-             return b.be().capacity_for(cfg_from(cfgv), st, headroom);
+             return b.be().capacity_for(cfg, st, headroom);
            }, pybind11::arg("cfg"), pybind11::arg("num_pairs"), pybind11::arg("max_list"), pybind11::arg("headroom") = 1.25)
       .def("read_status", [](PyBackend& b, const Tensor& bin) {
              Status st;
@@ -1181,41 +1186,38 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              }
              return status_dict(st);
            })
-      .def("make_plan", [](PyBackend& b, const std::vector<int64_t>& cfgv, const at::Device& device, int64_t capacity) {
-             // the plan API's outputs and workspaces: (dims (13 ints), color, extra_img | None, radii, geom, bin, img, backward-scratch bytes,
-             // alpha_img | None)
-             const Cfg cfg = cfg_from(cfgv);
+      .def("make_plan", [](PyBackend& b, const Cfg& cfg, const at::Device& device, int64_t capacity) {
+             // the plan API's outputs and workspaces: (dims, color, extra_img | None, radii, geom, bin, img, backward-scratch bytes, alpha_img | None)
              const Plan p = b.be().make_plan(cfg, device, capacity, false);
-             return pybind11::make_tuple(dims_vec(p.dims), p.color, or_none(p.extra_img), p.radii, p.geom, p.bin, p.img, b.be().sized(cfg, capacity).scratch,
+             return pybind11::make_tuple(p.dims, p.color, or_none(p.extra_img), p.radii, p.geom, p.bin, p.img, b.be().sized(cfg, capacity).scratch,
                                          or_none(p.alpha_img));
            })
       .def("check_pending", [](PyBackend& b, bool wait, int64_t only_token) { pybind11::gil_scoped_release nogil; b.be().check_pending(wait, only_token); },
            pybind11::arg("wait") = false,
            pybind11::arg("only_token") = -1)
       .def("release_workspaces", [](PyBackend& b) { pybind11::gil_scoped_release nogil; b.be().release_workspaces(); })
-      .def("forward", [](PyBackend& b, const std::vector<int64_t>& cfgv, const Tensor& viewbuf, const Tensor& means, const Tensor& cov, const Tensor& opac,
+      .def("forward", [](PyBackend& b, const Cfg& cfg, const Tensor& viewbuf, const Tensor& means, const Tensor& cov, const Tensor& opac,
                          const Tensor& colors, const c10::optional<Tensor>& extra, const c10::optional<Tensor>& frames, int64_t capacity, bool reuse_workspaces) {
              ForwardOut o;
              {
                pybind11::gil_scoped_release nogil;
-               o = b.be().forward(cfg_from(cfgv), viewbuf, means, cov, opac, colors, extra.has_value() ? *extra : Tensor(), frames.has_value() ? *frames : Tensor(),
+               o = b.be().forward(cfg, viewbuf, means, cov, opac, colors, extra.has_value() ? *extra : Tensor(), frames.has_value() ? *frames : Tensor(),
                                   capacity, reuse_workspaces);
              }
              pybind11::object saved = pybind11::none();
-             if (o.saved.valid) saved = pybind11::make_tuple(dims_vec(o.saved.dims), o.saved.geom, o.saved.bin, o.saved.img, o.saved.token);
+             if (o.saved.valid) saved = pybind11::make_tuple(o.saved.dims, o.saved.geom, o.saved.bin, o.saved.img, o.saved.token);
              return pybind11::make_tuple(o.color, or_none(o.extra_img), o.radii, saved, or_none(o.alpha_img));
            }, pybind11::arg("cfg"), pybind11::arg("viewbuf"), pybind11::arg("means"), pybind11::arg("cov"), pybind11::arg("opac"), pybind11::arg("colors"),
            pybind11::arg("extra"), pybind11::arg("frames"), pybind11::arg("capacity") = -1, pybind11::arg("reuse_workspaces") = false)
-      .def("backward", [](PyBackend& b, const std::vector<int64_t>& cfgv, const std::vector<int64_t>& dimsv, const Tensor& geom, const Tensor& bin, const Tensor& img,
+      .def("backward", [](PyBackend& b, const Cfg& cfg, const GsrDims& dims, const Tensor& geom, const Tensor& bin, const Tensor& img,
                           int64_t token, const Tensor& viewbuf, const Tensor& means, const Tensor& cov, const Tensor& opac, const Tensor& colors,
                           const c10::optional<Tensor>& extra, const Tensor& g_color, const c10::optional<Tensor>& g_extra, bool want_means2d, bool rows_in_workspace,
                           const c10::optional<Tensor>& frames, int want_views, const c10::optional<Tensor>& g_alpha) {
-             Saved ws;
-             ws.valid = true; ws.dims = dims_from(dimsv); ws.geom = geom; ws.bin = bin; ws.img = img; ws.token = token;
+             const Saved ws{true, dims, geom, bin, img, token};
              std::vector<Tensor> g;
              {
                pybind11::gil_scoped_release nogil;
-               g = b.be().backward(cfg_from(cfgv), ws, viewbuf, means, cov, opac, colors, extra.has_value() ? *extra : Tensor(), g_color,
+               g = b.be().backward(cfg, ws, viewbuf, means, cov, opac, colors, extra.has_value() ? *extra : Tensor(), g_color,
                                    g_extra.has_value() ? *g_extra : Tensor(), want_means2d, rows_in_workspace, frames.has_value() ? *frames : Tensor(), want_views,
                                    g_alpha.has_value() ? *g_alpha : Tensor());
              }
@@ -1235,9 +1237,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                            const c10::optional<Tensor>& frames, int64_t camera_gradient, int64_t sh_frame) {
     const Prepared p = prepare_call(means, cov, opac, colors, viewbuf, h, w, sh_degree, use_sh, views_per_set, extra, means2d, max_sh_eval, sh_planar, cov_3x3,
                                     extra_mode, debug, prefiltered, deterministic, scale_rot, frames, camera_gradient, sh_frame);
-    pybind11::object e = p.extra.has_value() ? pybind11::cast(*p.extra) : pybind11::none();
-    pybind11::object f = p.frames.has_value() ? pybind11::cast(*p.frames) : pybind11::none();
-    return pybind11::make_tuple(p.cfgv, p.means, p.cov, p.opac, p.colors, e, f, p.viewbuf);
+    return pybind11::make_tuple(p.cfg, p.means, p.cov, p.opac, p.colors, p.extra, p.frames, p.viewbuf);  // (an optional without a value: None)
   }, "the call shape of rasterize_views (checks, normalisation, flags) without the operator: what any backend object runs behind");
   m.def("rasterize_one_view", &rasterize_one_view);
   m.def("views_from_cameras", &views_from_cameras);
@@ -1248,13 +1248,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     return pybind11::make_tuple(or_none(std::get<0>(r)), or_none(std::get<1>(r)));
   });
   m.def("setup_views_orthographic", &setup_views_orthographic);
-  m.def("mark_visible", [](const std::vector<int64_t>& cfgv, const Tensor& viewbuf, const Tensor& means) { return mark_visible(cfg_from(cfgv), viewbuf, means); });
+  m.def("mark_visible", &mark_visible);
   m.def("adapt", &adapt, "Gaussian adapter, one launch each way: (means (G, P, 3), scale + quaternion records (G, P, 7), masked harmonics (G, P, 3, M))");
   m.def("cov_from_scale_rot", &cov_from_scale_rot);
   m.def("cov_from_scale_rot_backward", &cov_from_scale_rot_backward);
-  m.def("frames_arg", [](const std::vector<int64_t>& cfgv, const c10::optional<Tensor>& frames) {
+  m.def("frames_arg", [](const Cfg& cfg, const c10::optional<Tensor>& frames) {
     // -> (frames as the launches take them | None, F): the frames check of the ctypes launches of the plan API
-    const Tensor fr = frames_arg(cfg_from(cfgv), frames.has_value() ? *frames : Tensor());
+    const Tensor fr = frames_arg(cfg, frames.has_value() ? *frames : Tensor());
     return fr.defined() ? pybind11::make_tuple(fr, fr.size(1)) : pybind11::make_tuple(pybind11::none(), 0);
   });
   m.def("pack_view", [](const Tensor& vm, const Tensor& pm, const Tensor& cp, const Tensor& bg, double tx, double ty, const c10::optional<Tensor>& txt,

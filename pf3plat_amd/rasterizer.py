@@ -13,6 +13,7 @@ There is no CPU path here: tensors must live on a ROCm device and the HIP librar
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 from dataclasses import dataclass
 from typing import NamedTuple, Optional
 
@@ -191,9 +192,7 @@ class HipBackend:
 
     @staticmethod
     def _dims(cfg: RasterConfig, capacity: int) -> _lib.GsrDims:
-        return _lib.GsrDims(_lib.GSR_ABI_VERSION, cfg.num_views, cfg.num_sets, cfg.views_per_set, cfg.num_gaussians,
-                            cfg.height, cfg.width, cfg.sh_degree, cfg.sh_coeffs, cfg.max_sh_eval,
-                            int(cfg.has_extra), int(cfg.flags), int(capacity))
+        return _lib.load_torch_ext().launch_dims(cfg, int(capacity))  # (csrc/gsr_torch.cpp::Cfg::launch_dims: the one statement)
 
     def workspace_sizes(self, dims: _lib.GsrDims):
         g, b, i = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
@@ -245,7 +244,7 @@ class HipBackend:
     def capacity_for(self, cfg: RasterConfig, status: dict, headroom: float = 1.25) -> int:
         """pair_capacity that lets a call of this shape succeed, from the status block of an earlier call (gsr_capacity_for:
         every (view, tile) owns capacity / (views x tiles) entries of the index list, so the longest list decides) + headroom."""
-        return int(self._c.capacity_for(_cfg_vec(cfg), int(status["num_pairs"]), int(status["max_list"]), float(headroom)))
+        return int(self._c.capacity_for(cfg, int(status["num_pairs"]), int(status["max_list"]), float(headroom)))
 
     def release_workspaces(self):
         """Drop the cached workspaces of the no-autograd path (up to 8 sets of geom / bin / img stay alive otherwise), the size
@@ -258,8 +257,8 @@ class HipBackend:
         backward=True adds the gradient outputs and the backward's scratch."""
         v, n, s = cfg.num_views, cfg.num_gaussians, cfg.num_sets
         f32, u8 = torch.float32, torch.uint8
-        dims, color, extra_img, radii, geom, binb, img, scratch_bytes, alpha_img = self._c.make_plan(_cfg_vec(cfg), torch.device(device), int(capacity))
-        plan = dict(cfg=cfg, dims=_lib.GsrDims(*dims), device=device, color=color, extra_img=extra_img, radii=radii, geom=geom, bin=binb, img=img,
+        dims, color, extra_img, radii, geom, binb, img, scratch_bytes, alpha_img = self._c.make_plan(cfg, torch.device(device), int(capacity))
+        plan = dict(cfg=cfg, dims=dims, device=device, color=color, extra_img=extra_img, radii=radii, geom=geom, bin=binb, img=img,
                     alpha_img=alpha_img)  # (cfg.alpha: the accumulated alpha image, written by run_forward; None otherwise)
         if backward:
             if colors_shape is None:
@@ -292,7 +291,7 @@ class HipBackend:
         if color.shape != plan["color"].shape or color.dtype != torch.float32 or not color.is_contiguous():
             raise ValueError("out_color must be a contiguous fp32 tensor of the plan's image shape")
         cfg = plan["cfg"]
-        fr, nf = self._ext.frames_arg(_cfg_vec(cfg), frames) if cfg.scale_rot else (None, 0)
+        fr, nf = self._ext.frames_arg(cfg, frames) if cfg.scale_rot else (None, 0)
         ms = (ctypes.c_float * len(_lib.FWD_STAGES))() if profile else None
         # (nothing asked for: NULL options, the plain call)
         opt = None
@@ -343,7 +342,7 @@ class HipBackend:
         cfg.flags carry FLAG_FOV_GRADIENT also gets dL/dtanfovx, dL/dtanfovy in floats 35, 36 of the full camera gradient."""
         cfg = plan["cfg"]
         stream = _stream_ptr(plan["device"])
-        fr, nf = self._ext.frames_arg(_cfg_vec(cfg), frames) if cfg.scale_rot else (None, 0)
+        fr, nf = self._ext.frames_arg(cfg, frames) if cfg.scale_rot else (None, 0)
         ms = (ctypes.c_float * len(_lib.BWD_STAGES))() if profile else None
         partials = None
         if d_views is not None:
@@ -396,10 +395,8 @@ class HipBackend:
                   and verify it at the next call, at `check_pending()`, and - for a call that is differentiated - at the
                   end of its backward.  A workspace that turns out too small poisons that call's image with NaN
                   (k_tile_fwd) and raises at verification - it cannot pass silently."""
-        color, extra_img, radii, saved, alpha_img = self._c.forward(_cfg_vec(cfg), viewbuf, means, cov6, opac, colors, extra, frames,
+        color, extra_img, radii, saved, alpha_img = self._c.forward(cfg, viewbuf, means, cov6, opac, colors, extra, frames,
                                                                     -1 if capacity is None else int(capacity), bool(reuse_workspaces))
-        if saved is not None:
-            saved = (_lib.GsrDims(*saved[0]),) + tuple(saved[1:])
         return (color, extra_img, radii, saved, alpha_img) if cfg.alpha else (color, extra_img, radii, saved)
 
     def check_pending(self, wait: bool = False, only_token: Optional[int] = None):
@@ -419,8 +416,7 @@ class HipBackend:
         if saved is None:
             raise RuntimeError("this forward ran with reuse_workspaces=True (nothing was to be differentiated): it has no backward")
         dims, geom, binb, img, token = saved
-        dimsv = [getattr(dims, n) for n, _ in dims._fields_]
-        return self._c.backward(_cfg_vec(cfg), dimsv, geom, binb, img, int(token), viewbuf, means, cov6, opac, colors, extra, g_color,
+        return self._c.backward(cfg, dims, geom, binb, img, int(token), viewbuf, means, cov6, opac, colors, extra, g_color,
                                 g_extra_img if cfg.has_extra else None, bool(want_means2d), bool(rows_in_workspace), frames,
                                 2 if want_views == "depth" else (1 if want_views else 0), g_alpha_img)
 
@@ -452,13 +448,7 @@ class HipBackend:
         return torch.device("cuda", torch.cuda.current_device())
 
     def mark_visible(self, cfg: RasterConfig, viewbuf, means):
-        return self._ext.mark_visible(_cfg_vec(cfg), viewbuf, means).bool()
-
-
-def _cfg_vec(cfg: RasterConfig):
-    """RasterConfig as the thirteen integers the compiled backend takes."""
-    return [cfg.num_views, cfg.num_sets, cfg.views_per_set, cfg.num_gaussians, cfg.height, cfg.width, cfg.sh_degree, cfg.sh_coeffs,
-            cfg.max_sh_eval, int(cfg.has_extra), int(cfg.flags), int(cfg.scale_rot), int(cfg.alpha)]
+        return self._ext.mark_visible(cfg, viewbuf, means).bool()
 
 
 def cfg_repr(dims) -> str:
@@ -581,33 +571,28 @@ def rasterize_views(means: Tensor, cov6: Tensor, opacities: Tensor, colors: Tens
     if sh_frame not in SH_FRAMES:
         raise ValueError(f"sh_frame must be None, 'rasterizer' or 'e3nn', got {sh_frame!r}")
     sh_code = SH_FRAMES[sh_frame]
-    if isinstance(backend, HipBackend) and (not sh_code or getattr(backend, "sh_frame", False)):
-        # the product path, one crossing: checks, normalisation, call shape, flags and the compiled autograd function
-        # (csrc/gsr_torch.cpp::rasterize_views / RasterizeFn; a plain call when nothing can be differentiated)
-        if camera_gradient not in ("full", "depth"):
-            raise ValueError("camera_gradient must be 'full' or 'depth'")
-        return backend._ext.rasterize_views(
-            backend._c, means, cov6, opacities, colors, viewbuf, int(image_shape[0]), int(image_shape[1]), int(sh_degree), bool(use_sh),
-            int(views_per_set), extra, means2d, int(max_sh_eval), bool(sh_planar), bool(cov_3x3), EXTRA_MODES[extra_mode] if extra_mode is not None else 0,
-            bool(debug), bool(prefiltered), -1 if deterministic is None else int(bool(deterministic)), bool(scale_rot), frames,
-            2 if camera_gradient == "depth" else 1, sh_code, bool(return_alpha), bool(intrinsics_gradients))
-    if return_alpha:
+    product = isinstance(backend, HipBackend) and (not sh_code or getattr(backend, "sh_frame", False))
+    if not product and return_alpha:
         raise NotImplementedError("return_alpha needs the HIP backend")
-    if intrinsics_gradients:
+    if not product and intrinsics_gradients:
         raise NotImplementedError("intrinsics_gradients needs the HIP backend")
-    # any other backend object (tests slide the CPU oracle under the host wrappers): the SAME statement of the call shape - the
-    # compiled `prepare_call` (csrc/gsr_torch.cpp: checks, normalisation, flags; it touches no device) - then that backend's forward
     if camera_gradient not in ("full", "depth"):
         raise ValueError("camera_gradient must be 'full' or 'depth'")
-    cfgv, means, cov6, opacities, colors, extra, frames, viewbuf = _lib.load_torch_ext().prepare_call(
-        means, cov6, opacities, colors, viewbuf, int(image_shape[0]), int(image_shape[1]), int(sh_degree), bool(use_sh), int(views_per_set),
-        extra, means2d, int(max_sh_eval), bool(sh_planar), bool(cov_3x3), EXTRA_MODES[extra_mode] if extra_mode is not None else 0,
-        bool(debug), bool(prefiltered), -1 if deterministic is None else int(bool(deterministic)), bool(scale_rot), frames,
-        2 if camera_gradient == "depth" else 1, sh_code)
+    # the arguments of the compiled `rasterize_views` and `prepare_call` (csrc/gsr_torch.cpp), marshalled once for both
+    args = (means, cov6, opacities, colors, viewbuf, int(image_shape[0]), int(image_shape[1]), int(sh_degree), bool(use_sh), int(views_per_set),
+            extra, means2d, int(max_sh_eval), bool(sh_planar), bool(cov_3x3), EXTRA_MODES[extra_mode] if extra_mode is not None else 0,
+            bool(debug), bool(prefiltered), -1 if deterministic is None else int(bool(deterministic)), bool(scale_rot), frames,
+            2 if camera_gradient == "depth" else 1, sh_code)
+    if product:
+        # one crossing: checks, normalisation, call shape, flags and the compiled autograd function (rasterize_views / RasterizeFn; a
+        # plain call when nothing can be differentiated)
+        return backend._ext.rasterize_views(backend._c, *args, bool(return_alpha), bool(intrinsics_gradients))
+    # any other backend object (tests slide the CPU oracle under the host wrappers): the SAME statement of the call shape - the
+    # compiled `prepare_call` (checks, normalisation, flags; it touches no device) - then that backend's forward
+    cfg, means, cov6, opacities, colors, extra, frames, viewbuf = _lib.load_torch_ext().prepare_call(*args)
     if sh_code and not getattr(backend, "sh_frame", False):  # (checked above) the coefficients rotated in torch, rendered as usual
-        cfgv[10] &= ~(_lib.FLAG_SH_IN_FRAME | _lib.FLAG_SH_FRAME_E3NN)
+        cfg = dataclasses.replace(cfg, flags=cfg.flags & ~(_lib.FLAG_SH_IN_FRAME | _lib.FLAG_SH_FRAME_E3NN))
         colors = _rotate_in_frames(colors, frames, bool(sh_planar), sh_frame)
-    cfg = RasterConfig(*cfgv[:9], bool(cfgv[9]), int(cfgv[10]), bool(cfgv[11]))
     flags, has_extra = cfg.flags, cfg.has_extra
     if not (flags & _lib.FLAG_BACKWARD_FOLLOWS):  # nothing here can be differentiated: no autograd node, no saved workspaces
         color, extra_img, radii, _ = backend.forward(cfg, viewbuf, means, cov6, opacities, colors, extra, frames=frames,

@@ -1,6 +1,7 @@
 """The C-ABI library loads here (no GPU) and exports every symbol include/gsr.h declares; host-only entry points
 (version, workspace sizing, argument validation) behave; the product refuses to run without a ROCm device."""
 import ctypes
+import dataclasses
 import os
 import re
 
@@ -368,6 +369,70 @@ def test_compiled_torch_binding_loads_and_carries_the_policy_defaults():
     # the frames of the scale / rotation form are checked before any launch (F = 0 included)
     for frames in (torch.zeros(1, 3, 3, 3), torch.zeros(1, 0, 3, 3), torch.zeros(2, 1, 3, 3)):
         with pytest.raises(ValueError, match="frames must be"):
-            ext.frames_arg(rasterizer._cfg_vec(cfg), frames)
-    fr, nf = ext.frames_arg(rasterizer._cfg_vec(cfg), torch.eye(3).expand(1, 2, 3, 3))
-    assert nf == 2 and fr.is_contiguous() and ext.frames_arg(rasterizer._cfg_vec(cfg), None) == (None, 0)
+            ext.frames_arg(cfg, frames)
+    fr, nf = ext.frames_arg(cfg, torch.eye(3).expand(1, 2, 3, 3))
+    assert nf == 2 and fr.is_contiguous() and ext.frames_arg(cfg, None) == (None, 0)
+
+
+# ---- the call shape and the dims cross the compiled binding by field: RasterConfig <-> Cfg, _lib.GsrDims <-> GsrDims (no launch, no GPU)
+def test_binding_states_the_call_shapes_fields_in_the_dataclasss_order():
+    assert _lib.load_torch_ext().CFG_FIELDS == tuple(f.name for f in dataclasses.fields(rasterizer.RasterConfig))
+
+
+def test_launch_dims_carry_every_field_under_its_own_name():
+    """Twelve distinct values in what sizes a call - the eleven fields that reach the dims and the capacity (launch_dims validates
+    nothing): a transposed pair anywhere between the dataclass, the binding's table and Cfg::launch_dims shows as a field that is not
+    its namesake's."""
+    ext = _lib.load_torch_ext()
+    flags = _lib.FLAG_SH_IN_FRAME | _lib.FLAG_SH_PLANAR | 0x20  # (an SH-frame bit: launch dims keep it, sizing dims would not)
+    cfg = rasterizer.RasterConfig(num_views=11, num_sets=12, views_per_set=13, num_gaussians=14, height=15, width=16, sh_degree=17,
+                                  sh_coeffs=18, max_sh_eval=19, has_extra=True, flags=flags, scale_rot=True, alpha=True)
+    sizing = [f.name for f in dataclasses.fields(cfg) if f.name not in ("scale_rot", "alpha")]
+    cap = (1 << 40) + 21  # (past 32 bits: pair_capacity is the struct's one int64)
+    assert len({int(getattr(cfg, n)) for n in sizing} | {cap, _lib.GSR_ABI_VERSION}) == 13  # (has_extra is 1: distinct from the rest)
+    dims = ext.launch_dims(cfg, cap)
+    assert type(dims) is _lib.GsrDims
+    assert [n for n, _ in dims._fields_] == ["abi_version"] + sizing + ["pair_capacity"]
+    for name in sizing:
+        assert getattr(dims, name) == int(getattr(cfg, name)), name
+    assert dims.abi_version == _lib.GSR_ABI_VERSION == 5 and dims.pair_capacity == cap
+    assert bytes(rasterizer.HipBackend._dims(cfg, cap)) == bytes(dims)  # callable on the class, the same statement
+
+
+@pytest.mark.parametrize("alpha", [False, True])
+@pytest.mark.parametrize("has_extra, scale_rot", [(False, False), (True, False), (False, True), (True, True)])
+def test_call_shape_round_trips_through_the_binding(alpha, has_extra, scale_rot):
+    """Python -> Cfg (capacity_for's argument conversion) is covered by launch_dims above; Cfg -> Python by prepare_call, whose first
+    element is the RasterConfig of the call it was given; and a config read from its attributes comes back equal, bools as bools."""
+    ext = _lib.load_torch_ext()
+    s, n, m = 2, 8, 9
+    cov = torch.zeros(s, n, 7) if scale_rot else torch.zeros(s, n, 6)
+    frames = torch.eye(3).expand(s, 2, 3, 3) if scale_rot else None
+    got = ext.prepare_call(torch.zeros(s, n, 3), cov, torch.zeros(s, n), torch.zeros(s, n, m, 3), torch.zeros(3 * s, 48), 24, 40, 2, True, 3,
+                           torch.zeros(3 * s, n) if has_extra else None, None, 3, False, False, 0, True, False, 1, scale_rot, frames, 1, 0)[0]
+    want = rasterizer.RasterConfig(3 * s, s, 3, n, 24, 40, 2, m, 3, has_extra, _lib.FLAG_DEBUG | _lib.FLAG_DETERMINISTIC, scale_rot, False)
+    assert type(got) is rasterizer.RasterConfig and got == want
+    for cfg in (dataclasses.replace(want, alpha=alpha), dataclasses.replace(want, alpha=alpha, flags=_lib.FLAG_SH_IN_FRAME)):
+        back = ext.call_shape(cfg)
+        assert type(back) is rasterizer.RasterConfig and back == cfg
+        for f in dataclasses.fields(cfg):
+            assert type(getattr(back, f.name)) is (bool if f.name in ("has_extra", "scale_rot", "alpha") else int), f.name
+
+
+def test_binding_refuses_what_is_not_a_call_shape_or_not_dims():
+    ext = _lib.load_torch_ext()
+    be = rasterizer.HipBackend()
+    cfg = rasterizer.RasterConfig(1, 1, 1, 4, 8, 8, 0, 0)
+    as_list = [getattr(cfg, f.name) for f in dataclasses.fields(cfg)]
+    assert len(as_list) == 13
+    for call in (lambda: ext.launch_dims(as_list, 64), lambda: ext.frames_arg(as_list, None),
+                 lambda: be._c.capacity_for(as_list, 100, 10, 1.25), lambda: ext.launch_dims(dataclasses.replace(cfg, height=8.0), 64)):
+        with pytest.raises(TypeError):
+            call()
+    t, u8 = torch.zeros(1), torch.zeros(16, dtype=torch.uint8)
+    dims = ext.launch_dims(cfg, 64)
+
+    # (dummy CPU tensors: the argument conversion fails, nothing runs)
+    for d in (bytes(55), bytes(57), bytes(dims)[:-1], [getattr(dims, n) for n, _ in dims._fields_], None):
+        with pytest.raises(TypeError):
+            be._c.backward(cfg, d, u8, u8, u8, 0, t, t, t, t, t, None, t, None, False, False, None, 0, None)

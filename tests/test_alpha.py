@@ -3,6 +3,7 @@
 validate as before when the options carry the pointer; the flag mask and every workspace size are what they were; the Python surface
 has the switch, off by default."""
 import ctypes
+import dataclasses
 import inspect
 import os
 import re
@@ -83,8 +84,10 @@ def test_the_request_sizes_nothing_and_is_the_last_entry_of_the_call_shape():
     wanted = rasterizer.RasterConfig(3, 1, 3, 1000, 72, 40, 4, 25, 4, True, 1 << 4, False, True)
     assert wanted.alpha and not plain.alpha
     assert bytes(be._dims(plain, 1 << 16)) == bytes(be._dims(wanted, 1 << 16))
-    vp, vw = rasterizer._cfg_vec(plain), rasterizer._cfg_vec(wanted)
-    assert len(vp) == len(vw) == 13 and vp[:12] == vw[:12] and (vp[12], vw[12]) == (0, 1)
+    ext = _lib.load_torch_ext()
+    assert dataclasses.fields(rasterizer.RasterConfig)[-1].name == ext.CFG_FIELDS[-1] == "alpha"
+    assert plain != wanted and dataclasses.replace(plain, alpha=True) == wanted  # they differ in that field alone
+    assert bytes(ext.launch_dims(plain, 1 << 16)) == bytes(ext.launch_dims(wanted, 1 << 16))
 
 
 def test_python_surface_has_the_switch_off_by_default():

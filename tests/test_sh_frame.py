@@ -136,9 +136,11 @@ def test_sh_frame_argument_checks(oracle_backend):
     # the binding states the flags: GSR_FLAG_SH_IN_FRAME, with GSR_FLAG_SH_FRAME_E3NN for "e3nn"
     ext = _lib.load_torch_ext()
     for code, bits in ((0, 0), (1, _lib.FLAG_SH_IN_FRAME), (2, _lib.FLAG_SH_IN_FRAME | _lib.FLAG_SH_FRAME_E3NN)):
-        cfgv = ext.prepare_call(means, records, opac, sh, vb, 16, 16, 4, True, 1, None, None, 4, True, False, 0, False, False, -1, True, fr,
-                                1, code)[0]
-        assert cfgv[10] & (_lib.FLAG_SH_IN_FRAME | _lib.FLAG_SH_FRAME_E3NN) == bits
+        cfg = ext.prepare_call(means, records, opac, sh, vb, 16, 16, 4, True, 1, None, None, 4, True, False, 0, False, False, -1, True, fr,
+                               1, code)[0]
+        assert isinstance(cfg, rasterizer.RasterConfig)
+        assert cfg.flags & (_lib.FLAG_SH_IN_FRAME | _lib.FLAG_SH_FRAME_E3NN) == bits
+        assert cfg.alpha is False and cfg.scale_rot is True
 
 
 def _dims(flags, sh_coeffs=25):

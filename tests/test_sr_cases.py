@@ -67,7 +67,7 @@ def test_drawn_frames_pass_the_bindings_shape_rule_and_are_proper_rotations_per_
         if frames is None:
             assert desc["frames"] == 0
             continue
-        fr, nf = frames_arg(rasterizer._cfg_vec(cfg), frames)
+        fr, nf = frames_arg(cfg, frames)
         assert nf == frames.shape[1] == desc["frames"] and n % nf == 0 and tuple(fr.shape) == (s, nf, 3, 3), k
         f64 = frames.double()
         assert torch.allclose(f64 @ f64.transpose(-1, -2), torch.eye(3, dtype=torch.float64).expand_as(f64), atol=1e-5), k
