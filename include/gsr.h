@@ -573,7 +573,10 @@ int gsr_cost_volume_backward(int num_scenes, int num_views, int channels, int he
  *   exists.
  * gsr_camera_sync: pairwise (b, P, 4, 4), confidence (P b) -> absolute (b, v, 4, 4): camera_synchronization at its default arguments,
  *   one workgroup per scene: confidences normalised per column and the (4 v)^2 matrix formed in fp32 in the reference's order of
- *   operations, converted to fp64, squared 10 times in LDS, block column 0 divided by its mass, the rotations projected onto SO(3)
+ *   operations - the column sums of the normalisation included, which torch's CPU kernel takes row by row for columns in groups of
+ *   four and with four interleaved partial sums (rows 4 m + k; the rows left over go to the first; ((p0 + p1) + p2) + p3) for the
+ *   columns left over at v = 5, 6, 7 and for every column at v = 8: one fp32 ulp there moves the result by about 1e-6 -,
+ *   converted to fp64, squared 10 times in LDS, block column 0 divided by its mass, the rotations projected onto SO(3)
  *   as U diag(1, 1, det(U V^T)) V^T (8 sweeps of one-sided Jacobi), rounded once to fp32.  v = 2: camera_chaining (identity, then
  *   P(i, i+1) times the pose before it, fp32).  A scene one of whose v masses is exactly 0 takes camera_chaining FOR THAT SCENE, decided
  *   on the device; the reference decides for the whole batch after a host read: a difference for batches that mix such scenes.

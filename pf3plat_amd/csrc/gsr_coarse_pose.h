@@ -272,8 +272,19 @@ __global__ void __launch_bounds__(256) k_camera_sync(SyncArgs a) {
           conf[i][i] = conf[i][i] + c / 2.f; conf[j][j] = conf[j][j] + c / 2.f;
         }
       for (int j = 0; j < V; ++j) {
-        float sum = conf[0][j];
-        for (int i = 1; i < V; ++i) sum += conf[i][j];
+        // The column sum in the order of the reference's `conf.sum(dim=1)` (torch's CPU kernel, which the records are of): row by
+        // row for columns in groups of four; four interleaved partial sums over the rows 4 m + k - the rows left over added to the
+        // first, then ((p0 + p1) + p2) + p3 - for the columns left over at V = 5, 6, 7 and for all columns at V = 8.  Up to V = 4
+        // both are the sum in order.  (One fp32 ulp here moves the result by about 1e-6.)
+        float part[4] = {0.f, 0.f, 0.f, 0.f};
+        if (V == 8 || j >= 4) {
+          for (int m = 0; m < V / 4; ++m)
+            for (int k = 0; k < 4; ++k) part[k] += conf[4 * m + k][j];
+          for (int i = 4 * (V / 4); i < V; ++i) part[0] += conf[i][j];
+        } else {
+          for (int i = 0; i < V; ++i) part[0] += conf[i][j];
+        }
+        float sum = ((part[0] + part[1]) + part[2]) + part[3];
         sum = fmaxf(sum, 1e-9f);
         for (int i = 0; i < V; ++i) conf[i][j] = conf[i][j] / sum;
       }

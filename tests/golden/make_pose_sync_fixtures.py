@@ -1,7 +1,8 @@
 """Generates tests/golden/pose_sync_fixtures.npz by IMPORTING the reference's `camera_synchronization` (src/flow_util.py:623-743) on the
 CPU, with stub modules for what flow_util imports and the function does not use (cv2, open3d, pytorch3d.ops): seeded pairwise poses
 and confidences for v = 2, 3, 4 and b = 1, 2, one scene whose far pair's mean score lies below confidence_min, and one scene whose
-confidences are all zero - recorded with b = 1, where the reference's batch-wide fallback to camera_chaining is the per-scene one.
+confidences are all zero - recorded with b = 1, where the reference's batch-wide fallback to camera_chaining is the per-scene one;
+then v5_b2, v6_b1, v8_b1, v8_b2 and zero_v5 (five views, every confidence 0).
 The confidences go through the encoder's own lines (src/model/encoder/encoder_costvolume.py:370-373) first.
 
     python tests/golden/make_pose_sync_fixtures.py <path of a PF3plat checkout>
@@ -91,6 +92,13 @@ def main():
     Ps, means = scene_inputs(rng, 3, 1)
     means[:] = 0.0  # every confidence 0: the mass is 0 and the reference chains
     record("zero", Ps, means, 3)
+    # Appended after the records above, which stay bit for bit what they were (the generator's draws continue): 5, 6 and 8 views - a
+    # matrix of up to 32 x 32 - and five views with every confidence 0 (the fallback's chaining stride past four views).
+    for v, b in ((5, 2), (6, 1), (8, 1), (8, 2)):
+        record(f"v{v}_b{b}", *scene_inputs(rng, v, b), v)
+    Ps, means = scene_inputs(rng, 5, 1)
+    means[:] = 0.0
+    record("zero_v5", Ps, means, 5)
     out["names"] = np.array(names)
     np.savez_compressed(OUT, **out)
     print({k: v.shape for k, v in out.items()})

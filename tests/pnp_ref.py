@@ -92,17 +92,22 @@ class PlantedScene:
         return gauss_newton(ls.R, ls.t, self.cam(ls), self.points(ls)[m], ls.points_2d[m].astype(np.float64))
 
 
-def build_scene(seed, b, v, specs, behind=()):
+def build_scene(seed, b, v, specs, behind=(), focal=None):
     """specs: per list, in the pack's order, (n, inlier share, noisy) - share 1 and noisy False: exact matches.  Lists named in
     `behind` have every point behind the camera (the planted pose turns the camera away).  Each view's points are the unprojection
     of a random depth map in [1.5, 6]; a list's 3-D points are those at its ids_j, its planted pose a rotation of about 0.08 rad
     and a translation of about 0.25; inliers carry uniform noise in [-1, 1] px per axis, an outlier's 2-D point is redrawn until
-    it lies >= 20 px from its true projection.  The first two non-trivial lists contain ids 0 and H W - 1."""
+    it lies >= 20 px from its true projection.  The first two non-trivial lists contain ids 0 and H W - 1.  `focal`: (fx, fy), or
+    an array that broadcasts to (b, v, 2) for focal lengths per view, in place of FOCAL for both; nothing is drawn for it, and None
+    leaves every scene as it was."""
     rng = np.random.default_rng(seed)
     pairs = pairs_of(v)
     assert len(specs) == len(pairs) * b
     K = np.array([[FOCAL, 0, (W - 1) / 2], [0, FOCAL, (H - 1) / 2], [0, 0, 1]], dtype=np.float32)
     intrinsics = np.tile(K, (b, v, 1, 1))
+    if focal is not None:
+        f = np.broadcast_to(np.asarray(focal, dtype=np.float32), (b, v, 2))
+        intrinsics[..., 0, 0], intrinsics[..., 1, 1] = f[..., 0], f[..., 1]
     intrinsics[..., 0, 2] += rng.uniform(-1, 1, (b, v)).astype(np.float32)
     intrinsics[..., 1, 2] += rng.uniform(-1, 1, (b, v)).astype(np.float32)
     ys, xs = np.mgrid[0:H, 0:W]
@@ -177,6 +182,13 @@ def expected_confidence(scene, confidence_min=0.5):
     return np.array(out, dtype=np.float32)
 
 
+def ulps(got, want):
+    """The largest difference of two float32 matrices in float32 ulps of the larger one's largest entry, per matrix."""
+    scale = np.abs(want).reshape(*want.shape[:-2], -1).max(-1)
+    ulp = np.spacing(scale.astype(np.float32)).astype(np.float64)
+    return (np.abs(got.astype(np.float64) - want.astype(np.float64)).reshape(*want.shape[:-2], -1).max(-1) / ulp).max()
+
+
 # ------------------------------------------------------------------------------------------------------------------------
 # camera_synchronization restated
 # ------------------------------------------------------------------------------------------------------------------------
@@ -226,9 +238,22 @@ def camera_synchronization(Ps, confidence, v, squares=10):
         conf[i, i] = np.float32(conf[i, i] + np.float32(c / np.float32(2)))
         conf[j, j] = np.float32(conf[j, j] + np.float32(c / np.float32(2)))
     for j in range(v):
-        total = conf[0, j]
-        for i in range(1, v):
-            total = np.float32(total + conf[i, j])
+        # The float32 column sum in the order of torch's CPU kernel, which the reference's `conf.sum(dim=1)` runs and the records are
+        # of: columns in groups of four are summed row by row; the columns left over (j >= 4 when v is 5, 6 or 7) and all eight
+        # columns of v = 8 (the vectorised path) take four interleaved partial sums over the rows 4 m + k, the rows left over added
+        # to the first, then ((p0 + p1) + p2) + p3.  Up to four views both are the sum in order.  One float32 ulp in a column sum
+        # moves the result by about 1e-6: the records pin the order.
+        part = np.zeros(4, dtype=np.float32)
+        if v == 8 or j >= 4:
+            for m in range(v // 4):
+                for k in range(4):
+                    part[k] = np.float32(part[k] + conf[4 * m + k, j])
+            for i in range(4 * (v // 4), v):
+                part[0] = np.float32(part[0] + conf[i, j])
+        else:
+            for i in range(v):
+                part[0] = np.float32(part[0] + conf[i, j])
+        total = np.float32(np.float32(np.float32(part[0] + part[1]) + part[2]) + part[3])
         conf[:, j] = conf[:, j] / np.maximum(total, np.float32(1e-9))
     L = np.zeros((4 * v, 4 * v), dtype=np.float32)
     for i in range(v):

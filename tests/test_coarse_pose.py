@@ -115,7 +115,7 @@ PLANTED = [(name, l) for name in SCENES for l in planted_lists(name)]
 def test_sync_restatement_reproduces_every_reference_record():
     with np.load(FIXTURES) as fx:
         names = [str(n) for n in fx["names"]]
-        assert names == ["v2_b1", "v2_b2", "v3_b1", "v3_b2", "v4_b1", "v4_b2", "far_low", "zero"]
+        assert names == ["v2_b1", "v2_b2", "v3_b1", "v3_b2", "v4_b1", "v4_b2", "far_low", "zero", "v5_b2", "v6_b1", "v8_b1", "v8_b2", "zero_v5"]
         for name in names:
             Ps, conf, want, v = fx[name + "/pairwise"], fx[name + "/confidence"], fx[name + "/absolute"], int(fx[name + "/views"])
             b, pairs = Ps.shape[0], Ps.shape[1]
@@ -402,13 +402,6 @@ def test_repeated_call_same_bits_other_seed_same_mask_points_as_pixels():
     assert not any(t.requires_grad for t in a)
 
 
-def _ulps(got, want):
-    """The largest difference of two float32 matrices in float32 ulps of the larger one's largest entry, per matrix."""
-    scale = np.abs(want).reshape(*want.shape[:-2], -1).max(-1)
-    ulp = np.spacing(scale.astype(np.float32)).astype(np.float64)
-    return (np.abs(got.astype(np.float64) - want.astype(np.float64)).reshape(*want.shape[:-2], -1).max(-1) / ulp).max()
-
-
 @pytest.mark.gpu
 def test_synchronisation_agrees_with_the_reference_records():
     dev = torch.device("cuda")
@@ -418,14 +411,14 @@ def test_synchronisation_agrees_with_the_reference_records():
         v = int(rec[name + "/views"])
         got = pose.synchronize_cameras(torch.from_numpy(rec[name + "/pairwise"]).to(dev), torch.from_numpy(rec[name + "/confidence"]).to(dev), v)
         assert got.dtype == torch.float32 and not got.requires_grad
-        u = _ulps(got.cpu().numpy(), rec[name + "/absolute"])
+        u = ref.ulps(got.cpu().numpy(), rec[name + "/absolute"])
         print(f"MEASURED sync {name}: {u:.2f} ulps")
         assert u <= 4, (name, u)
     # the fallback scene batched with a normal one: each as its own b = 1 record (the decision is per scene)
     Ps = np.concatenate([rec["v3_b1/pairwise"], rec["zero/pairwise"]])
     conf = np.stack([rec["v3_b1/confidence"], rec["zero/confidence"]], 1).reshape(-1)  # list order: pair-major
     got = pose.synchronize_cameras(torch.from_numpy(Ps).to(dev), torch.from_numpy(conf).to(dev), 3).cpu().numpy()
-    assert _ulps(got[:1], rec["v3_b1/absolute"]) <= 4 and _ulps(got[1:], rec["zero/absolute"]) <= 4
+    assert ref.ulps(got[:1], rec["v3_b1/absolute"]) <= 4 and ref.ulps(got[1:], rec["zero/absolute"]) <= 4
     assert np.array_equal(got[1, 0], np.eye(4, dtype=np.float32))
 
 
