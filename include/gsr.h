@@ -593,6 +593,55 @@ int gsr_pnp_ransac(int num_scenes, int num_views, int height, int width, int num
                    void* scratch, float* pairwise, int32_t* inliers, int32_t* status, float* confidence, uint8_t* mask, void* stream);
 int gsr_camera_sync(int num_scenes, int num_views, const float* pairwise, const float* confidence, float* absolute, void* stream);
 
+/* The depth lift of the encoder (reference src/model/encoder/encoder_costvolume.py:265, 287-307, 506, 525-528: the two clamps, the
+ * one-hot "mono cue" and the unprojection; :211-221, 387-392: the Pluecker ray map).  All arrays f32; b scenes of v >= 1 views of
+ * h x w pixels, h, w >= 4 (any such size, not only multiples of 4); hq = h / 4, wq = w / 4 (integer division); D candidates.
+ * gsr_lift_depth: depth_raw, shift ((b v), 1, h, w); near, far (b, v); intrinsics (b, v, 3, 3), normalised; `lin` (D) the candidates'
+ *   positions in [0, 1] in device memory, or NULL for torch's float32 linspace(0, 1, D) (formed as the cost volume forms it: from the
+ *   start below the middle, from the end above it) -> depth ((b v), 1, h, w), xyz (b, v, 3, h, w), cue ((v b), D, hq, wq).  One launch.
+ *   depth = clamp(clamp(depth_raw, near, far) + shift, near, far) with the view's own bounds, clamp(x, lo, hi) = min(max(x, lo), hi):
+ *     one fp32 rounding (the addition), bit-equal to the float32 torch form.  A NaN in depth_raw or shift stays a NaN in depth and
+ *     in the pixel's xyz.
+ *   xyz[s, i, :, y, x] = K^-1 ((x + 0.5) / w, (y + 0.5) / h, 1)^T depth, K = intrinsics[s, i]: the FULL 3 x 3 inverse by cofactors
+ *     in fp64 once per view (no upper-triangular assumption; a singular K is the caller's error and is not checked), the ray in fp64,
+ *     rounded once, times the depth in fp32.  The reference unprojects twice (`xyz_up_h`, and `xyz_refine` after a third clamp with
+ *     the same bounds, which changes nothing): both are this tensor.
+ *   cue: VIEW-MAJOR rows as the cost volume's - row i b + s is view i of scene s.  down = the bilinear resize of depth to (hq, wq)
+ *     in torch's arithmetic (F.interpolate, align_corners = False: source index max((dst + 0.5) in / out - 0.5, 0) in fp32, the
+ *     second tap clamped to the last row / column; value l0y (l0x v00 + l1x v01) + l1y (l0x v10 + l1x v11)), its taps recomputed from
+ *     depth_raw and shift.  hyp_d = 1 / far[0, 0] + lin_d (1 / near[0, 0] - 1 / far[0, 0]) in fp32.  Every quarter-resolution pixel has
+ *     1 in channel argmin_d |down - hyp_d| - the first minimum, as torch.argmin: ties go to the lowest channel - and 0 in the other
+ *     D - 1.  TWO QUIRKS OF THE REFERENCE ARE KEPT: (1) the hypotheses are INVERSE depths and are compared with a DEPTH; (2) they come
+ *     from scene 0, view 0 for the whole batch, whatever the other views' bounds are (read on the device: no host synchronisation).
+ *     The written channel is in [0, D) whatever the inputs: a pixel with a NaN or infinite tap gets a valid, otherwise unspecified
+ *     channel.  The cue is written exactly once, as whole row segments; there is no zero-fill and no scatter, and no array of the
+ *     cue's size other than the cue.
+ * gsr_lift_depth_backward: the forward's inputs again (everything is recomputed) and the cotangents dL_ddepth ((b v), 1, h, w) and
+ *   dL_dxyz (b, v, 3, h, w), either or both NULL (taken as zero):
+ *     dL_dshift = m2 (dL_ddepth + sum_c dL_dxyz_c ray_c),  dL_ddepth_raw = m1 dL_dshift,
+ *   m1 = near <= depth_raw <= far and m2 = near <= clamp(depth_raw) + shift <= far, the clamps' pass-through masks, inclusive at the
+ *   bounds as torch's clamp backward; where a mask is false the gradient is an exact zero.  The sum is taken in fp64 and rounded once.
+ *   Either output may be NULL.  The cue has no gradient (the reference detaches it); near and far receive none.  One launch.
+ *   dL_dintrinsics (b, v, 3, 3), when not NULL: the chain through K^-1, dK = -K^-T (sum_p dL_dxyz_p ((x + 0.5) / w, (y + 0.5) / h, 1)
+ *   depth_p) K^-T, summed in fp64 in a fixed order - per thread, per wave, per workgroup of 1024 pixels into `scratch`
+ *   (gsr_lift_scratch_bytes(b, v, h, w) bytes, host arithmetic, 0 for sizes the calls refuse; 9 doubles per workgroup), then one
+ *   finishing launch that adds an image's workgroups in order: the same bits on every run.  Zero when dL_dxyz is NULL.
+ * gsr_plucker_rays: c2w (b, v, 4, 4) camera-to-world, of which the top three rows are read; intrinsics (b, v, 3, 3), normalised ->
+ *   out ((b v), 6, H, W), H, W >= 1: channels 0-2 the world-space unit direction of pixel centre ((x + 0.5) / W, (y + 0.5) / H) -
+ *   K^-1 (u, v, 1) normalised in camera space, then rotated by c2w[:3, :3] (the reference's get_world_rays) -, channels 3-5
+ *   cross(c2w[:3, 3], direction) (its plucker_embedding).  fp64 throughout, rounded once.  Forward only; one launch.
+ * All: GSR_ERR_INVALID_ARGUMENT, nothing launched, on a NULL required pointer, b < 0, v < 1, h or w < 4 (the lift), D < 1 or more than
+ * 2^31 - 1 elements in any array; b == 0: nothing is launched.  No floating-point atomics anywhere. */
+size_t gsr_lift_scratch_bytes(int num_scenes, int num_views, int height, int width);
+int gsr_lift_depth(int num_scenes, int num_views, int height, int width, int num_depth_candidates, const float* depth_raw,
+                   const float* shift, const float* near, const float* far, const float* intrinsics, const float* lin, float* depth,
+                   float* xyz, float* cue, void* stream);
+int gsr_lift_depth_backward(int num_scenes, int num_views, int height, int width, const float* depth_raw, const float* shift,
+                            const float* near, const float* far, const float* intrinsics, const float* dL_ddepth, const float* dL_dxyz,
+                            float* dL_ddepth_raw, float* dL_dshift, float* dL_dintrinsics, void* scratch, void* stream);
+int gsr_plucker_rays(int num_scenes, int num_views, int height, int width, const float* c2w, const float* intrinsics, float* out,
+                     void* stream);
+
 /* Measurement aid: 1 when gsr_forward runs the colour pass inside the binning launch for these dims (two launches: binning +
  * colour, per-tile sort + blend), 0 when the colour pass is a launch of its own (images of more than 4608 8x8 tiles, more than
  * four views per set, the windowed binning path), negative on bad dims. */

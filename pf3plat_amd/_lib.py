@@ -321,6 +321,14 @@ def load():
                                    + [vp] * 7)  # scratch, pairwise, inliers, status, confidence, mask, stream
     lib.gsr_camera_sync.restype = ctypes.c_int
     lib.gsr_camera_sync.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
+    lib.gsr_lift_scratch_bytes.restype = ctypes.c_size_t
+    lib.gsr_lift_scratch_bytes.argtypes = [ctypes.c_int] * 4
+    lib.gsr_lift_depth.restype = ctypes.c_int
+    lib.gsr_lift_depth.argtypes = [ctypes.c_int] * 5 + [vp] * 10  # sizes; depth_raw, shift, near, far, intrinsics, lin, depth, xyz, cue, stream
+    lib.gsr_lift_depth_backward.restype = ctypes.c_int  # sizes; the five inputs, dL_ddepth, dL_dxyz, dL_ddepth_raw, dL_dshift, dL_dintrinsics, scratch, stream
+    lib.gsr_lift_depth_backward.argtypes = [ctypes.c_int] * 4 + [vp] * 12
+    lib.gsr_plucker_rays.restype = ctypes.c_int
+    lib.gsr_plucker_rays.argtypes = [ctypes.c_int] * 4 + [vp] * 4  # sizes; c2w, intrinsics, out, stream
     if lib.gsr_abi_version() != GSR_ABI_VERSION:
         raise RuntimeError(f"libgsr_hip.so ABI {lib.gsr_abi_version()} != expected {GSR_ABI_VERSION}; rebuild")
     _lib = lib
@@ -338,6 +346,7 @@ EXPORTED_SYMBOLS = (
     "gsr_pose_loss", "gsr_pose_loss_backward", "gsr_pose_loss_units",
     "gsr_cost_volume", "gsr_cost_volume_backward", "gsr_cost_volume_scratch_bytes",
     "gsr_pnp_ransac", "gsr_pnp_ransac_scratch_bytes", "gsr_pnp_min_matches", "gsr_camera_sync",
+    "gsr_lift_depth", "gsr_lift_depth_backward", "gsr_lift_scratch_bytes", "gsr_plucker_rays",
 )
 # The stages of GsrForwardOptions.stage_ms / GsrBackwardOptions.stage_ms as run_forward / run_backward(profile=True) key them (the
 # names a failed debug-mode stage is reported with are the library's: gsr_stage_name).  On images of up to 20 480 tiles (the fused binning path) "preprocess" is the whole binning
