@@ -642,6 +642,33 @@ int gsr_lift_depth_backward(int num_scenes, int num_views, int height, int width
 int gsr_plucker_rays(int num_scenes, int num_views, int height, int width, const float* c2w, const float* intrinsics, float* out,
                      void* stream);
 
+/* The "multi guided by mono" attention of the depth predictor (reference src/model/encoder/costvolume/depth_predictor_multiview.py:
+ * 360-366), which follows the cost volume.  All arrays f32 and CHANNEL-MAJOR: q, k (n, E, L), v (n, C, L); n rows ((v b) in the
+ * reference), L = h_down w_down positions, E score channels, C value channels.
+ *   s[b, i, j] = sum_e q[b, e, i] k[b, e, j]          (no 1 / sqrt(E) factor: the reference has none)
+ *   p = softmax_j s
+ *   out[b, c, i] = sum_j p[b, i, j] v[b, c, j]        (n, C, L)
+ *   lse[b, i] = log sum_j exp s[b, i, j]              (n, L), kept for the backward
+ * gsr_mono_attention: one launch over (row, block of 128 queries, chunk of 64 value channels); the key axis is streamed 32 keys at a
+ *   time with the online softmax (running maximum and sum, rescaled accumulator), so scores of any size are safe and NO array of
+ *   L x L elements exists anywhere.  Every channel chunk forms the same scores and statistics in the same order.  Every product runs on the f32-input matrix instruction (v_mfma_f32_32x32x2_f32): exact f32, one rounding per
+ *   product, accumulated in key order.  exp and log are the accurate f32 functions.  The same bits on every run.
+ * gsr_mono_attention_backward: S and P are recomputed from q, k and lse;
+ *     delta[i] = sum_c dO[c, i] out[c, i],  dV[c, j] = sum_i dO[c, i] P[i, j],  dP[i, j] = sum_c dO[c, i] v[c, j],
+ *     dS = P (dP - delta),  dK[e, j] = sum_i dS[i, j] q[e, i],  dQ[e, i] = sum_j dS[i, j] k[e, j].
+ *   Three launches: delta into `scratch` (gsr_mono_attention_scratch_bytes(n, E, L, C) bytes: n L floats; host arithmetic, 0 for
+ *   sizes the calls refuse); a pass over blocks of 128 keys that streams the queries and leaves dK and dV; a pass over blocks of 128
+ *   queries that streams the keys and leaves dQ (the second pass recomputes P and dP: no sum ever crosses a workgroup).  No
+ *   atomics: every gradient has the same bits on every run.  Any of dL_dq, dL_dk, dL_dv may be NULL; a pass none of whose outputs is
+ *   wanted is not launched.  Saved state and scratch are O(n L (E + C)).
+ * Both: GSR_ERR_INVALID_ARGUMENT, nothing launched, unless 1 <= E <= 32, 1 <= C <= 256, L >= 1, n >= 1 and
+ * n max(E, C) L <= 2^31 - 1, or on a NULL required pointer.  No host synchronisation, no internal streams. */
+size_t gsr_mono_attention_scratch_bytes(int n, int E, int L, int C);
+int gsr_mono_attention(int n, int E, int L, int C, const float* q, const float* k, const float* v, float* out, float* lse, void* stream);
+int gsr_mono_attention_backward(int n, int E, int L, int C, const float* q, const float* k, const float* v, const float* out,
+                                const float* lse, const float* dL_dout, float* dL_dq, float* dL_dk, float* dL_dv, void* scratch,
+                                void* stream);
+
 /* Measurement aid: 1 when gsr_forward runs the colour pass inside the binning launch for these dims (two launches: binning +
  * colour, per-tile sort + blend), 0 when the colour pass is a launch of its own (images of more than 4608 8x8 tiles, more than
  * four views per set, the windowed binning path), negative on bad dims. */

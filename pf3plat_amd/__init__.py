@@ -30,3 +30,5 @@ from . import pose  # noqa: F401,E402
 from .pose import CoarsePoses, coarse_poses, pack_matches, pnp_ransac, synchronize_cameras  # noqa: F401,E402
 from . import lift  # noqa: F401,E402
 from .lift import LiftedDepth, lift_depth, plucker_rays  # noqa: F401,E402
+from . import mono_attention  # noqa: F401,E402
+from .mono_attention import mono_guided_attention  # noqa: F401,E402

@@ -329,6 +329,12 @@ def load():
     lib.gsr_lift_depth_backward.argtypes = [ctypes.c_int] * 4 + [vp] * 12
     lib.gsr_plucker_rays.restype = ctypes.c_int
     lib.gsr_plucker_rays.argtypes = [ctypes.c_int] * 4 + [vp] * 4  # sizes; c2w, intrinsics, out, stream
+    lib.gsr_mono_attention_scratch_bytes.restype = ctypes.c_size_t
+    lib.gsr_mono_attention_scratch_bytes.argtypes = [ctypes.c_int] * 4
+    lib.gsr_mono_attention.restype = ctypes.c_int
+    lib.gsr_mono_attention.argtypes = [ctypes.c_int] * 4 + [vp] * 6  # n, E, L, C; q, k, v, out, lse, stream
+    lib.gsr_mono_attention_backward.restype = ctypes.c_int  # ...; q, k, v, out, lse, dL_dout, dL_dq, dL_dk, dL_dv, scratch, stream
+    lib.gsr_mono_attention_backward.argtypes = [ctypes.c_int] * 4 + [vp] * 11
     if lib.gsr_abi_version() != GSR_ABI_VERSION:
         raise RuntimeError(f"libgsr_hip.so ABI {lib.gsr_abi_version()} != expected {GSR_ABI_VERSION}; rebuild")
     _lib = lib
@@ -347,6 +353,7 @@ EXPORTED_SYMBOLS = (
     "gsr_cost_volume", "gsr_cost_volume_backward", "gsr_cost_volume_scratch_bytes",
     "gsr_pnp_ransac", "gsr_pnp_ransac_scratch_bytes", "gsr_pnp_min_matches", "gsr_camera_sync",
     "gsr_lift_depth", "gsr_lift_depth_backward", "gsr_lift_scratch_bytes", "gsr_plucker_rays",
+    "gsr_mono_attention", "gsr_mono_attention_backward", "gsr_mono_attention_scratch_bytes",
 )
 # The stages of GsrForwardOptions.stage_ms / GsrBackwardOptions.stage_ms as run_forward / run_backward(profile=True) key them (the
 # names a failed debug-mode stage is reported with are the library's: gsr_stage_name).  On images of up to 20 480 tiles (the fused binning path) "preprocess" is the whole binning
