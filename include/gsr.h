@@ -669,6 +669,47 @@ int gsr_mono_attention_backward(int n, int E, int L, int C, const float* q, cons
                                 const float* lse, const float* dL_dout, float* dL_dq, float* dL_dk, float* dL_dv, void* scratch,
                                 void* stream);
 
+/* The refined poses of the encoder (reference src/model/encoder/encoder_costvolume.py:447-450, 460-473, with r6d2mat :189-209 and
+ * matrix_to_rotation_6d :223-224, and the three inversions `refine_sync_abspose.inverse()` :492, :530 and `c2w[1].inverse()`
+ * src/model/model_wrapper.py:150) and the per-step pose errors (model_wrapper.py:182-190, 306-313, 345;
+ * compute_geodesic_distance_from_two_matrices, src/flow_util.py:20-32).  All arrays f32; b scenes of v >= 1 views; poses are rows of
+ * 16 floats, row-major 4 x 4.  One thread per pose (per scene for the errors), fp64 inside the thread, one rounding on store.
+ * gsr_pose_refine: sync_pose (b, v, 4, 4), of which the top three rows are read; delta: row (s, i) begins at
+ *   delta + (s v + i) delta_row_stride and its first nine floats are read, delta_row_stride >= 9 - the first nine channels of the
+ *   pose head's (b, v, 139) output where they lie, no copy, nothing after them is touched; gamma: ONE float in device memory
+ *   -> c2w, w2c (b, v, 4, 4).  For pose (s, i):
+ *     enc = (row 0 of R, row 1 of R, t) of sync_pose[s, i];  for i >= 1: enc += gamma delta[s, i, 0:9].  VIEW 0 TAKES NO RESIDUAL
+ *       (:465-466), whatever its row of delta holds.
+ *     a1 = enc[0:3], a2 = enc[3:6], t = enc[6:9];  b1 = a1 / max(|a1|, 1e-12) - THE CLAMP OF F.normalize, not a division by the norm:
+ *       a zero row gives a zero row, finite -;  b2 = u / max(|u|, 1e-12), u = a2 - (b1 . a2) b1;  b3 = b1 x b2.
+ *     c2w = [[b1; b2; b3] | t], bottom row (0, 0, 0, 1): the b are the ROWS of the rotation, as the reference stacks them.
+ *     w2c = [R^T | -R^T t], bottom row (0, 0, 0, 1): THE RIGID INVERSE in place of the reference's batched LU.  c2w is rigid for
+ *       every value of delta and gamma (short of the clamp), so the two agree in value and in their gradients with respect to delta
+ *       and gamma.
+ * gsr_pose_refine_backward: the forward's inputs again (everything is recomputed) and the cotangents dL_dc2w, dL_dw2c (b, v, 4, 4),
+ *   either or both NULL (taken as zero; their bottom rows are not read) -> dL_ddelta (b, v, 9), contiguous, FULLY written, the rows of
+ *   view 0 zero; dL_dgamma, one float = sum over (s, i >= 1, k) of delta[s, i, k] dL_denc[s, i, k].  An output that is NULL is
+ *   skipped.  With dL_dR[i][j] = dL_dc2w[i][j] + dL_dw2c[j][i] - t[i] dL_dw2c[j][3] and dL_dt[i] = dL_dc2w[i][3] - sum_j R[i][j]
+ *   dL_dw2c[j][3], back through the cross product, the two normalisations (below the clamp: a division by 1e-12) and the
+ *   projection.  One launch of ONE workgroup of 256 threads, which walks the poses with stride 256, keeps an fp64 partial of
+ *   dL_dgamma per thread and folds the 256 partials in LDS by a fixed tree: no atomics, the same bits on every run.  sync_pose
+ *   receives nothing (the reference's coarse poses come back from numpy).
+ * gsr_pose_errors: c2w_pred, extrinsics_gt (b, v, 4, 4) -> out (3, b), forward only, one thread per scene:
+ *     gt_rel = extrinsics_gt[s, v - 1]^-1 extrinsics_gt[s, 0], the affine inverse [R^-1 | -R^-1 t] with bottom row (0, 0, 0, 1)
+ *       as everywhere in this library;  pred = c2w_pred[s, v - 1];
+ *     out[0, s] = acos(clamp((trace(R_pred R_gt^T) - 1) / 2, -1, 1)), RADIANS as the reference logs it;
+ *     out[1, s] = acos(clamp(t_pred / |t_pred| . t_gt / |t_gt|, -1, 1)) 180 / pi, degrees;  out[2, s] = |t_pred - t_gt|.
+ *   A ZERO TRANSLATION on either side gives NaN in out[1, s], as the reference's 0 / 0 does (the clamp keeps a NaN).
+ * All: GSR_ERR_INVALID_ARGUMENT, nothing launched, on a NULL required pointer, b < 0, v < 1, delta_row_stride < 9 or more than
+ * 2^31 - 1 elements in the poses or in delta as strided; b == 0: GSR_OK, nothing is launched.  No host synchronisation. */
+int gsr_pose_refine(int num_scenes, int num_views, const float* sync_pose, const float* delta, int delta_row_stride, const float* gamma,
+                    float* c2w, float* w2c, void* stream);
+int gsr_pose_refine_backward(int num_scenes, int num_views, const float* sync_pose, const float* delta, int delta_row_stride,
+                             const float* gamma, const float* dL_dc2w, const float* dL_dw2c, float* dL_ddelta, float* dL_dgamma,
+                             void* stream);
+int gsr_pose_errors(int num_scenes, int num_views, const float* c2w_pred, const float* extrinsics_gt, float* out /* (3, b) */,
+                    void* stream);
+
 /* Measurement aid: 1 when gsr_forward runs the colour pass inside the binning launch for these dims (two launches: binning +
  * colour, per-tile sort + blend), 0 when the colour pass is a launch of its own (images of more than 4608 8x8 tiles, more than
  * four views per set, the windowed binning path), negative on bad dims. */

@@ -28,6 +28,7 @@ from . import cost_volume  # noqa: F401,E402
 from .cost_volume import depth_candidates, plane_sweep_cost_volume  # noqa: F401,E402
 from . import pose  # noqa: F401,E402
 from .pose import CoarsePoses, coarse_poses, pack_matches, pnp_ransac, synchronize_cameras  # noqa: F401,E402
+from .pose import PoseErrors, RefinedPoses, pose_encoding, pose_errors, refine_poses  # noqa: F401,E402
 from . import lift  # noqa: F401,E402
 from .lift import LiftedDepth, lift_depth, plucker_rays  # noqa: F401,E402
 from . import mono_attention  # noqa: F401,E402

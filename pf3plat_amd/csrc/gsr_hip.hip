@@ -42,7 +42,7 @@
 //   gsr_pose_loss.h    pose loss                                   }  kernels and its own entry points
 //   gsr_cost_volume.h  plane-sweep cost volume                     }
 //   gsr_pnp_solver.h   namespace gsr::pnp: host + device arithmetic of the coarse-pose solver (a host program includes it alone)
-//   gsr_coarse_pose.h  PnP RANSAC kernels, k_camera_sync, entry points
+//   gsr_coarse_pose.h  PnP RANSAC kernels, k_camera_sync, entry points; the refined poses and the pose errors (k_pose_ops)
 #include "gsr_common.h"
 #include "gsr_binning.h"
 #include "gsr_tiles_fwd.h"

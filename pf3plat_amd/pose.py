@@ -2,12 +2,16 @@
 src/flow_util.py:623-743; the definition is stated in include/gsr.h): `pnp_ransac` replaces the loop of `cv2.solvePnPRansac` calls
 over (pair, scene) - and its copies to the host and back - with two launches (gsr_pnp_ransac), `synchronize_cameras` replaces
 `camera_synchronization` with one (gsr_camera_sync), and `coarse_poses` is the chain: three launches, no host synchronisation, no
-gradient (the reference's poses come back from numpy).  There is no CPU fallback."""
+gradient (the reference's poses come back from numpy).  `refine_poses` is what follows the pose transformer (:447-450, 460-473 and
+the `.inverse()` calls of :492, :530 and model_wrapper.py:150): the 6D + translation encoding, the head's residual, Gram-Schmidt,
+c2w and w2c in one launch each way (gsr_pose_refine / gsr_pose_refine_backward), differentiable in the residual and its gain;
+`pose_encoding` is the encoding alone; `pose_errors` the per-step diagnostics of model_wrapper.py:182-190 (gsr_pose_errors).
+There is no CPU fallback."""
 from __future__ import annotations
 
 import ctypes
 from dataclasses import dataclass
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 from torch import Tensor
@@ -164,3 +168,153 @@ def coarse_poses(xyz: Tensor, intrinsics_px: Tensor, packed: PackedCorrespondenc
                                                  seed, return_mask)
     absolute = synchronize_cameras(pairwise, conf, xyz.shape[1])
     return CoarsePoses(pairwise, absolute, conf, inliers, status, mask)
+
+
+class RefinedPoses(NamedTuple):
+    c2w: Tensor  # (b, v, 4, 4): the reference's refine_sync_abspose
+    w2c: Tensor  # (b, v, 4, 4): its .inverse()
+
+
+class PoseErrors(NamedTuple):
+    rotation: Tensor              # (b,) radians
+    translation_angle: Tensor     # (b,) degrees
+    translation_distance: Tensor  # (b,)
+
+
+def pose_encoding(c2w: Tensor) -> Tensor:
+    """(..., 4, 4) or (..., 3, 4) -> (..., 9): the reference's cat(matrix_to_rotation_6d(R), t) - rows 0 and 1 of the rotation, then the
+    translation -, what `embed_pose` reads (encoder_costvolume.py:448-450, 453).  Plain torch indexing on any device."""
+    if c2w.dim() < 2 or c2w.shape[-1] != 4 or c2w.shape[-2] not in (3, 4):
+        raise ValueError(f"pose_encoding: expected poses (..., 4, 4), got {tuple(c2w.shape)}")
+    return torch.cat([c2w[..., :2, :3].reshape(*c2w.shape[:-2], 6), c2w[..., :3, 3]], dim=-1)
+
+
+def _delta_rows(delta: Tensor):
+    """delta (b, v, 9) as the kernels read it: (tensor whose data_ptr is row (0, 0), floats per row).  Read where it lies if it is
+    float32 with last stride 1 and uniform row strides (`full[..., :9]` of a contiguous (b, v, C)); anything else is copied once."""
+    d = delta.detach()
+    b, v, _ = d.shape
+    if d.dtype == torch.float32 and d.stride(2) == 1:
+        row = d.stride(1) if v > 1 else (d.stride(0) if b > 1 else 9)
+        if row >= 9 and (b == 1 or d.stride(0) == v * row):
+            return d, row
+    return d.to(torch.float32).contiguous(), 9
+
+
+def _refine_args(sync_abspose, delta, gamma):
+    """The shape checks (before the device is looked at and before the library is loaded), then the device check."""
+    if sync_abspose.dim() != 4 or tuple(sync_abspose.shape[2:]) != (4, 4):
+        raise ValueError(f"refine_poses: expected sync_abspose (b, v, 4, 4), got {tuple(sync_abspose.shape)}")
+    b, v = sync_abspose.shape[:2]
+    if v < 1:
+        raise ValueError(f"refine_poses: needs at least one view, got {v}")
+    if delta.dim() != 3 or delta.shape[2] != 9:
+        raise ValueError(f"refine_poses: expected delta (b, v, 9) - the first nine channels of the pose head's output -, got {tuple(delta.shape)}")
+    if tuple(delta.shape[:2]) != (b, v):
+        raise ValueError(f"refine_poses: sync_abspose is of (b, v) = ({b}, {v}), delta of {tuple(delta.shape[:2])}")
+    if isinstance(gamma, Tensor) and gamma.numel() != 1:
+        raise ValueError(f"refine_poses: expected gamma with one element, got {tuple(gamma.shape)}")
+    tensors = [sync_abspose, delta] + ([gamma] if isinstance(gamma, Tensor) else [])
+    if not all(t.is_cuda for t in tensors):
+        raise RuntimeError("pf3plat_amd pose: tensors must be on a ROCm device (there is no CPU fallback path)")
+    if any(t.device != sync_abspose.device for t in tensors):
+        raise RuntimeError("refine_poses: every tensor must be on the same device")
+    return b, v
+
+
+class _RefinePoses(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, sync_abspose, delta, gamma):
+        b, v = _refine_args(sync_abspose, delta, gamma)
+        rows, stride = _delta_rows(delta)
+        if b * v * max(stride, 16) > 0x7fffffff:
+            raise ValueError("refine_poses: more than 2^31 - 1 elements in the poses or in delta as strided")
+        lib = _lib.load()
+        dev, f32 = sync_abspose.device, torch.float32
+        sync = _f32(sync_abspose)
+        if isinstance(gamma, Tensor):
+            g = gamma.detach().to(f32).reshape(1)
+        else:
+            g = torch.full((1,), float(gamma), dtype=f32, device=dev)
+        c2w = torch.empty((b, v, 4, 4), dtype=f32, device=dev)  # (both fully written by the call)
+        w2c = torch.empty((b, v, 4, 4), dtype=f32, device=dev)
+        with _on_device(dev):
+            rc = lib.gsr_pose_refine(b, v, sync.data_ptr(), rows.data_ptr(), stride, g.data_ptr(), c2w.data_ptr(), w2c.data_ptr(), _stream_ptr(dev))
+        if rc != 0:
+            raise RuntimeError(f"gsr_pose_refine failed with code {rc}")
+        ctx.save_for_backward(sync, delta, g)
+        ctx.gamma_like = gamma if isinstance(gamma, Tensor) else None
+        ctx.sizes = (b, v)
+        ctx.set_materialize_grads(False)
+        return c2w.to(sync_abspose.dtype), w2c.to(sync_abspose.dtype)
+
+    @staticmethod
+    def backward(ctx, g_c2w, g_w2c):
+        sync, delta, g = ctx.saved_tensors
+        b, v = ctx.sizes
+        _, need_delta, need_gamma = ctx.needs_input_grad
+        if not (need_delta or need_gamma) or (g_c2w is None and g_w2c is None) or b == 0:
+            return None, None, None
+        lib = _lib.load()
+        dev, f32 = sync.device, torch.float32
+        rows, stride = _delta_rows(delta)
+        ups = [None if t is None else _f32(t) for t in (g_c2w, g_w2c)]
+        d_delta = torch.empty((b, v, 9), dtype=f32, device=dev) if need_delta else None  # (fully written by the call)
+        d_gamma = torch.empty((1,), dtype=f32, device=dev) if need_gamma else None
+        ptr = lambda t: None if t is None else t.data_ptr()
+        with _on_device(dev):
+            rc = lib.gsr_pose_refine_backward(b, v, sync.data_ptr(), rows.data_ptr(), stride, g.data_ptr(), ptr(ups[0]), ptr(ups[1]),
+                                              ptr(d_delta), ptr(d_gamma), _stream_ptr(dev))
+        if rc != 0:
+            raise RuntimeError(f"gsr_pose_refine_backward failed with code {rc}")
+        like = ctx.gamma_like
+        return (None, d_delta.to(delta.dtype) if need_delta else None,
+                d_gamma.to(like.dtype).reshape(like.shape) if need_gamma else None)
+
+
+def refine_poses(sync_abspose: Tensor, delta: Tensor, gamma) -> RefinedPoses:
+    """sync_abspose (b, v, 4, 4) - `coarse_poses(...).absolute` -, delta (b, v, 9) - the first nine channels of the pose head's output -,
+    gamma -> RefinedPoses(c2w, w2c), both (b, v, 4, 4), as include/gsr.h defines them: the pose as (rows 0 and 1 of R, t), plus
+    gamma delta for every view but the first, Gram-Schmidt with F.normalize's clamp (the orthonormal vectors are the ROWS of R), and
+    w2c = [R^T | -R^T t] - the reference's three `.inverse()` calls without an LU.  Differentiable in delta and in gamma; sync_abspose
+    receives nothing (the reference's coarse poses come back from numpy).  The gradients are bit-reproducible (no atomics).
+    delta is read where it lies when it is float32 with last stride 1 and uniform row strides - `pose_branch(...)[..., :9]`;
+    anything else is copied once.  gamma: a 0-dim or one-element device tensor (the nn.Parameter), read on the device, or a Python
+    float, which gets no gradient.  One launch each way, no host synchronisation.  Inputs that are not float32 are converted; results
+    and gradients come back in the inputs' dtypes."""
+    return RefinedPoses(*_RefinePoses.apply(sync_abspose, delta, gamma))
+
+
+@torch.no_grad()
+def pose_errors(c2w_pred: Tensor, extrinsics_gt: Tensor) -> PoseErrors:
+    """c2w_pred (b, v, 4, 4) - `refine_poses(...).c2w` -, extrinsics_gt (b, v, 4, 4) - batch["context"]["extrinsics"] ->
+    PoseErrors(rotation, translation_angle, translation_distance), each (b,), of the LAST view against gt_rel = E[:, -1]^-1 E[:, 0]
+    (include/gsr.h): the geodesic angle in radians, the angle between the translation directions in degrees (NaN for a zero
+    translation, as the reference's 0 / 0) and the distance of the translations.  The reference's three logged scalars
+    (model_wrapper.py:182-190, 306-313, 345) are `rotation.mean()` (compute_geodesic_distance_from_two_matrices averages the batch),
+    `translation_angle[0]` (its torch.dot takes scene 0) and `translation_distance[0]` at b = 1 (it calls `.item()` there).
+    One launch, no gradient, no host synchronisation."""
+    for name, t in (("c2w_pred", c2w_pred), ("extrinsics_gt", extrinsics_gt)):
+        if t.dim() != 4 or tuple(t.shape[2:]) != (4, 4):
+            raise ValueError(f"pose_errors: expected {name} (b, v, 4, 4), got {tuple(t.shape)}")
+    b, v = c2w_pred.shape[:2]
+    if v < 1:
+        raise ValueError(f"pose_errors: needs at least one view, got {v}")
+    if tuple(extrinsics_gt.shape[:2]) != (b, v):
+        raise ValueError(f"pose_errors: c2w_pred is of (b, v) = ({b}, {v}), extrinsics_gt of {tuple(extrinsics_gt.shape[:2])}")
+    if b * v * 16 > 0x7fffffff:
+        raise ValueError("pose_errors: more than 2^31 - 1 elements in the poses")
+    if not (c2w_pred.is_cuda and extrinsics_gt.is_cuda):
+        raise RuntimeError("pf3plat_amd pose: tensors must be on a ROCm device (there is no CPU fallback path)")
+    if c2w_pred.device != extrinsics_gt.device:
+        raise RuntimeError("pose_errors: every tensor must be on the same device")
+    lib = _lib.load()
+    dev = c2w_pred.device
+    pred, gt = _f32(c2w_pred), _f32(extrinsics_gt)
+    out = torch.empty((3, b), dtype=torch.float32, device=dev)
+    with _on_device(dev):
+        rc = lib.gsr_pose_errors(b, v, pred.data_ptr(), gt.data_ptr(), out.data_ptr(), _stream_ptr(dev))
+    if rc != 0:
+        raise RuntimeError(f"gsr_pose_errors failed with code {rc}")
+    out = out.to(c2w_pred.dtype)
+    return PoseErrors(out[0], out[1], out[2])
