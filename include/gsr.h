@@ -669,6 +669,40 @@ int gsr_mono_attention_backward(int n, int E, int L, int C, const float* q, cons
                                 const float* lse, const float* dL_dout, float* dL_dq, float* dL_dk, float* dL_dv, void* scratch,
                                 void* stream);
 
+/* Multi-head attention: the softmax attention of LightGlue's SelfBlock and CrossBlock (reference src/model/LightGlue/lightglue/
+ * lightglue.py:133-224), of which the encoder's pose transformer is built (src/model/encoder/encoder_costvolume.py:401-441).  All f32.
+ * Operands: q is logically (B, H, N, D), k and v are logically (B, H, M, D); each comes with FOUR ELEMENT STRIDES (batch, head,
+ *   token, channel) and is read where it lies, offsets formed in 64 bits - the reference's two layouts without a copy:
+ *   qkv.unflatten(-1, (H, -1, 3)).transpose(1, 2)[..., i] has strides (3 N H D, 3 D, 3 H D, 3), .unflatten(-1, (H, -1))
+ *   .transpose(1, 2) has (N H D, D, H D, 1).
+ *     s[b, h, i, j] = scale * sum_c q[b, h, i, c] k[b, h, j, c]
+ *     p = softmax_j s
+ *     out[b, i, h, c] = sum_j p[b, h, i, j] v[b, h, j, c]
+ *     lse[b, h, i] = log sum_j exp s[b, h, i, j]          (B, H, N), kept for the backward
+ * Results are TOKEN-MAJOR and contiguous: out, dL_dout and dL_dq are (B, N, H, D), dL_dk and dL_dv (B, M, H, D) - what
+ *   context.transpose(1, 2).flatten(-2) hands to the output projection without a copy.
+ * gsr_attention: one launch over (batch, head, block of 128 queries).  As the mono attention above: the key axis is streamed 32 keys
+ *   at a time with the online softmax, so scores of any size are safe and NOTHING of N x M elements exists anywhere; every product
+ *   runs on v_mfma_f32_32x32x2_f32 (exact f32, accumulated in key order); expf and logf are the accurate functions.  `scale`
+ *   MULTIPLIES THE SCORE TILE: s is the f32 product scale * (q . k), rounded once after the channel sum, with the same bits in the
+ *   forward and in both backward passes; dQ and dK take the factor once, on the finished sum.
+ * gsr_attention_backward: S and P are recomputed from q, k and lse;
+ *     delta[b, h, i] = sum_c dO[b, i, h, c] out[b, i, h, c],  dV[j] = sum_i P[i, j] dO[i],  dP[i, j] = sum_c dO[i, c] v[j, c],
+ *     dS = P (dP - delta),  dK[j] = scale sum_i dS[i, j] q[i],  dQ[i] = scale sum_j dS[i, j] k[j].
+ *   Three launches: delta into `scratch` (gsr_attention_scratch_bytes(B, H, N, M, D) bytes: B H N floats; host arithmetic, 0 for
+ *   sizes the calls refuse); a pass over blocks of 128 keys that streams the queries and leaves dK and dV; a pass over blocks of 128
+ *   queries that streams the keys and leaves dQ.  Any of dL_dq, dL_dk, dL_dv may be NULL; a pass none of whose outputs is wanted is
+ *   not launched.  No atomics and no sum crosses a workgroup: forward and gradients have the same bits on every run.  Saved state and
+ *   scratch are O(B H (N + M) D).
+ * All: GSR_ERR_INVALID_ARGUMENT, nothing launched, unless B, H, N, M >= 1, 1 <= D <= 32, B H max(N, M) D <= 2^31 - 1, `scale` is
+ * finite and no required pointer (the stride arrays included) is NULL.  No host synchronisation, no internal streams. */
+size_t gsr_attention_scratch_bytes(int B, int H, int N, int M, int D);
+int gsr_attention(int B, int H, int N, int M, int D, float scale, const float* q, const int64_t* q_strides, const float* k,
+                  const int64_t* k_strides, const float* v, const int64_t* v_strides, float* out, float* lse, void* stream);
+int gsr_attention_backward(int B, int H, int N, int M, int D, float scale, const float* q, const int64_t* q_strides, const float* k,
+                           const int64_t* k_strides, const float* v, const int64_t* v_strides, const float* out, const float* lse,
+                           const float* dL_dout, float* dL_dq, float* dL_dk, float* dL_dv, void* scratch, void* stream);
+
 /* The refined poses of the encoder (reference src/model/encoder/encoder_costvolume.py:447-450, 460-473, with r6d2mat :189-209 and
  * matrix_to_rotation_6d :223-224, and the three inversions `refine_sync_abspose.inverse()` :492, :530 and `c2w[1].inverse()`
  * src/model/model_wrapper.py:150) and the per-step pose errors (model_wrapper.py:182-190, 306-313, 345;

@@ -33,3 +33,6 @@ from . import lift  # noqa: F401,E402
 from .lift import LiftedDepth, lift_depth, plucker_rays  # noqa: F401,E402
 from . import mono_attention  # noqa: F401,E402
 from .mono_attention import mono_guided_attention  # noqa: F401,E402
+from . import attention  # noqa: F401,E402
+from .attention import CrossBlock, LearnableFourierPositionalEncoding, SelfBlock, apply_cached_rotary_emb  # noqa: F401,E402
+from .attention import bidirectional_cross_attention, multi_head_attention  # noqa: F401,E402

@@ -335,6 +335,13 @@ def load():
     lib.gsr_mono_attention.argtypes = [ctypes.c_int] * 4 + [vp] * 6  # n, E, L, C; q, k, v, out, lse, stream
     lib.gsr_mono_attention_backward.restype = ctypes.c_int  # ...; q, k, v, out, lse, dL_dout, dL_dq, dL_dk, dL_dv, scratch, stream
     lib.gsr_mono_attention_backward.argtypes = [ctypes.c_int] * 4 + [vp] * 11
+    mha_head = [ctypes.c_int] * 5 + [ctypes.c_float] + [vp, i64p] * 3  # B, H, N, M, D; scale; q, k, v, each with its four element strides
+    lib.gsr_attention_scratch_bytes.restype = ctypes.c_size_t
+    lib.gsr_attention_scratch_bytes.argtypes = [ctypes.c_int] * 5
+    lib.gsr_attention.restype = ctypes.c_int
+    lib.gsr_attention.argtypes = mha_head + [vp] * 3  # ...; out, lse, stream
+    lib.gsr_attention_backward.restype = ctypes.c_int  # ...; out, lse, dL_dout, dL_dq, dL_dk, dL_dv, scratch, stream
+    lib.gsr_attention_backward.argtypes = mha_head + [vp] * 8
     lib.gsr_pose_refine.restype = ctypes.c_int
     lib.gsr_pose_refine.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, vp, vp, vp, vp]  # b, v; sync_pose, delta, its row stride, gamma, c2w, w2c, stream
     lib.gsr_pose_refine_backward.restype = ctypes.c_int  # ...; gamma, dL_dc2w, dL_dw2c, dL_ddelta, dL_dgamma, stream
@@ -361,6 +368,7 @@ EXPORTED_SYMBOLS = (
     "gsr_lift_depth", "gsr_lift_depth_backward", "gsr_lift_scratch_bytes", "gsr_plucker_rays",
     "gsr_mono_attention", "gsr_mono_attention_backward", "gsr_mono_attention_scratch_bytes",
     "gsr_pose_refine", "gsr_pose_refine_backward", "gsr_pose_errors",
+    "gsr_attention", "gsr_attention_backward", "gsr_attention_scratch_bytes",
 )
 # The stages of GsrForwardOptions.stage_ms / GsrBackwardOptions.stage_ms as run_forward / run_backward(profile=True) key them (the
 # names a failed debug-mode stage is reported with are the library's: gsr_stage_name).  On images of up to 20 480 tiles (the fused binning path) "preprocess" is the whole binning
