@@ -66,7 +66,8 @@ def find_hipcc() -> str:
 
 def hip_sources(csrc: str = None, header: str = None) -> list:
     """Every file libgsr_hip.so is built from: csrc/gsr_hip.hip - the one translation unit - and the headers next to it that it
-    includes (gsr_common.h, gsr_{binning,tiles_fwd,backward,cameras,covariance}.h, one per operator, preprocess_bwd.inc: all of csrc/ but the torch
+    includes (gsr_common.h, gsr_{binning,tiles_fwd,backward,cameras,covariance}.h, one header per operator - gsr_{image,adapter,pose_loss,
+    cost_volume,lift,mono_attention,attention,coarse_pose,pose_refine}.h -, gsr_pnp_solver.h, preprocess_bwd.inc: all of csrc/ but the torch
     binding, which is a library of its own; tests/test_abi.py holds this set to the #include graph) and include/gsr.h."""
     csrc = csrc or os.path.dirname(SRC)
     return [os.path.join(csrc, n) for n in sorted(os.listdir(csrc)) if n != "gsr_torch.cpp" and os.path.isfile(os.path.join(csrc, n))] + [header or HEADER]

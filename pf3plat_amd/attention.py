@@ -13,7 +13,7 @@ import torch
 from torch import Tensor, nn
 
 from . import _lib
-from .rasterizer import _on_device, _stream_ptr
+from ._call import launch, ptr, require_device, scratch
 
 MAX_HEAD_DIM = 32
 
@@ -49,11 +49,7 @@ def _attention_args(q, k, v, scale):
     scale = D ** -0.5 if scale is None else float(scale)
     if scale != scale or scale in (float("inf"), float("-inf")):
         raise ValueError(f"multi_head_attention: scale must be finite, got {scale}")
-    tensors = (q, k, v)
-    if not all(t.is_cuda for t in tensors):
-        raise RuntimeError("pf3plat_amd attention: tensors must be on a ROCm device (there is no CPU fallback path)")
-    if any(t.device != q.device for t in tensors):
-        raise RuntimeError("multi_head_attention: every tensor must be on the same device")
+    require_device("attention", "multi_head_attention", (q, k, v))
     return B, H, N, M, D, scale
 
 
@@ -61,16 +57,12 @@ class _MultiHeadAttention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, scale):
         B, H, N, M, D, scale = _attention_args(q, k, v, scale)
-        lib = _lib.load()
         dev, f32 = q.device, torch.float32
         qa, ka, va = _operand(q), _operand(k), _operand(v)
         out = torch.empty((B, N, H, D), dtype=f32, device=dev)  # token-major (both fully written by the call)
         lse = torch.empty((B, H, N), dtype=f32, device=dev)
-        with _on_device(dev):
-            rc = lib.gsr_attention(B, H, N, M, D, scale, qa.data_ptr(), _strides(qa), ka.data_ptr(), _strides(ka), va.data_ptr(), _strides(va),
-                                   out.data_ptr(), lse.data_ptr(), _stream_ptr(dev))
-        if rc != 0:
-            raise RuntimeError(f"gsr_attention failed with code {rc}")
+        launch("gsr_attention", dev, B, H, N, M, D, scale, qa.data_ptr(), _strides(qa), ka.data_ptr(), _strides(ka), va.data_ptr(), _strides(va),
+               out.data_ptr(), lse.data_ptr())
         ctx.save_for_backward(q, k, v, out, lse)  # O(B H (N + M) D); nothing of N x M
         ctx.sizes = (B, H, N, M, D, scale)
         return out.permute(0, 2, 1, 3).to(v.dtype)
@@ -82,7 +74,6 @@ class _MultiHeadAttention(torch.autograd.Function):
         need_q, need_k, need_v = ctx.needs_input_grad[:3]
         if not (need_q or need_k or need_v):
             return None, None, None, None
-        lib = _lib.load()
         dev, f32 = q.device, torch.float32
         qa, ka, va = _operand(q), _operand(k), _operand(v)
         g = g_out.detach().permute(0, 2, 1, 3)  # (B, N, H, D): contiguous already when the cotangent came through the transposed view
@@ -91,14 +82,9 @@ class _MultiHeadAttention(torch.autograd.Function):
         d_q = torch.empty((B, N, H, D), dtype=f32, device=dev) if need_q else None  # (fully written by the call)
         d_k = torch.empty((B, M, H, D), dtype=f32, device=dev) if need_k else None
         d_v = torch.empty((B, M, H, D), dtype=f32, device=dev) if need_v else None
-        scratch = torch.empty(max(int(lib.gsr_attention_scratch_bytes(B, H, N, M, D)) // 4, 1), dtype=f32, device=dev)
-        ptr = lambda t: None if t is None else t.data_ptr()
-        with _on_device(dev):
-            rc = lib.gsr_attention_backward(B, H, N, M, D, scale, qa.data_ptr(), _strides(qa), ka.data_ptr(), _strides(ka), va.data_ptr(),
-                                            _strides(va), out.data_ptr(), lse.data_ptr(), g.data_ptr(), ptr(d_q), ptr(d_k), ptr(d_v),
-                                            scratch.data_ptr(), _stream_ptr(dev))
-        if rc != 0:
-            raise RuntimeError(f"gsr_attention_backward failed with code {rc}")
+        work = scratch(_lib.load().gsr_attention_scratch_bytes(B, H, N, M, D), f32, dev)
+        launch("gsr_attention_backward", dev, B, H, N, M, D, scale, qa.data_ptr(), _strides(qa), ka.data_ptr(), _strides(ka), va.data_ptr(),
+               _strides(va), out.data_ptr(), lse.data_ptr(), g.data_ptr(), ptr(d_q), ptr(d_k), ptr(d_v), work.data_ptr())
         view = lambda d, like: d.permute(0, 2, 1, 3).to(like.dtype)
         return view(d_q, q) if need_q else None, view(d_k, k) if need_k else None, view(d_v, v) if need_v else None, None
 

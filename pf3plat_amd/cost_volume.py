@@ -8,12 +8,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from .rasterizer import _on_device, _stream_ptr
-
-
-def _f32(t: Tensor) -> Tensor:
-    t = t.detach()
-    return t if t.dtype == torch.float32 and t.is_contiguous() else t.to(torch.float32).contiguous()
+from ._call import f32, launch, require_device, scratch
 
 
 def _cost_volume_args(features, intrinsics, extrinsics, near, far, num_depth_candidates):
@@ -37,17 +32,13 @@ def _cost_volume_args(features, intrinsics, extrinsics, near, far, num_depth_can
     limit = 0x7fffffff
     if b * v * h * w * ((c + 3) // 4 * 4) > limit or b * v * d * h * w > limit:
         raise ValueError("plane_sweep_cost_volume: more than 2^31 - 1 elements in the features or the volume")
-    tensors = (features, intrinsics, extrinsics, near, far)
-    if not all(t.is_cuda for t in tensors):
-        raise RuntimeError("pf3plat_amd cost_volume: tensors must be on a ROCm device (there is no CPU fallback path)")
-    if any(t.device != features.device for t in tensors):
-        raise RuntimeError("plane_sweep_cost_volume: every tensor must be on the same device")
+    require_device("cost_volume", "plane_sweep_cost_volume", (features, intrinsics, extrinsics, near, far))
     return b, v, c, h, w, d
 
 
-def _scratch(lib, sizes, backward: bool, dev) -> Tensor:
+def _scratch(sizes, backward: bool, dev) -> Tensor:
     b, v, c, h, w, _ = sizes
-    return torch.empty(max(int(lib.gsr_cost_volume_scratch_bytes(b, v, c, h, w, int(backward))) // 4, 1), dtype=torch.float32, device=dev)
+    return scratch(_lib.load().gsr_cost_volume_scratch_bytes(b, v, c, h, w, int(backward)), torch.float32, dev)
 
 
 class _CostVolume(torch.autograd.Function):
@@ -55,15 +46,11 @@ class _CostVolume(torch.autograd.Function):
     def forward(ctx, features, intrinsics, extrinsics, near, far, num_depth_candidates):
         sizes = _cost_volume_args(features, intrinsics, extrinsics, near, far, num_depth_candidates)
         b, v, c, h, w, d = sizes
-        lib = _lib.load()
         dev = features.device
-        arrays = (_f32(features), _f32(intrinsics), _f32(extrinsics), _f32(near), _f32(far))
+        arrays = (f32(features), f32(intrinsics), f32(extrinsics), f32(near), f32(far))
         cost = torch.empty((v * b, d, h, w), dtype=torch.float32, device=dev)
-        scratch = _scratch(lib, sizes, False, dev)  # (the backward allocates its own: nothing but the inputs outlives this call)
-        with _on_device(dev):
-            rc = lib.gsr_cost_volume(*sizes, *(t.data_ptr() for t in arrays), cost.data_ptr(), scratch.data_ptr(), _stream_ptr(dev))
-        if rc != 0:
-            raise RuntimeError(f"gsr_cost_volume failed with code {rc}")
+        work = _scratch(sizes, False, dev)  # (the backward allocates its own: nothing but the inputs outlives this call)
+        launch("gsr_cost_volume", dev, *sizes, *(t.data_ptr() for t in arrays), cost.data_ptr(), work.data_ptr())
         ctx.save_for_backward(features, intrinsics, extrinsics, near, far)
         ctx.sizes = sizes
         return cost
@@ -75,17 +62,12 @@ class _CostVolume(torch.autograd.Function):
         b, v, c, h, w, _ = sizes
         if not ctx.needs_input_grad[0]:
             return None, None, None, None, None, None
-        lib = _lib.load()
         dev = features.device
-        arrays = (_f32(features), _f32(intrinsics), _f32(extrinsics), _f32(near), _f32(far))
+        arrays = (f32(features), f32(intrinsics), f32(extrinsics), f32(near), f32(far))
         d_features = torch.empty((b, v, c, h, w), dtype=torch.float32, device=dev)  # (fully written by the call)
-        scratch = _scratch(lib, sizes, True, dev)
-        up = _f32(g_cost)
-        with _on_device(dev):
-            rc = lib.gsr_cost_volume_backward(*sizes, *(t.data_ptr() for t in arrays), up.data_ptr(), d_features.data_ptr(),
-                                              scratch.data_ptr(), _stream_ptr(dev))
-        if rc != 0:
-            raise RuntimeError(f"gsr_cost_volume_backward failed with code {rc}")
+        work = _scratch(sizes, True, dev)
+        up = f32(g_cost)
+        launch("gsr_cost_volume_backward", dev, *sizes, *(t.data_ptr() for t in arrays), up.data_ptr(), d_features.data_ptr(), work.data_ptr())
         return d_features.to(features.dtype), None, None, None, None, None
 
 

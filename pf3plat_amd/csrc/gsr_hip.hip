@@ -41,8 +41,12 @@
 //   gsr_adapter.h      Gaussian adapter                            }  operators next to the raster path, each with its
 //   gsr_pose_loss.h    pose loss                                   }  kernels and its own entry points
 //   gsr_cost_volume.h  plane-sweep cost volume                     }
+//   gsr_lift.h         depth lift, mono cue, Pluecker rays         }
+//   gsr_mono_attention.h  mono-guided attention, the MFMA tile helpers (ma_*)  }
+//   gsr_attention.h    multi-head attention (k_mha_ops), on those helpers      }
 //   gsr_pnp_solver.h   namespace gsr::pnp: host + device arithmetic of the coarse-pose solver (a host program includes it alone)
-//   gsr_coarse_pose.h  PnP RANSAC kernels, k_camera_sync, entry points; the refined poses and the pose errors (k_pose_ops)
+//   gsr_coarse_pose.h  PnP RANSAC kernels, k_camera_sync, entry points
+//   gsr_pose_refine.h  the refined poses and the pose errors (k_pose_ops)
 #include "gsr_common.h"
 #include "gsr_binning.h"
 #include "gsr_tiles_fwd.h"
@@ -572,5 +576,9 @@ int gsr_mark_visible(const GsrDims* dims, const GsrView* views, const float* mea
 #include "gsr_adapter.h"
 #include "gsr_pose_loss.h"
 #include "gsr_cost_volume.h"
+#include "gsr_lift.h"
+#include "gsr_mono_attention.h"
+#include "gsr_attention.h"
 #include "gsr_pnp_solver.h"
 #include "gsr_coarse_pose.h"
+#include "gsr_pose_refine.h"

@@ -11,18 +11,13 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from .rasterizer import _on_device, _stream_ptr
+from ._call import f32, launch, ptr, require_device, scratch
 
 
 class LiftedDepth(NamedTuple):
     depth: Tensor     # ((b v), 1, h, w)
     xyz: Tensor       # (b, v, 3, h, w)
     mono_cue: Tensor  # ((v b), D, h // 4, w // 4), one-hot, no gradient
-
-
-def _f32(t: Tensor) -> Tensor:
-    t = t.detach()
-    return t if t.dtype == torch.float32 and t.is_contiguous() else t.to(torch.float32).contiguous()
 
 
 def _lift_args(depth_raw, shift, near, far, intrinsics, num_candidates):
@@ -49,11 +44,7 @@ def _lift_args(depth_raw, shift, near, far, intrinsics, num_candidates):
     limit = 0x7fffffff
     if b * v * 3 * h * w > limit or b * v * d * (h // 4) * (w // 4) > limit:
         raise ValueError("lift_depth: more than 2^31 - 1 elements in the points or the cue")
-    tensors = (depth_raw, shift, near, far, intrinsics)
-    if not all(t.is_cuda for t in tensors):
-        raise RuntimeError("pf3plat_amd lift: tensors must be on a ROCm device (there is no CPU fallback path)")
-    if any(t.device != depth_raw.device for t in tensors):
-        raise RuntimeError("lift_depth: every tensor must be on the same device")
+    require_device("lift", "lift_depth", (depth_raw, shift, near, far, intrinsics))
     return b, v, h, w, d
 
 
@@ -61,17 +52,12 @@ class _LiftDepth(torch.autograd.Function):
     @staticmethod
     def forward(ctx, depth_raw, shift, near, far, intrinsics, num_candidates):
         b, v, h, w, d = _lift_args(depth_raw, shift, near, far, intrinsics, num_candidates)
-        lib = _lib.load()
-        dev, f32 = depth_raw.device, torch.float32
-        arrays = (_f32(depth_raw), _f32(shift), _f32(near), _f32(far), _f32(intrinsics))
-        depth = torch.empty((b * v, 1, h, w), dtype=f32, device=dev)  # (all three fully written by the call)
-        xyz = torch.empty((b, v, 3, h, w), dtype=f32, device=dev)
-        cue = torch.empty((v * b, d, h // 4, w // 4), dtype=f32, device=dev)
-        with _on_device(dev):
-            rc = lib.gsr_lift_depth(b, v, h, w, d, *(t.data_ptr() for t in arrays), None, depth.data_ptr(), xyz.data_ptr(), cue.data_ptr(),
-                                    _stream_ptr(dev))
-        if rc != 0:
-            raise RuntimeError(f"gsr_lift_depth failed with code {rc}")
+        dev = depth_raw.device
+        arrays = (f32(depth_raw), f32(shift), f32(near), f32(far), f32(intrinsics))
+        depth = torch.empty((b * v, 1, h, w), dtype=torch.float32, device=dev)  # (all three fully written by the call)
+        xyz = torch.empty((b, v, 3, h, w), dtype=torch.float32, device=dev)
+        cue = torch.empty((v * b, d, h // 4, w // 4), dtype=torch.float32, device=dev)
+        launch("gsr_lift_depth", dev, b, v, h, w, d, *(t.data_ptr() for t in arrays), None, depth.data_ptr(), xyz.data_ptr(), cue.data_ptr())
         ctx.save_for_backward(depth_raw, shift, near, far, intrinsics)
         ctx.sizes = (b, v, h, w)
         ctx.set_materialize_grads(False)
@@ -85,20 +71,15 @@ class _LiftDepth(torch.autograd.Function):
         need_raw, need_shift, _, _, need_intr = ctx.needs_input_grad[:5]
         if not (need_raw or need_shift or need_intr) or (g_depth is None and g_xyz is None):
             return None, None, None, None, None, None
-        lib = _lib.load()
-        dev, f32 = depth_raw.device, torch.float32
-        arrays = (_f32(depth_raw), _f32(shift), _f32(near), _f32(far), _f32(intrinsics))
-        ups = [None if g is None else _f32(g) for g in (g_depth, g_xyz)]
-        d_raw = torch.empty((b * v, 1, h, w), dtype=f32, device=dev) if need_raw else None  # (fully written by the call)
-        d_shift = torch.empty((b * v, 1, h, w), dtype=f32, device=dev) if need_shift else None
-        d_intr = torch.empty((b, v, 3, 3), dtype=f32, device=dev) if need_intr else None
-        scratch = torch.empty(max(int(lib.gsr_lift_scratch_bytes(b, v, h, w)) // 8, 1), dtype=torch.float64, device=dev) if need_intr else None
-        ptr = lambda t: None if t is None else t.data_ptr()
-        with _on_device(dev):
-            rc = lib.gsr_lift_depth_backward(b, v, h, w, *(t.data_ptr() for t in arrays), ptr(ups[0]), ptr(ups[1]), ptr(d_raw), ptr(d_shift),
-                                             ptr(d_intr), ptr(scratch), _stream_ptr(dev))
-        if rc != 0:
-            raise RuntimeError(f"gsr_lift_depth_backward failed with code {rc}")
+        dev = depth_raw.device
+        arrays = (f32(depth_raw), f32(shift), f32(near), f32(far), f32(intrinsics))
+        ups = [None if g is None else f32(g) for g in (g_depth, g_xyz)]
+        d_raw = torch.empty((b * v, 1, h, w), dtype=torch.float32, device=dev) if need_raw else None  # (fully written by the call)
+        d_shift = torch.empty((b * v, 1, h, w), dtype=torch.float32, device=dev) if need_shift else None
+        d_intr = torch.empty((b, v, 3, 3), dtype=torch.float32, device=dev) if need_intr else None
+        work = scratch(_lib.load().gsr_lift_scratch_bytes(b, v, h, w), torch.float64, dev) if need_intr else None
+        launch("gsr_lift_depth_backward", dev, b, v, h, w, *(t.data_ptr() for t in arrays), ptr(ups[0]), ptr(ups[1]), ptr(d_raw), ptr(d_shift),
+               ptr(d_intr), ptr(work))
         return (d_raw.to(depth_raw.dtype) if need_raw else None, d_shift.to(shift.dtype) if need_shift else None, None, None,
                 d_intr.to(intrinsics.dtype) if need_intr else None, None)
 
@@ -130,16 +111,8 @@ def plucker_rays(c2w: Tensor, intrinsics: Tensor, shape: Tuple[int, int]) -> Ten
     H, W = int(shape[0]), int(shape[1])
     if b * v * 6 * H * W > 0x7fffffff:
         raise ValueError("plucker_rays: more than 2^31 - 1 elements in the ray map")
-    if not (c2w.is_cuda and intrinsics.is_cuda):
-        raise RuntimeError("pf3plat_amd lift: tensors must be on a ROCm device (there is no CPU fallback path)")
-    if c2w.device != intrinsics.device:
-        raise RuntimeError("plucker_rays: every tensor must be on the same device")
-    lib = _lib.load()
-    dev = c2w.device
-    arrays = (_f32(c2w), _f32(intrinsics))
-    out = torch.empty((b * v, 6, H, W), dtype=torch.float32, device=dev)
-    with _on_device(dev):
-        rc = lib.gsr_plucker_rays(b, v, H, W, *(t.data_ptr() for t in arrays), out.data_ptr(), _stream_ptr(dev))
-    if rc != 0:
-        raise RuntimeError(f"gsr_plucker_rays failed with code {rc}")
+    require_device("lift", "plucker_rays", (c2w, intrinsics))
+    arrays = (f32(c2w), f32(intrinsics))
+    out = torch.empty((b * v, 6, H, W), dtype=torch.float32, device=c2w.device)
+    launch("gsr_plucker_rays", c2w.device, b, v, H, W, *(t.data_ptr() for t in arrays), out.data_ptr())
     return out

@@ -18,42 +18,32 @@ import torch
 from torch import Tensor
 
 from . import _lib
+from ._call import call, f32, launch, ptr, require_device
 from .rasterizer import _on_device, _stream_ptr
 
 
 def _launch(prediction: Tensor, target: Tensor, mse_weight: float, ssim_weight: float, want_grad: bool):
     """-> (sums (n, 4): per image squared error, clipped squared error, SSIM map, 0; totals (4,): loss, mse, mean ssim, 0;
     dL/dprediction or None; elements per image).  Two launches (gsr_image_loss, gsr_image_loss_finish), no torch op."""
-    if not (prediction.is_cuda and target.is_cuda):
-        raise RuntimeError("pf3plat_amd losses: tensors must be on a ROCm device (there is no CPU fallback path)")
+    require_device("losses", "photometric_loss", (prediction, target))
     if prediction.shape != target.shape or prediction.dim() != 4 or prediction.shape[1] != 3:
         raise ValueError(f"expected two (n, 3, h, w) images, got {tuple(prediction.shape)} and {tuple(target.shape)}")
     lib = _lib.load()
-    f32 = torch.float32
-    pred = prediction.detach()
-    tgt = target.detach()
-    if pred.dtype != f32 or not pred.is_contiguous():
-        pred = pred.to(f32).contiguous()
-    if tgt.dtype != f32 or not tgt.is_contiguous():
-        tgt = tgt.to(f32).contiguous()
+    pred, tgt = f32(prediction), f32(target)
     n, _, h, w = pred.shape
     dev = pred.device
     if n == 0:
-        z = torch.zeros((1, 4), dtype=f32, device=dev)
+        z = torch.zeros((1, 4), dtype=torch.float32, device=dev)
         return z[:0], z[0], (torch.empty_like(pred) if want_grad else None), 3 * h * w
     slots = int(lib.gsr_image_loss_partials(n, h, w))
-    partials = torch.empty((slots, 4), dtype=f32, device=dev)
-    out = torch.empty((n + 1, 4), dtype=f32, device=dev)  # the images' sums, then the batch's totals
+    partials = torch.empty((slots, 4), dtype=torch.float32, device=dev)
+    out = torch.empty((n + 1, 4), dtype=torch.float32, device=dev)  # the images' sums, then the batch's totals
     grad = torch.empty_like(pred) if want_grad else None
     stream = _stream_ptr(dev)
     pp = partials.data_ptr()
     with _on_device(dev):
-        rc = lib.gsr_image_loss(n, h, w, pred.data_ptr(), tgt.data_ptr(), float(mse_weight), float(ssim_weight),
-                                None if grad is None else grad.data_ptr(), pp, stream)
-        if rc == 0:
-            rc = lib.gsr_image_loss_finish(n, h, w, pp, float(mse_weight), float(ssim_weight), out.data_ptr(), out[n].data_ptr(), stream)
-    if rc != 0:
-        raise RuntimeError(f"gsr_image_loss failed with code {rc}")
+        call("gsr_image_loss", stream, n, h, w, pred.data_ptr(), tgt.data_ptr(), float(mse_weight), float(ssim_weight), ptr(grad), pp)
+        call("gsr_image_loss_finish", stream, n, h, w, pp, float(mse_weight), float(ssim_weight), out.data_ptr(), out[n].data_ptr())
     return out[:n], out[n], grad, 3 * h * w
 
 
@@ -98,33 +88,22 @@ def _launch_metrics(ground_truth: Tensor, predicted: Tensor, want_map: bool):
     n, _, h, w = ground_truth.shape
     if h < 11 or w < 11:
         raise ValueError(f"win_size exceeds image extent: the 11 x 11 window of compute_ssim needs h, w >= 11, got {h} x {w}")
-    if not (ground_truth.is_cuda and predicted.is_cuda):
-        raise RuntimeError("pf3plat_amd losses: tensors must be on a ROCm device (there is no CPU fallback path)")
+    require_device("losses", "compute_image_metrics", (ground_truth, predicted))
     lib = _lib.load()
-    f32 = torch.float32
-    gt = ground_truth.detach()
-    pred = predicted.detach()
-    if gt.dtype != f32 or not gt.is_contiguous():
-        gt = gt.to(f32).contiguous()
-    if pred.dtype != f32 or not pred.is_contiguous():
-        pred = pred.to(f32).contiguous()
+    gt, pred = f32(ground_truth), f32(predicted)
     dev = gt.device
-    out = torch.empty((4, n), dtype=f32, device=dev)
-    smap = torch.empty((n, 3, h, w), dtype=f32, device=dev) if want_map else None
+    out = torch.empty((4, n), dtype=torch.float32, device=dev)
+    smap = torch.empty((n, 3, h, w), dtype=torch.float32, device=dev) if want_map else None
     if n == 0:
         return out, smap
     slots = int(lib.gsr_image_metrics_partials(n, h, w))
     if slots == 0:
         raise RuntimeError(f"gsr_image_metrics takes at most 21845 images in one call, got {n}")
-    partials = torch.empty((slots, 4), dtype=f32, device=dev)
+    partials = torch.empty((slots, 4), dtype=torch.float32, device=dev)
     stream = _stream_ptr(dev)
     with _on_device(dev):
-        rc = lib.gsr_image_metrics(n, h, w, gt.data_ptr(), pred.data_ptr(), None if smap is None else smap.data_ptr(),
-                                   partials.data_ptr(), stream)
-        if rc == 0:
-            rc = lib.gsr_image_metrics_finish(n, h, w, partials.data_ptr(), out.data_ptr(), stream)
-    if rc != 0:
-        raise RuntimeError(f"gsr_image_metrics failed with code {rc}")
+        call("gsr_image_metrics", stream, n, h, w, gt.data_ptr(), pred.data_ptr(), ptr(smap), partials.data_ptr())
+        call("gsr_image_metrics_finish", stream, n, h, w, partials.data_ptr(), out.data_ptr())
     return out, smap
 
 
@@ -246,11 +225,6 @@ def pack_correspondences(corr, conf) -> PackedCorrespondences:
     return PackedCorrespondences(ids_i, ids_j, weights, cf, tuple(offsets), off, num_scenes, len(pairs))
 
 
-def _f32(t: Tensor) -> Tensor:
-    t = t.detach()
-    return t if t.dtype == torch.float32 and t.is_contiguous() else t.to(torch.float32).contiguous()
-
-
 def _pose_loss_args(xyz, depth, poses, intrinsics, packed):
     """The shape checks (before the device is looked at and before the library is loaded), then the device check."""
     if xyz.dim() != 5 or xyz.shape[2] != 3:
@@ -267,22 +241,17 @@ def _pose_loss_args(xyz, depth, poses, intrinsics, packed):
     if packed.num_scenes != b or packed.num_pairs != v * (v - 1) // 2 or len(packed.offsets) != b * packed.num_pairs + 1:
         raise ValueError(f"pose_loss: the correspondences are packed for {packed.num_scenes} scenes and {packed.num_pairs} pairs, "
                          f"the points are of {b} scenes and {v} views ({v * (v - 1) // 2} pairs)")
-    tensors = (xyz, depth, poses, intrinsics, packed.ids_i, packed.ids_j, packed.weights, packed.conf, packed.offsets_device)
-    if not all(t.is_cuda for t in tensors):
-        raise RuntimeError("pf3plat_amd losses: tensors must be on a ROCm device (there is no CPU fallback path)")
-    if any(t.device != xyz.device for t in tensors):
-        raise RuntimeError("pose_loss: every tensor must be on the same device")
+    require_device("losses", "pose_loss", (xyz, depth, poses, intrinsics, packed.ids_i, packed.ids_j, packed.weights, packed.conf,
+                                           packed.offsets_device))
     return b, v, h, w
 
 
-def _pose_call(fn, b, v, h, w, packed, arrays, weight_2d, weight_3d, tail, dev):
+def _pose_call(name, b, v, h, w, packed, arrays, weight_2d, weight_3d, tail, dev):
     n = len(packed.offsets)
     host = (ctypes.c_int32 * n)(*packed.offsets)
-    with _on_device(dev):
-        rc = fn(b, v, h, w, packed.num_pairs, *(t.data_ptr() for t in arrays), packed.ids_i.data_ptr(), packed.ids_j.data_ptr(),
-                packed.weights.data_ptr(), packed.conf.data_ptr(), host, packed.offsets_device.data_ptr(), weight_2d, weight_3d,
-                *(t.data_ptr() for t in tail), _stream_ptr(dev))
-    return rc
+    launch(name, dev, b, v, h, w, packed.num_pairs, *(t.data_ptr() for t in arrays), packed.ids_i.data_ptr(), packed.ids_j.data_ptr(),
+           packed.weights.data_ptr(), packed.conf.data_ptr(), host, packed.offsets_device.data_ptr(), weight_2d, weight_3d,
+           *(t.data_ptr() for t in tail))
 
 
 def _pose_units(lib, packed) -> int:
@@ -298,15 +267,13 @@ class _PoseLoss(torch.autograd.Function):
     def forward(ctx, xyz, depth, poses, intrinsics, packed, weight_2d, weight_3d):
         b, v, h, w = _pose_loss_args(xyz, depth, poses, intrinsics, packed)
         lib = _lib.load()
-        dev, f32 = xyz.device, torch.float32
-        arrays = (_f32(xyz), _f32(depth), _f32(poses), _f32(intrinsics))
+        dev = xyz.device
+        arrays = (f32(xyz), f32(depth), f32(poses), f32(intrinsics))
         units = _pose_units(lib, packed)
-        partials = torch.empty((max(units, 1), 4), dtype=f32, device=dev)
-        lists = torch.empty((max(b * packed.num_pairs, 1), 4), dtype=f32, device=dev)
-        out = torch.empty(4, dtype=f32, device=dev)
-        rc = _pose_call(lib.gsr_pose_loss, b, v, h, w, packed, arrays, weight_2d, weight_3d, (partials, lists, out), dev)
-        if rc != 0:
-            raise RuntimeError(f"gsr_pose_loss failed with code {rc}")
+        partials = torch.empty((max(units, 1), 4), dtype=torch.float32, device=dev)
+        lists = torch.empty((max(b * packed.num_pairs, 1), 4), dtype=torch.float32, device=dev)
+        out = torch.empty(4, dtype=torch.float32, device=dev)
+        _pose_call("gsr_pose_loss", b, v, h, w, packed, arrays, weight_2d, weight_3d, (partials, lists, out), dev)
         ctx.save_for_backward(xyz, depth, poses, intrinsics, lists)
         ctx.call = (b, v, h, w, packed, weight_2d, weight_3d, units)
         loss, loss_3d, loss_2d = out[0], out[1], out[2]
@@ -317,18 +284,14 @@ class _PoseLoss(torch.autograd.Function):
     def backward(ctx, g_loss, _g_3d, _g_2d):
         xyz, depth, poses, intrinsics, lists = ctx.saved_tensors
         b, v, h, w, packed, weight_2d, weight_3d, units = ctx.call
-        lib = _lib.load()
-        dev, f32 = xyz.device, torch.float32
-        arrays = (_f32(xyz), _f32(depth), _f32(poses), _f32(intrinsics))
-        d_xyz = torch.empty((b, v, 3, h, w), dtype=f32, device=dev)  # (zero-filled by the call)
-        d_depth = torch.empty((b, v, h, w), dtype=f32, device=dev)
-        d_poses = torch.empty((b, v, 4, 4), dtype=f32, device=dev)
-        partials = torch.empty((max(units, 1), 12), dtype=f32, device=dev)
-        up = _f32(g_loss).reshape(1)
-        rc = _pose_call(lib.gsr_pose_loss_backward, b, v, h, w, packed, arrays, weight_2d, weight_3d,
-                        (lists, up, d_xyz, d_depth, d_poses, partials), dev)
-        if rc != 0:
-            raise RuntimeError(f"gsr_pose_loss_backward failed with code {rc}")
+        dev = xyz.device
+        arrays = (f32(xyz), f32(depth), f32(poses), f32(intrinsics))
+        d_xyz = torch.empty((b, v, 3, h, w), dtype=torch.float32, device=dev)  # (zero-filled by the call)
+        d_depth = torch.empty((b, v, h, w), dtype=torch.float32, device=dev)
+        d_poses = torch.empty((b, v, 4, 4), dtype=torch.float32, device=dev)
+        partials = torch.empty((max(units, 1), 12), dtype=torch.float32, device=dev)
+        up = f32(g_loss).reshape(1)
+        _pose_call("gsr_pose_loss_backward", b, v, h, w, packed, arrays, weight_2d, weight_3d, (lists, up, d_xyz, d_depth, d_poses, partials), dev)
         need = ctx.needs_input_grad
         return (d_xyz.to(xyz.dtype) if need[0] else None, d_depth.reshape(depth.shape).to(depth.dtype) if need[1] else None,
                 d_poses.to(poses.dtype) if need[2] else None, None, None, None, None)

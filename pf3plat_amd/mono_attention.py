@@ -9,12 +9,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from .rasterizer import _on_device, _stream_ptr
-
-
-def _f32(t: Tensor) -> Tensor:
-    t = t.detach()
-    return t if t.dtype == torch.float32 and t.is_contiguous() else t.to(torch.float32).contiguous()
+from ._call import f32, launch, ptr, require_device, scratch
 
 
 def _channel_major_q(mono_q: Tensor) -> Tensor:
@@ -42,11 +37,7 @@ def _attention_args(mono_q, mono_k, multi_v):
         raise ValueError(f"mono_guided_attention: supports 1 <= C <= 256 value channels, got {C}")
     if n * max(E, C) * L > 0x7fffffff:
         raise ValueError("mono_guided_attention: more than 2^31 - 1 elements in an array")
-    tensors = (mono_q, mono_k, multi_v)
-    if not all(t.is_cuda for t in tensors):
-        raise RuntimeError("pf3plat_amd mono_attention: tensors must be on a ROCm device (there is no CPU fallback path)")
-    if any(t.device != mono_q.device for t in tensors):
-        raise RuntimeError("mono_guided_attention: every tensor must be on the same device")
+    require_device("mono_attention", "mono_guided_attention", (mono_q, mono_k, multi_v))
     return n, E, L, C
 
 
@@ -54,15 +45,11 @@ class _MonoGuidedAttention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mono_q, mono_k, multi_v):
         n, E, L, C = _attention_args(mono_q, mono_k, multi_v)
-        lib = _lib.load()
-        dev, f32 = mono_q.device, torch.float32
-        q, k, v = _channel_major_q(mono_q), _f32(mono_k), _f32(multi_v)
-        out = torch.empty((n, C, L), dtype=f32, device=dev)  # (both fully written by the call)
-        lse = torch.empty((n, L), dtype=f32, device=dev)
-        with _on_device(dev):
-            rc = lib.gsr_mono_attention(n, E, L, C, q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(), _stream_ptr(dev))
-        if rc != 0:
-            raise RuntimeError(f"gsr_mono_attention failed with code {rc}")
+        dev = mono_q.device
+        q, k, v = _channel_major_q(mono_q), f32(mono_k), f32(multi_v)
+        out = torch.empty((n, C, L), dtype=torch.float32, device=dev)  # (both fully written by the call)
+        lse = torch.empty((n, L), dtype=torch.float32, device=dev)
+        launch("gsr_mono_attention", dev, n, E, L, C, q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr())
         ctx.save_for_backward(mono_q, mono_k, multi_v, out, lse)  # O(n L (E + C)); nothing of L x L
         ctx.sizes = (n, E, L, C)
         return out.to(multi_v.dtype)
@@ -74,19 +61,14 @@ class _MonoGuidedAttention(torch.autograd.Function):
         need_q, need_k, need_v = ctx.needs_input_grad
         if not (need_q or need_k or need_v):
             return None, None, None
-        lib = _lib.load()
-        dev, f32 = mono_q.device, torch.float32
-        q, k, v, g = _channel_major_q(mono_q), _f32(mono_k), _f32(multi_v), _f32(g_out)
-        d_q = torch.empty((n, E, L), dtype=f32, device=dev) if need_q else None  # (fully written by the call)
-        d_k = torch.empty((n, E, L), dtype=f32, device=dev) if need_k else None
-        d_v = torch.empty((n, C, L), dtype=f32, device=dev) if need_v else None
-        scratch = torch.empty(max(int(lib.gsr_mono_attention_scratch_bytes(n, E, L, C)) // 4, 1), dtype=f32, device=dev)
-        ptr = lambda t: None if t is None else t.data_ptr()
-        with _on_device(dev):
-            rc = lib.gsr_mono_attention_backward(n, E, L, C, q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(), g.data_ptr(),
-                                                 ptr(d_q), ptr(d_k), ptr(d_v), scratch.data_ptr(), _stream_ptr(dev))
-        if rc != 0:
-            raise RuntimeError(f"gsr_mono_attention_backward failed with code {rc}")
+        dev = mono_q.device
+        q, k, v, g = _channel_major_q(mono_q), f32(mono_k), f32(multi_v), f32(g_out)
+        d_q = torch.empty((n, E, L), dtype=torch.float32, device=dev) if need_q else None  # (fully written by the call)
+        d_k = torch.empty((n, E, L), dtype=torch.float32, device=dev) if need_k else None
+        d_v = torch.empty((n, C, L), dtype=torch.float32, device=dev) if need_v else None
+        work = scratch(_lib.load().gsr_mono_attention_scratch_bytes(n, E, L, C), torch.float32, dev)
+        launch("gsr_mono_attention_backward", dev, n, E, L, C, q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(),
+               g.data_ptr(), ptr(d_q), ptr(d_k), ptr(d_v), work.data_ptr())
         return (d_q.permute(0, 2, 1).to(mono_q.dtype) if need_q else None, d_k.to(mono_k.dtype) if need_k else None,
                 d_v.to(multi_v.dtype) if need_v else None)
 

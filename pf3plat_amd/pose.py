@@ -17,8 +17,8 @@ import torch
 from torch import Tensor
 
 from . import _lib
+from ._call import f32, launch, ptr, require_device, scratch
 from .losses import PackedCorrespondences, pack_correspondences
-from .rasterizer import _on_device, _stream_ptr
 
 MIN_MATCHES = 4  # a P3P solve on three matches and one to choose its root (gsr_pnp_min_matches)
 MAX_VIEWS = 8
@@ -48,11 +48,6 @@ def pack_matches(corr) -> PackedCorrespondences:
     return pack_correspondences(corr, conf)
 
 
-def _f32(t: Tensor) -> Tensor:
-    t = t.detach()
-    return t if t.dtype == torch.float32 and t.is_contiguous() else t.to(torch.float32).contiguous()
-
-
 def _pnp_args(xyz, intrinsics_px, packed, points_2d, hypotheses, reprojection_error, confidence_min):
     """The shape checks (before the device is looked at and before the library is loaded), then the device check."""
     if xyz.dim() != 5 or xyz.shape[2] != 3:
@@ -79,24 +74,20 @@ def _pnp_args(xyz, intrinsics_px, packed, points_2d, hypotheses, reprojection_er
     tensors = [xyz, intrinsics_px, packed.ids_i, packed.ids_j, packed.weights, packed.offsets_device]
     if points_2d is not None:
         tensors.append(points_2d)
-    if not all(t.is_cuda for t in tensors):
-        raise RuntimeError("pf3plat_amd pose: tensors must be on a ROCm device (there is no CPU fallback path)")
-    if any(t.device != xyz.device for t in tensors):
-        raise RuntimeError("pnp_ransac: every tensor must be on the same device")
+    require_device("pose", "pnp_ransac", tensors)
     return b, v, h, w
 
 
 def _pnp(xyz, intrinsics_px, packed, points_2d, hypotheses, reprojection_error, confidence_min, seed, return_mask):
     b, v, h, w = _pnp_args(xyz, intrinsics_px, packed, points_2d, hypotheses, reprojection_error, confidence_min)
-    lib = _lib.load()
     dev = xyz.device
     pairs, lists, total = packed.num_pairs, b * packed.num_pairs, packed.offsets[-1]
-    x, k = _f32(xyz), _f32(intrinsics_px)
-    pts = None if points_2d is None else _f32(points_2d)
-    ids_i, ids_j, wgt = packed.ids_i.contiguous(), packed.ids_j.contiguous(), _f32(packed.weights)
+    x, k = f32(xyz), f32(intrinsics_px)
+    pts = None if points_2d is None else f32(points_2d)
+    ids_i, ids_j, wgt = packed.ids_i.contiguous(), packed.ids_j.contiguous(), f32(packed.weights)
     if ids_i.dtype != torch.int64 or ids_j.dtype != torch.int64:
         raise ValueError("pnp_ransac: the packed ids are int64")
-    scratch = torch.empty(max(int(lib.gsr_pnp_ransac_scratch_bytes(b, v, int(hypotheses))) // 8, 1), dtype=torch.int64, device=dev)
+    work = scratch(_lib.load().gsr_pnp_ransac_scratch_bytes(b, v, int(hypotheses)), torch.int64, dev)
     pairwise = torch.empty((b, pairs, 4, 4), dtype=torch.float32, device=dev)
     inliers = torch.empty(lists, dtype=torch.int32, device=dev)
     status = torch.empty(lists, dtype=torch.int32, device=dev)
@@ -104,14 +95,9 @@ def _pnp(xyz, intrinsics_px, packed, points_2d, hypotheses, reprojection_error, 
     mask = torch.empty(total, dtype=torch.uint8, device=dev) if return_mask else None
     n = len(packed.offsets)
     host = (ctypes.c_int32 * n)(*packed.offsets)
-    with _on_device(dev):
-        rc = lib.gsr_pnp_ransac(b, v, h, w, pairs, x.data_ptr(), k.data_ptr(), ids_i.data_ptr(), ids_j.data_ptr(), wgt.data_ptr(),
-                                None if pts is None else pts.data_ptr(), host, packed.offsets_device.data_ptr(), int(hypotheses),
-                                float(reprojection_error), float(confidence_min), int(seed) & 0xffffffff, scratch.data_ptr(),
-                                pairwise.data_ptr(), inliers.data_ptr(), status.data_ptr(), conf.data_ptr(),
-                                None if mask is None else mask.data_ptr(), _stream_ptr(dev))
-    if rc != 0:
-        raise RuntimeError(f"gsr_pnp_ransac failed with code {rc}")
+    launch("gsr_pnp_ransac", dev, b, v, h, w, pairs, x.data_ptr(), k.data_ptr(), ids_i.data_ptr(), ids_j.data_ptr(), wgt.data_ptr(), ptr(pts),
+           host, packed.offsets_device.data_ptr(), int(hypotheses), float(reprojection_error), float(confidence_min),
+           int(seed) & 0xffffffff, work.data_ptr(), pairwise.data_ptr(), inliers.data_ptr(), status.data_ptr(), conf.data_ptr(), ptr(mask))
     return pairwise, inliers, status, conf, mask
 
 
@@ -142,18 +128,10 @@ def synchronize_cameras(pairwise: Tensor, confidence: Tensor, num_views: int) ->
     b = pairwise.shape[0]
     if tuple(confidence.shape) != (pairs * b,):
         raise ValueError(f"synchronize_cameras: expected confidence (P b,) = ({pairs * b},), got {tuple(confidence.shape)}")
-    if not (pairwise.is_cuda and confidence.is_cuda):
-        raise RuntimeError("pf3plat_amd pose: tensors must be on a ROCm device (there is no CPU fallback path)")
-    if pairwise.device != confidence.device:
-        raise RuntimeError("synchronize_cameras: every tensor must be on the same device")
-    lib = _lib.load()
-    dev = pairwise.device
-    pw, cf = _f32(pairwise), _f32(confidence)
-    out = torch.empty((b, v, 4, 4), dtype=torch.float32, device=dev)
-    with _on_device(dev):
-        rc = lib.gsr_camera_sync(b, v, pw.data_ptr(), cf.data_ptr(), out.data_ptr(), _stream_ptr(dev))
-    if rc != 0:
-        raise RuntimeError(f"gsr_camera_sync failed with code {rc}")
+    require_device("pose", "synchronize_cameras", (pairwise, confidence))
+    pw, cf = f32(pairwise), f32(confidence)
+    out = torch.empty((b, v, 4, 4), dtype=torch.float32, device=pairwise.device)
+    launch("gsr_camera_sync", pairwise.device, b, v, pw.data_ptr(), cf.data_ptr(), out.data_ptr())
     return out
 
 
@@ -215,10 +193,7 @@ def _refine_args(sync_abspose, delta, gamma):
     if isinstance(gamma, Tensor) and gamma.numel() != 1:
         raise ValueError(f"refine_poses: expected gamma with one element, got {tuple(gamma.shape)}")
     tensors = [sync_abspose, delta] + ([gamma] if isinstance(gamma, Tensor) else [])
-    if not all(t.is_cuda for t in tensors):
-        raise RuntimeError("pf3plat_amd pose: tensors must be on a ROCm device (there is no CPU fallback path)")
-    if any(t.device != sync_abspose.device for t in tensors):
-        raise RuntimeError("refine_poses: every tensor must be on the same device")
+    require_device("pose", "refine_poses", tensors)
     return b, v
 
 
@@ -229,19 +204,15 @@ class _RefinePoses(torch.autograd.Function):
         rows, stride = _delta_rows(delta)
         if b * v * max(stride, 16) > 0x7fffffff:
             raise ValueError("refine_poses: more than 2^31 - 1 elements in the poses or in delta as strided")
-        lib = _lib.load()
-        dev, f32 = sync_abspose.device, torch.float32
-        sync = _f32(sync_abspose)
+        dev = sync_abspose.device
+        sync = f32(sync_abspose)
         if isinstance(gamma, Tensor):
-            g = gamma.detach().to(f32).reshape(1)
+            g = gamma.detach().to(torch.float32).reshape(1)
         else:
-            g = torch.full((1,), float(gamma), dtype=f32, device=dev)
-        c2w = torch.empty((b, v, 4, 4), dtype=f32, device=dev)  # (both fully written by the call)
-        w2c = torch.empty((b, v, 4, 4), dtype=f32, device=dev)
-        with _on_device(dev):
-            rc = lib.gsr_pose_refine(b, v, sync.data_ptr(), rows.data_ptr(), stride, g.data_ptr(), c2w.data_ptr(), w2c.data_ptr(), _stream_ptr(dev))
-        if rc != 0:
-            raise RuntimeError(f"gsr_pose_refine failed with code {rc}")
+            g = torch.full((1,), float(gamma), dtype=torch.float32, device=dev)
+        c2w = torch.empty((b, v, 4, 4), dtype=torch.float32, device=dev)  # (both fully written by the call)
+        w2c = torch.empty((b, v, 4, 4), dtype=torch.float32, device=dev)
+        launch("gsr_pose_refine", dev, b, v, sync.data_ptr(), rows.data_ptr(), stride, g.data_ptr(), c2w.data_ptr(), w2c.data_ptr())
         ctx.save_for_backward(sync, delta, g)
         ctx.gamma_like = gamma if isinstance(gamma, Tensor) else None
         ctx.sizes = (b, v)
@@ -255,18 +226,13 @@ class _RefinePoses(torch.autograd.Function):
         _, need_delta, need_gamma = ctx.needs_input_grad
         if not (need_delta or need_gamma) or (g_c2w is None and g_w2c is None) or b == 0:
             return None, None, None
-        lib = _lib.load()
-        dev, f32 = sync.device, torch.float32
+        dev = sync.device
         rows, stride = _delta_rows(delta)
-        ups = [None if t is None else _f32(t) for t in (g_c2w, g_w2c)]
-        d_delta = torch.empty((b, v, 9), dtype=f32, device=dev) if need_delta else None  # (fully written by the call)
-        d_gamma = torch.empty((1,), dtype=f32, device=dev) if need_gamma else None
-        ptr = lambda t: None if t is None else t.data_ptr()
-        with _on_device(dev):
-            rc = lib.gsr_pose_refine_backward(b, v, sync.data_ptr(), rows.data_ptr(), stride, g.data_ptr(), ptr(ups[0]), ptr(ups[1]),
-                                              ptr(d_delta), ptr(d_gamma), _stream_ptr(dev))
-        if rc != 0:
-            raise RuntimeError(f"gsr_pose_refine_backward failed with code {rc}")
+        ups = [None if t is None else f32(t) for t in (g_c2w, g_w2c)]
+        d_delta = torch.empty((b, v, 9), dtype=torch.float32, device=dev) if need_delta else None  # (fully written by the call)
+        d_gamma = torch.empty((1,), dtype=torch.float32, device=dev) if need_gamma else None
+        launch("gsr_pose_refine_backward", dev, b, v, sync.data_ptr(), rows.data_ptr(), stride, g.data_ptr(), ptr(ups[0]), ptr(ups[1]),
+               ptr(d_delta), ptr(d_gamma))
         like = ctx.gamma_like
         return (None, d_delta.to(delta.dtype) if need_delta else None,
                 d_gamma.to(like.dtype).reshape(like.shape) if need_gamma else None)
@@ -304,17 +270,9 @@ def pose_errors(c2w_pred: Tensor, extrinsics_gt: Tensor) -> PoseErrors:
         raise ValueError(f"pose_errors: c2w_pred is of (b, v) = ({b}, {v}), extrinsics_gt of {tuple(extrinsics_gt.shape[:2])}")
     if b * v * 16 > 0x7fffffff:
         raise ValueError("pose_errors: more than 2^31 - 1 elements in the poses")
-    if not (c2w_pred.is_cuda and extrinsics_gt.is_cuda):
-        raise RuntimeError("pf3plat_amd pose: tensors must be on a ROCm device (there is no CPU fallback path)")
-    if c2w_pred.device != extrinsics_gt.device:
-        raise RuntimeError("pose_errors: every tensor must be on the same device")
-    lib = _lib.load()
-    dev = c2w_pred.device
-    pred, gt = _f32(c2w_pred), _f32(extrinsics_gt)
-    out = torch.empty((3, b), dtype=torch.float32, device=dev)
-    with _on_device(dev):
-        rc = lib.gsr_pose_errors(b, v, pred.data_ptr(), gt.data_ptr(), out.data_ptr(), _stream_ptr(dev))
-    if rc != 0:
-        raise RuntimeError(f"gsr_pose_errors failed with code {rc}")
+    require_device("pose", "pose_errors", (c2w_pred, extrinsics_gt))
+    pred, gt = f32(c2w_pred), f32(extrinsics_gt)
+    out = torch.empty((3, b), dtype=torch.float32, device=c2w_pred.device)
+    launch("gsr_pose_errors", c2w_pred.device, b, v, pred.data_ptr(), gt.data_ptr(), out.data_ptr())
     out = out.to(c2w_pred.dtype)
     return PoseErrors(out[0], out[1], out[2])

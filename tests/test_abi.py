@@ -74,7 +74,8 @@ def test_source_stamp_covers_every_file_the_library_is_built_from(tmp_path):
     # (preprocess_bwd.inc: the text of k_preprocess_bwd, which gsr_hip.hip compiles twice)
     assert {os.path.basename(s) for s in _lib.hip_sources()} == {
         "gsr_hip.hip", "gsr_common.h", "gsr_binning.h", "gsr_tiles_fwd.h", "gsr_backward.h", "gsr_cameras.h", "gsr_covariance.h",
-        "gsr_image.h", "gsr_adapter.h", "gsr_pose_loss.h", "gsr_cost_volume.h", "gsr_pnp_solver.h", "gsr_coarse_pose.h", "preprocess_bwd.inc", "gsr.h"}
+        "gsr_image.h", "gsr_adapter.h", "gsr_pose_loss.h", "gsr_cost_volume.h", "gsr_lift.h", "gsr_mono_attention.h", "gsr_attention.h",
+        "gsr_pnp_solver.h", "gsr_coarse_pose.h", "gsr_pose_refine.h", "preprocess_bwd.inc", "gsr.h"}
     with open(_lib.SRC) as f:  # every kernel lives in a header
         assert not [line for line in f if "__global__" in line]
     # ... and the stamp's file set IS the include graph of gsr_hip.hip: no file in csrc/ that changes the stamp without being

@@ -143,9 +143,12 @@ def test_symbols_are_declared_exported_and_listed():
         assert name in _lib.EXPORTED_SYMBOLS and hasattr(exported, name) and f"{name}(" in header, name
     assert len(lib.gsr_attention_scratch_bytes.argtypes) == 5 and len(lib.gsr_attention.argtypes) == 15
     assert len(lib.gsr_attention_backward.argtypes) == 20
-    with open(os.path.join(os.path.dirname(_lib.SRC), "gsr_cost_volume.h")) as f:  # the kernels live next to the mono kernels
-        text = f.read()
-    assert all(k in text for k in ("k_mha_fwd", "k_mha_bwd_kv", "k_mha_bwd_q", "k_mono_attn_fwd", "k_mono_attn_bwd_kv", "k_mono_attn_bwd_q"))
+    texts = []
+    for name in ("gsr_attention.h", "gsr_mono_attention.h"):  # the operator's own header, and the mono kernels' that it builds on
+        with open(os.path.join(os.path.dirname(_lib.SRC), name)) as f:
+            texts.append(f.read())
+    assert all(k in texts[0] for k in ("k_mha_fwd", "k_mha_bwd_kv", "k_mha_bwd_q", '#include "gsr_mono_attention.h"'))
+    assert all(k in texts[1] for k in ("k_mono_attn_fwd", "k_mono_attn_bwd_kv", "k_mono_attn_bwd_q"))
 
 
 def test_scratch_size_and_invalid_arguments_are_host_arithmetic():

@@ -156,7 +156,7 @@ def test_symbols_are_declared_exported_and_listed():
     for name in ("gsr_lift_depth", "gsr_lift_depth_backward", "gsr_lift_scratch_bytes", "gsr_plucker_rays"):
         assert name in _lib.EXPORTED_SYMBOLS and hasattr(exported, name) and f"{name}(" in header, name
     assert len(lib.gsr_lift_depth.argtypes) == 15 and len(lib.gsr_lift_depth_backward.argtypes) == 16 and len(lib.gsr_plucker_rays.argtypes) == 8
-    with open(os.path.join(os.path.dirname(_lib.SRC), "gsr_cost_volume.h")) as f:  # the kernels live where the issue put them
+    with open(os.path.join(os.path.dirname(_lib.SRC), "gsr_lift.h")) as f:  # the operator's own header
         text = f.read()
     assert all(k in text for k in ("k_lift_fwd", "k_lift_bwd", "k_lift_intr_finish", "k_plucker_rays"))
 

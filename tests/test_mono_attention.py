@@ -104,7 +104,7 @@ def test_symbols_are_declared_exported_and_listed():
         assert name in _lib.EXPORTED_SYMBOLS and hasattr(exported, name) and f"{name}(" in header, name
     assert len(lib.gsr_mono_attention_scratch_bytes.argtypes) == 4 and len(lib.gsr_mono_attention.argtypes) == 10
     assert len(lib.gsr_mono_attention_backward.argtypes) == 15
-    with open(os.path.join(os.path.dirname(_lib.SRC), "gsr_cost_volume.h")) as f:  # the kernels live where the issue put them
+    with open(os.path.join(os.path.dirname(_lib.SRC), "gsr_mono_attention.h")) as f:  # the operator's own header
         text = f.read()
     assert all(k in text for k in ("k_mono_attn_fwd", "k_mono_attn_bwd_kv", "k_mono_attn_bwd_q", "__builtin_amdgcn_mfma_f32_32x32x2f32"))
 
