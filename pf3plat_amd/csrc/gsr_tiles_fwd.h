@@ -423,6 +423,23 @@ struct BlendLds {
   float4 sXY[4][kFB / 2], sAB[4][kFB / 2], sCO[4][kFB / 2], sRG[4][kFB / 2], sBE[4][kFB / 2];
   float sP[2][kFwdWaves][64];  // segment products of batch b in sP[b & 1]
 };
+// One record into entry e of slot sb, conic moved to the exp2 domain: blend_range's put_records for any entry instead of "lane =
+// entry" (the rank pass of k_tile_fwd_prefix: e = the entry's position in the list).  put_records keeps its own text: written through
+// this function the blend of EVERY tile kernel compiled to other instructions, and k_tile_fwd and the 80-register instances are to
+// stay the code they were.
+__device__ __forceinline__ void park_record(BlendLds& lds, const int sb, const int e, float4 q, float2 q2, const float4& c) {
+  q.z = (-0.5f * kLog2e) * q.z; q.w = (-kLog2e) * q.w; q2.x = (-0.5f * kLog2e) * q2.x;  // to_exp2_domain
+  const int o = (e >> 1) * 4 + (e & 1);
+  float* xy = reinterpret_cast<float*>(lds.sXY[sb]); float* ab = reinterpret_cast<float*>(lds.sAB[sb]);
+  float* co = reinterpret_cast<float*>(lds.sCO[sb]); float* rg2 = reinterpret_cast<float*>(lds.sRG[sb]);
+  float* be = reinterpret_cast<float*>(lds.sBE[sb]);
+  xy[o] = q.x; xy[o + 2] = q.y; ab[o] = q.z; ab[o + 2] = q.w; co[o] = q2.x; co[o + 2] = q2.y;
+  rg2[o] = c.x; rg2[o + 2] = c.y; be[o] = c.z; be[o + 2] = c.w;
+}
+// k_tile_fwd_prefix hands the first batches of a list to its blend through LDS (blend_range, `primed`): the ids of the first
+// kPrimedIds positions - what the prologue reads for batches 0 ... 9 - lie over sP, which nobody touches before the first eval
+constexpr int kPrimedIds = 10 * kFB;
+static_assert(sizeof(uint32_t) * kPrimedIds <= sizeof(BlendLds::sP), "the handed-over ids fit the segment products' area");
 // the four waves' partial results on their way to wave 0 (blend_finish): used once, after the last batch - k_tile_fwd_prefix lays
 // it over its key array, which is dead by then (6 KB less: five workgroups per CU instead of four)
 struct BlendFin {
@@ -442,7 +459,10 @@ struct BlendAcc {
 
 // Batches [b0, nbat) of the list `plist` (entries at positions >= n read as null records), 256 threads.  Returns true when every
 // pixel's loop has stopped (workgroup-uniform: the decision is taken on bit-identical values in all four waves).
-template <bool kExtra, bool kTight = false>  // kTight: an instance built for 80 registers (see put_records)
+// kPrimed (k_tile_fwd_prefix, the first pass of a list its rank pass has just ranked: b0 == 0): the records of batches 0 and 1 are
+// parked already and the ids of positions < kPrimedIds lie over sP - the prologue reads no id from memory and requests only the
+// batches it holds in registers; the state at the loop's entry is the ordinary prologue's.
+template <bool kExtra, bool kTight = false, bool kPrimed = false>  // kTight: an instance built for 80 registers (see put_records)
 __device__ __forceinline__ bool blend_range(const GeomRec* geom, const float4* rgbc, const uint32_t* plist, const uint32_t n,
                                             const uint32_t b0, const uint32_t nbat, BlendLds& lds, BlendAcc& s, const float pxf,
                                             const float pyf) {
@@ -536,7 +556,7 @@ __device__ __forceinline__ bool blend_range(const GeomRec* geom, const float4* r
     asm volatile("" : "+v"(CR), "+v"(CG), "+v"(CB), "+v"(Tmin), "+v"(last));
     if (kExtra) asm volatile("" : "+v"(CE));
   };
-  auto put_records = [&](int sb, float4 q, float2 q2, const float4& c) {  // lane = entry of the batch
+  auto put_records = [&](int sb, float4 q, float2 q2, const float4& c) {  // lane = entry of the batch (park_record: any entry)
     q.z = (-0.5f * kLog2e) * q.z; q.w = (-kLog2e) * q.w; q2.x = (-0.5f * kLog2e) * q2.x;  // to_exp2_domain
     // (kTight: the offset formed here, from an opaque copy of the lane number, every time - held across the loops it was the one
     // value the 80-register instance spilled, and its reload a trip to memory in every tile's blend prologue)
@@ -565,7 +585,16 @@ __device__ __forceinline__ bool blend_range(const GeomRec* geom, const float4* r
     int lp = lane;
     if (kTight) asm volatile("" : "+v"(lp));
     const auto list_id = [&](uint32_t b) { return (b * kFB + lp < n) ? plist[b * kFB + lp] : 0u; };
-    if (lp < kFB) {
+    if constexpr (kPrimed) {  // w = 0 / 1 request b0 + 4 / b0 + 5, w = 2 / 3 request b0 + 2 / b0 + 3
+      if (lp < kFB) {
+        const uint32_t* sid = reinterpret_cast<const uint32_t*>(&sP[0][0][0]);
+        const auto handed_id = [&](uint32_t b) { return (b * kFB + lp < n) ? sid[b * kFB + lp] : 0u; };
+        const uint32_t w = (uint32_t)(wave - (int)b0) & 3u, bq = b0 + (w < 2 ? w + 4 : w);
+        const uint32_t idq = handed_id(bq);
+        id_next = handed_id(bq + 4);
+        stage_batch(geom, rgbc, n, bq * kFB, lane, idq, kExtra, sg, sg2, sc);
+      }
+    } else if (lp < kFB) {
       const uint32_t w = (uint32_t)(wave - (int)b0) & 3u, bw = b0 + w;
       if (w < 2) {
         const uint32_t id0 = list_id(bw), id4 = list_id(bw + 4);
@@ -767,6 +796,9 @@ __global__ __launch_bounds__(kFwdThreads, (kLds == 2048 && kGather && !kExtra) ?
 #ifndef GSR_LONG_RUN
 #define GSR_LONG_RUN 24  // runs of more keys than this are copied by the whole workgroup (k_tile_fwd_prefix)
 #endif
+#ifndef GSR_RUN_STEP
+#define GSR_RUN_STEP 18  // keys of a short run requested together (k_tile_fwd_prefix, the instances built for four waves per SIMD)
+#endif
 constexpr int kPrefix = GSR_PREFIX;  // list positions ranked before the blend starts (a multiple of kFB)
 static_assert(kPrefix % kFB == 0 && kPrefix >= 2 * kFB, "the prefix is whole batches");
 
@@ -891,7 +923,31 @@ __global__ __launch_bounds__(kFwdThreads, kCompact ? 6 : 4) void k_tile_fwd_pref
     if (is_long)
       ldesc[dbase + (uint32_t)__popcll(lmask & ((1ull << lane) - 1ull))] = make_uint4(bb0 + e0.x, start0, e0.y, kbase + lincl - lcnt);
   }
-  if (has && !miss && fits && !is_long) {
+  if (!kCompact && has && !miss && fits && !is_long) {
+    // kRunStep keys per step as 16-byte loads ALL requested before the first key is parked: a step is one round trip to
+    // memory (~1 us under this launch's load) and the four resident tiles of a CU are in this phase together, with nothing to hide
+    // it.  Runs average 5 keys but one in four is longer than 6: at six keys per step practically every wave made two dependent
+    // trips and half the tiles three.  The loads may run one key past the run (the buffer is padded), never further.
+    constexpr uint32_t kRunStep = GSR_RUN_STEP;
+    static_assert(kRunStep % 2 == 0 && kRunStep >= 6, "whole 16-byte loads");
+    const unsigned long long* src = p.keys + bb0 + e0.x;
+    unsigned long long* d0 = sk + start0;
+    for (uint32_t j = 0; j < e0.y; j += kRunStep) {
+      ull2 r[kRunStep / 2];
+#pragma unroll
+      for (uint32_t u = 0; u < kRunStep / 2; ++u) {
+        r[u] = ull2{0ull, 0ull};
+        if (j + 2 * u < e0.y) r[u] = *reinterpret_cast<const ull2*>(src + j + 2 * u);
+      }
+      unsigned long long* d = d0 + j;
+#pragma unroll
+      for (uint32_t u = 0; u < kRunStep / 2; ++u) {
+        if (j + 2 * u < e0.y) take(d + 2 * u, r[u].x);
+        if (j + 2 * u + 1 < e0.y) take(d + 2 * u + 1, r[u].y);
+      }
+    }
+  }
+  if (kCompact && has && !miss && fits && !is_long) {  // (the 80-register instance: six keys per step, as it was)
     // six keys per step as three 16-byte loads issued together; the loads may run one key past the run (the buffer is padded)
     const unsigned long long* src = p.keys + bb0 + e0.x;
     unsigned long long* d0 = sk + start0;
@@ -1030,8 +1086,20 @@ __global__ __launch_bounds__(kFwdThreads, kCompact ? 6 : 4) void k_tile_fwd_pref
   }
   // finish by ranking: every entry counts the smaller keys of its own bucket (keys are unique: they carry the Gaussian index) and goes
   // straight to its final slot in the global list; four bucket members per step, requested together
-  auto rank_positions = [&](uint32_t k0, uint32_t k1) {
+  // `prime` (the first rank pass of the instances built for four waves per SIMD): the pass knows every entry's final position
+  // and its Gaussian in the same thread, so what the blend's prologue would fetch through the list goes to it through LDS - the
+  // ids of positions < kPrimedIds, and the RECORDS of batches 0 and 1, requested here (their trip to memory runs under the rest of
+  // this pass) and parked where put_records parks them; positions from k1 on inside those two batches get the null record.
+  // A position below 2 kFB is ranked by a thread's FIRST key: a key and its rank lie in the same bucket of at most kSpanMax keys.
+  static_assert(kSpanMax + 2 * kFB <= kSortThreads, "a thread holds at most one record of batches 0 and 1");
+  auto rank_positions = [&](uint32_t k0, uint32_t k1, const bool prime) {
+    const GeomRec* geom = p.geom + (size_t)v * p.d.num_gaussians;  // (used under `prime` only)
+    const float4* rgbc = p.rgbc + (size_t)v * p.d.num_gaussians;
     uint32_t* out = p.point_list + obase;
+    uint32_t* sid = reinterpret_cast<uint32_t*>(&blds.sP[0][0][0]);
+    float4 hg = make_float4(0, 0, 0, 0), hc = hg;
+    float2 hg2 = make_float2(0, 0);
+    int held = -1;
     for (int k = (int)k0 + tid; k < (int)k1; k += kSortThreads) {
       const unsigned long long key = sk[k];
       const uint32_t b = ((uint32_t)(key >> 32) - dlo) >> shift;
@@ -1043,9 +1111,21 @@ __global__ __launch_bounds__(kFwdThreads, kCompact ? 6 : 4) void k_tile_fwd_pref
                 ((j + 3 < be && k3_ < key) ? 1 : 0);
       }
       out[rank] = (uint32_t)key;
+      if (prime) {
+        if (rank < kPrimedIds) sid[rank] = (uint32_t)key;
+        if (rank < 2 * kFB) {
+          stage_batch(geom, rgbc, 1u, 0u, 0, (uint32_t)key, kExtra, hg, hg2, hc);
+          held = rank;
+        }
+      }
+    }
+    if (prime) {
+      if (held >= 0) park_record(blds, held / kFB, held % kFB, hg, hg2, hc);
+      if (tid < 2 * kFB && tid >= (int)k1) park_record(blds, tid / kFB, tid % kFB, make_float4(0, 0, 0, 0), make_float2(0, 0), make_float4(0, 0, 0, 0));
     }
   };
-  if (bucketed) rank_positions(0u, ranked);
+  const bool primed = !kCompact && bucketed;  // workgroup-uniform
+  if (bucketed) rank_positions(0u, ranked, primed);
   GSR_STAMP(5);
   GSR_STAMP(6);
   __builtin_amdgcn_s_setprio(0);
@@ -1096,11 +1176,15 @@ __global__ __launch_bounds__(kFwdThreads, kCompact ? 6 : 4) void k_tile_fwd_pref
     // pass 0: the whole batches inside the ranked prefix (all of the list when everything was ranked); pass 1: from there to the end
     const bool whole = ranked >= n;
     const uint32_t b1 = whole ? nbat : ranked / kFB;
-    bool done = blend_range<kExtra, kCompact>(geom, rgbc, plist, whole ? n : b1 * kFB, b0, b1, blds, acc, (float)pxi, (float)pyi);
+    // (the primed entry as an instantiation of its own beside the ordinary one, which the second pass takes: the ordinary one is
+    // also k_tile_fwd's, and stays the code it was)
+    const uint32_t nb = whole ? n : b1 * kFB;
+    bool done = (primed && pass == 0) ? blend_range<kExtra, kCompact, !kCompact>(geom, rgbc, plist, nb, b0, b1, blds, acc, (float)pxi, (float)pyi)
+                                      : blend_range<kExtra, kCompact>(geom, rgbc, plist, nb, b0, b1, blds, acc, (float)pxi, (float)pyi);
     done = done || whole || __all(acc.Tb < 0.0001f);  // (Tb: the same bits in all four waves)
     if (done) break;
     __builtin_amdgcn_s_setprio(2);
-    rank_positions(ranked, n);
+    rank_positions(ranked, n, false);
     __builtin_amdgcn_s_setprio(0);
     ranked = n;
     b0 = b1;
