@@ -703,6 +703,57 @@ int gsr_attention_backward(int B, int H, int N, int M, int D, float scale, const
                            const int64_t* k_strides, const float* v, const int64_t* v_strides, const float* out, const float* lse,
                            const float* dL_dout, float* dL_dq, float* dL_dk, float* dL_dv, void* scratch, void* stream);
 
+/* Match assignment: the tail of LightGlue - MatchAssignment.forward after its two projections, sigmoid_log_double_softmax and
+ * filter_matches (reference src/model/LightGlue/lightglue/lightglue.py:259-312) and the list building of :586-597 - for a whole batch
+ * of (pair, scene) lists at once.  Forward only (the reference runs the matcher under no_grad).
+ * A call has L >= 1 lists; list l has m_l >= 0 keypoints of the first image and n_l >= 0 of the second.  Operands are packed along
+ *   the keypoint axis, contiguous f32: mdesc0 (sum m_l, d), mdesc1 (sum n_l, d) - the outputs of final_proj, NOT yet divided by
+ *   d ** 0.25 -, z0 (sum m_l), z1 (sum n_l) the matchability logits.  The two offset arrays (L + 1 int32 each, list l is entries
+ *   offsets[l] .. offsets[l + 1]) are given on the host and on the device, as the PnP call takes its own: they come from shapes.
+ *   1 <= d <= 256; offsets_m[L] d and offsets_n[L] d at most 2^31 - 1; `scale` (the reference: d ** -0.5) and `threshold` finite.
+ * With ls = logsigmoid, per list (indices local to the list):
+ *     s[i, j]  = scale * sum_c mdesc0[i, c] mdesc1[j, c]      (the f32 sum over c in order, times scale: one more rounding)
+ *     lr[i]    = log sum_j exp s[i, j]        lc[j] = log sum_i exp s[i, j]
+ *     a[i, j]  = 2 s[i, j] - lc[j] + ls(z1[j])        m0[i] = the lowest j that maximises a[i, .]
+ *     b[i, j]  = 2 s[i, j] - lr[i] + ls(z0[i])        m1[j] = the lowest i that maximises b[., j]
+ *     max0[i]  = a[i, m0[i]] - lr[i] + ls(z0[i])      (the reference's scores[:, :m, :n].max(2).values)
+ *     mutual0[i] = (m1[m0[i]] == i)     mscores0[i] = mutual0 ? exp(max0[i]) : 0     valid0 = mutual0 and mscores0 > threshold
+ *     mutual1[j] = (m0[m1[j]] == j)     mscores1[j] = mutual1 ? mscores0[m1[j]] : 0
+ *     matches0[i] = valid0[i] ? m0[i] : -1            matches1[j] = (mutual1[j] and valid0[m1[j]]) ? m1[j] : -1
+ *   - the reference's lines with the per-row and per-column constants taken out of the two arg-maxima.  In f32 the arg-maxima compare
+ *   2 s + (ls(z) - l)[the other index], one fused rounding, and max0 is formed from s at the arg-maximum in the reference's order of
+ *   operations: ((s - lr[i]) + (s - lc[j])) + (ls(z0[i]) + ls(z1[j])), each s - l as log_softmax forms it, (s - max) - log sum exp(. - max)
+ *   (l is kept as the pair: where a row is peaked s - max is exact).  ls(z) = min(z, 0) - log1p(exp(-|z|)).
+ * Differences from the reference: the dust-bin row and column (scores[:, :-1, -1], scores[:, -1, :-1]) are not computed -
+ *   filter_matches never reads them; the reference divides each operand by d ** 0.25, here one factor multiplies the sum; TIES GO TO
+ *   THE LOWEST INDEX (torch.max promises no order); a list with m_l = 0 or n_l = 0 has no matches: -1 and 0 everywhere, as the
+ *   reference's lines 563-583; NaN or infinite inputs are the caller's error (every index read back stays inside its list).
+ * Outputs: matches0 (sum m_l), matches1 (sum n_l) int32; mscores0, mscores1 f32; and the COMPACT form: for list l the valid
+ *   (i, matches0[i], mscores0[i]) in ascending i in idx0, idx1 (int32), score (f32) at entries offsets_m[l] .. + count[l], count (L)
+ *   int32.  The capacity is sum m_l: no prefix sum crosses lists and nothing is read back; entries past a list's count are not
+ *   written.  With kpts0 (sum m_l, 2), kpts1 (sum n_l, 2) (x, y), both or neither, and an image width w >= 1, the same launch writes
+ *   next to each compact entry ids_i = trunc(y0) w + trunc(x0), ids_j likewise (int64: the reference's `.long()` of
+ *   src/model/encoder/encoder_costvolume.py:340-342) and points (.., 2) = (x0, y0), the sub-pixel point the PnP call takes.
+ * Three launches of one kernel on the caller's stream (one when no list has both sides), no host synchronisation:
+ *   1. statistics: grid over (list, side, block of 128 owned keypoints); the owned descriptors in registers, the other image's
+ *      streamed in tiles of 32 through LDS, each s tile on v_mfma_f32_32x32x2_f32 over the channels in order; lr by the online
+ *      log-sum-exp (a running maximum: scores of any size are safe); lc by the MIRRORED pass, the other half of the grid's rows.
+ *   2. arg-maxima: the same tiling and the same s bits (the same products in the same order, scale at the same place): m0 and m1
+ *      with s there.
+ *   3. filter and compaction: one workgroup per list; rows in ascending chunks of 256 ranked by a workgroup scan.
+ *   `scratch`: gsr_match_assignment_scratch_bytes(L, offsets_m, offsets_n, d) bytes - 16 per keypoint of either image; host
+ *   arithmetic, 0 for sizes the call refuses.  NOTHING of m x n elements exists.  No atomics, no sum across workgroups, expf / logf /
+ *   log1pf the accurate functions: the same bits on every run.
+ * GSR_ERR_INVALID_ARGUMENT, nothing launched: L < 1, d outside 1 .. 256, negative or decreasing offsets, a total times d above
+ *   2^31 - 1, a `scale` or `threshold` that is not finite, a NULL required pointer (kpts0, kpts1, ids_i, ids_j, points may be NULL
+ *   together), keypoints without a positive width or without their three outputs. */
+size_t gsr_match_assignment_scratch_bytes(int L, const int32_t* offsets_m_host, const int32_t* offsets_n_host, int d);
+int gsr_match_assignment(int L, int d, float scale, float threshold, int width, const float* mdesc0, const float* mdesc1, const float* z0,
+                         const float* z1, const int32_t* offsets_m_host, const int32_t* offsets_m_device, const int32_t* offsets_n_host,
+                         const int32_t* offsets_n_device, const float* kpts0, const float* kpts1, void* scratch, int32_t* matches0,
+                         int32_t* matches1, float* mscores0, float* mscores1, int32_t* idx0, int32_t* idx1, float* score, int64_t* ids_i,
+                         int64_t* ids_j, float* points, int32_t* count, void* stream);
+
 /* The refined poses of the encoder (reference src/model/encoder/encoder_costvolume.py:447-450, 460-473, with r6d2mat :189-209 and
  * matrix_to_rotation_6d :223-224, and the three inversions `refine_sync_abspose.inverse()` :492, :530 and `c2w[1].inverse()`
  * src/model/model_wrapper.py:150) and the per-step pose errors (model_wrapper.py:182-190, 306-313, 345;

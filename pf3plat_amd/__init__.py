@@ -36,3 +36,5 @@ from .mono_attention import mono_guided_attention  # noqa: F401,E402
 from . import attention  # noqa: F401,E402
 from .attention import CrossBlock, LearnableFourierPositionalEncoding, SelfBlock, apply_cached_rotary_emb  # noqa: F401,E402
 from .attention import bidirectional_cross_attention, multi_head_attention  # noqa: F401,E402
+from . import matching  # noqa: F401,E402
+from .matching import MatchAssignment, Matches, match_assignment, pack_matched  # noqa: F401,E402

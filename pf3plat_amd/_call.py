@@ -1,4 +1,4 @@
-"""What every ctypes wrapper of an operator (cost_volume, lift, mono_attention, attention, pose, losses) does around its own checks and
+"""What every ctypes wrapper of an operator (cost_volume, lift, mono_attention, attention, matching, pose, losses) does around its own checks and
 allocations: the float32 view of an input, the device check, a scratch array from a byte count, and the library call on the tensors'
 device and torch's current stream.  The rasterizer's path has its own (rasterizer.HipBackend)."""
 from __future__ import annotations

@@ -343,6 +343,11 @@ def load():
     lib.gsr_attention.argtypes = mha_head + [vp] * 3  # ...; out, lse, stream
     lib.gsr_attention_backward.restype = ctypes.c_int  # ...; out, lse, dL_dout, dL_dq, dL_dk, dL_dv, scratch, stream
     lib.gsr_attention_backward.argtypes = mha_head + [vp] * 8
+    lib.gsr_match_assignment_scratch_bytes.restype = ctypes.c_size_t
+    lib.gsr_match_assignment_scratch_bytes.argtypes = [ctypes.c_int, i32p, i32p, ctypes.c_int]  # L, host offsets of either image, d
+    lib.gsr_match_assignment.restype = ctypes.c_int  # L, d; scale, threshold; width; mdesc0, mdesc1, z0, z1; host + device offsets, twice; ...
+    lib.gsr_match_assignment.argtypes = ([ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_int] + [vp] * 4 + [i32p, vp, i32p, vp]
+                                         + [vp] * 15)  # kpts0, kpts1, scratch; matches0/1, mscores0/1, idx0, idx1, score, ids_i, ids_j, points, count; stream
     lib.gsr_pose_refine.restype = ctypes.c_int
     lib.gsr_pose_refine.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, vp, vp, vp, vp]  # b, v; sync_pose, delta, its row stride, gamma, c2w, w2c, stream
     lib.gsr_pose_refine_backward.restype = ctypes.c_int  # ...; gamma, dL_dc2w, dL_dw2c, dL_ddelta, dL_dgamma, stream
@@ -370,6 +375,7 @@ EXPORTED_SYMBOLS = (
     "gsr_mono_attention", "gsr_mono_attention_backward", "gsr_mono_attention_scratch_bytes",
     "gsr_pose_refine", "gsr_pose_refine_backward", "gsr_pose_errors",
     "gsr_attention", "gsr_attention_backward", "gsr_attention_scratch_bytes",
+    "gsr_match_assignment", "gsr_match_assignment_scratch_bytes",
 )
 # The stages of GsrForwardOptions.stage_ms / GsrBackwardOptions.stage_ms as run_forward / run_backward(profile=True) key them (the
 # names a failed debug-mode stage is reported with are the library's: gsr_stage_name).  On images of up to 20 480 tiles (the fused binning path) "preprocess" is the whole binning
