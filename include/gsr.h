@@ -800,6 +800,17 @@ int gsr_pose_errors(int num_scenes, int num_views, const float* c2w_pred, const 
  * four views per set, the windowed binning path), negative on bad dims. */
 int gsr_colour_in_binning(const GsrDims* dims);
 
+/* Debug aid for tests: the order in which the single view's forward tile launch deals the `count` (1 ... 256) tiles of one XCD to
+ * that XCD's workgroups, from what the previous forward left per tile: `walked` entries (tile_total) and `list_length` (ranges).
+ * A tile's list_length is end - start of its `ranges` words where those are a range the tile launch writes for that tile (start ==
+ * tile x slot and at most a slot long, or longer than a slot and in the tail pool behind tiles x slot), and 0 for any other words.
+ * An XCD whose tiles list fewer than 512 keys on average, or with a tile whose words are not what a forward leaves (walked is whole
+ * batches of 32 or the whole list, at most the list, and not 0 of a list with entries), keeps heaviest first, every other round of
+ * 32 mirrored.
+ * order_out[k] = index, inside the XCD's run of tiles, of the tile its k-th workgroup (workgroup 8 k + xcd of the launch) takes.
+ * Host code, integer arithmetic: what the device builds.  A permutation of 0 ... count - 1 whatever the words hold. */
+int gsr_tile_deal_order(const uint32_t* walked, const uint32_t* list_length, int count, uint32_t* order_out);
+
 /* Debug aid for tests: byte offsets of the sub-buffers inside `bin` (status, counts, tile_total, ranges, keys,
  * point_list) and `img` (final_T, n_contrib), then - NINE entries - `bin`'s tile_order: one uint32 per (view, tile), the tile every
  * workgroup of the tile launch took where the forward deals its tiles by the previous call's walked counts (one view of 257 ... 1024

@@ -260,6 +260,8 @@ def load():
     lib.gsr_forward_ex.argtypes = [dp] + [vp] * 12 + [ctypes.POINTER(GsrForwardOptions), vp]
     lib.gsr_colour_in_binning.restype = ctypes.c_int
     lib.gsr_colour_in_binning.argtypes = [dp]
+    lib.gsr_tile_deal_order.restype = ctypes.c_int
+    lib.gsr_tile_deal_order.argtypes = [ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.c_int, ctypes.POINTER(ctypes.c_uint32)]
     lib.gsr_backward_ex.restype = ctypes.c_int
     lib.gsr_backward_ex.argtypes = [dp] + [vp] * 18 + [ctypes.POINTER(GsrBackwardOptions), vp]
     lib.gsr_pose_partials_bytes.restype = ctypes.c_size_t
@@ -376,6 +378,7 @@ EXPORTED_SYMBOLS = (
     "gsr_pose_refine", "gsr_pose_refine_backward", "gsr_pose_errors",
     "gsr_attention", "gsr_attention_backward", "gsr_attention_scratch_bytes",
     "gsr_match_assignment", "gsr_match_assignment_scratch_bytes",
+    "gsr_tile_deal_order",
 )
 # The stages of GsrForwardOptions.stage_ms / GsrBackwardOptions.stage_ms as run_forward / run_backward(profile=True) key them (the
 # names a failed debug-mode stage is reported with are the library's: gsr_stage_name).  On images of up to 20 480 tiles (the fused binning path) "preprocess" is the whole binning

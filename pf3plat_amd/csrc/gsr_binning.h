@@ -505,7 +505,11 @@ __global__ __launch_bounds__(kBinThreads, (!kColor && kMaxT == kBinTwoMaxT) ? 8 
   const int T = p.g.T, N = p.d.num_gaussians;
   if constexpr (kColor) {
     if (row >= p.rows) {  // (workgroup-uniform) one of the kDealBlocks workgroups behind the rows: the tile launch's deal, nothing else
+      const bool dbg = GSR_ABL(p.d.flags, GSR_FLAG_DEBUG_TIMING);  // (stamp slots rows ... rows + 7: behind the binning workgroups')
+      unsigned long long* stamp = dbg_stamps(p, (size_t)row);
+      GSR_STAMP(0);
       build_tile_order(p, row - p.rows, w, lane);
+      GSR_STAMP(1);
       return;
     }
   }

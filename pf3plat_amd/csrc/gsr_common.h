@@ -354,28 +354,198 @@ __host__ __device__ __forceinline__ bool fwd_deal_active(const Params& p) {
 __device__ __forceinline__ uint32_t* tile_order_of(const Params& p) {
   return p.blk_total + ((((size_t)p.d.num_views * p.rows * 4 + 255) & ~(size_t)255) >> 2);
 }
-// K1's side: wave c (0 ... 3) of a workgroup ranks keys 64 c ... 64 c + 63 of XCD `xcd` among the XCD's <= kBalanceMax keys - the
-// keys pass as lane broadcasts, no LDS, no barrier - and stores tile_order[block] = tile for the workgroups that take them.
-__device__ __forceinline__ void build_tile_order_wave(const Params& p, const int xcd, const int c, const int lane) {
-  const int T = p.g.T, cnt = (T >> 3) + (xcd < (T & 7) ? 1 : 0), base = xcd_remap(xcd, T);  // this XCD's tiles: [base, base + cnt)
-  if (cnt > kBalanceMax || 64 * c >= cnt) return;
-  const uint32_t* tot = p.tile_total + base;
-  uint32_t key[4], mine = 0;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int i = lane + 64 * q;
-    key[q] = i < cnt ? deal_key(tot[i], i) : 0u;  // (0: below every key)
-    mine = q == c ? key[q] : mine;
+// ---- The forward's deal by a measured time model.  Stamps of the 1024-tile single view under 24 random and 192 structured deals
+// (docs/KERNEL_HISTORY.md, profiles/r11_deal_model.md; tools/deal_model.py): the four tile workgroups of a compute unit start their
+// blends in the order of their de-phase slots (workgroup >> 8) and END in that order - the tile of slot 3 ended last on 256 of 256
+// units - so what a unit is busy for is not the sum of its tiles' batches: its end, in microseconds, follows
+//     0.143 n0 + 0.143 n1 + 0.121 n2 + 0.699 n3  +  0.00053 l0 + 0.00035 l1 + 0.00025 l2 + 0.00040 l3  (+ a constant)
+// with n_s the batches the tile of slot s walks and l_s its list length (least squares over half of the deals; on the other half
+// the modelled slowest unit follows the stamped end of the launch with r = 0.86 - 0.91, the largest batch sum with r = 0.41).
+// deal_term is that cost of one tile in one slot in units of 2^-16 us, on the previous call's walked entries (batches x 32:
+// tile_total) and list length (ranges); both clamped, so that a unit's four terms and a shift by 5 stay inside 32 bits whatever
+// the words hold.  Integer arithmetic: the host's answer (gsr_tile_deal_order, for the tests) is the device's.
+constexpr int kDealPasses = 8;          // exchanges per XCD at the most (below)
+constexpr int kDealMaxTiles = 128;      // tiles of an XCD the model deals: four slots x 32 units (fwd_deal_active: T <= 4 kCUs)
+constexpr uint32_t kDealClamp = 0x3fffu;
+// The coefficients were measured on tiles that list 615 - 1663 keys and walk 7 - 14 batches.  Below that range nothing says that a
+// unit ends as the model has it, and a light tile launch is not bound by its blends: an XCD whose tiles listed fewer than
+// kDealMinMeanList keys on average in the previous call (a fresh workspace lists none) keeps the shipped order.
+constexpr uint32_t kDealMinMeanList = 512u;
+__host__ __device__ __forceinline__ uint32_t deal_term(const int slot, const uint32_t walked, const uint32_t len) {
+  const uint32_t wn = slot == 3 ? 1432u : slot == 2 ? 249u : 294u, wl = slot == 0 ? 35u : slot == 1 ? 23u : slot == 2 ? 17u : 26u;
+  return wn * (walked < kDealClamp ? walked : kDealClamp) + wl * (len < kDealClamp ? len : kDealClamp);
+}
+// A tile's list length from the words in `ranges`: counted only where the words are a range this plan's tile launch writes for that
+// tile - its own slot of `stride` entries, or a longer list in the tail pool; (0, 0) after a tile that could not place its list.
+// Anything else (a workspace no forward has run in yet holds whatever the allocator left) lists nothing, and an XCD of such
+// words keeps the shipped order (kDealMinMeanList).
+__host__ __device__ __forceinline__ uint32_t deal_list_length(const uint2 r, const uint32_t tile, const uint32_t stride, const uint32_t tail_off) {
+  const uint32_t n = r.y - r.x;
+  const bool own = r.x == tile * stride && n <= stride, tail = r.x >= tail_off && n > stride;
+  return own || tail ? n : 0u;
+}
+// Are a tile's two words what a forward leaves?  Its blend walks whole batches of 32 entries or its whole list, never more than
+// the list and never nothing of a list that has entries.  An XCD with one tile whose words are not (a hint from elsewhere, a
+// workspace no forward has run in) keeps the shipped order.
+__host__ __device__ __forceinline__ bool deal_words_plausible(const uint32_t walked, const uint32_t len) {
+  return walked <= len && ((walked & 31u) == 0u || walked == len) && (walked != 0u || len == 0u);
+}
+// What a candidate exchange leaves on the costlier of its two units: tile a (slot sa of the unit that costs cw) against tile b
+// (slot sb of a unit that costs cd).
+__host__ __device__ __forceinline__ uint32_t deal_exchange(const uint32_t cw, const uint32_t cd, const int sa, const uint32_t wa, const uint32_t la,
+                                                           const int sb, const uint32_t wb, const uint32_t lb) {
+  const uint32_t nw = cw - deal_term(sa, wa, la) + deal_term(sa, wb, lb), nd = cd - deal_term(sb, wb, lb) + deal_term(sb, wa, la);
+  return nw > nd ? nw : nd;
+}
+// The XCD's k-th workgroup (k = workgroup >> 3) runs in slot k >> 5 on unit k & 31 (observed dispatch order; speed only).  The deal:
+//   1. the shipped order - heaviest first by deal_key, every other round mirrored (deal_position); that is all for an XCD
+//      of short lists (kDealMinMeanList);
+//   2. up to kDealPasses times: the costliest unit (lowest index on a tie) gives one of its tiles for a tile of another unit - the
+//      exchange that leaves the smaller cost on the costlier of the two units, if that is below what the unit costs now (ties: the
+//      lowest lane, its first tile before its second, the lowest slot of the costly unit); no such exchange: done.
+// A permutation of the XCD's tiles whatever the words hold: step 1 is one (deal_key's low bits), step 2 only exchanges.
+// The slot order inside a unit is part of step 2's moves only through exchanges with other units; on the measured deals 8, 32 and
+// 400 passes ended alike (K2 23.3 - 23.5 us against the shipped order's 23.5 - 24.2), so a search over the 24 orders is not made.
+// Host statement (serial), the reference of the tests: out[k] = index inside the XCD of the tile of its k-th workgroup.
+static inline void tile_deal_order_host(const uint32_t* walked, const uint32_t* len, const int cnt, uint32_t* out) {
+  auto key = [&](int i) { return (((walked[i] < 0xfffffeu ? walked[i] : 0xfffffeu) + 1u) << 8) | (uint32_t)(255 - i); };
+  auto pos = [&](int k) { const int r = k >> 5, in = k & 31, ln = cnt - (r << 5) < 32 ? cnt - (r << 5) : 32; return (r << 5) + ((r & 1) ? ln - 1 - in : in); };
+  for (int i = 0; i < cnt; ++i) {
+    int rank = 0;
+    for (int j = 0; j < cnt; ++j) rank += key(j) > key(i) ? 1 : 0;
+    out[pos(rank)] = (uint32_t)i;  // (deal_position is its own inverse)
   }
-  int rank = 0;  // keys above mine = my position in heaviest-first order
+  if (cnt > kDealMaxTiles) return;
+  uint32_t listed = 0;
+  bool plausible = true;
+  for (int i = 0; i < cnt; ++i) {
+    listed += len[i] < kDealClamp ? len[i] : kDealClamp;
+    plausible = plausible && deal_words_plausible(walked[i], len[i]);
+  }
+  if (!plausible || listed < kDealMinMeanList * (uint32_t)cnt) return;  // (outside the measured range: the shipped order)
+  for (int pass = 0; pass < kDealPasses; ++pass) {
+    uint32_t cost[32] = {};
+    for (int k = 0; k < cnt; ++k) cost[k & 31] += deal_term(k >> 5, walked[out[k]], len[out[k]]);
+    int worst = 0;
+    for (int c = 1; c < 32; ++c) worst = cost[c] > cost[worst] ? c : worst;
+    uint32_t best = cost[worst];
+    int bk = -1, bka = -1;
+    for (int lane = 0; lane < 64; ++lane)
+      for (int sel = 0; sel < 2; ++sel) {
+        const int k = lane + 64 * sel;
+        if (k >= cnt || (k & 31) == worst) continue;
+        for (int sa = 0; sa < 4; ++sa) {
+          const int ka = 32 * sa + worst;
+          if (ka >= cnt) continue;
+          const uint32_t m = deal_exchange(cost[worst], cost[k & 31], sa, walked[out[ka]], len[out[ka]], k >> 5, walked[out[k]], len[out[k]]);
+          if (m < best) { best = m; bk = k; bka = ka; }
+        }
+      }
+    if (bk < 0) break;
+    const uint32_t t = out[bk];
+    out[bk] = out[bka];
+    out[bka] = t;
+  }
+}
+// K1's side, ONE wave per XCD (no LDS, no barrier: everything passes between lanes - DPP maxima, lane reads by scalar index, one
+// LDS permute per pass): lane l holds the tiles of workgroups l and l + 64 of the XCD - slots (l >> 5) and 2 + (l >> 5) of unit
+// l & 31.  A lone wave issues an instruction every 5 - 7 cycles: ranking 128 keys and finding each workgroup's tile are ~1 700
+// instructions, a pass ~200.  Stamped on the 300 k view: the deal workgroups end 14.9 - 15.4 us after the launch's first workgroup
+// starts, the colour waves 25.6 us (a first form - 16 passes, every reduction and broadcast an LDS permute - ended at 23.1 - 24.7
+// us and made the forward 0.6 us SLOWER than the shipped order).  kDealPasses = 8: on the CPU replay of the headline's counts the
+// first 8 exchanges per XCD bring the modelled slowest unit from 23.37 to 22.93 us, 32 to 22.68 (the search ends by itself after
+// ~36), and imposed on the device through the hint 8, 32 and all of them measured alike.
+__device__ __forceinline__ void build_tile_order_model(const Params& p, const int xcd, const int lane) {
+  static_assert(4 * kCUs / 8 <= kDealMaxTiles, "fwd_deal_active's calls fit the model's 128 tiles per XCD");
+  const int T = p.g.T, cnt = (T >> 3) + (xcd < (T & 7) ? 1 : 0), base = xcd_remap(xcd, T);  // this XCD's tiles: [base, base + cnt)
+  if (cnt > kDealMaxTiles) return;
+  const uint32_t* tot = p.tile_total + base;
+  const uint2* rng = p.ranges + base;
+  // 1. the shipped order: rank of my two keys among all, then the tile whose rank my workgroups take
+  uint32_t key[2];
+  int rank[2] = {0, 0}, tile[2] = {0, 0};
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
+  for (int q = 0; q < 2; ++q) key[q] = lane + 64 * q < cnt ? deal_key(tot[lane + 64 * q], lane + 64 * q) : 0u;  // (0: below every key)
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
     if (64 * q >= cnt) break;
 #pragma unroll 8
-    for (int j = 0; j < 64; ++j) rank += (uint32_t)__builtin_amdgcn_readlane((int)key[q], j) > mine ? 1 : 0;
+    for (int j = 0; j < 64; ++j) {
+      const uint32_t kj = (uint32_t)__builtin_amdgcn_readlane((int)key[q], j);
+      rank[0] += kj > key[0] ? 1 : 0;
+      rank[1] += kj > key[1] ? 1 : 0;
+    }
   }
-  const int i = lane + 64 * c;
-  if (i < cnt) tile_order_of(p)[(deal_position(rank, cnt) << 3) | xcd] = (uint32_t)(base + i);
+  const bool valid[2] = {lane < cnt, lane + 64 < cnt};
+  const int want[2] = {valid[0] ? deal_position(lane, cnt) : -1, valid[1] ? deal_position(lane + 64, cnt) : -1};
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    if (64 * q >= cnt) break;
+#pragma unroll 8
+    for (int j = 0; j < 64; ++j) {
+      const int rj = j + 64 * q < cnt ? __builtin_amdgcn_readlane(rank[q], j) : -2;
+      tile[0] = rj == want[0] ? j + 64 * q : tile[0];
+      tile[1] = rj == want[1] ? j + 64 * q : tile[1];
+    }
+  }
+  uint32_t wk[2], ln[2];
+  bool plausible = true;
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const uint2 r = valid[q] ? rng[tile[q]] : make_uint2(0u, 0u);
+    const uint32_t w_raw = valid[q] ? tot[tile[q]] : 0u, l_raw = deal_list_length(r, (uint32_t)(base + tile[q]), p.stride, p.tail_off);
+    plausible = plausible && deal_words_plausible(w_raw, l_raw);
+    wk[q] = min(w_raw, kDealClamp);
+    ln[q] = min(l_raw, kDealClamp);
+  }
+  // 2. the exchanges (inside the measured range only: kDealMinMeanList)
+  const int cu = lane & 31, slot[2] = {lane >> 5, 2 + (lane >> 5)};
+  const uint32_t listed = (uint32_t)__builtin_amdgcn_readlane((int)wave_inclusive_scan_u32(ln[0] + ln[1]), 63);
+  const bool search = __ballot(!plausible) == 0ull && listed >= kDealMinMeanList * (uint32_t)cnt;  // (wave-uniform)
+  for (int pass = 0; pass < (search ? kDealPasses : 0); ++pass) {
+    const uint32_t mine = (valid[0] ? deal_term(slot[0], wk[0], ln[0]) : 0u) + (valid[1] ? deal_term(slot[1], wk[1], ln[1]) : 0u);
+    const uint32_t cost = mine + (uint32_t)__shfl_xor((int)mine, 32);  // my unit's
+    const uint32_t top = wave_max_u32((cost << 5) | (uint32_t)(31 - cu));  // (wave-uniform from here: lanes are read by scalar index)
+    const int worst = 31 - (int)(top & 31u);
+    const uint32_t cw = top >> 5;
+    uint32_t best = cw;
+    int pick = -1;
+    uint32_t wa[4], la[4];
+#pragma unroll
+    for (int sa = 0; sa < 4; ++sa) {  // the costly unit's four tiles
+      wa[sa] = (uint32_t)__builtin_amdgcn_readlane((int)wk[sa >> 1], (sa & 1) * 32 + worst);
+      la[sa] = (uint32_t)__builtin_amdgcn_readlane((int)ln[sa >> 1], (sa & 1) * 32 + worst);
+    }
+#pragma unroll
+    for (int sel = 0; sel < 2; ++sel) {
+#pragma unroll
+      for (int sa = 0; sa < 4; ++sa) {
+        const uint32_t m = deal_exchange(cw, cost, sa, wa[sa], la[sa], slot[sel], wk[sel], ln[sel]);
+        const bool ok = valid[sel] && cu != worst && 32 * sa + worst < cnt && m < best;
+        best = ok ? m : best;
+        pick = ok ? sel * 4 + sa : pick;
+      }
+    }
+    const uint32_t low = ~wave_max_u32(~best);
+    const unsigned long long who = __ballot(pick >= 0 && best == low);
+    if (who == 0ull) break;  // (wave-uniform) nothing helps the costliest unit
+    const int from = __builtin_ctzll(who), choice = __builtin_amdgcn_readlane(pick, from), sel = choice >> 2, sa = choice & 3;
+    const int to = (sa & 1) * 32 + worst;  // the lane that holds the costly unit's tile, in its register sa >> 1
+    const int tb = __builtin_amdgcn_readlane(sel ? tile[1] : tile[0], from), ta = __builtin_amdgcn_readlane(sa >> 1 ? tile[1] : tile[0], to);
+    const uint32_t wb = (uint32_t)__builtin_amdgcn_readlane((int)(sel ? wk[1] : wk[0]), from);
+    const uint32_t lb = (uint32_t)__builtin_amdgcn_readlane((int)(sel ? ln[1] : ln[0]), from);
+    const uint32_t was = sa == 0 ? wa[0] : sa == 1 ? wa[1] : sa == 2 ? wa[2] : wa[3], las = sa == 0 ? la[0] : sa == 1 ? la[1] : sa == 2 ? la[2] : la[3];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const bool takes_a = lane == from && sel == q, takes_b = lane == to && (sa >> 1) == q;
+      tile[q] = takes_a ? ta : takes_b ? tb : tile[q];
+      wk[q] = takes_a ? was : takes_b ? wb : wk[q];
+      ln[q] = takes_a ? las : takes_b ? lb : ln[q];
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 2; ++q)
+    if (valid[q]) tile_order_of(p)[((lane + 64 * q) << 3) | xcd] = (uint32_t)(base + tile[q]);
 }
 // Who builds it: kDealBlocks workgroups of the fused binning launch BEHIND its `rows` binning workgroups, one per XCD's table (the
 // tile launch runs after that kernel, the previous call's tile launch - which left the counts - before it).  They are workgroups of
@@ -385,7 +555,7 @@ __device__ __forceinline__ void build_tile_order_wave(const Params& p, const int
 // A single view that takes the binning launch WITHOUT colour waves (a device that does not grant it the LDS) gets the table from
 // a launch of its own, k_tile_order, in front: those instances stay the code they were (the two-per-CU one spills with it).
 __device__ __forceinline__ void build_tile_order(const Params& p, const int xcd, const int w, const int lane) {
-  if (w < 4) build_tile_order_wave(p, xcd, w, lane);
+  if (w == 0) build_tile_order_model(p, xcd, lane);
 }
 __global__ __launch_bounds__(256) void k_tile_order(const Params p) {
   build_tile_order(p, (int)blockIdx.x, (int)(threadIdx.x >> 6), (int)(threadIdx.x & 63));

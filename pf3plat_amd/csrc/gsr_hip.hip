@@ -228,6 +228,13 @@ int gsr_colour_in_binning(const GsrDims* dims) {
   return color_in_bin_for(*dims, make_grid(dims->width, dims->height), dev) ? 1 : 0;
 }
 
+// Debug aid for tests: the host statement of the forward tile launch's deal (gsr_common.h: tile_deal_order_host) for one XCD.
+int gsr_tile_deal_order(const uint32_t* walked, const uint32_t* list_length, int count, uint32_t* order_out) {
+  if (!walked || !list_length || !order_out || count < 1 || count > kBalanceMax) return GSR_ERR_INVALID_ARGUMENT;
+  tile_deal_order_host(walked, list_length, count, order_out);
+  return GSR_OK;
+}
+
 static size_t scratch_bytes_of(const GsrDims& d) {
   const size_t rows = (size_t)d.num_views * (size_t)d.num_gaussians;
   if (!(d.flags & GSR_FLAG_DETERMINISTIC)) return rows * GSR_SCREEN_GRAD_FLOATS * sizeof(float);

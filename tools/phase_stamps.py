@@ -56,6 +56,19 @@ def q(x, qs=(0.0, 0.1, 0.5, 0.9, 1.0)):
     return [round(v, 2) for v in torch.quantile(x.double(), torch.tensor(qs, dtype=torch.float64)).tolist()]
 
 
+def _dump_read(recs, slots_raw, plan, lay, VT, us):
+    """Appends the last call's per-tile record: workgroup, its start, blend start / end (us, low word of the clock), hardware CU id."""
+    r_, s_ = slots_raw(24576, VT)[:, :4], slots_raw(8192, VT)
+    d_ = plan["bin"][lay["tile_order"]: lay["tile_order"] + VT * 4].view(torch.int32).cpu().long()
+    h_ = (r_[:, 1] >> 32) & 0xffffffff
+    st_ = torch.zeros(VT, dtype=torch.float64)
+    st_[d_] = us(s_[:, 0])  # (stamps of the sort are per workgroup, those of the blend per tile)
+    bid_ = torch.zeros(VT, dtype=torch.int64)
+    bid_[d_] = torch.arange(VT)
+    recs.append(torch.stack([bid_.double(), st_, ((r_[:, 3] >> 32) & 0xffffffff).double() * 0.01, (r_[:, 3] & 0xffffffff).double() * 0.01,
+                             (((h_ >> 16) & 0xf) * 4096 + ((h_ >> 13) & 0x7) * 256 + ((h_ >> 12) & 1) * 16 + ((h_ >> 8) & 0xf)).double()], 1).numpy())
+
+
 def main():
     n = int(os.environ.get("PS_N", 131072))
     V = int(os.environ.get("PS_V", 3))
@@ -135,6 +148,10 @@ def main():
         print(f"  colour units ({int(ok.sum())} stamped): start", q(c[:, 0] - t0), "| issue", q(c[:, 1] - c[:, 0]), "| wait", q(c[:, 2] - c[:, 1]),
               "| eval", q(c[:, 3] - c[:, 2]), "| end", q(c[:, 3] - t0))
         print(f"  K1 ends: binning waves {round((b[:, 4].max() - t0).item(), 2)} us, colour waves {round((c[:, 3].max() - t0).item(), 2)} us")
+    if V == 1 and rows + 8 <= 256:  # the deal workgroups behind the rows (gsr_common.h build_tile_order): stamp slots rows ... rows + 7
+        d = slots(rows, 8)
+        if (d[:, 1] > 0).all():
+            print(f"  deal workgroups: start {q(d[:, 0] - t0)} | end {q(d[:, 1] - t0)} | duration {q(d[:, 1] - d[:, 0])}")
     pm = plan["bin"][lay["counts"]: lay["counts"] + blocks * (T + 8) * 8].view(torch.int32).reshape(blocks, T + 8, 2)[:, :T, 1].sum(1).cpu().double()
     if set_mode:
         pm = pm.reshape(V, rows).sum(0)
@@ -187,6 +204,59 @@ def main():
     sol = torch.linalg.lstsq(A, (cu_end - cu_first).unsqueeze(1)).solution.flatten()
     print(f"  per CU: (end - first blend start) = {sol[0].item():.3f} us x batches + {sol[1].item():.2f}; corr(end, batches) {cc(cu_end, cu_walk)}")
     print(f"  K2 ends {round(cu_end.max().item(), 2)} us after its first tile's start (mean CU end {round(cu_end.mean().item(), 2)})")
+    if os.environ.get("PS_DUMP"):  # per-tile records of PS_DUMP_REPS stamped calls, for tools/deal_model.py (fits and replays on the CPU)
+        import numpy as np
+
+        # PS_DEALS: "random:<n>" or an .npz whose `orders` (n, tiles) are tables to run INSTEAD of the shipped deal - imposed through the
+        # hint: the tile wanted at heaviest-first position q of its XCD gets the count (tiles of the XCD - q), and the builder sorts by it
+        deals, spec = [None], os.environ.get("PS_DEALS", "")
+        if spec.startswith("random:"):
+            gen = torch.Generator().manual_seed(7)
+            for _ in range(int(spec[7:])):
+                o = torch.zeros(VT, dtype=torch.int64)
+                for x in range(8):
+                    mine = torch.tensor([xcd_remap(8 * k + x, VT) for k in range((VT - x + 7) // 8)])
+                    o[x::8] = mine[torch.randperm(len(mine), generator=gen)]
+                deals.append(o)
+        elif spec:
+            deals += [torch.from_numpy(o).long() for o in np.load(spec)["orders"]]
+        tt = plan["bin"][lay["tile_total"]: lay["tile_total"] + VT * 4].view(torch.int32)
+        recs, deal_of_rec, us_per_call = [], [], []
+        for di, deal in enumerate(deals):
+            hint = None
+            if deal is not None:
+                hint = torch.zeros(VT, dtype=torch.int32)
+                for x in range(8):
+                    mine = deal[x::8]
+                    k = torch.arange(len(mine))
+                    rnd, j = k >> 5, k & 31
+                    ln_ = torch.clamp(len(mine) - (rnd << 5), max=32)
+                    hint[mine] = (len(mine) - ((rnd << 5) + torch.where(rnd % 2 == 1, ln_ - 1 - j, j))).to(torch.int32)
+                hint = hint.to(dev)
+
+            def call():
+                if hint is not None:
+                    tt.copy_(hint)
+                be.run_forward(plan, vb, *ins)
+
+            for _ in range(20):
+                call()
+            e0.record()
+            for _ in range(100):
+                call()
+            e1.record()
+            torch.cuda.synchronize()
+            us_per_call.append(e0.elapsed_time(e1) * 10)
+            for _ in range(int(os.environ.get("PS_DUMP_REPS", 8)) if deal is None else 2):
+                for _ in range(4):  # (the stamped call follows calls of its own kind, as in a loop of calls)
+                    call()
+                torch.cuda.synchronize()
+                deal_of_rec.append(di)
+                _dump_read(recs, slots_raw, plan, lay, VT, us)
+        np.savez_compressed(os.environ["PS_DUMP"], recs=np.stack(recs), walked=walked.numpy(), list_length=ln.numpy(), deal_of_rec=np.array(deal_of_rec),
+                            us_per_call=np.array(us_per_call), columns=np.array(["workgroup", "start_us", "blend_start_us", "blend_end_us", "cu"]))
+        print(f"  wrote {os.environ['PS_DUMP']}: {len(recs)} stamped calls x {VT} tiles; forward us per call (stamped build, stamps on) by deal:",
+              [round(u, 2) for u in us_per_call])
     ms = be.run_forward(plan, vb, *ins, profile=True)
     print("  profile-mode stage ms (stamped build):", {k: round(v, 4) for k, v in ms.items()})
 
