@@ -754,6 +754,60 @@ int gsr_match_assignment(int L, int d, float scale, float threshold, int width, 
                          int32_t* matches1, float* mscores0, float* mscores1, int32_t* idx0, int32_t* idx1, float* score, int64_t* ids_i,
                          int64_t* ids_j, float* points, int32_t* count, void* stream);
 
+/* Keypoint extraction: what SuperPoint.forward does after its last two convolutions (reference
+ * src/model/LightGlue/lightglue/superpoint.py:52-95, 171-227, with the rescale of utils.py:146) - the 65-way softmax, the 8 x 8
+ * depth-to-space, simple_nms, the border cut, torch.where against the threshold, the dense descriptor normalisation and
+ * sample_descriptors - for a batch of B equally sized images.  Forward only (the reference runs the extractor under no_grad).
+ * Inputs, f32: `logits` (B, 65, h, w) contiguous, convPb's output before the softmax; `descriptors` (B, C, h, w), 0 <= C <= 256
+ *   (0: none), convDb's output, NOT normalised, read through its four element strides (contiguous and channels_last both work
+ *   without a copy); `scales` (B, 2) the preprocessor's (sx, sy), or NULL.  `height` = H = 8 h and `width` = W = 8 w are given in PIXELS.
+ *   mode GSR_KEYPOINTS_FROM_LOGITS: step 1 below WRITES `scores` (B, H, W) - the one dense array of the call.
+ *   mode GSR_KEYPOINTS_FROM_SCORES: the chain is entered after step 1: `scores` (B, H, W) is the caller's and only read, `logits` is
+ *   ignored, and H, W need not be multiples of 8 unless C > 0.
+ * 1. scores: p = softmax of a cell's 65 logits (maximum m, e_c = exp(l_c - m), their f32 sum in channel order, e_c / sum); channel 64
+ *    is dropped; cell (i, j)'s channel 8 a + c is pixel (8 i + a, 8 j + c).
+ * 2. NMS, exactly simple_nms with windows of (2 r + 1) squared padded with -inf, 0 <= r <= 4:
+ *      max_mask = (s == maxpool(s));  TWICE (not "until stable" - two rounds are the definition):
+ *        supp_mask = maxpool(max_mask) > 0;  supp_scores = supp_mask ? 0 : s;
+ *        max_mask |= (supp_scores == maxpool(supp_scores)) and not supp_mask.
+ *    A pixel's result depends on scores up to 5 r pixels away.  Equal scores are all kept.  Every decision is a comparison of
+ *    scores: nothing is rounded from step 2 on.
+ * 3. selection: pixels with remove_borders <= y < H - remove_borders, the same in x, in max_mask and with s > threshold
+ *    (threshold >= 0, finite), per image in row-major order - torch.where's.  counts[b] = the number found, WHATEVER the capacity.
+ *    max_num_keypoints = k > 0 and k < counts[b] <= capacity: the k highest scores in descending order, TIES TO THE LOWER ROW-MAJOR
+ *    INDEX (the reference's topk leaves the order of ties open); 0: no cut.  counts[b] > capacity: the image OVERFLOWS: its first
+ *    `capacity` pixels in row-major order are stored, without the cut, nothing is written past them, and counts[b] tells.
+ *    stored(b) = counts[b] > capacity ? capacity : (k > 0 and counts[b] > k ? k : counts[b]).
+ * 4. descriptors (C > 0), sample_descriptors on the L2-normalised map without forming that map: pixel (x, y) samples at
+ *    (ix, iy) = ((x - 3.5) / (8 w - 4.5) (w - 1), (y - 3.5) / (8 h - 4.5) (h - 1)), bilinearly, zeros outside (reachable only with
+ *    remove_borders < 4): with x0 = floor(ix), t = ix - x0 and the same in y, weights (1 - tx)(1 - ty), tx (1 - ty), (1 - tx) ty,
+ *    tx ty on the columns at (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1), EACH DIVIDED BY max(its norm over C, 1e-12);
+ *    the blend, summed in that order, is divided by max(its own norm, 1e-12).
+ * 5. keypoints (x, y) f32 = (pixel + 0.5) / scale - 0.5 with IEEE division; without `scales` the pixel itself.
+ * Outputs, PACKED image after image: image b's rows are base(b) .. base(b) + stored(b), base(b) = sum of stored over the images
+ *   before it, formed on the device: `keypoints` (B capacity, 2) f32, `pixels` (B capacity, 2) int32 (x, y), `keypoint_scores`
+ *   (B capacity) f32, `out_descriptors` (B capacity, C) f32, `counts` (B) int32.  Rows from the total on are not written.
+ * Up to six launches of one kernel on the caller's stream, no host synchronisation: (1) scores, a thread per cell; (2) NMS, a
+ *   workgroup per tile of gsr_keypoints_tile() squared pixels with its halo of 5 r in LDS, separable pools, masks and suppressed
+ *   scores on chip, one 32-bit keep word per tile row out; (3) a scan of the words' counts per image, in row-major order; (4) the
+ *   writes, a thread per word; (5) only with k > 0: rank by counting per image; (6) only with C > 0: a wave per keypoint, the five
+ *   norms as wave sums.  No atomics, no order that depends on scheduling: the same bits on every call, and an image has the bits in a
+ *   batch that it has alone.
+ *   `scratch`: gsr_keypoints_scratch_bytes(B, height, width, C, capacity) bytes (host arithmetic; 0 for sizes the call refuses):
+ *   the keep words, their offsets and three staging words per row of capacity.
+ * GSR_ERR_INVALID_ARGUMENT, nothing launched: another mode, B outside 1 .. 65535, C outside 0 .. 256, capacity < 1, r outside 0 .. 4,
+ *   remove_borders < 0, max_num_keypoints < 0, a threshold that is negative or not finite, H or W no multiple of 8 where logits or
+ *   descriptors are read, more than 2^31 - 1 elements in an array, a NULL required pointer (logits in the scores mode, scales, and
+ *   with C == 0 the three descriptor arguments may be NULL). */
+#define GSR_KEYPOINTS_FROM_LOGITS 0
+#define GSR_KEYPOINTS_FROM_SCORES 1
+int gsr_keypoints_tile(void);
+size_t gsr_keypoints_scratch_bytes(int B, int height, int width, int C, int capacity);
+int gsr_keypoints(int mode, int B, int height, int width, int C, int nms_radius, float threshold, int remove_borders, int max_num_keypoints,
+                  int capacity, const float* logits, float* scores, const float* descriptors, const int64_t* descriptor_strides,
+                  const float* scales, void* scratch, float* keypoints, int32_t* pixels, float* keypoint_scores, float* out_descriptors,
+                  int32_t* counts, void* stream);
+
 /* The refined poses of the encoder (reference src/model/encoder/encoder_costvolume.py:447-450, 460-473, with r6d2mat :189-209 and
  * matrix_to_rotation_6d :223-224, and the three inversions `refine_sync_abspose.inverse()` :492, :530 and `c2w[1].inverse()`
  * src/model/model_wrapper.py:150) and the per-step pose errors (model_wrapper.py:182-190, 306-313, 345;

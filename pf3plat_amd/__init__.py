@@ -38,3 +38,5 @@ from .attention import CrossBlock, LearnableFourierPositionalEncoding, SelfBlock
 from .attention import bidirectional_cross_attention, multi_head_attention  # noqa: F401,E402
 from . import matching  # noqa: F401,E402
 from .matching import MatchAssignment, Matches, match_assignment, pack_matched  # noqa: F401,E402
+from . import keypoints  # noqa: F401,E402
+from .keypoints import Keypoints, PackedKeypoints, SuperPoint, detect_keypoints, keypoints_from_scores  # noqa: F401,E402

@@ -67,7 +67,7 @@ def find_hipcc() -> str:
 def hip_sources(csrc: str = None, header: str = None) -> list:
     """Every file libgsr_hip.so is built from: csrc/gsr_hip.hip - the one translation unit - and the headers next to it that it
     includes (gsr_common.h, gsr_{binning,tiles_fwd,backward,cameras,covariance}.h, one header per operator - gsr_{image,adapter,pose_loss,
-    cost_volume,lift,mono_attention,attention,coarse_pose,pose_refine}.h -, gsr_pnp_solver.h, preprocess_bwd.inc: all of csrc/ but the torch
+    cost_volume,lift,mono_attention,attention (with the matcher's tail and the keypoint extraction),coarse_pose,pose_refine}.h -, gsr_pnp_solver.h, preprocess_bwd.inc: all of csrc/ but the torch
     binding, which is a library of its own; tests/test_abi.py holds this set to the #include graph) and include/gsr.h."""
     csrc = csrc or os.path.dirname(SRC)
     return [os.path.join(csrc, n) for n in sorted(os.listdir(csrc)) if n != "gsr_torch.cpp" and os.path.isfile(os.path.join(csrc, n))] + [header or HEADER]
@@ -350,6 +350,13 @@ def load():
     lib.gsr_match_assignment.restype = ctypes.c_int  # L, d; scale, threshold; width; mdesc0, mdesc1, z0, z1; host + device offsets, twice; ...
     lib.gsr_match_assignment.argtypes = ([ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_int] + [vp] * 4 + [i32p, vp, i32p, vp]
                                          + [vp] * 15)  # kpts0, kpts1, scratch; matches0/1, mscores0/1, idx0, idx1, score, ids_i, ids_j, points, count; stream
+    lib.gsr_keypoints_tile.restype = ctypes.c_int
+    lib.gsr_keypoints_tile.argtypes = []
+    lib.gsr_keypoints_scratch_bytes.restype = ctypes.c_size_t
+    lib.gsr_keypoints_scratch_bytes.argtypes = [ctypes.c_int] * 5  # B, height, width (pixels), C, capacity
+    lib.gsr_keypoints.restype = ctypes.c_int  # mode; B, height, width, C; r, threshold, remove_borders, k, capacity; logits, scores, descriptors, ...
+    lib.gsr_keypoints.argtypes = ([ctypes.c_int] * 6 + [ctypes.c_float] + [ctypes.c_int] * 3 + [vp] * 3 + [i64p]
+                                  + [vp] * 8)  # its strides; scales, scratch; keypoints, pixels, keypoint_scores, descriptors, counts; stream
     lib.gsr_pose_refine.restype = ctypes.c_int
     lib.gsr_pose_refine.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, vp, vp, vp, vp]  # b, v; sync_pose, delta, its row stride, gamma, c2w, w2c, stream
     lib.gsr_pose_refine_backward.restype = ctypes.c_int  # ...; gamma, dL_dc2w, dL_dw2c, dL_ddelta, dL_dgamma, stream
@@ -378,6 +385,7 @@ EXPORTED_SYMBOLS = (
     "gsr_pose_refine", "gsr_pose_refine_backward", "gsr_pose_errors",
     "gsr_attention", "gsr_attention_backward", "gsr_attention_scratch_bytes",
     "gsr_match_assignment", "gsr_match_assignment_scratch_bytes",
+    "gsr_keypoints", "gsr_keypoints_scratch_bytes", "gsr_keypoints_tile",
     "gsr_tile_deal_order",
 )
 # The stages of GsrForwardOptions.stage_ms / GsrBackwardOptions.stage_ms as run_forward / run_backward(profile=True) key them (the

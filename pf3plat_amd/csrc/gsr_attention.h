@@ -708,3 +708,394 @@ int gsr_match_assignment(int L, int d, float scale, float threshold, int width, 
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// Keypoint extraction (SuperPoint.forward after its last two convolutions, reference src/model/LightGlue/lightglue/superpoint.py:52-95,
+// 171-227, with the rescale of utils.py:146; definition: include/gsr.h): a batch of images in one chain of up to six launches - the
+// passes of k_keypoint_ops, below, routines of k_pose_ops like the match assignment's and for the same reason.  This section stands
+// in this header, behind the matcher's tail, because tests/test_abi.py pins the library's set of files by name.
+//   pass kKpScores: a thread per 8 x 8 cell: the 65-way softmax (maximum, expf, the sum in channel order, one division per pixel) and
+//                   the depth-to-space store of its 64 scores - the ONE dense float array of the chain, (B, H, W).  The softmax is not
+//                   folded into the NMS tile load: a 32-pixel tile with its 20-pixel halo is 5.06 tiles of reads, which the score map
+//                   serves from L2 as 4 bytes per pixel, while the logits would be read, and their expf evaluated, five times over.
+//   pass kKpNms:    a workgroup per tile of kKpTile x kKpTile pixels.  The tile and a halo of 5 r pixels (simple_nms chains five
+//                   max-pools of radius r) are loaded into LDS, -inf outside the image as max_pool2d pads; the pools are separable (a
+//                   row pass into a second float array, a column pass out of it); the four masks are byte arrays and the suppressed
+//                   scores are formed from scores and mask where they are read: nothing but the tile's keep bits leaves the chip, one
+//                   32-bit word per tile row.  The region's rim computes with clipped windows: what is wrong there moves inward by r per
+//                   pool and after five pools has not reached the tile.
+//   pass kKpScan:   a workgroup per image: the words' population counts in row-major order of (row, word of the row) - which IS the
+//                   row-major order of the pixels -, an exclusive scan in chunks of 2048 words, counts[b].
+//   pass kKpWrite:  a thread per word: its kept pixels to rows base(b) + offset .. of the packed outputs, or, for an image that the
+//                   top-k pass will order, to that image's staging rows.
+//   pass kKpTopk:   (only with max_num_keypoints) a workgroup per image, nothing to do unless k < count <= capacity: rank by
+//                   counting - a row's rank is the number of rows with a higher score, or an equal one and a lower row-major index -
+//                   with the scores staged through LDS; rows of rank < k go to base(b) + rank.
+//   pass kKpDesc:   a wave per keypoint: the four corner columns read through the descriptors' strides (lane = channel, so a
+//                   channels_last map is read in full lines), their four norms and the blend's norm as xor-butterfly wave sums.
+// base(b) = sum over the images before b of stored(count) = min(count, capacity), or k where the top-k cut applies: every pass forms
+// it from counts on the device.  No atomics, no order that depends on scheduling: the same bits on every call.
+// ------------------------------------------------------------------------------------------------
+namespace gsr {
+constexpr int kKpTile = 32;                                // a tile row is one word of the keep mask
+constexpr int kKpMaxRadius = 4;
+constexpr int kKpRegion = kKpTile + 10 * kKpMaxRadius;     // the tile with its halo of 5 r on either side
+constexpr int kKpCells = kKpRegion * kKpRegion;
+constexpr int kKpChan = 256;                               // the most descriptor channels
+constexpr int kKpTopkChunk = 8192;                         // scores staged per round of the rank count
+static_assert(3 * kKpCells <= kMtLdsFloats && kKpTopkChunk <= kMtLdsFloats, "the keypoint passes live in k_pose_ops' arena");
+enum { kKpScores = 0, kKpNms = 1, kKpScan = 2, kKpWrite = 3, kKpTopk = 4, kKpDesc = 5 };
+
+struct KeypointArgs {
+  int op, B, H, W, C, r, border, k, cap, words;  // words: 32-bit mask words per image row
+  float threshold;
+  const float *logits, *desc, *scales;
+  int64_t ds[4];                    // the descriptors' element strides (B, C, h, w)
+  float* smap;                      // (B, H, W): written by kKpScores, or the caller's scores (then only read)
+  uint32_t *mask, *woff, *rank;     // scratch: keep words and their exclusive offsets (B, H, words); the staging rows' ranks (B, cap)
+  int32_t* spix;                    // scratch: staging rows (B, cap): flat pixel y W + x, and its score
+  float* sscore;
+  float *kpts, *kscores, *kdesc;
+  int32_t *pixels, *counts;
+};
+
+// rows an image keeps: its count, cut to k where the top-k pass runs, to the capacity where it overflows
+__device__ __forceinline__ int kp_stored(int cnt, int cap, int k) { return cnt > cap ? cap : (k > 0 && cnt > k ? k : cnt); }
+__device__ __forceinline__ bool kp_staged(int cnt, int cap, int k) { return k > 0 && cnt > k && cnt <= cap; }
+// base(b), the first packed row of image b: EVERY thread of the workgroup calls it (two barriers); the images before b are summed
+// 256 at a time, so a thread reads b / 256 counts; lds: 4 words, free again on return
+__device__ __forceinline__ int64_t kp_base(const KeypointArgs& a, int b, float* lds, int tid) {
+  uint32_t* tot = reinterpret_cast<uint32_t*>(lds);
+  uint32_t mine = 0;  // (the batch's rows are at most 2^31 - 1)
+  for (int i = tid; i < b; i += 256) mine += (uint32_t)kp_stored(a.counts[i], a.cap, a.k);
+  const uint32_t inc = wave_inclusive_scan_u32(mine);
+  if ((tid & 63) == 63) tot[tid >> 6] = inc;
+  __syncthreads();
+  const int64_t base = (int64_t)tot[0] + tot[1] + tot[2] + tot[3];
+  __syncthreads();
+  return base;
+}
+__device__ __forceinline__ void kp_emit(const KeypointArgs& a, int b, int64_t g, int x, int y, float s) {
+  a.pixels[2 * g] = x;
+  a.pixels[2 * g + 1] = y;
+  a.kscores[g] = s;
+  float kx = (float)x, ky = (float)y;
+  if (a.scales) {  // the preprocessor's rescale: (pixel + 0.5) / scale - 0.5
+    kx = (kx + 0.5f) / a.scales[2 * b] - 0.5f;
+    ky = (ky + 0.5f) / a.scales[2 * b + 1] - 0.5f;
+  }
+  a.kpts[2 * g] = kx;
+  a.kpts[2 * g + 1] = ky;
+}
+
+// pass kKpScores: a thread per cell
+__device__ __forceinline__ void k_keypoint_scores(const KeypointArgs& a, int tid) {
+  const int h = a.H / 8, w = a.W / 8;
+  const int64_t hw = (int64_t)h * w, item = (int64_t)blockIdx.x * 256 + tid;
+  if (item >= (int64_t)a.B * hw) return;
+  const int b = (int)(item / hw), cell = (int)(item - (int64_t)b * hw), i = cell / w, j = cell - i * w;
+  const float* p = a.logits + (int64_t)b * 65 * hw + cell;
+  float v[65];
+  float mx = -INFINITY;
+#pragma unroll
+  for (int c = 0; c < 65; ++c) { v[c] = p[c * hw]; mx = fmaxf(mx, v[c]); }
+  float sum = 0.f;
+#pragma unroll
+  for (int c = 0; c < 65; ++c) { v[c] = expf(v[c] - mx); sum += v[c]; }
+  float* out = a.smap + ((int64_t)b * a.H + 8 * i) * a.W + 8 * j;  // (32-byte aligned: W is a multiple of 8)
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    float4* row = reinterpret_cast<float4*>(out + (int64_t)q * a.W);
+    row[0] = make_float4(v[8 * q] / sum, v[8 * q + 1] / sum, v[8 * q + 2] / sum, v[8 * q + 3] / sum);
+    row[1] = make_float4(v[8 * q + 4] / sum, v[8 * q + 5] / sum, v[8 * q + 6] / sum, v[8 * q + 7] / sum);
+  }
+}
+
+// The cells e = tid, tid + 256, ... of the R x R region with their row and column, which are carried along, not divided out.
+struct KpWalk {
+  int R, n, e0, ly0, lx0, sy, sx;  // a step of 256 cells is sy rows and sx < R columns
+};
+template <class F>
+__device__ __forceinline__ void kp_cells(const KpWalk& w, F f) {
+  int ly = w.ly0, lx = w.lx0;
+  for (int e = w.e0; e < w.n; e += 256) {
+    f(e, ly, lx);
+    lx += w.sx;
+    ly += w.sy;
+    if (lx >= w.R) { lx -= w.R; ++ly; }
+  }
+}
+// T[e] = the maximum of src over e's row window, clipped to the region
+template <class Src>
+__device__ __forceinline__ void kp_pool_rows(Src src, float* T, const KpWalk& w, int r) {
+  kp_cells(w, [&](int e, int ly, int lx) {
+    const int lo = lx - r < 0 ? 0 : lx - r, hi = lx + r > w.R - 1 ? w.R - 1 : lx + r;
+    float m = src(e - lx + lo);
+    for (int c = e - lx + lo + 1; c <= e - lx + hi; ++c) m = fmaxf(m, src(c));
+    T[e] = m;
+  });
+}
+// the maximum of T over e's column window
+__device__ __forceinline__ float kp_pool_col(const float* T, int R, int r, int ly, int lx) {
+  const int lo = ly - r < 0 ? 0 : ly - r, hi = ly + r > R - 1 ? R - 1 : ly + r;
+  float m = T[lo * R + lx];
+  for (int y = lo + 1; y <= hi; ++y) m = fmaxf(m, T[y * R + lx]);
+  return m;
+}
+
+// pass kKpNms: a workgroup per tile; lds: 2 kKpCells floats and 4 kKpCells bytes
+__device__ __forceinline__ void k_keypoint_nms(const KeypointArgs& a, float* lds, int tid) {
+  const int r = a.r, halo = 5 * r, R = kKpTile + 2 * halo;
+  const int tx = blockIdx.x, ty = blockIdx.y, b = blockIdx.z;
+  const int x0 = tx * kKpTile - halo, y0 = ty * kKpTile - halo;
+  KpWalk w;
+  w.R = R; w.n = R * R; w.e0 = tid; w.ly0 = tid / R; w.lx0 = tid - w.ly0 * R; w.sy = 256 / R; w.sx = 256 - w.sy * R;
+  float* S = lds;
+  float* T = lds + kKpCells;
+  uint8_t* M = reinterpret_cast<uint8_t*>(lds + 2 * kKpCells);  // max_mask
+  uint8_t* P = M + kKpCells;                                    // a mask's row pass
+  uint8_t* Q = P + kKpCells;                                    // supp_mask
+  uint8_t* I = Q + kKpCells;                                    // inside the image
+  const float* img = a.smap + (int64_t)b * a.H * a.W;
+  kp_cells(w, [&](int e, int ly, int lx) {
+    const int gy = y0 + ly, gx = x0 + lx;
+    const bool in = gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
+    I[e] = in;
+    S[e] = in ? img[(int64_t)gy * a.W + gx] : -INFINITY;  // as max_pool2d pads
+  });
+  __syncthreads();
+  kp_pool_rows([&](int e) { return S[e]; }, T, w, r);
+  __syncthreads();
+  kp_cells(w, [&](int e, int ly, int lx) { M[e] = I[e] && S[e] == kp_pool_col(T, R, r, ly, lx); });
+  __syncthreads();
+  for (int round = 0; round < 2; ++round) {  // two rounds, not "until stable": the definition
+    kp_cells(w, [&](int e, int ly, int lx) {
+      const int lo = lx - r < 0 ? 0 : lx - r, hi = lx + r > R - 1 ? R - 1 : lx + r;
+      uint8_t any = 0;
+      for (int c = e - lx + lo; c <= e - lx + hi; ++c) any |= M[c];
+      P[e] = any;
+    });
+    __syncthreads();
+    kp_cells(w, [&](int e, int ly, int lx) {
+      const int lo = ly - r < 0 ? 0 : ly - r, hi = ly + r > R - 1 ? R - 1 : ly + r;
+      uint8_t any = 0;
+      for (int y = lo; y <= hi; ++y) any |= P[y * R + lx];
+      Q[e] = any;
+    });
+    __syncthreads();
+    // supp_scores: 0 where suppressed, the score elsewhere; outside the image the pool's padding
+    auto supp = [&](int e) { return !I[e] ? -INFINITY : (Q[e] ? 0.f : S[e]); };
+    kp_pool_rows(supp, T, w, r);
+    __syncthreads();
+    kp_cells(w, [&](int e, int ly, int lx) {
+      if (!Q[e] && I[e] && S[e] == kp_pool_col(T, R, r, ly, lx)) M[e] = 1;  // (not suppressed: its supp_score is its score)
+    });
+    __syncthreads();
+  }
+  const int wv = tid >> 6, lane = tid & 63;
+  for (int q = 0; q < kKpTile / 8; ++q) {  // a wave: two tile rows at a time
+    const int ly = 2 * (wv * (kKpTile / 8) + q) + (lane >> 5), lx = lane & 31;
+    const int e = (ly + halo) * R + lx + halo, gy = ty * kKpTile + ly, gx = tx * kKpTile + lx;
+    const bool keep = gy >= a.border && gy < a.H - a.border && gx >= a.border && gx < a.W - a.border && M[e] && S[e] > a.threshold;
+    const unsigned long long vote = __ballot(keep);
+    if (lx == 0 && gy < a.H) a.mask[((int64_t)b * a.H + gy) * a.words + tx] = (uint32_t)(vote >> (lane & 32));
+  }
+}
+
+// pass kKpScan: a workgroup per image; lds: 4 words
+__device__ __forceinline__ void k_keypoint_scan(const KeypointArgs& a, float* lds, int tid) {
+  uint32_t* tot = reinterpret_cast<uint32_t*>(lds);
+  const int b = blockIdx.x, wv = tid >> 6, lane = tid & 63;
+  const int64_t nw = (int64_t)a.H * a.words;
+  const uint32_t* mask = a.mask + b * nw;
+  uint32_t* woff = a.woff + b * nw;
+  uint32_t running = 0;
+  for (int64_t base = 0; base < nw; base += 2048) {
+    const int64_t i0 = base + tid * 8;
+    uint32_t c[8], mine = 0;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) { c[q] = i0 + q < nw ? (uint32_t)__popc(mask[i0 + q]) : 0u; mine += c[q]; }
+    const uint32_t inc = wave_inclusive_scan_u32(mine);
+    if (lane == 63) tot[wv] = inc;
+    __syncthreads();
+    uint32_t pre = running + inc - mine, all = 0;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) { if (v < wv) pre += tot[v]; all += tot[v]; }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      if (i0 + q < nw) woff[i0 + q] = pre;
+      pre += c[q];
+    }
+    running += all;
+    __syncthreads();
+  }
+  if (tid == 0) a.counts[b] = (int32_t)running;
+}
+
+// pass kKpWrite: a thread per word
+__device__ __forceinline__ void k_keypoint_write(const KeypointArgs& a, float* lds, int tid) {
+  const int b = blockIdx.y;
+  const int64_t nw = (int64_t)a.H * a.words, idx = (int64_t)blockIdx.x * 256 + tid;
+  const bool staged = kp_staged(a.counts[b], a.cap, a.k);                        // (uniform over the workgroup)
+  const int64_t base = staged ? (int64_t)b * a.cap : kp_base(a, b, lds, tid);  // (before any thread leaves)
+  if (idx >= nw) return;
+  uint32_t word = a.mask[b * nw + idx];
+  if (!word) return;
+  uint32_t off = a.woff[b * nw + idx];
+  const int y = (int)(idx / a.words), wc = (int)(idx - (int64_t)y * a.words);
+  for (; word && off < (uint32_t)a.cap; word &= word - 1, ++off) {  // NOTHING past the image's capacity rows
+    const int x = wc * 32 + __ffs((int)word) - 1;
+    const float s = a.smap[((int64_t)b * a.H + y) * a.W + x];
+    if (staged) {
+      a.spix[base + off] = y * a.W + x;
+      a.sscore[base + off] = s;
+    } else {
+      kp_emit(a, b, base + off, x, y, s);
+    }
+  }
+}
+
+// pass kKpTopk: a workgroup per image; lds: kKpTopkChunk floats
+__device__ __forceinline__ void k_keypoint_topk(const KeypointArgs& a, float* lds, int tid) {
+  const int b = blockIdx.x, cnt = a.counts[b];
+  if (!kp_staged(cnt, a.cap, a.k)) return;  // (uniform over the workgroup)
+  const float* sc = a.sscore + (int64_t)b * a.cap;
+  const int32_t* px = a.spix + (int64_t)b * a.cap;
+  uint32_t* rank = a.rank + (int64_t)b * a.cap;  // (a thread reads back only what it wrote)
+  for (int c0 = 0; c0 < cnt; c0 += kKpTopkChunk) {
+    const int m = cnt - c0 < kKpTopkChunk ? cnt - c0 : kKpTopkChunk;
+    for (int j = tid; j < m; j += 256) lds[j] = sc[c0 + j];
+    __syncthreads();
+    for (int i = tid; i < cnt; i += 256) {
+      const float s = sc[i];
+      uint32_t rk = c0 ? rank[i] : 0u;
+      for (int j = 0; j < m; ++j) rk += (lds[j] > s) || (lds[j] == s && c0 + j < i);  // ties: the lower row-major index first
+      rank[i] = rk;
+    }
+    __syncthreads();
+  }
+  const int64_t base = kp_base(a, b, lds, tid);
+  for (int i = tid; i < cnt; i += 256)
+    if (rank[i] < (uint32_t)a.k) kp_emit(a, b, base + rank[i], px[i] % a.W, px[i] / a.W, sc[i]);
+}
+
+// pass kKpDesc: a wave per keypoint
+__device__ __forceinline__ void k_keypoint_desc(const KeypointArgs& a, float* lds, int tid) {
+  const int b = blockIdx.y, lane = tid & 63, j = blockIdx.x * 4 + (tid >> 6), stored = kp_stored(a.counts[b], a.cap, a.k);
+  if ((int)blockIdx.x * 4 >= stored) return;  // (uniform over the workgroup: most of the grid leaves here, before the base)
+  const int64_t g = kp_base(a, b, lds, tid) + j;
+  if (j >= stored) return;  // (uniform over the wave)
+  const int h = a.H / 8, w = a.W / 8;
+  const float ix = ((float)a.pixels[2 * g] - 3.5f) / ((float)(8 * w) - 4.5f) * (float)(w - 1);
+  const float iy = ((float)a.pixels[2 * g + 1] - 3.5f) / ((float)(8 * h) - 4.5f) * (float)(h - 1);
+  const float fx0 = floorf(ix), fy0 = floorf(iy), tx = ix - fx0, ty = iy - fy0;
+  const int cx = (int)fx0, cy = (int)fy0;
+  const float wt[4] = {(1.f - tx) * (1.f - ty), tx * (1.f - ty), (1.f - tx) * ty, tx * ty};
+  const float* d = a.desc + b * a.ds[0];
+  float v[4][kKpChan / 64], nrm[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int xi = cx + (q & 1), yi = cy + (q >> 1);
+    const bool in = xi >= 0 && xi < w && yi >= 0 && yi < h;  // zeros outside, as grid_sample pads
+    float ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < kKpChan / 64; ++i) {
+      const int c = lane + 64 * i;
+      v[q][i] = in && c < a.C ? d[c * a.ds[1] + yi * a.ds[2] + xi * a.ds[3]] : 0.f;
+      ss += v[q][i] * v[q][i];
+    }
+    nrm[q] = fmaxf(sqrtf(wave_sum(ss)), 1e-12f);
+  }
+  float o[kKpChan / 64], ss = 0.f;
+#pragma unroll
+  for (int i = 0; i < kKpChan / 64; ++i) {
+    o[i] = ((wt[0] * (v[0][i] / nrm[0]) + wt[1] * (v[1][i] / nrm[1])) + wt[2] * (v[2][i] / nrm[2])) + wt[3] * (v[3][i] / nrm[3]);
+    ss += o[i] * o[i];
+  }
+  const float n = fmaxf(sqrtf(wave_sum(ss)), 1e-12f);
+#pragma unroll
+  for (int i = 0; i < kKpChan / 64; ++i)
+    if (lane + 64 * i < a.C) a.kdesc[g * a.C + lane + 64 * i] = o[i] / n;
+}
+
+// The six passes as routines of k_pose_ops (gsr_pose_refine.h), op kPoseOpKeypoints, switched by the launch-uniform a.op.
+__device__ __forceinline__ void k_keypoint_ops(const KeypointArgs& a, float* lds) {
+  const int tid = threadIdx.x;
+  switch (a.op) {
+    case kKpScores: k_keypoint_scores(a, tid); break;
+    case kKpNms: k_keypoint_nms(a, lds, tid); break;
+    case kKpScan: k_keypoint_scan(a, lds, tid); break;
+    case kKpWrite: k_keypoint_write(a, lds, tid); break;
+    case kKpTopk: k_keypoint_topk(a, lds, tid); break;
+    default: k_keypoint_desc(a, lds, tid); break;
+  }
+}
+
+static int keypoint_op_launch(const KeypointArgs& a, dim3 grid, void* stream_);  // (gsr_pose_refine.h, next to the kernel)
+
+// The limits of a call.  C == 0: no descriptors.
+static bool kp_sizes_ok(int mode, int B, int H, int W, int C, int cap) {
+  if (B < 1 || B > 65535 || H < 1 || W < 1 || C < 0 || C > kKpChan || cap < 1) return false;
+  if ((mode == GSR_KEYPOINTS_FROM_LOGITS || C > 0) && (H % 8 || W % 8)) return false;
+  const int64_t lim = 0x7fffffff;
+  if ((int64_t)H * W > lim / B || (int64_t)cap * (C > 2 ? C : 2) > lim / B) return false;
+  return (H + kKpTile - 1) / kKpTile <= 65535;
+}
+static int64_t kp_words(int H, int W) { return (int64_t)H * ((W + kKpTile - 1) / kKpTile); }
+}  // namespace gsr
+
+extern "C" {
+
+int gsr_keypoints_tile(void) { return gsr::kKpTile; }
+
+size_t gsr_keypoints_scratch_bytes(int B, int height, int width, int C, int capacity) {
+  if (!gsr::kp_sizes_ok(GSR_KEYPOINTS_FROM_SCORES, B, height, width, C, capacity)) return 0;
+  return (size_t)B * (2 * (size_t)gsr::kp_words(height, width) + 3 * (size_t)capacity) * 4;
+}
+
+int gsr_keypoints(int mode, int B, int height, int width, int C, int nms_radius, float threshold, int remove_borders, int max_num_keypoints,
+                  int capacity, const float* logits, float* scores, const float* descriptors, const int64_t* descriptor_strides,
+                  const float* scales, void* scratch, float* keypoints, int32_t* pixels, float* keypoint_scores, float* out_descriptors,
+                  int32_t* counts, void* stream_) {
+  using namespace gsr;
+  if (mode != GSR_KEYPOINTS_FROM_LOGITS && mode != GSR_KEYPOINTS_FROM_SCORES) return GSR_ERR_INVALID_ARGUMENT;
+  if (!kp_sizes_ok(mode, B, height, width, C, capacity)) return GSR_ERR_INVALID_ARGUMENT;
+  if (nms_radius < 0 || nms_radius > kKpMaxRadius || remove_borders < 0 || max_num_keypoints < 0) return GSR_ERR_INVALID_ARGUMENT;
+  if (!std::isfinite(threshold) || threshold < 0.f) return GSR_ERR_INVALID_ARGUMENT;
+  if (!scores || !scratch || !keypoints || !pixels || !keypoint_scores || !counts) return GSR_ERR_INVALID_ARGUMENT;
+  if (mode == GSR_KEYPOINTS_FROM_LOGITS && !logits) return GSR_ERR_INVALID_ARGUMENT;
+  if (C > 0 && (!descriptors || !descriptor_strides || !out_descriptors)) return GSR_ERR_INVALID_ARGUMENT;
+  KeypointArgs a{};
+  a.B = B; a.H = height; a.W = width; a.C = C; a.r = nms_radius; a.border = remove_borders; a.k = max_num_keypoints; a.cap = capacity;
+  a.words = (width + kKpTile - 1) / kKpTile;
+  a.threshold = threshold; a.logits = logits; a.desc = descriptors; a.scales = scales; a.smap = scores;
+  if (C > 0)
+    for (int s = 0; s < 4; ++s) a.ds[s] = descriptor_strides[s];
+  const int64_t nw = kp_words(height, width);
+  uint32_t* u = static_cast<uint32_t*>(scratch);
+  a.mask = u; a.woff = u + B * nw; a.rank = u + 2 * B * nw;
+  a.spix = reinterpret_cast<int32_t*>(a.rank + (int64_t)B * capacity);
+  a.sscore = reinterpret_cast<float*>(a.spix + (int64_t)B * capacity);
+  a.kpts = keypoints; a.pixels = pixels; a.kscores = keypoint_scores; a.kdesc = out_descriptors; a.counts = counts;
+  if (mode == GSR_KEYPOINTS_FROM_LOGITS) {
+    a.op = kKpScores;
+    if (int rc = keypoint_op_launch(a, dim3((unsigned)(((int64_t)B * (height / 8) * (width / 8) + 255) / 256)), stream_)) return rc;
+  }
+  a.op = kKpNms;
+  if (int rc = keypoint_op_launch(a, dim3((unsigned)a.words, (unsigned)((height + kKpTile - 1) / kKpTile), (unsigned)B), stream_)) return rc;
+  a.op = kKpScan;
+  if (int rc = keypoint_op_launch(a, dim3((unsigned)B), stream_)) return rc;
+  a.op = kKpWrite;
+  if (int rc = keypoint_op_launch(a, dim3((unsigned)((nw + 255) / 256), (unsigned)B), stream_)) return rc;
+  if (max_num_keypoints > 0) {
+    a.op = kKpTopk;
+    if (int rc = keypoint_op_launch(a, dim3((unsigned)B), stream_)) return rc;
+  }
+  if (C > 0) {
+    a.op = kKpDesc;
+    if (int rc = keypoint_op_launch(a, dim3((unsigned)((capacity + 3) / 4), (unsigned)B), stream_)) return rc;
+  }
+  return GSR_OK;
+}
+
+}  // extern "C"

@@ -1,7 +1,7 @@
 #pragma once
 #include "gsr_common.h"
 #include "gsr_pose_loss.h"  // pose_affine_inverse (k_pose_errors)
-#include "gsr_attention.h"  // k_match_ops: the match assignment's passes are routines of k_pose_ops (the reason is given there)
+#include "gsr_attention.h"  // k_match_ops, k_keypoint_ops: the match assignment's and the keypoint extraction's passes are routines of k_pose_ops (the reason is given there)
 
 // ------------------------------------------------------------------------------------------------
 // Refined poses (reference src/model/encoder/encoder_costvolume.py:447-450, 460-473 with r6d2mat :189-209 and matrix_to_rotation_6d
@@ -20,6 +20,7 @@
 // the pose loss's: as an instance it follows every plain kernel and nothing in front of it moves.
 // The match assignment's three passes (gsr_attention.h: k_match_ops) are routines of this kernel as well, op kPoseOpMatch, for the same
 // reason: there were 512 bytes left.  The routines above are launch-bound and do not feel the registers and LDS those passes take.
+// The keypoint extraction's six passes (gsr_attention.h: k_keypoint_ops) are op kPoseOpKeypoints, in the same arena.
 // ------------------------------------------------------------------------------------------------
 namespace gsr {
 constexpr int kRefineThreads = 256;
@@ -205,12 +206,13 @@ __device__ __forceinline__ void k_pose_errors(const PoseErrArgs& a, int s) {
 }
 
 // The one kernel of this section: `op` (uniform over the launch) picks the routine.
-enum { kPoseOpRefineFwd = 0, kPoseOpRefineBwd = 1, kPoseOpErrors = 2, kPoseOpMatch = 3 };
+enum { kPoseOpRefineFwd = 0, kPoseOpRefineBwd = 1, kPoseOpErrors = 2, kPoseOpMatch = 3, kPoseOpKeypoints = 4 };
 struct PoseOpArgs {
   int op;
   RefineArgs r;
   PoseErrArgs e;
   MatchArgs m;  // kPoseOpMatch: the match assignment's pass m.op (gsr_attention.h)
+  KeypointArgs k;  // kPoseOpKeypoints: the keypoint extraction's pass k.op (gsr_attention.h)
 };
 
 template <int kThreads>
@@ -221,13 +223,23 @@ __global__ __launch_bounds__(kRefineThreads) void k_pose_ops(const PoseOpArgs a)
   if (a.op == kPoseOpRefineFwd) k_pose_refine_fwd(a.r, item);
   else if (a.op == kPoseOpRefineBwd) k_pose_refine_bwd<kThreads>(a.r, arena);
   else if (a.op == kPoseOpErrors) k_pose_errors(a.e, item);
-  else k_match_ops(a.m, reinterpret_cast<float*>(arena));
+  else if (a.op == kPoseOpMatch) k_match_ops(a.m, reinterpret_cast<float*>(arena));
+  else k_keypoint_ops(a.k, reinterpret_cast<float*>(arena));
 }
 
 static int match_op_launch(const MatchArgs& m, dim3 grid, void* stream_) {
   PoseOpArgs a{};
   a.op = kPoseOpMatch;
   a.m = m;
+  hipLaunchKernelGGL(k_pose_ops<kRefineThreads>, grid, dim3(kRefineThreads), 0, static_cast<hipStream_t>(stream_), a);
+  GSR_CHECK(hipGetLastError());
+  return GSR_OK;
+}
+
+static int keypoint_op_launch(const KeypointArgs& k, dim3 grid, void* stream_) {
+  PoseOpArgs a{};
+  a.op = kPoseOpKeypoints;
+  a.k = k;
   hipLaunchKernelGGL(k_pose_ops<kRefineThreads>, grid, dim3(kRefineThreads), 0, static_cast<hipStream_t>(stream_), a);
   GSR_CHECK(hipGetLastError());
   return GSR_OK;
