@@ -398,6 +398,67 @@ int gsr_image_metrics(int num_images, int height, int width, const float* ground
                       float* ssim_map /* NULL = none */, float* partials, void* stream);
 int gsr_image_metrics_finish(int num_images, int height, int width, const float* partials, float* metrics, void* stream);
 
+/* The perceptual distance's head: what lpips.LPIPS(net="vgg"), version "0.1", in eval() mode does AFTER its VGG16 convolutions
+ * (reference src/loss/loss_lpips.py and compute_lpips, src/evaluation/metrics.py:27-33, which call that package with
+ * normalize=True).  The package is not part of the reference tree, so this text is the definition the operator is held to.
+ *   input     two image batches (N, 3, H, W) in [0, 1]; x <- 2 x - 1 (normalize=True), then (x - shift) / scale per channel,
+ *             shift = (-.030, -.088, -.188), scale = (.458, .448, .450).
+ *   features  VGG16 `features`, tapped after relu1_2, relu2_2, relu3_3, relu4_3, relu5_3: C_l = 64, 128, 256, 512, 512 channels on
+ *             floor(H / 2^l) x floor(W / 2^l) pixels, l = 0 .. 4 (a 2 x 2 max-pool opens slices 2 to 5).  The convolutions are the
+ *             caller's (torch / MIOpen); everything from here on is this operator.
+ *   head      per layer l, for the feature maps a, b (N, C, h, w) of the two images and non-negative weights w_c (the `lin` layers):
+ *               r_a = sqrt(sum_c a_c^2), n_a = r_a + 1e-10, a^_c = a_c / n_a, the same for b, at every pixel;
+ *               d_l(n) = (1 / (h w)) sum over the pixels of sum_c w_c (a^_c - b^_c)^2;      value(n) = sum_l d_l(n).
+ *             The difference a^_c - b^_c is formed per channel: the expanded form sum w a^2 / n_a^2 + sum w b^2 / n_b^2 -
+ *             2 sum w a b / (n_a n_b) loses the value in f32 when the prediction approaches the target (6 % at a relative
+ *             difference of 1e-3, C = 512) and is not used.
+ *   gradient  given g_n = dL/dvalue(n), at every pixel: u_c = 2 g_n w_c (a^_c - b^_c) / (h w), s = sum_c u_c a_c,
+ *               dL/da_c = u_c / n_a - a_c s / (r_a n_a^2);        dL/db_c the same with a and b exchanged and the sign of u flipped.
+ *             It is evaluated as (u_c - t_c q) / n_a + t_c q eps / n_a^2 with t = a / r_a, q = sum_c u_c t_c, eps = 1e-10 - the same
+ *             number, since r_a / n_a = 1 - eps / n_a -, which cancels exactly where u is parallel to a (always at one channel); the
+ *             form above returns rounding noise there in f32.
+ *   DEPARTURE at a pixel whose feature vector is entirely zero (r_a = 0) autograd of the package's lines returns NaN (0 / 0 in
+ *             sqrt's backward) - the reason the reference skips optimiser steps on NaN gradients.  This operator returns an exact 0
+ *             for that vector's gradient (the ReLU behind it would zero any finite value anyway); the VALUE at such a pixel follows
+ *             the definition, a^ = 0.  The other image's vector at that pixel has its usual gradient.
+ *             "Entirely zero" is decided on the f32 sum of squares: a non-zero vector whose elements are all below about 1e-23
+ *             underflows it and is treated as zero, value and gradient (VGG features are not of that size).
+ * GsrLpipsLayers, passed BY VALUE, is the layer table: 1 <= num_layers <= GSR_LPIPS_MAX_LAYERS rows of the two feature arrays
+ * (N, channels, height, width), contiguous f32, and the `channels` weights; 1 <= channels <= 1024, height, width >= 1,
+ * height x width <= 2^31 - 1.  The layers need not be a VGG pyramid: any channel counts and sizes.
+ * gsr_lpips_head: ONE launch for all layers.  A unit of work is (layer, image, run of gsr_lpips_head_pixel_run(channels) consecutive
+ *   pixels): a workgroup of 256 threads holds its unit's two feature blocks in registers - lanes along the pixels, the channels
+ *   (stride h w) dealt over 256 / run groups of at most gsr_lpips_head_channel_slots() each - so the norms (first trip over the
+ *   channels) and the differences (second trip) read memory once.  It writes ONE float per workgroup into `partials`
+ *   (gsr_lpips_head_partials(num_images, layers) floats: host arithmetic, 0 for what the launch refuses - num_images < 1, a bad
+ *   table, more than 16 777 215 units: a launch takes at most 2^32 - 1 threads).
+ * gsr_lpips_head_finish: one workgroup, a fixed order, no atomics: values (num_images) and per_layer (num_images,
+ *   GSR_LPIPS_MAX_LAYERS) = d_l(n), 0 in the columns from num_layers on.  The same bits on every call, and an image has the bits
+ *   in a batch that it has alone.
+ * gsr_lpips_head_backward: ONE launch for all layers, the same units; `g` (num_images) f32; dL_da, dL_db: HOST arrays of num_layers
+ *   device pointers, each shaped like its feature array; an array pointer or any entry may be NULL: that gradient is neither
+ *   computed nor stored.  Nothing to write: nothing is launched.  Every element of a requested gradient is written.
+ * GSR_ERR_INVALID_ARGUMENT, nothing launched: whatever the partials query refuses, a NULL feature, weight, partials or output
+ * pointer.  num_images == 0 is refused too (there is nothing to size). */
+#define GSR_LPIPS_MAX_LAYERS 5
+typedef struct GsrLpipsLayer {
+  const float* a;       /* (N, channels, height, width) */
+  const float* b;       /* the same shape */
+  const float* weight;  /* (channels) */
+  int32_t channels, height, width, reserved_;
+} GsrLpipsLayer;
+typedef struct GsrLpipsLayers {
+  int32_t num_layers, reserved_;
+  GsrLpipsLayer layer[GSR_LPIPS_MAX_LAYERS];
+} GsrLpipsLayers;
+int gsr_lpips_head_channel_slots(void);
+int gsr_lpips_head_pixel_run(int channels); /* 0 for channels outside 1 .. 1024 */
+size_t gsr_lpips_head_partials(int num_images, GsrLpipsLayers layers);
+int gsr_lpips_head(int num_images, GsrLpipsLayers layers, float* partials, void* stream);
+int gsr_lpips_head_finish(int num_images, GsrLpipsLayers layers, const float* partials, float* values, float* per_layer, void* stream);
+int gsr_lpips_head_backward(int num_images, GsrLpipsLayers layers, const float* g, float* const* dL_da /* NULL = none */,
+                            float* const* dL_db /* NULL = none */, void* stream);
+
 /* The encoder-side Gaussian adapter, the step right in front of the raster path (reference
  * src/model/encoder/common/gaussian_adapter.py:60-87 with get_world_rays), one launch: G groups (scene x source view) of P
  * pixel-aligned Gaussians each, M = (sh_degree + 1)^2 for sh_degree 0..4.

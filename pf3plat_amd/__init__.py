@@ -40,3 +40,5 @@ from . import matching  # noqa: F401,E402
 from .matching import MatchAssignment, Matches, match_assignment, pack_matched  # noqa: F401,E402
 from . import keypoints  # noqa: F401,E402
 from .keypoints import Keypoints, PackedKeypoints, SuperPoint, detect_keypoints, keypoints_from_scores  # noqa: F401,E402
+from . import lpips  # noqa: F401,E402
+from .lpips import LPIPS, load_lpips_state_dict, lpips_distance  # noqa: F401,E402

@@ -57,6 +57,18 @@ class GsrBackwardOptions(ctypes.Structure):
                 ("depth_term_only", ctypes.c_int32), ("reserved_", ctypes.c_int32), ("dL_dalpha_img", ctypes.c_void_p)]
 
 
+LPIPS_MAX_LAYERS = 5
+
+
+class GsrLpipsLayer(ctypes.Structure):
+    _fields_ = [("a", ctypes.c_void_p), ("b", ctypes.c_void_p), ("weight", ctypes.c_void_p), ("channels", ctypes.c_int32),
+                ("height", ctypes.c_int32), ("width", ctypes.c_int32), ("reserved_", ctypes.c_int32)]
+
+
+class GsrLpipsLayers(ctypes.Structure):  # passed by value
+    _fields_ = [("num_layers", ctypes.c_int32), ("reserved_", ctypes.c_int32), ("layer", GsrLpipsLayer * LPIPS_MAX_LAYERS)]
+
+
 def find_hipcc() -> str:
     for cand in (os.environ.get("HIPCC"), "/opt/rocm/bin/hipcc", shutil.which("hipcc")):
         if cand and os.path.exists(cand):
@@ -66,7 +78,7 @@ def find_hipcc() -> str:
 
 def hip_sources(csrc: str = None, header: str = None) -> list:
     """Every file libgsr_hip.so is built from: csrc/gsr_hip.hip - the one translation unit - and the headers next to it that it
-    includes (gsr_common.h, gsr_{binning,tiles_fwd,backward,cameras,covariance}.h, one header per operator - gsr_{image,adapter,pose_loss,
+    includes (gsr_common.h, gsr_{binning,tiles_fwd,backward,cameras,covariance}.h, one header per operator - gsr_{image (with the perceptual distance's head),adapter,pose_loss,
     cost_volume,lift,mono_attention,attention (with the matcher's tail and the keypoint extraction),coarse_pose,pose_refine}.h -, gsr_pnp_solver.h, preprocess_bwd.inc: all of csrc/ but the torch
     binding, which is a library of its own; tests/test_abi.py holds this set to the #include graph) and include/gsr.h."""
     csrc = csrc or os.path.dirname(SRC)
@@ -278,6 +290,18 @@ def load():
     lib.gsr_image_metrics.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp]
     lib.gsr_image_metrics_finish.restype = ctypes.c_int
     lib.gsr_image_metrics_finish.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp]
+    lib.gsr_lpips_head_channel_slots.restype = ctypes.c_int
+    lib.gsr_lpips_head_channel_slots.argtypes = []
+    lib.gsr_lpips_head_pixel_run.restype = ctypes.c_int
+    lib.gsr_lpips_head_pixel_run.argtypes = [ctypes.c_int]
+    lib.gsr_lpips_head_partials.restype = ctypes.c_size_t
+    lib.gsr_lpips_head_partials.argtypes = [ctypes.c_int, GsrLpipsLayers]
+    lib.gsr_lpips_head.restype = ctypes.c_int
+    lib.gsr_lpips_head.argtypes = [ctypes.c_int, GsrLpipsLayers, vp, vp]  # num_images, the table; partials, stream
+    lib.gsr_lpips_head_finish.restype = ctypes.c_int
+    lib.gsr_lpips_head_finish.argtypes = [ctypes.c_int, GsrLpipsLayers, vp, vp, vp, vp]  # ...; partials, values, per_layer, stream
+    lib.gsr_lpips_head_backward.restype = ctypes.c_int  # ...; g, host arrays of dL_da and dL_db pointers (or None), stream
+    lib.gsr_lpips_head_backward.argtypes = [ctypes.c_int, GsrLpipsLayers, vp, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), vp]
     lib.gsr_pack_view.restype = ctypes.c_int
     lib.gsr_pack_view.argtypes = [vp, vp, vp, ctypes.c_int, vp, ctypes.c_float, ctypes.c_float, vp, vp, ctypes.c_float, vp, vp]
     lib.gsr_mark_visible.restype = ctypes.c_int
@@ -377,6 +401,8 @@ EXPORTED_SYMBOLS = (
     "gsr_image_loss", "gsr_image_loss_partials", "gsr_image_loss_finish", "gsr_pack_view", "gsr_setup_views_backward",
     "gsr_adapt", "gsr_adapt_backward", "gsr_adapt_partials_bytes", "gsr_adapt_backward_ex", "gsr_adapt_partials_bytes_ex", "gsr_setup_views_backward_ex",
     "gsr_image_metrics", "gsr_image_metrics_partials", "gsr_image_metrics_finish",
+    "gsr_lpips_head", "gsr_lpips_head_backward", "gsr_lpips_head_finish", "gsr_lpips_head_partials", "gsr_lpips_head_pixel_run",
+    "gsr_lpips_head_channel_slots",
     "gsr_pose_loss", "gsr_pose_loss_backward", "gsr_pose_loss_units",
     "gsr_cost_volume", "gsr_cost_volume_backward", "gsr_cost_volume_scratch_bytes",
     "gsr_pnp_ransac", "gsr_pnp_ransac_scratch_bytes", "gsr_pnp_min_matches", "gsr_camera_sync",

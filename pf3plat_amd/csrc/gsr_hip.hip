@@ -37,7 +37,7 @@
 //   gsr_cameras.h      camera set-up, with its entry points
 //   gsr_covariance.h   covariance kernels, with their entry points
 //   gsr_hip.hip        dims_ok, base_params, forward_impl / backward_impl, the rasterizer's entry points; no kernel
-//   gsr_image.h        image loss and evaluation metrics           }
+//   gsr_image.h        image loss, evaluation metrics, the perceptual distance's head (routines of k_pose_ops)  }
 //   gsr_adapter.h      Gaussian adapter                            }  operators next to the raster path, each with its
 //   gsr_pose_loss.h    pose loss                                   }  kernels and its own entry points
 //   gsr_cost_volume.h  plane-sweep cost volume                     }
@@ -46,7 +46,7 @@
 //   gsr_attention.h    multi-head attention (k_mha_ops), on those helpers; the match assignment's passes and entry points  }
 //   gsr_pnp_solver.h   namespace gsr::pnp: host + device arithmetic of the coarse-pose solver (a host program includes it alone)
 //   gsr_coarse_pose.h  PnP RANSAC kernels, k_camera_sync, entry points
-//   gsr_pose_refine.h  the refined poses and the pose errors (k_pose_ops, which also runs the match assignment's passes)
+//   gsr_pose_refine.h  the refined poses and the pose errors (k_pose_ops, which also runs the match assignment's, the keypoint extraction's and the perceptual head's passes)
 #include "gsr_common.h"
 #include "gsr_binning.h"
 #include "gsr_tiles_fwd.h"

@@ -442,3 +442,317 @@ int gsr_image_metrics_finish(int num_images, int height, int width, const float*
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// The perceptual distance's head (lpips.LPIPS(net="vgg") after its convolutions; definition: include/gsr.h): per layer the two
+// feature maps normalised along their channels, the weighted squared difference, the spatial mean - and its gradient.  Purely
+// memory-bound: 64 MB per 256 x 256 image pair, read ONCE in either direction.
+// A unit of work = (layer, image, run of P consecutive pixels) = one workgroup of 256 threads, thread = (channel group g, pixel p),
+// tid = g P + p: lanes run along consecutive pixels (a wave-instruction reads 64 / min(P, 64) channels' runs of min(P, 64) floats
+// each), the channel stride is h w.  The layer's C channels are dealt over G = 256 / P groups, channel s G + g in slot s of group g;
+// G is the smallest power of two that leaves a thread at most kLpSlots = 64 channels: C <= 64 -> one group, runs of 256 pixels;
+// C = 512 -> 8 groups, runs of 32 (128-byte rows); C = 1024 -> 16 groups, runs of 16.  A thread holds its slots of a, b AND the
+// weights in registers (192 of them: the arrays are indexed by unrolled loops only), so the two trips over the channels the
+// definition forces - the norms, then the differences a^_c - b^_c - and the gradient's third read memory once; every load of a
+// unit is issued before the first is used (up to 128 KB of features in flight per CU - what one workgroup per CU needs to keep the
+// memory busy).  Channel sums across the groups go through LDS and are added by every thread of a pixel in group order; a unit's
+// value by a wave butterfly and four LDS words; one float per workgroup leaves, and lpips_finish adds an image's slots in a fixed
+// order, a wave per image: no atomics, the same bits on every call, an image's value independent of the batch around it.
+// The gradient recomputes everything from the same registers, in the projection form given at its code, and stores dL/da, dL/db
+// (either optional per layer) at the addresses it read; a vector with r = 0 stores exact zeros (the stated departure from
+// autograd's NaN).
+// These are routines of k_pose_ops (gsr_pose_refine.h gives the reason: a kernel of its own would move .text), op kPoseOpLpips; its
+// registers - one workgroup per CU - are what the register-resident unit wants anyway.  Loads are one dword per lane: 16-byte loads
+// would need h w a multiple of four and a second path for every other size (not built).
+// ------------------------------------------------------------------------------------------------
+namespace gsr {
+constexpr int kLpSlots = 64;        // channels a thread holds
+constexpr int kLpThreads = 256;     // = kRefineThreads (static_assert next to the kernel)
+constexpr int kLpMaxChannels = 1024;
+constexpr uint32_t kLpMaxUnits = 0xffffffffu / kLpThreads;  // a launch takes at most 2^32 - 1 threads: 16 777 215 workgroups of 256
+constexpr float kLpEps = 1e-10f;
+enum { kLpForward = 0, kLpFinish = 1, kLpBackward = 2 };
+
+struct LpLayer {
+  const float *a, *b, *w;
+  float *da, *db;     // backward: either may be null
+  int C, hw;
+  int lg;             // log2 of the channel groups G; P = 256 >> lg pixels per unit
+  uint32_t upi, base; // units per image; the layer's first unit
+  float inv_hw;
+};
+struct LpipsArgs {
+  int op, N, L;
+  LpLayer layer[GSR_LPIPS_MAX_LAYERS];
+  const float* g;        // backward: (N)
+  float* partials;       // forward: one float per unit; finish reads them
+  float *values, *per_layer;
+};
+
+__host__ __device__ inline int lp_log_groups(int C) {
+  int lg = 0;
+  while (((C + (1 << lg) - 1) >> lg) > kLpSlots) ++lg;
+  return lg;
+}
+
+// the layer of unit u and the unit's place in it (uniform over the workgroup; selects, so that the table stays in scalar registers)
+__device__ __forceinline__ LpLayer lp_layer_of(const LpipsArgs& A, uint32_t u) {
+  LpLayer y = A.layer[0];
+#pragma unroll
+  for (int l = 1; l < GSR_LPIPS_MAX_LAYERS; ++l)
+    if (l < A.L && u >= A.layer[l].base) y = A.layer[l];
+  return y;
+}
+
+template <bool kBackward>
+__device__ __forceinline__ void lpips_unit(const LpipsArgs& A, float* lds) {
+  const int tid = threadIdx.x;
+  const uint32_t u = blockIdx.x;
+  const LpLayer y = lp_layer_of(A, u);
+  const uint32_t local = u - y.base, img = local / y.upi, run = local - img * y.upi;
+  const int G = 1 << y.lg, P = kLpThreads >> y.lg;
+  const int g = tid >> (8 - y.lg), p = tid & (P - 1);
+  const int64_t pix = (int64_t)run * P + p;
+  const bool valid = pix < (int64_t)y.hw;
+  const int C = y.C;
+  const size_t hw = (size_t)y.hw, off = ((size_t)img * C + g) * hw + (size_t)(valid ? pix : 0), step = (size_t)G * hw;
+  const float* pa = y.a + off;
+  const float* pb = y.b + off;
+  const bool want_a = kBackward && y.da != nullptr, want_b = kBackward && y.db != nullptr;
+  if (kBackward && !want_a && !want_b) return;  // (uniform: before any barrier)
+  float va[kLpSlots], vb[kLpSlots], vw[kLpSlots];
+  // every load of the unit, before anything is used; blocks of 8 slots past the layer's channels are skipped by a uniform branch
+#pragma unroll
+  for (int sb = 0; sb < kLpSlots / 8; ++sb) {
+    if ((sb * 8) * G < C) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const int s = sb * 8 + k, c = s * G + g;
+        const bool ok = valid && c < C;
+        va[s] = ok ? pa[(size_t)s * step] : 0.f;
+        vb[s] = ok ? pb[(size_t)s * step] : 0.f;
+        vw[s] = c < C ? y.w[c] : 0.f;
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) { va[sb * 8 + k] = 0.f; vb[sb * 8 + k] = 0.f; vw[sb * 8 + k] = 0.f; }
+    }
+  }
+  // ---- first trip: the squared norms, this thread's slots in order, then the groups of the pixel in order
+  float sa = 0.f, sb2 = 0.f;
+#pragma unroll
+  for (int sb = 0; sb < kLpSlots / 8; ++sb) {
+    if ((sb * 8) * G < C) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) { const int s = sb * 8 + k; sa += va[s] * va[s]; sb2 += vb[s] * vb[s]; }
+    }
+  }
+  float* const la = lds;                    // four arrays of kLpThreads floats
+  float* const lb = lds + kLpThreads;
+  float* const ls = lds + 2 * kLpThreads;
+  float* const lt = lds + 3 * kLpThreads;
+  la[tid] = sa; lb[tid] = sb2;
+  __syncthreads();
+  float ra2 = 0.f, rb2 = 0.f;
+  for (int q = 0; q < G; ++q) { ra2 += la[q * P + p]; rb2 += lb[q * P + p]; }
+  const float ra = sqrtf(ra2), rb = sqrtf(rb2), na = ra + kLpEps, nb = rb + kLpEps;
+  const float ia = 1.f / na, ib = 1.f / nb;
+  if (!kBackward) {
+    // ---- second trip: the weighted squared differences of the normalised vectors
+    float t = 0.f;
+#pragma unroll
+    for (int sb = 0; sb < kLpSlots / 8; ++sb) {
+      if ((sb * 8) * G < C) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          const int s = sb * 8 + k;
+          const float d = va[s] * ia - vb[s] * ib;
+          t += vw[s] * (d * d);
+        }
+      }
+    }
+    t = wave_sum(t);
+    if ((tid & 63) == 0) ls[tid >> 6] = t;
+    __syncthreads();
+    if (tid == 0) A.partials[u] = ((ls[0] + ls[1]) + ls[2]) + ls[3];
+  } else {
+    // The gradient in its projection form.  With t = a / r_a (a unit vector), q = sum_c u_c t_c and r_a / n_a = 1 - eps / n_a,
+    //   dL/da_c = u_c / n_a - a_c s / (r_a n_a^2) = (u_c - t_c q) / n_a + t_c q eps / n_a^2,   u_c = k w_c (a^_c - b^_c), k = 2 g_n / (h w):
+    // the first form subtracts two terms that agree to eps / n_a when u is parallel to a (always at C = 1, where float32 then returns
+    // noise 1e3 times the gradient); the second cancels exactly there - t = a / r_a by IEEE division is +-1 at C = 1 - and leaves the
+    // eps term.  dL/db the same with the sign of u flipped.  The sides that want no gradient skip their divisions (uniform).
+    const bool za = ra == 0.f, zb = rb == 0.f;
+    float rho_a = ia, rho_b = ib;  // a^_c = va rho_a, whether va holds a_c or t_c
+    if (want_a) {
+      rho_a = ra * ia;
+#pragma unroll
+      for (int sb = 0; sb < kLpSlots / 8; ++sb) {
+        if ((sb * 8) * G < C) {
+#pragma unroll
+          for (int k = 0; k < 8; ++k) va[sb * 8 + k] = za ? 0.f : va[sb * 8 + k] / ra;
+        }
+      }
+    }
+    if (want_b) {
+      rho_b = rb * ib;
+#pragma unroll
+      for (int sb = 0; sb < kLpSlots / 8; ++sb) {
+        if ((sb * 8) * G < C) {
+#pragma unroll
+          for (int k = 0; k < 8; ++k) vb[sb * 8 + k] = zb ? 0.f : vb[sb * 8 + k] / rb;
+        }
+      }
+    }
+    // ---- second trip: q_a = sum_c u_c ta_c, q_b = sum_c u_c tb_c
+    const float kk = 2.f * A.g[img] * y.inv_hw;
+    float ta = 0.f, tb = 0.f;
+#pragma unroll
+    for (int sb = 0; sb < kLpSlots / 8; ++sb) {
+      if ((sb * 8) * G < C) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          const int s = sb * 8 + k;
+          const float uc = kk * vw[s] * (va[s] * rho_a - vb[s] * rho_b);
+          ta += uc * va[s]; tb += uc * vb[s];
+        }
+      }
+    }
+    ls[tid] = ta; lt[tid] = tb;
+    __syncthreads();
+    float q_a = 0.f, q_b = 0.f;
+    for (int q = 0; q < G; ++q) { q_a += ls[q * P + p]; q_b += lt[q * P + p]; }
+    const float e_a = q_a * (kLpEps * ia) * ia, e_b = q_b * (kLpEps * ib) * ib;
+    // ---- third trip: the stores; an all-zero vector: exact zeros
+    float* const qa = want_a ? y.da + off : nullptr;
+    float* const qb = want_b ? y.db + off : nullptr;
+#pragma unroll
+    for (int sb = 0; sb < kLpSlots / 8; ++sb) {
+      if ((sb * 8) * G < C) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          const int s = sb * 8 + k, c = s * G + g;
+          if (valid && c < C) {
+            const float uc = kk * vw[s] * (va[s] * rho_a - vb[s] * rho_b);
+            if (want_a) qa[(size_t)s * step] = za ? 0.f : (uc - va[s] * q_a) * ia + va[s] * e_a;
+            if (want_b) qb[(size_t)s * step] = zb ? 0.f : (vb[s] * q_b - uc) * ib - vb[s] * e_b;
+          }
+        }
+      }
+    }
+  }
+}
+
+// One workgroup: wave v takes the images v, v + 4, ...; per layer the image's slots lane by lane in steps of 64, a butterfly, the
+// layer's 1 / (h w); the value is the layers' sum in layer order.
+__device__ __forceinline__ void lpips_finish(const LpipsArgs& A) {
+  const int lane = threadIdx.x & 63;
+  for (int n = threadIdx.x >> 6; n < A.N; n += kLpThreads / 64) {
+    float value = 0.f;
+#pragma unroll
+    for (int l = 0; l < GSR_LPIPS_MAX_LAYERS; ++l) {
+      float d = 0.f;
+      if (l < A.L) {
+        const LpLayer& y = A.layer[l];
+        const float* ps = A.partials + y.base + (size_t)n * y.upi;
+        float t = 0.f;
+        for (uint32_t k = lane; k < y.upi; k += 64) t += ps[k];
+        d = wave_sum(t) * y.inv_hw;
+        value += d;
+      }
+      if (lane == 0) A.per_layer[(size_t)n * GSR_LPIPS_MAX_LAYERS + l] = d;
+    }
+    if (lane == 0) A.values[n] = value;
+  }
+}
+
+__device__ __forceinline__ void k_lpips_ops(const LpipsArgs& A, float* lds) {
+  if (A.op == kLpForward) lpips_unit<false>(A, lds);
+  else if (A.op == kLpBackward) lpips_unit<true>(A, lds);
+  else lpips_finish(A);
+}
+
+static int lpips_op_launch(const LpipsArgs& a, unsigned blocks, void* stream_);  // (gsr_pose_refine.h, next to the kernel)
+
+// The table as the kernels take it; false for what the launch refuses.  *units: the workgroups of the forward and the backward.
+static bool lpips_table(int N, const GsrLpipsLayers& t, LpipsArgs* out, uint64_t* units) {
+  if (N < 1 || t.num_layers < 1 || t.num_layers > GSR_LPIPS_MAX_LAYERS) return false;
+  LpipsArgs A{};
+  A.N = N; A.L = t.num_layers;
+  uint64_t base = 0;
+  for (int l = 0; l < t.num_layers; ++l) {
+    const GsrLpipsLayer& s = t.layer[l];
+    if (s.channels < 1 || s.channels > kLpMaxChannels || s.height < 1 || s.width < 1) return false;
+    const int64_t hw = (int64_t)s.height * s.width;
+    if (hw > 0x7fffffffll) return false;
+    LpLayer& y = A.layer[l];
+    y.a = s.a; y.b = s.b; y.w = s.weight;
+    y.C = s.channels; y.hw = (int)hw;
+    y.lg = lp_log_groups(s.channels);
+    const int64_t P = kLpThreads >> y.lg;
+    y.upi = (uint32_t)((hw + P - 1) / P);
+    y.base = (uint32_t)base;
+    y.inv_hw = (float)(1.0 / (double)hw);
+    base += (uint64_t)y.upi * (uint64_t)N;
+    if (base > (uint64_t)kLpMaxUnits) return false;
+  }
+  *out = A;
+  *units = base;
+  return true;
+}
+
+}  // namespace gsr
+
+extern "C" {
+
+int gsr_lpips_head_channel_slots(void) { return gsr::kLpSlots; }
+
+int gsr_lpips_head_pixel_run(int channels) {
+  if (channels < 1 || channels > gsr::kLpMaxChannels) return 0;
+  return gsr::kLpThreads >> gsr::lp_log_groups(channels);
+}
+
+size_t gsr_lpips_head_partials(int num_images, GsrLpipsLayers layers) {
+  gsr::LpipsArgs A;
+  uint64_t units = 0;
+  return gsr::lpips_table(num_images, layers, &A, &units) ? (size_t)units : 0;
+}
+
+int gsr_lpips_head(int num_images, GsrLpipsLayers layers, float* partials, void* stream_) {
+  gsr::LpipsArgs A;
+  uint64_t units = 0;
+  if (!gsr::lpips_table(num_images, layers, &A, &units) || !partials) return GSR_ERR_INVALID_ARGUMENT;
+  for (int l = 0; l < A.L; ++l)
+    if (!A.layer[l].a || !A.layer[l].b || !A.layer[l].w) return GSR_ERR_INVALID_ARGUMENT;
+  A.op = gsr::kLpForward;
+  A.partials = partials;
+  return gsr::lpips_op_launch(A, (unsigned)units, stream_);
+}
+
+int gsr_lpips_head_finish(int num_images, GsrLpipsLayers layers, const float* partials, float* values, float* per_layer, void* stream_) {
+  gsr::LpipsArgs A;
+  uint64_t units = 0;
+  if (!gsr::lpips_table(num_images, layers, &A, &units) || !partials || !values || !per_layer) return GSR_ERR_INVALID_ARGUMENT;
+  A.op = gsr::kLpFinish;
+  A.partials = const_cast<float*>(partials);
+  A.values = values; A.per_layer = per_layer;
+  return gsr::lpips_op_launch(A, 1u, stream_);
+}
+
+int gsr_lpips_head_backward(int num_images, GsrLpipsLayers layers, const float* g, float* const* dL_da, float* const* dL_db, void* stream_) {
+  gsr::LpipsArgs A;
+  uint64_t units = 0;
+  if (!gsr::lpips_table(num_images, layers, &A, &units) || !g) return GSR_ERR_INVALID_ARGUMENT;
+  bool any = false;
+  for (int l = 0; l < A.L; ++l) {
+    if (!A.layer[l].a || !A.layer[l].b || !A.layer[l].w) return GSR_ERR_INVALID_ARGUMENT;
+    A.layer[l].da = dL_da ? dL_da[l] : nullptr;
+    A.layer[l].db = dL_db ? dL_db[l] : nullptr;
+    any = any || A.layer[l].da || A.layer[l].db;
+  }
+  if (!any) return GSR_OK;
+  A.op = gsr::kLpBackward;
+  A.g = g;
+  return gsr::lpips_op_launch(A, (unsigned)units, stream_);
+}
+
+}  // extern "C"

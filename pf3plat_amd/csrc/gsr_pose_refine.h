@@ -2,6 +2,7 @@
 #include "gsr_common.h"
 #include "gsr_pose_loss.h"  // pose_affine_inverse (k_pose_errors)
 #include "gsr_attention.h"  // k_match_ops, k_keypoint_ops: the match assignment's and the keypoint extraction's passes are routines of k_pose_ops (the reason is given there)
+#include "gsr_image.h"      // k_lpips_ops: so are the perceptual distance's head, its finish and its gradient
 
 // ------------------------------------------------------------------------------------------------
 // Refined poses (reference src/model/encoder/encoder_costvolume.py:447-450, 460-473 with r6d2mat :189-209 and matrix_to_rotation_6d
@@ -21,6 +22,8 @@
 // The match assignment's three passes (gsr_attention.h: k_match_ops) are routines of this kernel as well, op kPoseOpMatch, for the same
 // reason: there were 512 bytes left.  The routines above are launch-bound and do not feel the registers and LDS those passes take.
 // The keypoint extraction's six passes (gsr_attention.h: k_keypoint_ops) are op kPoseOpKeypoints, in the same arena.
+// The perceptual distance's head (gsr_image.h: k_lpips_ops) is op kPoseOpLpips: 4 KB of the arena, and the kernel's one workgroup per
+// CU with its whole register file is the shape those routines are written for.
 // ------------------------------------------------------------------------------------------------
 namespace gsr {
 constexpr int kRefineThreads = 256;
@@ -206,14 +209,16 @@ __device__ __forceinline__ void k_pose_errors(const PoseErrArgs& a, int s) {
 }
 
 // The one kernel of this section: `op` (uniform over the launch) picks the routine.
-enum { kPoseOpRefineFwd = 0, kPoseOpRefineBwd = 1, kPoseOpErrors = 2, kPoseOpMatch = 3, kPoseOpKeypoints = 4 };
+enum { kPoseOpRefineFwd = 0, kPoseOpRefineBwd = 1, kPoseOpErrors = 2, kPoseOpMatch = 3, kPoseOpKeypoints = 4, kPoseOpLpips = 5 };
 struct PoseOpArgs {
   int op;
   RefineArgs r;
   PoseErrArgs e;
   MatchArgs m;  // kPoseOpMatch: the match assignment's pass m.op (gsr_attention.h)
   KeypointArgs k;  // kPoseOpKeypoints: the keypoint extraction's pass k.op (gsr_attention.h)
+  LpipsArgs l;     // kPoseOpLpips: the perceptual head's routine l.op (gsr_image.h)
 };
+static_assert(kLpThreads == kRefineThreads && 4 * kLpThreads <= kMtLdsFloats, "the perceptual head's units are this kernel's workgroups");
 
 template <int kThreads>
 __global__ __launch_bounds__(kRefineThreads) void k_pose_ops(const PoseOpArgs a) {
@@ -224,7 +229,8 @@ __global__ __launch_bounds__(kRefineThreads) void k_pose_ops(const PoseOpArgs a)
   else if (a.op == kPoseOpRefineBwd) k_pose_refine_bwd<kThreads>(a.r, arena);
   else if (a.op == kPoseOpErrors) k_pose_errors(a.e, item);
   else if (a.op == kPoseOpMatch) k_match_ops(a.m, reinterpret_cast<float*>(arena));
-  else k_keypoint_ops(a.k, reinterpret_cast<float*>(arena));
+  else if (a.op == kPoseOpKeypoints) k_keypoint_ops(a.k, reinterpret_cast<float*>(arena));
+  else k_lpips_ops(a.l, reinterpret_cast<float*>(arena));
 }
 
 static int match_op_launch(const MatchArgs& m, dim3 grid, void* stream_) {
@@ -241,6 +247,15 @@ static int keypoint_op_launch(const KeypointArgs& k, dim3 grid, void* stream_) {
   a.op = kPoseOpKeypoints;
   a.k = k;
   hipLaunchKernelGGL(k_pose_ops<kRefineThreads>, grid, dim3(kRefineThreads), 0, static_cast<hipStream_t>(stream_), a);
+  GSR_CHECK(hipGetLastError());
+  return GSR_OK;
+}
+
+static int lpips_op_launch(const LpipsArgs& l, unsigned blocks, void* stream_) {
+  PoseOpArgs a{};
+  a.op = kPoseOpLpips;
+  a.l = l;
+  hipLaunchKernelGGL(k_pose_ops<kRefineThreads>, dim3(blocks), dim3(kRefineThreads), 0, static_cast<hipStream_t>(stream_), a);
   GSR_CHECK(hipGetLastError());
   return GSR_OK;
 }
