@@ -764,6 +764,45 @@ int gsr_attention_backward(int B, int H, int N, int M, int D, float scale, const
                            const int64_t* k_strides, const float* v, const int64_t* v_strides, const float* out, const float* lse,
                            const float* dL_dout, float* dL_dq, float* dL_dk, float* dL_dv, void* scratch, void* stream);
 
+/* Ragged multi-head attention: the attention of LightGlue's matcher transformer (reference src/model/LightGlue/lightglue/
+ * lightglue.py:133-256: SelfBlock on both images, the bidirectional CrossBlock; heads of 64 channels), for every (pair, scene) list
+ * of a batch in one launch.  Forward only (the reference runs the matcher under no_grad).  All f32.
+ * Units: a call has U >= 1 units.  Unit u is a query row range [q_begin[u], q_begin[u] + q_count[u]) and a key row range
+ *   [k_begin[u], k_begin[u] + k_count[u]) of ONE row space of T rows - the packed token buffer; counts >= 0, every range inside
+ *   [0, T].  Self-attention of both images of L lists is 2 L units whose key range is their query range; both directions of the
+ *   cross-attention are 2 L units whose key range is the partner's.  The four arrays (U int32 each) are given on the host - the grid is
+ *   sized from them - and on the device, where the kernel reads them (clamped to [0, T]), as the match assignment takes its offsets.
+ *   The query ranges of a call should be disjoint: a row two units own is written by both.
+ * Operands: q, k, v are each logically (T, H, D) with THREE ELEMENT STRIDES (token, head, channel), read where they lie, offsets
+ *   formed in 64 bits: the interleaved Wqkv output, (T, 3 H D) viewed as (T, H, D, 3)[..., i], has (3 H D, 3 D, 3); a plain
+ *   projection has (H D, D, 1).  1 <= D <= 64.
+ * Rotary encoding: `rot`, or NULL, is (2, T, D) contiguous - cosines, then sines, row t for packed row t - and D is even.  q and k
+ *   (not v) are rotated while they are staged, as apply_cached_rotary_emb (lightglue.py:57-58), each product and the sum rounded:
+ *     x'[2 p] = x[2 p] cos[2 p] - x[2 p + 1] sin[2 p]        x'[2 p + 1] = x[2 p + 1] cos[2 p + 1] + x[2 p] sin[2 p + 1]
+ * With i a query row and j a key row of unit u:
+ *     s[h, i, j] = scale * sum_c q'[i, h, c] k'[j, h, c]        (the f32 sum over c in order, rounded once more by scale)
+ *     p = softmax over the unit's keys j of s
+ *     out[i, h, c] = sum_j p[h, i, j] v[j, h, c]               (T, H, D), token-major and contiguous
+ *     lse[h, i] = log sum_j exp s[h, i, j]                      (H, T)
+ *   A unit with k_count = 0 writes out = 0 and lse = -inf for its rows (the reference's Attention.forward returns zeros there,
+ *   :107-108).  Rows no unit owns as queries are NOT written.
+ * One launch over (unit, block of 128 queries, head): the keys are streamed 32 at a time with the online softmax, NOTHING of n x m
+ *   elements exists anywhere; every product runs on v_mfma_f32_32x32x2_f32 (exact f32, accumulated in key order); expf and logf are
+ *   the accurate functions.  A workgroup finds its unit by a scan of the device counts: no table is built, no host read, and
+ *   `scratch` (gsr_ragged_attention_scratch_bytes(...) bytes: 16 for a call it accepts, 0 for one it refuses; host arithmetic) is
+ *   not touched.  No atomics: the same bits on every call.  A call none of whose units has a query launches nothing.
+ * GSR_ERR_INVALID_ARGUMENT, nothing launched, unless U, T, H >= 1, 1 <= D <= 64, D is even when `rot` is given, every begin and
+ *   count is >= 0 and every range ends at or before T, T H D <= 2^31 - 1 (and H times the query blocks, which only overlapping units
+ *   can push there), `scale` is finite and no required pointer (the host and device arrays, the stride arrays and `scratch`
+ *   included; `rot` may be NULL) is NULL.  All of it is host arithmetic.  No host synchronisation, no internal streams. */
+size_t gsr_ragged_attention_scratch_bytes(int U, int T, int H, int D, const int32_t* q_begin_host, const int32_t* q_count_host,
+                                          const int32_t* k_begin_host, const int32_t* k_count_host);
+int gsr_ragged_attention(int U, int T, int H, int D, float scale, const int32_t* q_begin_host, const int32_t* q_begin_device,
+                         const int32_t* q_count_host, const int32_t* q_count_device, const int32_t* k_begin_host,
+                         const int32_t* k_begin_device, const int32_t* k_count_host, const int32_t* k_count_device, const float* q,
+                         const int64_t* q_strides, const float* k, const int64_t* k_strides, const float* v, const int64_t* v_strides,
+                         const float* rot, float* out, float* lse, void* scratch, void* stream);
+
 /* Match assignment: the tail of LightGlue - MatchAssignment.forward after its two projections, sigmoid_log_double_softmax and
  * filter_matches (reference src/model/LightGlue/lightglue/lightglue.py:259-312) and the list building of :586-597 - for a whole batch
  * of (pair, scene) lists at once.  Forward only (the reference runs the matcher under no_grad).

@@ -35,9 +35,11 @@ from . import mono_attention  # noqa: F401,E402
 from .mono_attention import mono_guided_attention  # noqa: F401,E402
 from . import attention  # noqa: F401,E402
 from .attention import CrossBlock, LearnableFourierPositionalEncoding, SelfBlock, apply_cached_rotary_emb  # noqa: F401,E402
-from .attention import bidirectional_cross_attention, multi_head_attention  # noqa: F401,E402
+from .attention import bidirectional_cross_attention, multi_head_attention, ragged_attention  # noqa: F401,E402
 from . import matching  # noqa: F401,E402
 from .matching import MatchAssignment, Matches, match_assignment, pack_matched  # noqa: F401,E402
+from . import matcher  # noqa: F401,E402
+from .matcher import LightGlue, TransformerLayer, pair_lists  # noqa: F401,E402
 from . import keypoints  # noqa: F401,E402
 from .keypoints import Keypoints, PackedKeypoints, SuperPoint, detect_keypoints, keypoints_from_scores  # noqa: F401,E402
 from . import lpips  # noqa: F401,E402

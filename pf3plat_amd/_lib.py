@@ -79,7 +79,7 @@ def find_hipcc() -> str:
 def hip_sources(csrc: str = None, header: str = None) -> list:
     """Every file libgsr_hip.so is built from: csrc/gsr_hip.hip - the one translation unit - and the headers next to it that it
     includes (gsr_common.h, gsr_{binning,tiles_fwd,backward,cameras,covariance}.h, one header per operator - gsr_{image (with the perceptual distance's head),adapter,pose_loss,
-    cost_volume,lift,mono_attention,attention (with the matcher's tail and the keypoint extraction),coarse_pose,pose_refine}.h -, gsr_pnp_solver.h, preprocess_bwd.inc: all of csrc/ but the torch
+    cost_volume,lift,mono_attention,attention (with the ragged attention, the matcher's tail and the keypoint extraction),coarse_pose,pose_refine}.h -, gsr_pnp_solver.h, preprocess_bwd.inc: all of csrc/ but the torch
     binding, which is a library of its own; tests/test_abi.py holds this set to the #include graph) and include/gsr.h."""
     csrc = csrc or os.path.dirname(SRC)
     return [os.path.join(csrc, n) for n in sorted(os.listdir(csrc)) if n != "gsr_torch.cpp" and os.path.isfile(os.path.join(csrc, n))] + [header or HEADER]
@@ -369,6 +369,11 @@ def load():
     lib.gsr_attention.argtypes = mha_head + [vp] * 3  # ...; out, lse, stream
     lib.gsr_attention_backward.restype = ctypes.c_int  # ...; out, lse, dL_dout, dL_dq, dL_dk, dL_dv, scratch, stream
     lib.gsr_attention_backward.argtypes = mha_head + [vp] * 8
+    lib.gsr_ragged_attention_scratch_bytes.restype = ctypes.c_size_t
+    lib.gsr_ragged_attention_scratch_bytes.argtypes = [ctypes.c_int] * 4 + [i32p] * 4  # U, T, H, D; host q_begin, q_count, k_begin, k_count
+    lib.gsr_ragged_attention.restype = ctypes.c_int  # U, T, H, D; scale; the four arrays, host + device each; q, k, v with three strides; ...
+    lib.gsr_ragged_attention.argtypes = ([ctypes.c_int] * 4 + [ctypes.c_float] + [i32p, vp] * 4 + [vp, i64p] * 3
+                                         + [vp] * 5)  # rot, out, lse, scratch; stream
     lib.gsr_match_assignment_scratch_bytes.restype = ctypes.c_size_t
     lib.gsr_match_assignment_scratch_bytes.argtypes = [ctypes.c_int, i32p, i32p, ctypes.c_int]  # L, host offsets of either image, d
     lib.gsr_match_assignment.restype = ctypes.c_int  # L, d; scale, threshold; width; mdesc0, mdesc1, z0, z1; host + device offsets, twice; ...
@@ -410,6 +415,7 @@ EXPORTED_SYMBOLS = (
     "gsr_mono_attention", "gsr_mono_attention_backward", "gsr_mono_attention_scratch_bytes",
     "gsr_pose_refine", "gsr_pose_refine_backward", "gsr_pose_errors",
     "gsr_attention", "gsr_attention_backward", "gsr_attention_scratch_bytes",
+    "gsr_ragged_attention", "gsr_ragged_attention_scratch_bytes",
     "gsr_match_assignment", "gsr_match_assignment_scratch_bytes",
     "gsr_keypoints", "gsr_keypoints_scratch_bytes", "gsr_keypoints_tile",
     "gsr_tile_deal_order",

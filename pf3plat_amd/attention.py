@@ -7,13 +7,13 @@ projections, the LayerNorm, the GELU and the rotary embedding stay torch."""
 from __future__ import annotations
 
 import ctypes
-from typing import Optional, Tuple
+from typing import Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor, nn
 
 from . import _lib
-from ._call import launch, ptr, require_device, scratch
+from ._call import f32, launch, ptr, require_device, scratch
 
 MAX_HEAD_DIM = 32
 
@@ -108,6 +108,85 @@ def bidirectional_cross_attention(qk0: Tensor, qk1: Tensor, v0: Tensor, v1: Tens
     m0 = multi_head_attention(qk0, qk1, v1, scale)
     m1 = multi_head_attention(qk1, qk0, v0, scale) if need_m1 else None
     return m0, m1
+
+
+MAX_RAGGED_HEAD_DIM = 64
+
+
+def _ranges(ranges, name: str, T: int):
+    begins, counts = [], []
+    for r in ranges:
+        if len(r) != 2 or int(r[0]) != r[0] or int(r[1]) != r[1]:
+            raise ValueError(f"ragged_attention: {name} holds (begin, count) pairs of Python ints, got {r!r}")
+        b, c = int(r[0]), int(r[1])
+        if b < 0 or c < 0 or b + c > T:
+            raise ValueError(f"ragged_attention: {name} range ({b}, {c}) does not lie inside the {T} rows")
+        begins.append(b)
+        counts.append(c)
+    return begins, counts
+
+
+def _ragged_args(q, k, v, q_ranges, k_ranges, scale, rot):
+    """The shape checks (before the device is looked at and before the library is loaded), then the device check."""
+    if q.dim() != 3:
+        raise ValueError(f"ragged_attention: expected q (T, H, D), got {tuple(q.shape)}")
+    T, H, D = q.shape
+    for name, t in (("k", k), ("v", v)):
+        if tuple(t.shape) != (T, H, D):
+            raise ValueError(f"ragged_attention: expected {name} (T, H, D) = ({T}, {H}, {D}), got {tuple(t.shape)}")
+    if T < 1 or H < 1:
+        raise ValueError(f"ragged_attention: needs T, H >= 1, got T={T}, H={H}")
+    if not 1 <= D <= MAX_RAGGED_HEAD_DIM:
+        raise ValueError(f"ragged_attention: supports 1 <= D <= {MAX_RAGGED_HEAD_DIM} channels per head, got {D}")
+    if T * H * D > 0x7fffffff:
+        raise ValueError("ragged_attention: more than 2^31 - 1 elements in an array")
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if t.dtype != torch.float32:
+            raise ValueError(f"ragged_attention: {name} must be float32 (it is read where it lies), got {t.dtype}")
+    qb, qc = _ranges(q_ranges, "q_ranges", T)
+    kb, kc = _ranges(k_ranges, "k_ranges", T)
+    if len(qb) != len(kb) or len(qb) < 1:
+        raise ValueError(f"ragged_attention: needs as many q_ranges as k_ranges and at least one unit, got {len(qb)} and {len(kb)}")
+    if rot is not None:
+        if tuple(rot.shape) != (2, T, D):
+            raise ValueError(f"ragged_attention: expected rot (2, T, D) = (2, {T}, {D}), cosines then sines, got {tuple(rot.shape)}")
+        if D % 2:
+            raise ValueError(f"ragged_attention: a rotary encoding needs an even D, got {D}")
+    scale = D ** -0.5 if scale is None else float(scale)
+    if scale != scale or scale in (float("inf"), float("-inf")):
+        raise ValueError(f"ragged_attention: scale must be finite, got {scale}")
+    require_device("attention", "ragged_attention", [q, k, v] + ([rot] if rot is not None else []))
+    return T, H, D, scale, (qb, qc, kb, kc)
+
+
+@torch.no_grad()
+def ragged_attention(q: Tensor, k: Tensor, v: Tensor, q_ranges: Sequence[Tuple[int, int]], k_ranges: Sequence[Tuple[int, int]],
+                     scale: Optional[float] = None, rot: Optional[Tensor] = None, out: Optional[Tensor] = None, return_lse: bool = False):
+    """Softmax attention of U units over ONE packed row space, as include/gsr.h defines it (gsr_ragged_attention): q, k, v (T, H, D)
+    float32 of any strides, read where they lie; unit u attends its query rows q_ranges[u] = (begin, count) to its key rows
+    k_ranges[u]; 1 <= D <= 64; `scale` defaults to D ** -0.5.  `rot` (2, T, D), cosines then sines, rotates q and k (not v) while they
+    are loaded, as `apply_cached_rotary_emb`.  Returns contiguous (T, H, D): rows of a unit without keys are zero, rows no unit owns
+    keep what `out` held (zeros when `out` is not given); with return_lse also the (H, T) log-sum-exp of the scores, -inf for a unit
+    without keys, unwritten for rows no unit owns.  Forward only, as the reference runs the matcher under no_grad.  One launch
+    for all units and heads, nothing of n x m elements, no host synchronisation, the same bits on every call.  There is no CPU fallback."""
+    T, H, D, scale, arrays = _ragged_args(q, k, v, q_ranges, k_ranges, scale, rot)
+    dev, U = q.device, len(arrays[0])
+    qa, ka, va = q.detach(), k.detach(), v.detach()
+    ra = f32(rot) if rot is not None else None
+    if out is None:
+        out = torch.zeros((T, H, D), dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (T, H, D) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"ragged_attention: out must be a contiguous float32 ({T}, {H}, {D}) on the operands' device")
+    lse = torch.empty((H, T), dtype=torch.float32, device=dev)
+    host = [(ctypes.c_int32 * U)(*a) for a in arrays]
+    both = torch.tensor(arrays, dtype=torch.int32)
+    both = both.pin_memory().to(dev, non_blocking=True)  # (from Python ints: goes up without waiting)
+    work = scratch(_lib.load().gsr_ragged_attention_scratch_bytes(U, T, H, D, *host), torch.float32, dev)
+    s3 = lambda t: (ctypes.c_int64 * 3)(*t.stride())
+    launch("gsr_ragged_attention", dev, U, T, H, D, scale, host[0], both[0].data_ptr(), host[1], both[1].data_ptr(), host[2],
+           both[2].data_ptr(), host[3], both[3].data_ptr(), qa.data_ptr(), s3(qa), ka.data_ptr(), s3(ka), va.data_ptr(), s3(va), ptr(ra),
+           out.data_ptr(), lse.data_ptr(), work.data_ptr())
+    return (out, lse) if return_lse else out
 
 
 def rotate_half(x: Tensor) -> Tensor:

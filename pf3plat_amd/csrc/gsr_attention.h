@@ -386,6 +386,284 @@ int gsr_attention_backward(int B, int H, int N, int M, int D, float scale, const
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------------
+// Ragged multi-head attention (the attention of LightGlue's matcher transformer, reference lightglue.py:133-256 as
+// src/model/encoder/encoder_costvolume.py:79, 334-337 builds and calls it; definition: include/gsr.h): k_mha_fwd's tile scheme - four
+// waves, a wave owns 32 queries, key tiles of 32 through two LDS buffers, the score tile in registers as the next product's B operand -
+// with what the matcher needs and the pose transformer has not:
+//   UNITS: a workgroup is (unit, block of 128 queries, head); a unit is a query row range and a key row range of ONE packed row space
+//     of T rows, read from the device copies of the four arrays (clamped to [0, T]: a wrong device copy reads nothing outside the
+//     operands).  The grid is sized on the host from the host copies; a workgroup finds its unit by a wave scan over the units' block
+//     counts, 64 units a step (rg_find): no table, no launch in front, no host read.
+//   HEADS OF 64: channels 32 .. 63 are a second half - the score tile sums over up to 32 channel pairs, the owned q is 32 registers,
+//     there are two 32 x 32 output accumulators; the half is skipped where D <= 32 (launch-uniform).
+//   ROTARY AT LOAD: with `rot` the rows of q and k are rotated while they are staged: the fetch takes x, cos and sin into registers
+//     (one tile ahead, as the keys themselves), the partner channel comes from the neighbouring lane (the lane index of a load runs
+//     along the channels) when the registers go to LDS; x cos + (-+ partner) sin in the reference's order of operations.
+// LDS: the owned image [64][129], K tiles 2 x [64][33], V tiles 2 x [32][72]: 68 352 bytes, two workgroups on a CU.  ds_read_b32 and
+// ds_write_b32 bank by address mod 32 within a half wave: the K and owned images are filled by channel (line strides 33 and 129: odd)
+// and read by token, the V image is filled and read by channel; a half wave never meets a bank twice.
+// A unit without keys writes out = 0, lse = -inf.  No atomics, every trip count fixed by the arrays: the same bits on every call.
+// ------------------------------------------------------------------------------------------------
+namespace gsr {
+constexpr int kRgChan = 64;                       // the most channels per head
+constexpr int kRgOwnS = kMaOwn + 1;               // line stride of the owned [c][query] image
+constexpr int kRgOwnFloats = kRgChan * kRgOwnS;   // ... which after the loop holds four [token][33] output tiles
+constexpr int kRgKFloats = kRgChan * 33;          // a key tile's [c][33] image
+constexpr int kRgVS = 72;                         // line stride of the [key][channel] value image
+constexpr int kRgVFloats = 32 * kRgVS;
+constexpr int kRgLdsFloats = kRgOwnFloats + 2 * kRgKFloats + 2 * kRgVFloats;
+static_assert(kRgOwnFloats >= 4 * 32 * 33, "the output tiles live in the owned image");
+
+struct RaggedArgs {
+  int U, T, H, D;
+  float scale;
+  const int32_t *qb, *qc, *kb, *kc;  // the device copies: a unit's first query row, its queries, its first key row, its keys
+  const float *q, *k, *v, *rot;      // rot: (2, T, D) cosines then sines, or NULL
+  int64_t qs[3], ks[3], vs[3];       // element strides: token, head, channel
+  float *out, *lse;                  // (T, H, D), (H, T)
+};
+
+__device__ __forceinline__ int rg_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+
+// The unit that holds query block `g` of the call (blocks of 128 queries, unit after unit) and the block's index inside it; false
+// past the last block.  Every lane of the wave calls it and gets the same answer.
+__device__ __forceinline__ bool rg_find(const RaggedArgs& a, int g, int lane, int* unit, int* blk) {
+  int base = 0;
+  for (int u0 = 0; u0 < a.U; u0 += 64) {
+    const int u = u0 + lane;
+    const int nb = u < a.U ? (rg_clamp(a.qc[u], a.T) + kMaOwn - 1) / kMaOwn : 0;
+    const int inc = (int)wave_inclusive_scan_u32((uint32_t)nb);
+    const unsigned long long hit = __ballot(base + inc > g);
+    if (hit) {
+      const int first = __ffsll((long long)hit) - 1;
+      *unit = u0 + first;
+      *blk = g - base - __shfl(inc - nb, first);
+      return true;
+    }
+    base += __shfl(inc, 63);
+  }
+  return false;
+}
+
+// Rows [tok0, tok0 + 32) of a range of ntok rows x channels [c0, c0 + 32) of a strided operand into 4 registers of each of 256
+// threads, mh_fetch's element order; `base` is the range's first row at the head; zero outside [0, ntok) x [0, D).
+__device__ __forceinline__ void rg_fetch(const float* base, int64_t st, int64_t sc, int D, int ntok, int tok0, int c0, int tid, float* regs) {
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int idx = tid + 256 * u, tok = tok0 + (idx >> 5), c = c0 + (idx & 31);
+    regs[u] = (c < D && tok < ntok) ? base[(int64_t)tok * st + (int64_t)c * sc] : 0.f;
+  }
+}
+
+// apply_cached_rotary_emb on a staged element: (x cos) + (rotate_half(x) sin), rotate_half(x)[2 p] = -x[2 p + 1], [2 p + 1] = x[2 p];
+// the partner channel is the neighbouring lane's.  Every lane of the wave calls it.
+__device__ __forceinline__ float rg_rotate(float x, float cs, float sn, int tid) {
+  const float xp = __shfl_xor(x, 1);
+  return x * cs + ((tid & 1) ? xp : -xp) * sn;
+}
+
+template <bool kRot>
+__device__ __forceinline__ void k_ragged_fwd(const RaggedArgs& a, float* lds) {
+  constexpr int VS = kRgVS;
+  float* Qs = lds;
+  float(*Ks)[kRgKFloats] = reinterpret_cast<float(*)[kRgKFloats]>(lds + kRgOwnFloats);
+  float(*Vs)[kRgVFloats] = reinterpret_cast<float(*)[kRgVFloats]>(lds + kRgOwnFloats + 2 * kRgKFloats);
+  const int tid = threadIdx.x, lane = tid & 63, x = lane & 31, h = lane >> 5, wv = tid >> 6;
+  const int H = a.H, D = a.D, T = a.T;
+  const int g = (int)blockIdx.x / H, hd = (int)blockIdx.x - g * H;
+  int unit, blk;
+  if (!rg_find(a, g, lane, &unit, &blk)) return;  // (workgroup-uniform)
+  const int q0 = rg_clamp(a.qb[unit], T), nq = rg_clamp(a.qc[unit], T - q0);
+  const int k0 = rg_clamp(a.kb[unit], T), nk = rg_clamp(a.kc[unit], T - k0);
+  const int i0 = blk * kMaOwn, DP = (D + 1) / 2, NT = (nk + kMaTile - 1) / kMaTile;
+  const bool two = D > 32;  // (launch-uniform)
+  const float* qh = a.q + (int64_t)q0 * a.qs[0] + (int64_t)hd * a.qs[1];
+  const float* kh = a.k + (int64_t)k0 * a.ks[0] + (int64_t)hd * a.ks[1];
+  const float* vh = a.v + (int64_t)k0 * a.vs[0] + (int64_t)hd * a.vs[1];
+  const float *qcos = nullptr, *qsin = nullptr, *kcos = nullptr, *ksin = nullptr;
+  if (kRot) {
+    qcos = a.rot + (int64_t)q0 * D; qsin = qcos + (int64_t)T * D;
+    kcos = a.rot + (int64_t)k0 * D; ksin = kcos + (int64_t)T * D;
+  }
+  float kp[8], vp[8], cp[8], sp[8];  // a tile one ahead: k, v and (kRot) k's cosines and sines; registers 4 half + u
+  auto fetch = [&](int tok0) {
+#pragma unroll
+    for (int half = 0; half < 2; ++half)
+      if (half == 0 || two) {
+        rg_fetch(kh, a.ks[0], a.ks[2], D, nk, tok0, 32 * half, tid, kp + 4 * half);
+        rg_fetch(vh, a.vs[0], a.vs[2], D, nk, tok0, 32 * half, tid, vp + 4 * half);
+        if (kRot) {
+          rg_fetch(kcos, D, 1, D, nk, tok0, 32 * half, tid, cp + 4 * half);
+          rg_fetch(ksin, D, 1, D, nk, tok0, 32 * half, tid, sp + 4 * half);
+        }
+      }
+  };
+  auto put = [&](int buf) {
+#pragma unroll
+    for (int half = 0; half < 2; ++half)
+      if (half == 0 || two) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int idx = tid + 256 * u, tok = idx >> 5, c = 32 * half + (idx & 31);
+          const float kv = kRot ? rg_rotate(kp[4 * half + u], cp[4 * half + u], sp[4 * half + u], tid) : kp[4 * half + u];
+          Ks[buf][c * 33 + tok] = kv;
+          Vs[buf][tok * VS + c] = vp[4 * half + u];
+        }
+      }
+  };
+  // the owned queries, rotated, as [c][kRgOwnS]
+#pragma unroll
+  for (int half = 0; half < 2; ++half)
+    if (half == 0 || two) {
+#pragma unroll 4
+      for (int idx = tid; idx < 32 * kMaOwn; idx += 256) {
+        const int t = idx >> 5, c = 32 * half + (idx & 31), tok = i0 + t;
+        const bool ok = c < D && tok < nq;
+        float xv = ok ? qh[(int64_t)tok * a.qs[0] + (int64_t)c * a.qs[2]] : 0.f;
+        if (kRot) {
+          const float cs = ok ? qcos[(int64_t)tok * D + c] : 0.f, sn = ok ? qsin[(int64_t)tok * D + c] : 0.f;
+          xv = rg_rotate(xv, cs, sn, tid);
+        }
+        Qs[c * kRgOwnS + t] = xv;
+      }
+    }
+  fetch(0);
+  put(0);
+  __syncthreads();
+  float qreg[32];  // q'[c = 2 p + h][i]
+#pragma unroll
+  for (int p = 0; p < 32; ++p) qreg[p] = p < DP ? Qs[(2 * p + h) * kRgOwnS + wv * 32 + x] : 0.f;
+  ma_f16 acc0 = ma_zero(), acc1 = ma_zero();
+  float m = -INFINITY, l = 0.f;
+  for (int tile = 0; tile < NT; ++tile) {
+    const int cur = tile & 1, nxt = cur ^ 1, j0 = tile * kMaTile;
+    const bool more = tile + 1 < NT;
+    if (more) fetch(j0 + kMaTile);
+    ma_f16 s = ma_zero();  // S^T[j][i]
+#pragma unroll
+    for (int p = 0; p < 32; ++p)
+      if (p < DP) s = ma_mfma(Ks[cur][(2 * p + h) * 33 + x], qreg[p], s);
+    float mx = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      s[r] = j0 + ma_row(r, h) < nk ? s[r] * a.scale : -INFINITY;
+      mx = fmaxf(mx, s[r]);
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    const float m_new = fmaxf(m, mx), alpha = expf(m - m_new);  // (every tile holds a key: m_new is finite; exp(-inf) = 0)
+    float sum = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      s[r] = expf(s[r] - m_new);
+      sum += s[r];
+    }
+    sum += __shfl_xor(sum, 32);
+    l = l * alpha + sum;
+    m = m_new;
+    acc0 *= alpha;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc0 = ma_mfma(Vs[cur][ma_row(r, h) * VS + x], s[r], acc0);
+    if (two) {
+      acc1 *= alpha;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc1 = ma_mfma(Vs[cur][ma_row(r, h) * VS + 32 + x], s[r], acc1);
+    }
+    if (more) put(nxt);
+    __syncthreads();
+  }
+  if (nk > 0) {  // (no keys: the accumulators are the zeros they began as)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      acc0[r] = acc0[r] / l;
+      acc1[r] = acc1[r] / l;
+    }
+  }
+  // a wave's accumulators (register r = channel ma_row(r, h) of the half, of the lane's query) through its [token][33] tile of the
+  // owned image, then up to 32 contiguous floats per token and half
+  float* os = Qs + wv * 32 * 33;
+  float* dst = a.out + ((int64_t)q0 * H + hd) * D;
+  const int64_t hdD = (int64_t)H * D;
+#pragma unroll
+  for (int half = 0; half < 2; ++half)
+    if (half == 0 || two) {
+      __syncthreads();  // (the owned image, or the half stored before this one, has been read)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) os[x * 33 + ma_row(r, h)] = half == 0 ? acc0[r] : acc1[r];
+      __syncthreads();
+#pragma unroll
+      for (int u = 0; u < 16; ++u) {
+        const int idx = lane + 64 * u, t = idx >> 5, c = 32 * half + (idx & 31), tok = i0 + wv * 32 + t;
+        if (c < D && tok < nq) dst[(int64_t)tok * hdD + c] = os[t * 33 + (idx & 31)];
+      }
+    }
+  const int i = i0 + wv * 32 + x;
+  if (i < nq && h == 0) a.lse[(int64_t)hd * T + q0 + i] = nk > 0 ? m + logf(l) : -INFINITY;
+}
+
+// A kernel of its own, and a template instance so that it follows every plain kernel and none of them moves (the comment above
+// k_mha_ops): 68 KB of LDS and two accumulators are not what k_mha_ops' three waves per SIMD, or k_pose_ops' one-workgroup routines,
+// should be sized by.  Two workgroups on a CU: the LDS allows no more.
+template <int kThreads>
+__global__ __launch_bounds__(kThreads, 2) void k_ragged_ops(const RaggedArgs a) {
+  __shared__ float lds[kRgLdsFloats];
+  if (a.rot) k_ragged_fwd<true>(a, lds);
+  else k_ragged_fwd<false>(a, lds);
+}
+
+// The limits of a call, from the host copies; on success the number of query blocks of 128 over all units.
+static bool rg_sizes_ok(int U, int T, int H, int D, float scale, bool with_rot, const int32_t* qb, const int32_t* qc, const int32_t* kb,
+                        const int32_t* kc, int64_t* blocks) {
+  if (U < 1 || T < 1 || H < 1 || D < 1 || D > kRgChan || !std::isfinite(scale) || (with_rot && (D & 1))) return false;
+  if (!qb || !qc || !kb || !kc) return false;
+  const int64_t lim = 0x7fffffff;
+  if ((int64_t)T * H > lim / D) return false;  // (T H D <= 2^31 - 1)
+  int64_t nb = 0;
+  for (int u = 0; u < U; ++u) {
+    if (qb[u] < 0 || qc[u] < 0 || kb[u] < 0 || kc[u] < 0) return false;
+    if ((int64_t)qb[u] + qc[u] > T || (int64_t)kb[u] + kc[u] > T) return false;
+    nb += (qc[u] + kMaOwn - 1) / kMaOwn;
+  }
+  if (nb * H > lim) return false;  // (the grid; only overlapping query ranges can reach it)
+  *blocks = nb;
+  return true;
+}
+}  // namespace gsr
+
+extern "C" {
+
+size_t gsr_ragged_attention_scratch_bytes(int U, int T, int H, int D, const int32_t* q_begin_host, const int32_t* q_count_host,
+                                          const int32_t* k_begin_host, const int32_t* k_count_host) {
+  int64_t blocks;
+  if (!gsr::rg_sizes_ok(U, T, H, D, 1.f, false, q_begin_host, q_count_host, k_begin_host, k_count_host, &blocks)) return 0;
+  return 16;  // (a workgroup SEARCHES its unit: no table; never 0 for an accepted call)
+}
+
+int gsr_ragged_attention(int U, int T, int H, int D, float scale, const int32_t* q_begin_host, const int32_t* q_begin_device,
+                         const int32_t* q_count_host, const int32_t* q_count_device, const int32_t* k_begin_host,
+                         const int32_t* k_begin_device, const int32_t* k_count_host, const int32_t* k_count_device, const float* q,
+                         const int64_t* q_strides, const float* k, const int64_t* k_strides, const float* v, const int64_t* v_strides,
+                         const float* rot, float* out, float* lse, void* scratch, void* stream_) {
+  using namespace gsr;
+  int64_t blocks;
+  if (!rg_sizes_ok(U, T, H, D, scale, rot != nullptr, q_begin_host, q_count_host, k_begin_host, k_count_host, &blocks))
+    return GSR_ERR_INVALID_ARGUMENT;
+  if (!q_begin_device || !q_count_device || !k_begin_device || !k_count_device || !q || !q_strides || !k || !k_strides || !v ||
+      !v_strides || !out || !lse || !scratch)
+    return GSR_ERR_INVALID_ARGUMENT;
+  if (blocks == 0) return GSR_OK;  // (no unit has a query: nothing to write)
+  RaggedArgs a{};
+  a.U = U; a.T = T; a.H = H; a.D = D; a.scale = scale;
+  a.qb = q_begin_device; a.qc = q_count_device; a.kb = k_begin_device; a.kc = k_count_device;
+  a.q = q; a.k = k; a.v = v; a.rot = rot; a.out = out; a.lse = lse;
+  for (int s = 0; s < 3; ++s) { a.qs[s] = q_strides[s]; a.ks[s] = k_strides[s]; a.vs[s] = v_strides[s]; }
+  hipLaunchKernelGGL(k_ragged_ops<256>, dim3((unsigned)(blocks * H)), dim3(256), 0, static_cast<hipStream_t>(stream_), a);
+  GSR_CHECK(hipGetLastError());
+  return GSR_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
 // Match assignment (LightGlue's MatchAssignment.forward, sigmoid_log_double_softmax and filter_matches, reference lightglue.py:259-312
 // and the list building of :586-597; definition: include/gsr.h): L ragged lists in one chain of three launches - the passes of
 // k_match_ops, below -, nothing of m x n elements anywhere.  The two streaming passes share one device function, k_match_stream:

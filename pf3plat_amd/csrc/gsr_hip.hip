@@ -43,7 +43,7 @@
 //   gsr_cost_volume.h  plane-sweep cost volume                     }
 //   gsr_lift.h         depth lift, mono cue, Pluecker rays         }
 //   gsr_mono_attention.h  mono-guided attention, the MFMA tile helpers (ma_*)  }
-//   gsr_attention.h    multi-head attention (k_mha_ops), on those helpers; the match assignment's passes and entry points  }
+//   gsr_attention.h    multi-head attention (k_mha_ops) and the ragged attention of the matcher's transformer (k_ragged_ops), on those helpers; the match assignment's passes and entry points  }
 //   gsr_pnp_solver.h   namespace gsr::pnp: host + device arithmetic of the coarse-pose solver (a host program includes it alone)
 //   gsr_coarse_pose.h  PnP RANSAC kernels, k_camera_sync, entry points
 //   gsr_pose_refine.h  the refined poses and the pose errors (k_pose_ops, which also runs the match assignment's, the keypoint extraction's and the perceptual head's passes)
