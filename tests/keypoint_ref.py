@@ -67,6 +67,24 @@ SCORE_CASES = {
     "u24x72": (36, 1, TILE - 8, 2 * TILE + 8, "uniform", 4),
     "q32x64": (37, 1, TILE, 2 * TILE, "eighths", 4),
 }
+# ---- the loops only large calls enter (scores form, judged exactly against `select`; no record of the reference is needed) ---------
+SCAN_CHUNK = 2048    # mask words (32 pixels of a row each) a trip of the scan pass takes; it carries the keypoints counted so far
+BASE_STEP = 256      # images a trip of an image's first packed row (the counts before it, summed by 256 threads) takes
+TOPK_CHUNK = 8192    # found keypoints a trip of the top-k pass ranks against; it carries every keypoint's rank so far
+# name: (seed, H, W, nms_radius, remove_borders), one image in eighths: H x ceil(W / 32) words
+SCAN_CASES = {
+    "w2048": (50, 1024, 40, 1, 0),   # 2048 words: one trip exactly
+    "w2049": (51, 2049, 24, 1, 0),   # one word in the second trip
+    "w2080": (51, 1040, 40, 2, 4),   # 2080 words, two a row
+}
+BATCH_CASE = (81, 260, 8, 8, 1, 0, 0.95, 2, 8)  # seed, B, H, W, nms_radius, remove_borders, threshold, max_num_keypoints of the cut, C
+# name: (seed, H, W, found count, max_num_keypoints): eighths, nms_radius 0 and no border - every pixel above the threshold is found -,
+# the last non-zero pixels zeroed until `found` are left
+TOPK_CASES = {
+    "k8192": (61, 100, 100, TOPK_CHUNK, 6000),       # one trip exactly
+    "k8193": (62, 100, 100, TOPK_CHUNK + 1, 6000),   # a second trip of one keypoint
+    "k3trips": (63, 140, 140, None, 12000),          # as drawn: more than two chunks
+}
 STAIR_OFFSETS = TILE + 25         # start offsets 0 ... TILE + 24
 STAIR_EDGE = TILE + 24 + 20 + 12  # the long edge of a staircase image: the last stair of the last offset, and 11 pixels more
 STAIR_THIN = 12                   # the short edge of the horizontal and vertical ones; the stairs lie on line 5
@@ -114,6 +132,67 @@ def score_case(name):
     if kind == "uniform":
         return torch.rand(B, H, W, generator=g)
     return torch.randint(0, 9, (B, H, W), generator=g).float() / 8
+
+
+def eighths(seed, *shape):
+    return torch.randint(0, 9, shape, generator=gen(seed)).float() / 8
+
+
+@functools.lru_cache(maxsize=None)
+def scan_case(name):
+    """(scores (1, H, W), parameters, what `select` finds) of a SCAN_CASES entry."""
+    seed, H, W, r, border = SCAN_CASES[name]
+    s = eighths(seed, 1, H, W)
+    kw = dict(nms_radius=r, remove_borders=border)
+    return s, kw, select(s, **kw)
+
+
+def mask_words(pixels, W):
+    """The index of each pixel's mask word in the image's row-major order of (row, word of the row)."""
+    return pixels[:, 1] * ((W + 31) // 32) + pixels[:, 0] // 32
+
+
+@functools.lru_cache(maxsize=None)
+def batch_case():
+    """(scores (B, H, W) uniform, descriptors (B, C, H / 8, W / 8), parameters) of BATCH_CASE."""
+    seed, B, H, W, r, border, thr, _, C = BATCH_CASE
+    g = gen(seed)
+    s = torch.rand(B, H, W, generator=g)
+    desc = torch.randn(B, C, H // 8, W // 8, generator=g)
+    return s, desc, dict(nms_radius=r, remove_borders=border, detection_threshold=thr)
+
+
+@functools.lru_cache(maxsize=None)
+def topk_case(name):
+    """(scores (1, H, W), parameters with the cut, what `select` finds and keeps, the found keypoints' scores in row-major order)."""
+    seed, H, W, found, k = TOPK_CASES[name]
+    s = eighths(seed, 1, H, W)
+    if found is not None:
+        flat = s.view(-1)
+        flat[torch.nonzero(flat)[found:, 0]] = 0.0
+    kw = dict(nms_radius=0, remove_borders=0, max_num_keypoints=k)
+    staged = select(s, nms_radius=0, remove_borders=0)[0][1]
+    return s, kw, select(s, **kw), staged
+
+
+def chunk_ranks(scores, chunk=None):
+    """The top-k pass's count, chunk by chunk: row c holds for every keypoint i the keypoints j of chunk c with a higher score, or an
+    equal one and j < i.  The rows' sum is the keypoint's place in the stable descending sort."""
+    chunk = TOPK_CHUNK if chunk is None else chunk
+    n = scores.numel()
+    idx = torch.arange(n)
+    rows = []
+    for c0 in range(0, n, chunk):
+        part = scores[c0:c0 + chunk]
+        up = torch.sort(part).values
+        rk = part.numel() - torch.searchsorted(up, scores, right=True)  # the higher ones
+        for v in part.unique():
+            tie = part == v
+            before = torch.cumsum(tie, 0) - tie.long()  # of the chunk's keypoints below j, those equal to v
+            j = (idx - c0).clamp(0, part.numel())
+            rk = rk + torch.where(scores == v, torch.cat([before, tie.sum()[None]])[j], torch.zeros_like(rk))
+        rows.append(rk)
+    return torch.stack(rows)
 
 
 @functools.lru_cache(maxsize=None)

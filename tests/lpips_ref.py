@@ -49,7 +49,13 @@ CASES = {
     "zeros": (305, 3, ((64, 9, 7), (192, 5, 4)), "zeros"),
     "near": (306, 2, ((512, 7, 9),), "near"),
     "far": (307, 2, ((65, 7, 9),), "far"),
+    # the finish pass past its first trips: a wave takes the images n, n + 4, ..., a lane the units k, k + 64, ... of an image's layer
+    "n9": (308, 9, ((64, 5, 7), (128, 3, 4)), "relu"),   # wave 0: images 0, 4 and 8
+    "u65": (309, 2, ((512, 33, 63),), "relu"),           # runs of 32 pixels: 65 units an image, lane 0 alone takes a second
+    "u129": (310, 2, ((512, 50, 82),), "relu"),          # 129 units an image: a third trip of one lane
+    "u65c64": (311, 5, ((64, 129, 129),), "relu"),       # runs of 256: 66 units an image, and a fifth image for wave 0
 }
+FINISH_CASES = {"n9": (9, (1, 1)), "u65": (2, (65,)), "u129": (2, (129,)), "u65c64": (5, (66,))}  # name: (images, units an image per layer)
 
 
 def rel_l2(a, b):

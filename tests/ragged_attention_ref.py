@@ -22,6 +22,35 @@ SIX = ((70, 150), (0, 33), (1, 77), (45, 0), (131, 323), (40, 1))
 # name: (form, sizes, H, D, with rot, interleaved layout, seed).  Forms: "general" - every unit a query range and a key range of its
 # own, no gaps (at a query row k and v hold the fence, at a key row q holds NaN); "self" - the key range is the query range, one
 # unowned fence row between units; "cross" - lists (m, n), two units per list with swapped partners, fence rows between ranges.
+FIND_STEP = 64  # units a trip of the kernel's unit search (rg_find) takes; a query block is 128 rows
+TWO_BLOCKS = (130, 40)  # a unit of two query blocks: after it the search's running block count is no longer the unit count
+
+
+def many_units(count, seed, two_blocks_at, without_queries, with_queries):
+    """`count` units with (queries, keys) drawn from {0, 1, 2, 3, 5} x {0, 1, 2, 4, 7}, the unit `two_blocks_at` TWO_BLOCKS, the units
+    `without_queries` (0, keys) - they sit at the edges of a trip of the search -, the units `with_queries` at least (1, keys)."""
+    g = torch.Generator().manual_seed(seed)
+    nq = torch.tensor([0, 1, 2, 3, 5])[torch.randint(0, 5, (count,), generator=g)].tolist()
+    nk = torch.tensor([0, 1, 2, 4, 7])[torch.randint(0, 5, (count,), generator=g)].tolist()
+    for u in without_queries:
+        nq[u] = 0
+    for u in with_queries:
+        nq[u] = max(nq[u], 1)
+    nq[two_blocks_at], nk[two_blocks_at] = TWO_BLOCKS
+    return tuple(zip(nq, nk))
+
+
+# More units than one trip of the search: name: (units, seed of the counts, the two-block unit, units without queries, units with).
+# "u64": one trip, the last block in the last lane; "u65": the only block of the second trip in its lane 0, behind an empty lane 63 and
+# a two-block unit in the first trip; "u130": three trips, empty units on both sides of 63 | 64 and 127 | 128, a two-block unit in
+# the second trip, the last unit with queries.
+MANY = {
+    "u64": (64, 21, 10, (62,), (0, 63)),
+    "u65": (65, 22, 10, (63,), (0, 64)),
+    "u130": (130, 23, 70, (63, 64, 127, 128), (0, 65, 129)),
+}
+MANY_SIZES = {name: many_units(*spec) for name, spec in MANY.items()}
+
 CASES = {
     "w64": ("general", SIX, 4, 64, True, True, 1),
     "w63": ("general", SIX, 3, 63, False, False, 2),
@@ -34,7 +63,13 @@ CASES = {
     "blocks": ("general", ((260, 517),), 3, 64, True, True, 9),  # more than two query blocks, 17 key tiles
     "self": ("self", (70, 131, 0, 1, 45), 4, 64, True, True, 10),
     "cross": ("cross", ((70, 150), (45, 0), (1, 77), (131, 40)), 4, 64, False, False, 11),
+    "u64": ("general", MANY_SIZES["u64"], 2, 64, True, True, 31),
+    "u65": ("general", MANY_SIZES["u65"], 2, 64, True, True, 32),
+    "u130": ("general", MANY_SIZES["u130"], 2, 64, True, True, 33),
+    "u65d8": ("general", MANY_SIZES["u65"], 2, 8, False, False, 34),
+    "u130d8": ("general", MANY_SIZES["u130"], 2, 8, False, False, 35),
 }
+MANY_CASES = tuple(n for n in CASES if n.startswith("u"))
 # The online-softmax constructions of tests/attention_ref.py at D = 64: (seed, B, H, N, M, D, amp, pattern, scale); a batch entry is a unit.
 STREAM_CASES = {
     "ramp_up": (9, 1, 2, 260, 517, 64, 30.0, "ramp_up", None),
@@ -126,6 +161,23 @@ def key_rows(T, q_ranges, k_ranges):
 def widened(ranges, T):
     """Every non-empty range one row longer on either side, inside [0, T]: what a kernel that overruns a range would read."""
     return tuple((max(b - 1, 0), min(b + c + 1, T) - max(b - 1, 0)) if c else (b, c) for b, c in ranges)
+
+
+def search_trips(q_ranges):
+    """Per trip of the unit search over FIND_STEP units: (the unit that holds the trip's first query block or None, the query blocks
+    of the units before the trip - what the search carries into it)."""
+    blocks = [(c + 127) // 128 for _, c in q_ranges]
+    out = []
+    for u0 in range(0, len(blocks), FIND_STEP):
+        first = next((u for u in range(u0, min(u0 + FIND_STEP, len(blocks))) if blocks[u]), None)
+        out.append((first, sum(blocks[:u0])))
+    return out
+
+
+def without_carry(k_ranges):
+    """The key ranges a search that forgot its carried count would pair the queries with: a unit past the first trip attends the keys of
+    the unit FIND_STEP before it."""
+    return tuple(k_ranges[u - FIND_STEP] if u >= FIND_STEP else k_ranges[u] for u in range(len(k_ranges)))
 
 
 @functools.lru_cache(maxsize=None)

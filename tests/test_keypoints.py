@@ -8,7 +8,10 @@ keypoint scores and descriptors within max(FLOOR, 4 x |float32 restatement - flo
 restatement and never above 1e-4; rescaled keypoints within 2^-22 (pixel + 0.5) / scale of float64.
 
 Measured on one MI355X: every pixel, count and order equal on every case; keypoint scores within 4.0e-7 (bars 4.1e-7 to 1.6e-6),
-descriptors within 6.5e-7 (bars 6.6e-7 to 2.6e-6), at most 0.26 of a bar; rescaled keypoints within 0.23 of their bound."""
+descriptors within 6.5e-7 (bars 6.6e-7 to 2.6e-6), at most 0.26 of a bar; rescaled keypoints within 0.23 of their bound.
+
+The loops only large calls enter (docs/PARITY.md section 22.1): the scan past 2048 mask words, the packed base of an image past
+256, the top-k rank count past 8192 staged keypoints - scores form, exact; the CPU test states what each case reaches."""
 import ctypes
 import functools
 import os
@@ -89,6 +92,63 @@ def test_floors_are_of_the_size_of_the_worst_float32_loss():
     print(f"float32 restatement: scores {worst_s:.3e}, descriptors {worst_d:.3e}")
     assert ref.FLOOR_SCORES / 10 <= worst_s <= ref.FLOOR_SCORES * 1.5 and ref.FLOOR_DESCRIPTORS / 10 <= worst_d <= ref.FLOOR_DESCRIPTORS * 1.5
     assert max(ref.FLOOR_SCORES, ref.FLOOR_DESCRIPTORS) * 4 <= ref.CAP
+
+
+def test_large_cases_take_the_scan_the_base_and_the_top_k_past_their_first_trip():
+    """The three loops of gsr_attention.h's keypoint passes that only large calls enter, each with what it carries.
+    k_keypoint_scan: 2048 mask words a trip, `running` the keypoints counted so far - keypoints lie on both sides of word 2048, so
+    a lost count moves the later ones onto the first rows.  kp_base: the counts of the images before b, 256 a trip - image 256 is not
+    empty, so the rows of 257 ... 259 start past a second trip's sum, in the write, the top-k and the descriptor pass.
+    k_keypoint_topk: 8192 staged keypoints a trip, every keypoint's rank so far reloaded - equal scores lie on both sides of every
+    chunk edge, and the ranks without any one chunk's share keep another set."""
+    from pf3plat_amd import keypoints
+
+    with open(os.path.join(os.path.dirname(_lib.SRC), "gsr_attention.h")) as f:
+        text = f.read()
+    for line in (f"base += {ref.SCAN_CHUNK})", f"i += {ref.BASE_STEP}) mine +=", f"kKpTopkChunk = {ref.TOPK_CHUNK};"):
+        assert line in text, line  # the trip lengths the cases are sized by are the source's
+    # the scan
+    words = {}
+    for name, (_, H, W, r, border) in ref.SCAN_CASES.items():
+        s, _, want = ref.scan_case(name)
+        pix, sc, n = want[0]
+        w = ref.mask_words(pix, W)
+        words[name] = H * (-(-W // keypoints.TILE))
+        first = int((w < ref.SCAN_CHUNK).sum())
+        print(f"scan {name}: {words[name]} words, {n} keypoints, {n - first} of them in words from {ref.SCAN_CHUNK} on")
+        assert n == first + int((w >= ref.SCAN_CHUNK).sum()) and first > 0
+        assert (n - first > 0) == (words[name] > ref.SCAN_CHUNK)
+        assert sc.numel() - sc.unique().numel() > n // 2  # eighths: ties
+    assert words == {"w2048": ref.SCAN_CHUNK, "w2049": ref.SCAN_CHUNK + 1, "w2080": ref.SCAN_CHUNK + 32}
+    # the batch
+    _, B, H, W, r, border, thr, k, C = ref.BATCH_CASE
+    s, desc, kw = ref.batch_case()
+    counts = [n for _, _, n in ref.select(s, **kw)]
+    print(f"batch: {B} images, counts 0 .. {max(counts)}, {counts.count(0)} empty, {sum(n > k for n in counts)} above the cut of {k}; the last: {counts[250:]}")
+    assert B > ref.BASE_STEP + 1 and tuple(s.shape) == (B, 8, 8) and tuple(desc.shape) == (B, 8, 1, 1)
+    assert counts[0] > 0 and counts[ref.BASE_STEP] > 0 and counts.count(0) > 0 and len(set(counts)) > 3
+    assert all(counts[b] > k for b in range(ref.BASE_STEP + 1, B))  # the images whose base takes a second trip are staged by the cut
+    assert any(0 < n <= k for n in counts) and any(n > k for n in counts[:ref.BASE_STEP])
+    # the top-k
+    trips = {}
+    for name, (_, H, W, found, k) in ref.TOPK_CASES.items():
+        s, kw, want, staged = ref.topk_case(name)
+        n = want[0][2]
+        trips[name] = -(-n // ref.TOPK_CHUNK)
+        assert n == staged.numel() == (found or n) and n / 2 < k < n <= H * W and len(want[0][1]) == k and staged.unique().numel() == 8
+        shares = ref.chunk_ranks(staged)
+        rank = shares.sum(0)
+        order = torch.sort(staged, descending=True, stable=True).indices
+        assert torch.equal(rank[order], torch.arange(n)) and shares.shape[0] == trips[name]
+        print(f"top-k {name}: {n} found, {k} kept, {trips[name]} chunks")
+        for c in range(trips[name] if trips[name] > 1 else 0):  # without chunk c's share of the ranks another set is kept
+            assert not torch.equal(rank - shares[c] < k, rank < k), (name, c)
+        for edge in range(ref.TOPK_CHUNK, n, ref.TOPK_CHUNK):  # equal scores on both sides of the edge, the earlier one kept
+            lo, after = torch.arange(n) < edge, staged[edge:edge + ref.TOPK_CHUNK]
+            assert bool((lo & (rank < k) & torch.isin(staged, after)).any()), (name, edge)
+            assert bool((rank[edge:edge + ref.TOPK_CHUNK] < k).any())  # ... and one past the edge is kept: its rank counts the earlier equal ones
+    assert trips == {"k8192": 1, "k8193": 2, "k3trips": 3}
+    assert ref.TOPK_CASES["k8192"][3] == ref.TOPK_CHUNK and ref.TOPK_CASES["k8193"][3] == ref.TOPK_CHUNK + 1
 
 
 REFERENCE_CONVS = {"conv1a": (64, 1, 3), "conv1b": (64, 64, 3), "conv2a": (64, 64, 3), "conv2b": (64, 64, 3), "conv3a": (128, 64, 3),
@@ -369,6 +429,73 @@ def test_hip_repeats_bit_for_bit_and_images_do_not_touch_one_another():
     assert same_bits(whole, run(slice(None))) and same_bits(whole, hip_logits("batch")[0])
     for b in range(logits.shape[0]):
         assert same_bits(whole[b:b + 1], run(slice(b, b + 1))), b
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", tuple(ref.SCAN_CASES))
+def test_hip_scan_carries_its_count_past_2048_words(name):
+    """One image of 2048, 2049 and 2080 mask words, in eighths: pixels, order, count and scores equal the restatement's."""
+    s, kw, want = ref.scan_case(name)
+    got, counts = hip_scores(s, capacity=s.shape[1] * s.shape[2], **kw)
+    print(f"scan {name}: {counts[0]} keypoints")
+    assert_selected(got, counts, want)
+
+
+BATCH_ROWS = 16  # the capacity of the 260-image calls: rows an image may fill
+
+
+@functools.lru_cache(maxsize=None)
+def hip_batch(form):
+    s, desc, kw = ref.batch_case()
+    k, C = ref.BATCH_CASE[7:]
+    kw = dict(kw, max_num_keypoints=k) if form == "cut" else kw
+    got, counts = hip_scores(s, **({"descriptors": desc.to(DEV)} if form == "descriptors" else {}), capacity=BATCH_ROWS, **kw)
+    return got, counts, ref.select(s, **kw)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("form", ("plain", "cut", "descriptors"))
+def test_hip_batch_of_260_images_sums_the_rows_before_an_image_past_256(form):
+    """260 images of 8 x 8, some empty: as they are found (the write pass forms the first row of the images from 257 on), cut to the
+    2 highest (those images are staged: the top-k pass forms it), with descriptors (the descriptor pass does; one cell an image, so a
+    keypoint's descriptor is its image's normalised cell and names the image the row was taken for)."""
+    got, counts, want = hip_batch(form)
+    assert max(counts) <= BATCH_ROWS  # (no image overflows the capacity)
+    assert_selected(got, counts, want)
+    if form == "descriptors":
+        desc = ref.batch_case()[1]
+        sampled = lambda dtype: torch.cat([ref.sample(pix, desc[b], dtype) for b, (pix, _, _) in enumerate(want)])
+        err = ref.rel_l2(cat(got, "descriptors"), sampled(F64))
+        bar = max(ref.FLOOR_DESCRIPTORS, 4.0 * ref.rel_l2(sampled(F32), sampled(F64)))
+        last = ref.rel_l2(torch.cat([g["descriptors"] for g in got[ref.BASE_STEP + 1:]]),
+                          torch.cat([ref.sample(pix, desc[b], F64) for b, (pix, _, _) in enumerate(want) if b > ref.BASE_STEP]))
+        print(f"batch of {len(got)}: descriptors rel-L2 {err:.3e}, of the images past {ref.BASE_STEP} {last:.3e}, bar {bar:.3e}")
+        assert err <= bar <= ref.CAP and last <= bar
+    else:
+        assert all(g["descriptors"] is None for g in got)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("form", ("plain", "cut", "descriptors"))
+def test_hip_image_258_alone_has_the_rows_it_has_in_the_batch(form):
+    s, desc, kw = ref.batch_case()
+    k, C = ref.BATCH_CASE[7:]
+    kw = dict(kw, max_num_keypoints=k) if form == "cut" else kw
+    b = ref.BASE_STEP + 2
+    alone, counts = hip_scores(s[b:b + 1], **({"descriptors": desc[b:b + 1].to(DEV)} if form == "descriptors" else {}), capacity=BATCH_ROWS, **kw)
+    assert counts == hip_batch(form)[1][b:b + 1] and counts[0] > k and same_bits(alone, hip_batch(form)[0][b:b + 1])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", tuple(ref.TOPK_CASES))
+def test_hip_top_k_ranks_past_a_chunk_of_8192(name):
+    """8192, 8193 and 17394 keypoints found of eight distinct scores, the cut between half of them and all: the kept ones, in
+    descending order with ties to the lower row-major index, equal the restatement's stable sort."""
+    s, kw, want, _ = ref.topk_case(name)
+    got, counts = hip_scores(s, capacity=s.shape[1] * s.shape[2], **kw)
+    print(f"top-k {name}: {counts[0]} found, {len(got[0]['pixels'])} kept")
+    assert len(got[0]["pixels"]) == kw["max_num_keypoints"] < counts[0]
+    assert_selected(got, counts, want)
 
 
 @pytest.mark.gpu

@@ -1,6 +1,9 @@
 """LightGlue's transformer on the device (pf3plat_amd.matcher): the restatement of tests/matcher_ref.py against the records of the
 reference's own LightGlue (CPU), the module's state dict, refusals and checks (CPU), and TransformerLayer / LightGlue / the
-pair_lists -> LightGlue -> pack_matched chain against the records and the float64 restatement (GPU)."""
+pair_lists -> LightGlue -> pack_matched chain against the records and the float64 restatement (GPU); one layer on 34 lists - 68
+units in either attention, past a trip of the ragged attention's unit search (docs/PARITY.md section 24.1)."""
+import functools
+
 import pytest
 import torch
 
@@ -22,9 +25,60 @@ def _all_calls():
         yield f"chain{i}", a, b
 
 
+MANY_SEED, MANY_LAYER = 91, 3
+
+
+@functools.lru_cache(maxsize=None)
+def many_lists():
+    """34 lists, 68 units in either attention of a layer - the unit search of the ragged attention takes 64 a trip -: sides of 1 to 20
+    keypoints, list 5 (140, 3) - a side of two query blocks in the first trip -, list 20 and list 31 with an empty side, list 33
+    (2, 131) - two query blocks in the second trip of the self-attention, image 1 of the last list, and of the cross-attention."""
+    g = torch.Generator().manual_seed(MANY_SEED)
+    sides = torch.randint(1, 21, (34, 2), generator=g).tolist()
+    sides[5], sides[20], sides[31], sides[33] = [140, 3], [9, 0], [0, 7], [2, 131]
+    return tuple((m, n) for m, n in sides)
+
+
+@functools.lru_cache(maxsize=None)
+def many_layer(dtype=torch.float64):
+    """Layer MANY_LAYER of rec9 on each of the 34 lists in `dtype`, list by list: (x0', x1'), or None where a side is empty (the
+    reference passes such a list through no layer)."""
+    lists = ref.inputs(many_lists(), MANY_SEED)
+    return [ref.layer(ref.state_of("rec9"), MANY_LAYER, *(t[None] for t in l), dtype) if m and n else None
+            for l, (m, n) in zip(lists, many_lists())]
+
+
+def _layer_calls():
+    """(label, float64 result, float32 result) of the one-layer calls on the 34 lists: the descriptors alone."""
+    for l, (a, b) in enumerate(zip(many_layer(torch.float64), many_layer(torch.float32))):
+        if a is not None:
+            yield f"many{l}", {"desc0": a[0], "desc1": a[1]}, {"desc0": b[0], "desc1": b[1]}
+
+
 # ---- CPU
+def test_many_lists_take_the_unit_search_of_both_attentions_past_its_first_trip():
+    sizes = many_lists()
+    lay = matcher.list_layout([m for m, _ in sizes], [n for _, n in sizes])
+    step, rows = 64, sum(m + n for m, n in sizes)
+    print(f"{len(sizes)} lists, {rows} rows, {len(lay.self_ranges)} units in either attention")
+    assert len(sizes) > 32 and len(lay.self_ranges) == len(lay.cross_q) == len(lay.cross_k) == 2 * len(sizes) > step and 900 <= rows <= 1100
+    assert sum(1 for m, n in sizes if m == 0 or n == 0) == 2 and (140, 3) in sizes[:32] and sizes[-1] == (2, 131)
+    assert all(1 <= s <= 20 for l, mn in enumerate(sizes) if l not in (5, 20, 31, 33) for s in mn)
+    for ranges in (lay.self_ranges, lay.cross_q):
+        blocks = [(c + 127) // 128 for _, c in ranges]
+        assert sum(blocks[:step]) not in (0, step)       # what the search carries into its second trip is not the unit count
+        assert blocks[-1] == 2 and sum(blocks[step:]) >= 4  # ... and there it finds a unit of two blocks behind others
+    # a search without the carry would pair unit u >= 64 with the keys of unit u - 64: other lists' rows
+    assert all(lay.cross_k[u] != lay.cross_k[u - step] and lay.self_ranges[u] != lay.self_ranges[u - step] for u in range(step, 2 * len(sizes)))
+    worst = max(ref.rel_l2(r32[key], r64[key]) for _, r64, r32 in _layer_calls() for key in ("desc0", "desc1"))
+    print(f"one layer on the 34 lists: worst float32 loss {worst:.3e}, bar {BAR:.3e}")
+    assert 4.0 * worst <= BAR
+
+
 def test_module_floor_is_the_worst_float32_loss():
     worst, worst_max0 = 0.0, 0.0
+    for label, r64, r32 in _layer_calls():
+        worst = max(worst, ref.rel_l2(r32["desc0"], r64["desc0"]), ref.rel_l2(r32["desc1"], r64["desc1"]))
     for label, r64, r32 in _all_calls():
         for key in ("desc0", "desc1"):
             if r64[key].numel():
@@ -181,6 +235,32 @@ def test_transformer_layer_on_the_ragged_lists():
         worst = max(worst, ref.rel_l2(got0, w0[0]), ref.rel_l2(got1, w1[0]))
     print(f"one layer: {worst:.3e}, bar {BAR:.3e}")
     assert worst <= BAR and not bool(torch.isnan(out).any())
+
+
+@gpu
+def test_transformer_layer_on_34_lists():
+    """One layer (rec9's fourth) on 34 lists - 68 units in either attention, more than a trip of the unit search - against the float64
+    restatement list by list; twice: the same bits."""
+    module = _module("rec9").cuda()
+    sizes = many_lists()
+    lists = ref.inputs(sizes, MANY_SEED)
+    lay = matcher.list_layout([m for m, _ in sizes], [n for _, n in sizes])
+    x = torch.cat([l[0] for l in lists] + [l[1] for l in lists]).cuda()
+    kpts = torch.cat([l[2] for l in lists] + [l[3] for l in lists]).cuda()
+    rot = module.posenc(matcher.normalize_keypoints(kpts, ref.SIZE))[:, 0].contiguous()
+    out = module.transformers[MANY_LAYER](x, rot, lay)
+    assert out.shape == x.shape and not bool(torch.isnan(out).any())
+    M0 = lay.offsets0[-1]
+    worst, at = 0.0, None
+    for l, want in enumerate(many_layer()):
+        if want is None:
+            continue
+        got0, got1 = out[lay.offsets0[l]:lay.offsets0[l + 1]], out[M0 + lay.offsets1[l]:M0 + lay.offsets1[l + 1]]
+        for err in (ref.rel_l2(got0, want[0][0]), ref.rel_l2(got1, want[1][0])):
+            assert err <= BAR, (l, sizes[l], err, BAR)  # (every list by itself: a short list does not hide behind a long one)
+            worst, at = (err, l) if err > worst else (worst, at)
+    print(f"one layer on 34 lists: worst {worst:.3e} (list {at}, {sizes[at]}), bar {BAR:.3e}")
+    assert torch.equal(module.transformers[MANY_LAYER](x, rot, lay), out)
 
 
 @gpu

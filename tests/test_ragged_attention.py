@@ -1,8 +1,10 @@
 """Ragged multi-head attention (pf3plat_amd.attention.ragged_attention, gsr_ragged_attention): every case of
 tests/ragged_attention_ref.py against the float64 restatement of the reference's lines, within max(FLOOR, 4 x the float32 restatement's
 own loss); the fences, the rotary sensitivity and the floors are checked on the CPU, where the argument checks and the C entry points'
-refusals are checked too."""
+refusals are checked too.  Cases of 64, 65 and 130 units take the kernel's unit search past its first trip of 64 (docs/PARITY.md
+section 24.1); the CPU test states what each reaches."""
 import ctypes
+import os
 
 import pytest
 import torch
@@ -73,6 +75,45 @@ def test_rotary_sensitivity(name):
     args = (torch.nan_to_num(c["q"]), c["k"], c["v"], c["q_ranges"], c["k_ranges"], c["scale"])
     assert ref.owned_error(ref.attention(*args, None)[0], true, own) > 1000.0 * bar
     assert ref.owned_error(ref.attention(*args, c["rot"].flip(0))[0], true, own) > 1000.0 * bar
+
+
+def test_many_unit_cases_take_the_unit_search_past_its_first_trip():
+    """The kernel finds a workgroup's unit by a scan over the units' query-block counts, 64 units a trip, and carries the blocks of
+    the trips before (rg_find in gsr_attention.h).  "u64" ends in one trip with its last block in the last lane; "u65" has the only
+    block of its second trip in lane 0, behind a lane 63 without blocks; "u130" takes three trips with block-less units on both sides
+    of either trip edge.  Everywhere a two-block unit lies before the edge, so that the carried count is not the unit count.  A search
+    without the carry pairs the queries past unit 63 with the keys of the unit 64 before: that moves the result by far more than a bar."""
+    step = ref.FIND_STEP
+    with open(os.path.join(os.path.dirname(_lib.SRC), "gsr_attention.h")) as f:
+        assert f"u0 < a.U; u0 += {step})" in f.read()  # the trip the cases are sized by is the source's
+    want = {"u64": (64, [0]), "u65": (65, [0, 64]), "u130": (130, [0, 65, 129])}  # units; per trip the unit of its first block
+    for name in ref.MANY_CASES:
+        c = ref.case_of(name)
+        form, sizes, H, D, with_rot, interleaved, _ = ref.CASES[name]
+        qr, kr = c["q_ranges"], c["k_ranges"]
+        units, trips = want[name[:-2] if name.endswith("d8") else name]
+        got = ref.search_trips(qr)
+        print(name, "units", len(qr), "rows", c["T"], "trips (first unit with a block, blocks carried in)", got)
+        assert form == "general" and len(qr) == units and len(got) == -(-units // step) and H == 2 and c["T"] < 1000
+        assert (D, with_rot, interleaved) == ((8, False, False) if name.endswith("d8") else (64, True, True))
+        assert [first for first, _ in got] == trips
+        for trip, (first, carried) in enumerate(got):
+            assert (carried > 0 and carried != trip * step) or trip == 0  # what is carried is a block count, not the unit count
+            assert qr[first][1] > 0
+        assert qr[units - 1][1] > 0  # the last unit has queries: the last block of the call is found in the last trip
+        assert all(q in (0, 1, 2, 3, 5) and k in (0, 1, 2, 4, 7) or (q, k) == ref.TWO_BLOCKS for q, k in sizes)
+        assert sum((q, k) == ref.TWO_BLOCKS for q, k in sizes) == 1
+        for edge in range(step, units, step):  # no blocks in the lanes at a trip's edge
+            assert qr[edge - 1][1] == 0 and (edge + 1 >= units or qr[edge][1] == 0), (name, edge)
+        if units > step:
+            own, true, bar = ref.owned_rows(c["T"], qr), ref.restatement(name)[0], ref.bars(name)["out"]
+            later = ref.owned_rows(c["T"], qr[step:])
+            lost = ref.attention(c["q"], c["k"], c["v"], qr, ref.without_carry(kr), c["scale"], c["rot"])[0]
+            assert torch.equal(lost[own & ~later], true[own & ~later])
+            assert ref.owned_error(lost, true, own) > 1000.0 * bar and ref.owned_error(lost, true, later) > 1000.0 * bar
+    assert ref.search_trips(ref.case_of("u64")["q_ranges"])[0][0] == 0 and ref.case_of("u64")["q_ranges"][63][1] > 0
+    assert ref.case_of("u64")["q_ranges"][62][1] == 0  # (its last lane holds blocks behind a lane that holds none)
+    assert ref.MANY_SIZES["u65"][10] == ref.TWO_BLOCKS and ref.MANY_SIZES["u130"][70] == ref.TWO_BLOCKS
 
 
 def test_select_case_is_a_gather_in_exact_arithmetic():
